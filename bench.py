@@ -13,11 +13,16 @@ memory through the streamed upload ("incl. H2D of X0"),
 metric = particle*steps/s, whole job: sum over ranks of rk5 steps actually taken (active packets
 only, Output.py:385) / max-over-ranks wall time.
 
-Untimed extras of the N = 1 line (each with its own roofline object): the other image quantity,
-stored samples through the LDS tiles at 512 x 512 and at the reference's default 800 x 800, 512
-spacecraft lines of sight over the same stored samples, the adaptive driver at 1e6 and 1e7 packets.
+A plain run sets up, warms up, times the K passes and prints the line.  ``--full`` adds what takes
+runs of its own: the pass including the upload of X0, the stream-copy ceiling and shader clock of
+the roofline, the CPU baseline, and the untimed extras of the N = 1 line (each with its own
+roofline object): the other image quantity, stored samples through the LDS tiles at 512 x 512 and
+at the reference's default 800 x 800, 512 spacecraft lines of sight over the same stored samples,
+the adaptive driver at 1e6 and 1e7 packets.  ``--dump-outputs DIR`` writes what the last timed
+pass computed (dump_outputs) before anything else runs.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --full                     # the headline plus every side measurement
     python bench.py --with-comm                # N = 1, but through every N > 1 branch (RCCL world of one)
     python bench.py --mode variable            # the adaptive-step driver (Output.py:221-366)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -55,6 +60,7 @@ HBM_PEAK_GBS = 8000.0                   # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 GUIDE_COPY_GBS = 6290.0                 # same guide: float4 copy, measured
 SEED = 1234
 INFILE = os.path.join(ROOT, 'nexoclom_amd', 'inputfiles', 'Na.mercury.bench.input')
+DUMP_BUDGET = 60 << 20                  # --dump-outputs: under 64 MB in all, .npy headers included
 
 
 def parse(argv=None):
@@ -62,6 +68,15 @@ def parse(argv=None):
     p.add_argument('--gpus', type=int, default=1)
     p.add_argument('--steps', type=int, default=10)
     p.add_argument('--warmup', type=int, default=2)
+    p.add_argument('--full', action='store_true',
+                   help='also run the side measurements: the pass including the upload of X0, '
+                        'the stream-copy ceiling and clock, the untimed extras and the CPU '
+                        'baseline (--no-h2d-pass / --no-extras / --no-cpu-baseline leave parts '
+                        'of them out)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write what the last timed pass computed as DIR/<name>.npy (float64): '
+                        'the image and its packet counts, or with --mode variable the final '
+                        'states and step sizes (a seeded sample of the packets beyond 64 MB)')
     p.add_argument('--packets', type=int, default=None,
                    help='packets per GPU (default 1e7 for both drivers)')
     p.add_argument('--dims', type=int, default=512)
@@ -79,7 +94,26 @@ def parse(argv=None):
                    help='skip the pass that includes the upload of X0 (counter-mode profilers '
                         'serialise kernels, and the pipelined pass needs two running side by side)')
     p.add_argument('--cpu-packets', type=int, default=150_000)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error('--steps must be at least 1 and --warmup at least 0')
+    return args
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET):
+    """Write ``arrays`` (name -> array, all of the same length) as path/<name>.npy in float64.
+    Arrays that would take more than ``budget`` bytes in all keep the same rows, a sample fixed by
+    SEED and their length, so that two builds dump the same packets."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(a, dtype=np.float64) for k, a in arrays.items()}
+    n, = {len(a) for a in arrays.values()}
+    row_bytes = sum(a.itemsize*int(np.prod(a.shape[1:])) for a in arrays.values())
+    keep = budget//row_bytes
+    if keep < n:
+        rows = np.sort(np.random.default_rng(SEED).choice(n, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def quiet():
@@ -498,32 +532,45 @@ def _run_rank(args, cp, make_context, emit, state, on_peer_failure):
             ctx.barrier()           # RCCL all-reduce of one double on the handle's stream
 
     def one_step(on):
+        """One pass; the variable driver returns its (final states, step sizes), the constant
+        pass leaves its image on the device."""
         if variable:
-            ctx.integrate_var(float(run_inputs.options.resolution), opt.outeredge)
-            return
+            return ctx.integrate_var(float(run_inputs.options.resolution), opt.outeredge)
         ctx.image_clear()
         ctx.integrate_const_async(opt.step_size, n_iter, opt.outeredge, image=True)
         if on:
             ctx.image_allreduce()
 
     def timed(on, steps):
-        """K passes bracketed by barrier + synchronize on both sides."""
+        """K passes bracketed by barrier + synchronize on both sides; also returns what the last
+        pass returned."""
         kernel_ms = []
         job_barrier(on)
         ctx.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            one_step(on)
+            last = one_step(on)
             ctx.synchronize()
             kernel_ms.append(ctx.last_kernel_ms())     # HIP events on the handle's stream
         ctx.synchronize()
         job_barrier(on)
-        return time.perf_counter() - t0, kernel_ms
+        return time.perf_counter() - t0, kernel_ms, last
 
     for _ in range(args.warmup):
         one_step(comm)
         ctx.synchronize()
-    elapsed, kernel_ms = timed(comm, args.steps)
+    elapsed, kernel_ms, last = timed(comm, args.steps)
+
+    # what a caller of the timed path receives from its last pass, before anything else runs on
+    # the device (after the reduce every rank holds the global image; rank 0 writes)
+    if args.dump_outputs and rank == 0:
+        if variable:
+            final, hs = last
+            dump_outputs(args.dump_outputs, {'final_state': final, 'step_size': hs})
+        else:
+            image, counts = ctx.image_download()
+            dump_outputs(args.dump_outputs, {'image': image, 'packet_image': counts})
+    del last
 
     ctr = ctx.counters()
     trips = ctx.wave_trips() if hasattr(ctx, 'wave_trips') else None
@@ -539,13 +586,13 @@ def _run_rank(args, cp, make_context, emit, state, on_peer_failure):
     # --with-comm on one rank: the plain pass beside it, so the line shows what the collectives cost
     plain = None
     if comm and world == 1:
-        plain_s, _ = timed(False, args.steps)
+        plain_s, _, _ = timed(False, args.steps)
         plain = plain_s/args.steps
 
     # ---- the same pass with X0 coming from host memory (never the headline) ---
     incl, pipeline = [], 'sequential: upload, then the pass' if variable else \
         'pipelined: one persistent launch consumes the queue while it crosses PCIe'
-    for _ in range(0 if args.no_h2d_pass else 2):
+    for _ in range(2 if args.full and not args.no_h2d_pass else 0):
         job_barrier(comm)
         ctx.synchronize()
         t0 = time.perf_counter()
@@ -592,7 +639,7 @@ def _run_rank(args, cp, make_context, emit, state, on_peer_failure):
     if rank == 0:
         k_ms = float(np.mean(kernel_ms))
         achieved = ALGO_BYTES_PER_PARTICLE_STEP*ctr['particle_steps']/(k_ms*1e-3)/1e9
-        extras = world == 1 and not args.no_extras
+        extras = args.full and world == 1 and not args.no_extras
         clock_mhz = ctx.shader_clock_mhz() if extras and hasattr(ctx, 'shader_clock_mhz') else None
         copy_gbs = ctx.stream_copy_gbs() if extras and hasattr(ctx, 'stream_copy_gbs') else None
         traffic, secondary = (None, None) if variable else \
@@ -685,7 +732,7 @@ def _run_rank(args, cp, make_context, emit, state, on_peer_failure):
             # packets (Input.py:218) and at 1e7, which is what Input.run launches at once
             line['variable_step'] = variable_leg(ctx, inputs_var, 1_000_000)
             line['variable_step_1e7'] = variable_leg(ctx, inputs_var, 10_000_000, passes=2)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             with quiet():
                 line['cpu_baseline'] = cpu_baseline(args, inputs_var if variable else inputs,
                                                     variable)

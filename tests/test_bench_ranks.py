@@ -12,8 +12,8 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGV = ['--packets', '1500', '--steps', '2', '--warmup', '1', '--dims', '64', '--no-extras',
-        '--no-cpu-baseline']
+PLAIN_ARGV = ['--packets', '1500', '--steps', '2', '--warmup', '1', '--dims', '64']
+ARGV = PLAIN_ARGV + ['--full', '--no-extras', '--no-cpu-baseline']
 
 
 def _worker(rank, world, port, tmpdir, broken_rank, fault):
@@ -142,6 +142,55 @@ def test_with_comm_on_one_rank_takes_the_collective_branches(tmp_path, capsys):
     # warmup + timed + incl-H2D passes reduce the image; the plain comparison passes do not
     assert ctx.log.count('image_allreduce') == 1 + 2 + 2 and len(ctx.calls) == 1 + 2 + 2 + 2
     assert ctx.log.count('comm_init') == ctx.log.count('comm_destroy') == 1
+
+
+def test_a_plain_run_times_only_its_steps_and_dumps_the_last_pass(tmp_path):
+    """Without --full: warm-up + the timed passes and nothing else on the device; --dump-outputs
+    writes the image of the last timed pass, the same from run to run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from nexoclom_amd.distributed import ControlPlane
+    from tests.oracle_context import OracleContext
+    dumps = []
+    for run in range(2):
+        dump = tmp_path / f'run{run}'
+        args = bench.parse(PLAIN_ARGV + ['--steps', '3', '--dump-outputs', str(dump)])
+        ctx = OracleContext(cp=ControlPlane(1, 0))
+        lines = []
+        assert bench.run_rank(args, ctx.cp, lambda: ctx, emit=lines.append) == 0
+        line = json.loads(lines[0])
+        assert len(ctx.calls) == 1 + 3 and line['steps'] == 3       # warm-up + timed, no more
+        assert line['h2d_pass'] == 'skipped' and line['value_incl_h2d'] is None
+        assert line['cpu_baseline'] is None and 'stored_samples_image' not in line
+        np.testing.assert_allclose(line['value'],
+                                   line['particle_steps_per_pass']/(line['ms_per_step']*1e-3))
+        image, counts = ctx.image_download()
+        got = {p.name: np.load(p) for p in dump.iterdir()}
+        assert set(got) == {'image.npy', 'packet_image.npy'}
+        assert all(a.dtype == np.float64 and a.shape == (64, 64) for a in got.values())
+        assert np.array_equal(got['image.npy'], image)
+        assert np.array_equal(got['packet_image.npy'], counts.astype(float))
+        assert got['packet_image.npy'].sum() == ctx._ctr['samples_binned'] > 0
+        dumps.append(got)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+
+
+def test_dump_outputs_keeps_the_same_seeded_rows_of_every_array_within_the_budget(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    final = np.arange(8000.).reshape(1000, 8)
+    hs = np.arange(1000.)
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), {'final_state': final, 'step_size': hs},
+                           budget=72*100)
+    a = {n: np.load(tmp_path / 'a' / f'{n}.npy') for n in ('final_state', 'step_size')}
+    b = {n: np.load(tmp_path / 'b' / f'{n}.npy') for n in ('final_state', 'step_size')}
+    assert a['final_state'].shape == (100, 8) and a['step_size'].shape == (100,)
+    assert np.array_equal(a['final_state'][:, 0]/8, a['step_size'])        # the same rows
+    assert np.all(np.diff(a['step_size']) > 0)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    bench.dump_outputs(str(tmp_path / 'all'), {'step_size': hs}, budget=8*1000)
+    assert np.array_equal(np.load(tmp_path / 'all' / 'step_size.npy'), hs)
 
 
 def test_eight_ranks_run_the_whole_bench_logic(tmp_path):
