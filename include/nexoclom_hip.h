@@ -436,6 +436,38 @@ int nxc_los_accumulate_rows(nxc_handle *h, const nxc_los_desc *d, int64_t S, con
                             uint8_t *included, int64_t used_cap, int64_t *used_pairs,
                             int64_t *n_used);
 
+/* ---- ModelDensity: number density at points ------------------------------------------------------
+ * data_simulation/ModelDensity.py:56-85: for each of Q query points, the frac sum and the number of
+ * stored samples within dr of it, summed over any number of accumulate calls.  The points come
+ * indexed (ModelDensity.DensityIndex): sorted by the cell of a uniform grid of edge h >= dr (1 +
+ * 2^-20) with origin `origin` and dims[3] cells (at most 2^24 in all), cell (cx, cy, cz) =
+ * floor((q - origin) * (1/h)) per axis, linear cell (cz * ny + cy) * nx + cx, its points
+ * cell_start[c] .. cell_start[c + 1] - 1 of `points` (cell_start[0] = 0, cell_start[ncells] = Q).
+ * A sample at p counts for point q iff, with d = q - p in fp64, (dx*dx + dy*dy) + dz*dz <= dr*dr
+ * (KDTree.query_ball_point's set).
+ *   nxc_density_set              copies the index to the device and zeroes the resident sums
+ *   nxc_density_accumulate[_f32] adds P samples held on the host (x, y, z, frac; float32 ones are
+ *                                widened exactly as restore() does, Output.py:555-570)
+ *   nxc_density_accumulate_rows  adds rows [first, first + count) of a row store (x, y, z, frac)
+ *   nxc_density_download         sum_frac[Q], count[Q], in the index's (sorted) point order */
+typedef struct nxc_density_desc {
+    double origin[3];
+    double h;                 /* cell edge                                                        */
+    double dr;                /* ball radius, same unit as the points                             */
+    int64_t dims[3];          /* cells along x, y, z                                              */
+    int64_t n_points;         /* Q (0 allowed: every accumulate is then a no-op)                  */
+    const double *points;     /* host [Q][3], sorted by cell                                      */
+    const int32_t *cell_start;/* host [dims[0] * dims[1] * dims[2] + 1]                           */
+} nxc_density_desc;
+
+int nxc_density_set(nxc_handle *h, const nxc_density_desc *d);
+int nxc_density_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                           const double *z, const double *frac);
+int nxc_density_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                               const float *z, const float *frac);
+int nxc_density_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_density_download(nxc_handle *h, double *sum_frac, double *count);
+
 /* ---- a-9 / multi-GPU: sum of the per-GPU image pairs over RCCL ---------------------------------
  * One process per GPU.  Rank 0 calls nxc_comm_unique_id and hands the 128 bytes to the other
  * ranks (any side channel); every rank then calls nxc_comm_init (NXC_ERR_ARG when RCCL refuses

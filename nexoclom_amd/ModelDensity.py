@@ -1,0 +1,173 @@
+"""ModelDensity: number density at arbitrary points, accumulated on the GPU.
+
+Drop-in for data_simulation/ModelDensity.py:18-85 of the reference:
+``ModelDensity(inputs, xpts, ypts, zpts, dr=0.05)`` with the points and ``dr`` in planet radii and
+the attributes type, origin, unit, dr, Vpix, density, packets, totalsource, atoms_per_packet,
+sourcerate, outid and outputfiles.
+
+The reference builds a KD-tree over every catalogued Output's rows and asks it for the rows within
+``dr`` of each point (``query_ball_point``), then sums their ``frac``.  Here the POINTS are indexed
+once (``DensityIndex``: a uniform grid of cell edge >= dr, built with NumPy) and the HIP kernel
+k_density reads every row once, where it lies -- in HBM after ``Input.run`` or uploaded from the
+host for restored / variable-step Outputs -- and adds {frac, 1} to each point whose ball holds it.
+The membership test is query_ball_point's: with d = q - p in fp64,
+``(dx*dx + dy*dy) + dz*dz <= dr*dr``.
+
+Kept quirk of the reference (ModelDensity.py:56): ``Vpix = 4/3/pi * dr**3`` in cm^3, i.e.
+(4/(3 pi)) dr^3 and not the volume of the ball (4 pi/3) dr^3.  The density is scaled by it as
+written.  Bokeh display is out of scope.
+"""
+import numpy as np
+
+from .units import Quantity
+
+MAX_CELLS = 1 << 24           # cells of the point grid (int32 starts; cell coordinates < 2^24)
+CELL_SLACK = 1.0 + 2.0**-20   # h >= dr * CELL_SLACK: the neighbour cells cover the ball despite rounding
+
+
+class DensityIndex:
+    """The query points sorted by the cell of a uniform grid (what nxc_density_set takes).
+
+    ``points``: (Q, 3) in planet radii.  Points with a non-finite coordinate are left out of the
+    index (their density is 0).  Attributes: ``order`` -- the input position of each indexed
+    point, in index order; ``points`` -- those points (n, 3); ``cell_start`` -- int32, ncells + 1;
+    ``origin``, ``h`` (cell edge), ``dims`` (cells along x, y, z).  Cell of q along an axis:
+    floor((q - origin) * (1 / h)); linear cell (cz * ny + cy) * nx + cx.  The edge starts at
+    dr * (1 + 2^-20) and only grows (to keep the grid under MAX_CELLS), which keeps every point
+    within dr of a row in the row's cell or a neighbour of it."""
+
+    def __init__(self, points, dr):
+        points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+        dr = float(dr)
+        if not (np.isfinite(dr) and dr > 0):
+            raise ValueError('dr must be a positive number')
+        self.dr = dr
+        finite = np.flatnonzero(np.isfinite(points).all(axis=1))
+        P = points[finite]
+        h = dr * CELL_SLACK
+        if len(P) == 0:
+            self.origin, self.h, self.dims = np.zeros(3), h, (1, 1, 1)
+            self.order = np.zeros(0, dtype=np.int64)
+            self.points = np.zeros((0, 3))
+            self.cell_start = np.zeros(2, dtype=np.int32)
+            return
+        origin = P.min(axis=0)
+        while True:
+            top = np.floor((P.max(axis=0) - origin) * (1.0 / h)) + 1.0
+            cells = float(np.prod(top))
+            if cells <= MAX_CELLS:
+                break
+            h *= max(1.01, 1.001 * (cells / MAX_CELLS) ** (1.0 / 3.0))
+        cell = np.floor((P - origin) * (1.0 / h)).astype(np.int64)
+        dims = tuple(int(v) for v in cell.max(axis=0) + 1)
+        linear = (cell[:, 2] * dims[1] + cell[:, 1]) * dims[0] + cell[:, 0]
+        order = np.argsort(linear, kind='stable')
+        ncells = dims[0] * dims[1] * dims[2]
+        counts = np.bincount(linear, minlength=ncells)
+        self.origin, self.h, self.dims = origin, h, dims
+        self.order = finite[order]
+        self.points = np.ascontiguousarray(P[order])
+        self.cell_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+
+    def scatter(self, values, size):
+        """Per-indexed-point values back to the input's point order (0 for left-out points)."""
+        out = np.zeros(size)
+        out[self.order] = values
+        return out
+
+
+def vpix_cm3(dr, radius_km):
+    """ModelDensity.py:56 as written: 4/3/pi * dr**3 [R^3] in cm^3 (not the ball's volume)."""
+    R_cm = float(radius_km) * 1e5
+    return 4/3/np.pi*dr**3 * R_cm**3
+
+
+class ModelDensity:
+    def __init__(self, inputs, xpts, ypts, zpts, dr=0.05, *, cp=None, reduce='rccl',
+                 context=None, device=0):
+        """Number density at the points (xpts, ypts, zpts) [planet radii] from every catalogued
+        Output of ``inputs`` (ModelDensity.py:18-85).  ``cp``: the control plane of a shared run
+        (``Input.run(..., cp=cp)``): each rank sums its own Outputs, then the per-point sums and
+        the source totals are summed over the ranks before scaling."""
+        self.type = 'density'
+        self.inputs = inputs
+        self.origin = inputs.geometry.planet
+        self.unit = 'R_' + self.origin.object
+        unit_km = float(self.origin.radius.value)
+        dr = float(dr.to(self.unit)) if isinstance(dr, Quantity) and dr.unit else float(dr)
+        self.dr = Quantity(dr, self.unit)
+        self.Vpix = Quantity(vpix_cm3(dr, unit_km), 'cm3')
+        xyz = [np.asarray(v, dtype=np.float64).ravel() for v in (xpts, ypts, zpts)]
+        if not len(xyz[0]) == len(xyz[1]) == len(xyz[2]):
+            raise ValueError('xpts, ypts and zpts must have the same length')
+        Q = len(xyz[0])
+        self.density = np.zeros(Q)
+        self.packets = np.zeros(Q)
+        self.totalsource = 0.
+        self._ctx, self._device = context, device
+        self.counters = {}
+
+        self.outid, self.outputfiles, self.npackets, _ = inputs.search()
+        shared = cp is not None and cp.world > 1
+        if self.npackets == 0 and not shared:
+            raise RuntimeError('No packets found for these Inputs.')
+        index = DensityIndex(np.stack(xyz, axis=1), dr)
+        sums, counts = self._accumulate(index)
+        self.density += index.scatter(sums, Q)
+        self.packets += index.scatter(counts, Q)
+        if shared:
+            from .distributed import allreduce_small, guarded
+            with guarded(cp, self.context()):
+                both = allreduce_small(np.concatenate([
+                    self.density, self.packets, [float(self.totalsource), float(self.npackets)]]),
+                    cp, self.context(), reduce)
+            self.density, self.packets = both[:Q].copy(), both[Q:2*Q].copy()
+            self.totalsource, self.npackets = float(both[2*Q]), int(round(both[2*Q + 1]))
+            if self.npackets == 0:
+                raise RuntimeError('No packets found for these Inputs.')
+        mod_rate = self.totalsource / inputs.options.endtime.value
+        self.atoms_per_packet = 1e23 / mod_rate
+        self.sourcerate = Quantity(1., '1e23/s')
+        self.density = self.density * self.atoms_per_packet/float(self.Vpix)
+
+    def context(self):
+        if self._ctx is None:
+            # the device the catalogued runs were made on, when there is one: their rows are still
+            # in its HBM; else a fresh one
+            shared = [getattr(run, '_ctx', None) for run in getattr(self.inputs, '_catalogue', ())]
+            shared = [ctx for ctx in shared if ctx is not None and getattr(ctx, '_h', True)]
+            if shared:
+                self._ctx = shared[-1]
+            else:
+                from . import hip_api
+                self._ctx = hip_api.Context(self._device)
+        return self._ctx
+
+    def _accumulate(self, index):
+        """(frac sums, counts) per indexed point over this process's catalogue
+        (ModelDensity.py:62-82).  Rows in HBM are read where they are, one launch per run of
+        adjacent slices of a store; other Outputs upload X's x, y, z, frac."""
+        from .Output import Output
+        ctx = self.context()
+        ctx.density_set(index.points, index.cell_start, index.origin, index.h, index.dr,
+                        index.dims)
+        span = None                               # (store, first row, row count)
+        for run in self.inputs._catalogue:
+            print(f'Output filename: {run.filename}')
+            view = run.resident_rows(ctx) if isinstance(run, Output) else None
+            if view is not None:
+                store, first, count, _ = view
+                if span is not None and span[0] is store and span[1] + span[2] == first:
+                    span = (store, span[1], span[2] + count)
+                else:
+                    if span is not None:
+                        ctx.density_accumulate(rows=span)
+                    span = (store, first, count)
+            else:
+                X = run.X
+                if len(X) and 'x' in X:
+                    ctx.density_accumulate(*(X[c].values for c in ('x', 'y', 'z', 'frac')))
+            self.totalsource += run.totalsource
+        if span is not None:
+            ctx.density_accumulate(rows=span)
+        return ctx.density_download()

@@ -412,6 +412,17 @@ struct nxc_handle {
     double *d_reduce = nullptr;      // one double for control-plane reductions
     double *d_reduce_n = nullptr;    // nxc_allreduce_f64's staging (grow-only)
     size_t reduce_n_cap = 0;
+
+    // ModelDensity (nxc_density_set): the point index and the {frac sum, count} pair per point
+    bool have_density = false;
+    DensityK dens{};
+    int64_t dens_q = 0;
+    double *d_dens_pts = nullptr;    // [Q][4]: x, y, z, 0 (two 16-byte loads per candidate)
+    size_t dens_pts_cap = 0;
+    int *d_dens_cell = nullptr;      // cell starts [ncells + 1]
+    size_t dens_cell_cap = 0;
+    double *d_dens_acc = nullptr;    // interleaved pair [Q][2], as the image's
+    size_t dens_acc_cap = 0;
 };
 
 static int order_on_device(nxc_handle *h, double k2max, const long long *d_lifetimes,
@@ -1426,6 +1437,43 @@ int image_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T *
     return image_run<T>(h, p, d, d + p, d + 2 * p, d + 3 * p, d + 4 * p);
 }
 
+// ModelDensity over samples on the device (k_density)
+template <typename T>
+int density_run(nxc_handle *h, int64_t p, const T *dx, const T *dy, const T *dz, const T *dfrac)
+{
+    if (p == 0 || h->dens_q == 0) return NXC_OK;
+    int per_cu = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_density<T>, NXC_BLOCK, 0));
+    int64_t grid = (int64_t)h->n_cu * (per_cu > 0 ? per_cu : 1);
+    grid = std::max<int64_t>(1, std::min<int64_t>(grid, (p + NXC_BLOCK - 1) / NXC_BLOCK));
+    int rc;
+    if ((rc = begin_timed(h))) return rc;
+    hipLaunchKernelGGL(k_density<T>, dim3((unsigned)grid), dim3(NXC_BLOCK), 0, h->stream, h->dens,
+                       p, dx, dy, dz, dfrac, h->d_dens_pts, h->d_dens_cell, h->d_dens_acc);
+    HIPCHK(hipGetLastError());
+    if ((rc = end_timed(h))) return rc;
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+}
+
+// ... over samples in host memory, 64-bit or as save() keeps them (32-bit)
+template <typename T>
+int density_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T *z, const T *frac)
+{
+    if (!h || !h->have_density) return fail(NXC_ERR_STATE, "nxc_density_set has not been called");
+    if (p < 0 || (p && (!x || !y || !z || !frac))) return fail(NXC_ERR_ARG, "bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    if (p == 0 || h->dens_q == 0) return NXC_OK;
+    const size_t col = (size_t)p * sizeof(T);
+    int rc = ensure(reinterpret_cast<void **>(&h->d_samples), &h->samples_cap, 4 * col);
+    if (rc) return rc;
+    T *d = reinterpret_cast<T *>(h->d_samples);
+    const T *src[4] = {x, y, z, frac};
+    for (int c = 0; c < 4; c++)
+        HIPCHK(hipMemcpyAsync(d + c * p, src[c], col, hipMemcpyHostToDevice, h->stream));
+    return density_run<T>(h, p, d, d + p, d + 2 * p, d + 3 * p);
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1504,7 +1552,8 @@ int nxc_destroy(nxc_handle *h)
     void *ptrs[] = {h->d_blob, h->d_image, h->d_packets, h->d_ctr, h->d_scratch,
                     h->d_steps, h->d_reduce, h->d_order, h->d_bounce, h->d_moonpos, h->d_offsets,
                     h->d_source, h->d_queue, h->d_samples, h->d_tiles, h->d_hist, h->d_rec, h->d_piece_hist,
-                    h->d_blob_img, h->d_reduce_n, h->d_losblk};
+                    h->d_blob_img, h->d_reduce_n, h->d_losblk, h->d_dens_pts, h->d_dens_cell,
+                    h->d_dens_acc};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     pool_flush(h);
@@ -2522,6 +2571,106 @@ int nxc_los_accumulate_rows(nxc_handle *h, const nxc_los_desc *d, int64_t S, con
                                       c + 7 * t, static_cast<const long long *>(r->d_index) + first,
                                       index_shift, n_index, radiance, npackets, included, used_cap, used_pairs,
                                       n_used);
+    });
+}
+
+int nxc_density_set(nxc_handle *h, const nxc_density_desc *d)
+{
+    return guarded([&]() -> int {
+    if (!h || !d) return fail(NXC_ERR_ARG, "null argument");
+    const int64_t Q = d->n_points;
+    if (!(d->dr > 0.0) || !std::isfinite(d->dr) || !(d->h >= d->dr * (1.0 + std::ldexp(1.0, -20))) ||
+        !std::isfinite(d->h) || Q < 0 || Q > INT32_MAX || (Q && !d->points) || !d->cell_start)
+        return fail(NXC_ERR_ARG, "bad nxc_density_desc");
+    int64_t ncells = 1;
+    for (int a = 0; a < 3; a++) {
+        if (d->dims[a] < 1 || d->dims[a] > (int64_t(1) << 24) || !std::isfinite(d->origin[a]))
+            return fail(NXC_ERR_ARG, "bad nxc_density_desc grid");
+        ncells *= d->dims[a];
+        if (ncells > (int64_t(1) << 24)) return fail(NXC_ERR_ARG, "more than 2^24 density cells");
+    }
+    // the kernel reads points cell_start[c] .. cell_start[c + 1] - 1: the starts must be a
+    // non-decreasing walk from 0 to Q
+    const int32_t *cs = d->cell_start;
+    if (cs[0] != 0 || cs[ncells] != Q) return fail(NXC_ERR_ARG, "cell starts do not span the points");
+    for (int64_t c = 0; c < ncells; c++)
+        if (cs[c + 1] < cs[c]) return fail(NXC_ERR_ARG, "cell starts are not sorted");
+    HIPCHK(hipSetDevice(h->device));
+    h->have_density = false;
+    std::vector<double> pts((size_t)Q * 4, 0.0);
+    for (int64_t j = 0; j < Q; j++)
+        for (int a = 0; a < 3; a++) pts[4 * j + a] = d->points[3 * j + a];
+    int rc;
+    if ((rc = ensure(reinterpret_cast<void **>(&h->d_dens_pts), &h->dens_pts_cap, pts.size() * 8)) ||
+        (rc = ensure(reinterpret_cast<void **>(&h->d_dens_cell), &h->dens_cell_cap,
+                     (size_t)(ncells + 1) * 4)) ||
+        (rc = ensure(reinterpret_cast<void **>(&h->d_dens_acc), &h->dens_acc_cap, (size_t)Q * 16)))
+        return rc;
+    if (Q) HIPCHK(hipMemcpyAsync(h->d_dens_pts, pts.data(), pts.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_dens_cell, cs, (size_t)(ncells + 1) * 4, hipMemcpyHostToDevice, h->stream));
+    if (Q) HIPCHK(hipMemsetAsync(h->d_dens_acc, 0, (size_t)Q * 16, h->stream));
+    HIPCHK(stream_sync(h));
+    DensityK K{};
+    for (int a = 0; a < 3; a++) {
+        K.o[a] = d->origin[a];
+        K.n[a] = (int)d->dims[a];
+    }
+    K.inv_h = 1.0 / d->h;
+    K.r_cell = d->dr / d->h + 1e-6;
+    K.dr2 = d->dr * d->dr;
+    h->dens = K;
+    h->dens_q = Q;
+    h->have_density = true;
+    return NXC_OK;
+    });
+}
+
+int nxc_density_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                           const double *z, const double *frac)
+{
+    return guarded([&]() -> int { return density_accumulate(h, p, x, y, z, frac); });
+}
+
+int nxc_density_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                               const float *z, const float *frac)
+{
+    return guarded([&]() -> int { return density_accumulate(h, p, x, y, z, frac); });
+}
+
+int nxc_density_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_density) return fail(NXC_ERR_STATE, "nxc_density_set has not been called");
+    int rc = rows_check(h, r, first, count);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    // columns 1, 2, 3, 7 of the store = x, y, z, frac
+    const long long t = r->total;
+    if (r->f32) {
+        const float *c = static_cast<const float *>(r->d_cols) + first;
+        return density_run<float>(h, count, c + t, c + 2 * t, c + 3 * t, c + 7 * t);
+    }
+    const double *c = static_cast<const double *>(r->d_cols) + first;
+    return density_run<double>(h, count, c + t, c + 2 * t, c + 3 * t, c + 7 * t);
+    });
+}
+
+int nxc_density_download(nxc_handle *h, double *sum_frac, double *count)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_density) return fail(NXC_ERR_STATE, "nxc_density_set has not been called");
+    if (h->dens_q && (!sum_frac || !count)) return fail(NXC_ERR_ARG, "bad arguments");
+    if (h->dens_q == 0) return NXC_OK;
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<double> pair((size_t)h->dens_q * 2);
+    HIPCHK(hipMemcpyAsync(pair.data(), h->d_dens_acc, pair.size() * 8, hipMemcpyDeviceToHost,
+                          h->stream));
+    HIPCHK(stream_sync(h));
+    for (int64_t j = 0; j < h->dens_q; j++) {
+        sum_frac[j] = pair[2 * j];
+        count[j] = pair[2 * j + 1];
+    }
+    return NXC_OK;
     });
 }
 

@@ -2491,3 +2491,98 @@ __global__ void k_sum_counters(const DevCounters *__restrict__ pieces, int n, De
         *out = t;
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// ModelDensity (ModelDensity.py:56-85): for every stored row, the query points within dr of it.
+// The Q points are indexed on the host (ModelDensity.DensityIndex): sorted by the cell of a
+// uniform grid of edge h >= dr (1 + 2^-20) with origin o, cell (cx, cy, cz) = floor((q - o) / h)
+// component by component (computed as (q - o) * (1 / h)), cell_start[c] .. cell_start[c + 1] the
+// points of linear cell c = (cz * ny + cy) * nx + cx.  A row at p can only reach points in the
+// cells next to its own: its cell c(p) differs from c(q) by at most one along each axis (the
+// rounding of the cell coordinates is far below the 2^-20 of slack in h, as long as they stay
+// below 2^24, which the host's cap on the number of cells guarantees).  Along an axis a neighbour
+// is visited only when the row's offset in its cell, t, is within dr / h (+ 1e-6) of that side.
+// A row whose cell coordinate lies outside [-1, n + 1) along any axis has no neighbour cell: the
+// query box grown by h >= dr, the whole cull.
+//
+// Membership is the reference's (KDTree.query_ball_point, checked against it in the tests):
+// d = q - p in fp64, (dx*dx + dy*dy) + dz*dz <= dr*dr, one rounding per operation.  A hit adds
+// {frac, 1} to the point's fp64 pair with image_add_pairs (one request per hit; counts exact
+// below 2^53).  The points are visited in the uniform loop every lane of the wave runs until all
+// its lanes have walked their candidate ranges: one candidate per lane per trip, so the pair add
+// stays wave-cooperative.
+struct DensityK {
+    double o[3];
+    double inv_h;
+    double r_cell;           // dr / h + 1e-6: how close to a face a row reaches the next cell
+    double dr2;              // dr * dr
+    int n[3];                // grid dims
+    int reserved;
+};
+
+// The candidate cells of a row: x0..x1 along x, likewise y and z; false when there are none.
+NXC_DEV bool density_cells(const DensityK &K, const double p[3], int lo[3], int hi[3])
+{
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const double t = (p[a] - K.o[a]) * K.inv_h;
+        if (!(t >= -1.0 && t < (double)K.n[a] + 1.0)) return false;
+        const double c = floor(t);
+        const double f = t - c;
+        const int ci = (int)c;
+        int l = f <= K.r_cell ? ci - 1 : ci;
+        int u = f >= 1.0 - K.r_cell ? ci + 1 : ci;
+        l = l < 0 ? 0 : l;
+        u = u > K.n[a] - 1 ? K.n[a] - 1 : u;
+        if (l > u) return false;
+        lo[a] = l;
+        hi[a] = u;
+    }
+    return true;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_density(DensityK K, int64_t n, const T *__restrict__ x, const T *__restrict__ y,
+          const T *__restrict__ z, const T *__restrict__ frac, const double *__restrict__ pts,
+          const int *__restrict__ cell_start, double *__restrict__ acc2)
+{
+    // wave-uniform trip count (the accumulation is wave-cooperative); the last trip is ragged
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n;
+         base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        double p[3] = {0.0, 0.0, 0.0}, w = 0.0;
+        int lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1};
+        bool live = false;
+        if (i < n) {
+            p[0] = (double)x[i]; p[1] = (double)y[i]; p[2] = (double)z[i];
+            w = (double)frac[i];
+            live = density_cells(K, p, lo, hi);
+        }
+        // the candidate points of one (cy, cz) row of cells are one contiguous range [j, e)
+        int cy = lo[1], cz = lo[2], j = 0, e = 0;
+        auto advance = [&]() {
+            while (live && j >= e) {
+                if (cz > hi[2]) { live = false; break; }
+                const int row = (cz * K.n[1] + cy) * K.n[0];
+                j = cell_start[row + lo[0]];
+                e = cell_start[row + hi[0] + 1];
+                if (++cy > hi[1]) { cy = lo[1]; ++cz; }
+            }
+        };
+        advance();
+        while (__ballot(live) != 0) {
+            bool hit = false;
+            int q = 0;
+            if (live) {
+                const double dx = pts[4 * (int64_t)j] - p[0];
+                const double dy = pts[4 * (int64_t)j + 1] - p[1];
+                const double dz = pts[4 * (int64_t)j + 2] - p[2];
+                hit = (dx * dx + dy * dy) + dz * dz <= K.dr2;
+                q = j++;
+                advance();
+            }
+            image_add_pairs(hit, q, w, acc2);
+        }
+    }
+}

@@ -35,7 +35,9 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_stream_copy_gbs', 'nxc_shader_clock_mhz', 'nxc_pcg64_uniforms',
            'nxc_integrate_const_streamed', 'nxc_image_mode', 'nxc_allreduce_f64',
            'nxc_comm_set_timeout', 'nxc_comm_abort', 'nxc_comm_request_abort',
-           'nxc_comm_test_stall', 'nxc_packets_upload_pieces')
+           'nxc_comm_test_stall', 'nxc_packets_upload_pieces', 'nxc_density_set',
+           'nxc_density_accumulate', 'nxc_density_accumulate_f32', 'nxc_density_accumulate_rows',
+           'nxc_density_download')
 ABI_VERSION = 3
 
 
@@ -72,6 +74,12 @@ class nxc_los_desc(C.Structure):
                 ('n_lines', C.c_int32), ('reserved', C.c_int32),
                 ('line_n', C.c_int64*NXC_MAX_LINES), ('line_v', _dp*NXC_MAX_LINES),
                 ('line_g', _dp*NXC_MAX_LINES), ('n_ladder', C.c_int64), ('ladder', _dp)]
+
+
+class nxc_density_desc(C.Structure):
+    _fields_ = [('origin', C.c_double*3), ('h', C.c_double), ('dr', C.c_double),
+                ('dims', C.c_int64*3), ('n_points', C.c_int64), ('points', _dp),
+                ('cell_start', C.POINTER(C.c_int32))]
 
 
 class nxc_source_desc(C.Structure):
@@ -655,6 +663,49 @@ class Context:
         return dict(radiance=radiance, npackets=npackets,
                     included=None if included is None else included.astype(bool),
                     used=None if used is None else used[:, :m], n_used=int(n_used.value))
+
+    # -- ModelDensity -----------------------------------------------------------------------
+    def density_set(self, points, cell_start, origin, h, dr, dims):
+        """Upload a query-point index (ModelDensity.DensityIndex: points (Q, 3) sorted by cell,
+        int32 cell starts, grid origin, cell edge h and dims) and zero the per-point sums."""
+        pts = _f64(points).reshape(-1, 3)
+        starts = np.ascontiguousarray(cell_start, dtype=np.int32)
+        d = nxc_density_desc()
+        d.origin[:] = [float(v) for v in origin]
+        d.h, d.dr = float(h), float(dr)
+        d.dims[:] = [int(v) for v in dims]
+        d.n_points = len(pts)
+        d.points = _p(pts) if len(pts) else None
+        d.cell_start = starts.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self.lib.nxc_density_set(self._h, C.byref(d)))
+        self._density_q = len(pts)
+
+    def density_accumulate(self, x=None, y=None, z=None, frac=None, rows=None):
+        """Add samples to the per-point sums: four host columns (float32 ones go over as they
+        are and are widened on the device), or ``rows = (RowStore, first, count)``."""
+        if rows is not None:
+            store, first, count = rows
+            if store._r is None:
+                raise HipError('the row store has been freed')
+            self._check(self.lib.nxc_density_accumulate_rows(self._h, store._r, C.c_int64(first),
+                                                             C.c_int64(count)))
+            return
+        cols = (x, y, z, frac)
+        if all(getattr(c, 'dtype', None) == np.float32 for c in cols):
+            cols = [np.ascontiguousarray(c) for c in cols]
+            ptr = [c.ctypes.data_as(C.POINTER(C.c_float)) for c in cols]
+            self._check(self.lib.nxc_density_accumulate_f32(self._h, C.c_int64(len(cols[0])), *ptr))
+            return
+        cols = [_f64(c) for c in cols]
+        self._check(self.lib.nxc_density_accumulate(self._h, C.c_int64(len(cols[0])),
+                                                    *(_p(c) for c in cols)))
+
+    def density_download(self):
+        """(frac sums, counts) per indexed point, float64, in the index's point order."""
+        q = getattr(self, '_density_q', 0)
+        total, count = np.zeros(q), np.zeros(q)
+        self._check(self.lib.nxc_density_download(self._h, _p(total), _p(count)))
+        return total, count
 
     # -- RCCL -------------------------------------------------------------------------------
     def comm_unique_id(self):
