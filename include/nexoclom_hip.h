@@ -63,8 +63,10 @@ typedef enum {
     NXC_ERR_STATE = -5,      /* handle not in the state the call needs                  */
     NXC_ERR_NOMEM = -6,      /* device memory: an allocation failed or the result would
                                 not fit (callers may split the work and call again)     */
-    NXC_ERR_INCOMPLETE = -7  /* nxc_synchronize after nxc_integrate_const_streamed: the
+    NXC_ERR_INCOMPLETE = -7, /* nxc_synchronize after nxc_integrate_const_streamed: the
                                 kernel gave up waiting for its queue; results are partial */
+    NXC_ERR_OVERFLOW = -8    /* a device pair list (nxc_pairs) was too small for the pairs
+                                a pass found; nothing was truncated silently            */
 } nxc_status;
 
 /* Scalars and table consumed by state() (what Output.__init__ hangs on `output`,
@@ -467,6 +469,66 @@ int nxc_density_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const f
                                const float *z, const float *frac);
 int nxc_density_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
 int nxc_density_download(nxc_handle *h, double *sum_frac, double *count);
+
+/* ---- LOSResultFitted: packet weights refitted to observed radiances ------------------------------
+ * data_simulation/LOSResultFitted.py:118-214 per Output, over the (spectrum, row) pairs its UNFITTED
+ * line-of-sight pass found with weight > 0 (compute_iteration.py:210's `used`).
+ *   nxc_pairs_create       a device pair list of `capacity` pairs (the Output's sum of npackets over
+ *                          the spectra bounds it: every used pair is a counted one)
+ *   nxc_los_set_pairs      the nxc_los_accumulate* calls that follow (until set to NULL) write their
+ *                          used pairs into p in place of used_pairs (which must then be NULL): rows
+ *                          as numbered in the call's sample range.  More pairs than the capacity:
+ *                          NXC_ERR_OVERFLOW (p then holds none that can be trusted)
+ *   nxc_pairs_count / nxc_pairs_download   the pairs of the last pass (any order): spectrum, row
+ *   nxc_fit_set            per spectrum: position [3][S] (host), ratio_j = data / unfitted model,
+ *                          weight_j (weight_mode 3: the reference's 1/sigma*2; nullable otherwise),
+ *                          mask_j; zeroes the fitted radiance sums
+ *   nxc_fit_source_rows / nxc_fit_source[_f32]   the samples the pairs' rows index: rows
+ *                          [first, first + count) of a store (packet = index - index_shift) or P host
+ *                          columns x, y, z, vy, frac with their packet index
+ *   nxc_fit_packets        per packet i over the pairs with mask_j: num_i = sum ratio_j w,
+ *                          den_i = sum w, cnt_i = pairs; w = 1, 1/d, 1/d^2 (weight_mode 0, 1, 2; d as
+ *                          the pair test forms it) or weight_j; f_i = num_i / den_i (0 where
+ *                          den_i = 0); mult_i = f_i / mean(f over den > 0), the mean in a fixed
+ *                          order; all 0 when no packet was seen.  stats: {sum f, packets seen}.
+ *                          Outputs nullable; the multipliers stay on the device
+ *   nxc_fit_radiance       adds, for every pair (no mask), frac mult_i gg / 1e6 / Apix to its
+ *                          spectrum's sum: the weight of nxc_los_accumulate with d's dphi, vrplanet,
+ *                          unit and g-value tables (ladder and thresholds unused)
+ *   nxc_fit_rows           (store sources) the rows with frac' = frac mult_i in fp64, narrowed to
+ *                          the store's type, with compress only those with frac' > 0, in their order,
+ *                          as a new store of the same layout; lengths_out[n_packets] (nullable):
+ *                          rows kept per packet
+ *   nxc_fit_download       the fitted radiance sums [S] */
+typedef struct nxc_pairs nxc_pairs;
+int nxc_pairs_create(nxc_handle *h, int64_t capacity, nxc_pairs **out);
+int nxc_pairs_free(nxc_handle *h, nxc_pairs *p);
+int nxc_pairs_count(const nxc_pairs *p, int64_t *n);
+int nxc_pairs_download(nxc_handle *h, const nxc_pairs *p, int64_t *spectrum, int64_t *row);
+int nxc_los_set_pairs(nxc_handle *h, nxc_pairs *p);
+
+typedef struct nxc_fit_desc {
+    int64_t n_spectra;        /* S                                                                */
+    int32_t weight_mode;      /* 0 none, 1 'dist', 2 'dist2', 3 'sigma'                            */
+    int32_t reserved;
+    const double *position;   /* host [3][S]: spacecraft x, y, z                                   */
+    const double *ratio;      /* host [S]                                                         */
+    const double *weight;     /* host [S] (weight_mode 3)                                          */
+    const uint8_t *mask;      /* host [S]                                                         */
+} nxc_fit_desc;
+
+int nxc_fit_set(nxc_handle *h, const nxc_fit_desc *d);
+int nxc_fit_source_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count,
+                        int64_t index_shift);
+int nxc_fit_source(nxc_handle *h, int64_t P, const double *x, const double *y, const double *z,
+                   const double *vy, const double *frac, const int64_t *index);
+int nxc_fit_source_f32(nxc_handle *h, int64_t P, const float *x, const float *y, const float *z,
+                       const float *vy, const float *frac, const int64_t *index);
+int nxc_fit_packets(nxc_handle *h, const nxc_pairs *p, int64_t n_packets, double *num, double *den,
+                    int32_t *cnt, double *mult, double *stats);
+int nxc_fit_radiance(nxc_handle *h, const nxc_pairs *p, const nxc_los_desc *d);
+int nxc_fit_rows(nxc_handle *h, int compress, nxc_rows **out, int64_t *lengths_out);
+int nxc_fit_download(nxc_handle *h, double *radiance);
 
 /* ---- a-9 / multi-GPU: sum of the per-GPU image pairs over RCCL ---------------------------------
  * One process per GPU.  Rank 0 calls nxc_comm_unique_id and hands the 128 bytes to the other

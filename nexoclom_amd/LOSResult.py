@@ -11,25 +11,47 @@ Division of labour: everything per SPECTRUM that involves libm trigonometry -- t
 the geometric ladder of pre-selection spheres along the line of sight, the cone-angle threshold --
 is set up here with NumPy (``los_geometry``, ``arccos_threshold``), so that the thresholds are the
 reference's own doubles; every (sample, spectrum) pair test runs in the HIP kernel
-(``nxc_los_accumulate``).  The fitted-result machinery (LOSResultFitted, source maps, masks,
-PostgreSQL caching of iterations) is out of scope.
+(``nxc_los_accumulate``).
+
+``make_mask`` and ``determine_source_rate`` restate LOSResult.py:171-200,278-308; the source-rate
+fit is NOT called by ``simulate_data_from_inputs`` here (the reference calls it at the end): call it
+explicitly before handing the result to ``LOSResultFitted`` (LOSResultFitted.py).  Source maps and
+the PostgreSQL caching of iterations are out of scope.
 """
 import numpy as np
 import pandas as pd
 
 from .ModelImage import ModelResult
+from .units import Quantity
 
 POSITION = ('x', 'y', 'z')
 BORESIGHT = ('xbore', 'ybore', 'zbore')
 
 
 class SpacecraftData:
-    """Minimal stand-in for MESSENGERuvvs.MESSENGERdata: positions and boresights per spectrum."""
+    """Minimal stand-in for MESSENGERuvvs.MESSENGERdata: positions and boresights per spectrum,
+    optionally the observed ``radiance`` [kR], its ``sigma`` and the tangent altitude ``alttan``
+    (data columns of the same names), and the model results fitted to it (``model_result``)."""
 
-    def __init__(self, x, y, z, xbore, ybore, zbore, species='Na', query='synthetic'):
+    def __init__(self, x, y, z, xbore, ybore, zbore, species='Na', query='synthetic', *,
+                 radiance=None, sigma=None, alttan=None):
         columns = dict(zip(POSITION + BORESIGHT, (x, y, z, xbore, ybore, zbore)))
+        for name, values in (('radiance', radiance), ('sigma', sigma), ('alttan', alttan)):
+            if values is not None:
+                columns[name] = values
         self.data = pd.DataFrame(columns, dtype=float)
         self.species, self.query, self.frame = species, query, 'Model'
+        self.model_result = {}
+
+    def add_model_result(self, result, label):
+        """Keep ``result`` under ``label`` with its radiance and mask as data columns
+        model_<label>, mask_<label> (what LOSResultFitted reads, LOSResultFitted.py:21,140).  A
+        result without a mask (determine_source_rate not called) masks nothing."""
+        self.model_result[label] = result
+        self.data['model_' + label] = np.asarray(result.radiance, dtype=float)
+        mask = getattr(result, 'mask', None)
+        self.data['mask_' + label] = (np.ones(len(self.data), dtype=bool) if mask is None
+                                      else np.asarray(mask, dtype=bool))
 
     def set_frame(self, frame):
         self.frame = frame
@@ -111,6 +133,9 @@ class LOSResult(ModelResult):
         self.radiance = pd.Series(np.zeros(len(rows)), index=rows)
         self.npackets_los = pd.Series(np.zeros(len(rows), dtype=np.int64), index=rows)
         self.included = None
+        self.mask = None
+        self.goodness_of_fit = None
+        self.masking = kwargs.get('masking', None)                    # LOSResult.py:101
         self.label = kwargs.get('label', 'LOSResult')
         self._ctx, self._device = context, device
         self.iterations = []
@@ -129,8 +154,9 @@ class LOSResult(ModelResult):
                 self._ctx = hip_api.Context(self._device)
         return self._ctx
 
-    def compute_iteration(self, output, scdata, used_cap=0):
-        """One catalogued Output against all spectra (compute_iteration.py:90-240)."""
+    def compute_iteration(self, output, scdata, used_cap=0, pairs=None):
+        """One catalogued Output against all spectra (compute_iteration.py:90-240).  ``pairs``: a
+        device pair list (hip_api.PairList) that receives the pairs with weight > 0."""
         from .Output import Output
         if not isinstance(output, Output):       # a file; a catalogued Output is used as stored:
             output = Output.restore(output)      # the binding widens just the columns it sends
@@ -145,13 +171,14 @@ class LOSResult(ModelResult):
         setup = (self.dphi, np.sin(self.dphi), np.sin(self.dphi*2), arccos_threshold(self.dphi),
                  float(output.vrplanet)/self.unit_km, self.unit_km*1e5,
                  self.g_tables(float(output.aplanet)), ladder, sc)
+        extra = {} if pairs is None else {'pairs': pairs}
         view = output.resident_rows(self.context())
         if view is not None:
             # the Output's rows are still in HBM: no host round trip
             store, first, count, packet0 = view
             res = self.context().los_accumulate(*setup, n_index=int(output.npackets),
                                                 used_cap=used_cap,
-                                                rows=(store, first, count, packet0))
+                                                rows=(store, first, count, packet0), **extra)
         else:
             samples = output.X
             if 'Index' in samples.columns:
@@ -161,7 +188,7 @@ class LOSResult(ModelResult):
             n_index = int(len(output.X0)) if len(output.X0) else int(index.max()) + 1
             res = self.context().los_accumulate(
                 *setup, *(samples[c].values for c in ('x', 'y', 'z', 'vy', 'frac')),
-                index=index, n_index=n_index, used_cap=used_cap)
+                index=index, n_index=n_index, used_cap=used_cap, **extra)
         assert self.context().counters()['nonfinite'] == 0, 'Non-finite weights'
         res['totalsource'] = output.totalsource
         for key in ('radiance', 'npackets'):
@@ -202,3 +229,61 @@ class LOSResult(ModelResult):
         per_second = self.totalsource / self.inputs.options.endtime.value
         self.atoms_per_packet = 1e23 / per_second
         self.radiance *= self.atoms_per_packet/1e3      # kR
+
+    def make_mask(self, data):
+        """(mask, sigma limit) of the ``masking`` keyword (LOSResult.py:171-200): ';'-separated
+        'middle<p>', 'minalt<a>', 'minsnr<s>', 'siglimit<n>'.
+
+        Deviation: 'middle<p>' keeps the spectra whose radiance lies within the central p per cent
+        of the ``radiance`` column, np.nanpercentile at (100 - p)/2 and 100 - (100 - p)/2; the
+        reference hands the whole DataFrame to astropy's PercentileInterval."""
+        radiance = np.asarray(data['radiance'], dtype=float)
+        mask = np.ones(len(radiance), dtype=bool)
+        sigmalimit = None
+        if self.masking is not None:
+            for masktype in self.masking.split(';'):
+                masktype = masktype.strip().lower()
+                if masktype.startswith('middle'):
+                    low = (100. - float(masktype[6:]))/2
+                    lim = np.nanpercentile(radiance, [low, 100. - low])
+                    mask = mask & (radiance >= lim[0]) & (radiance <= lim[1])
+                elif masktype.startswith('minalt'):
+                    mask = mask & (np.asarray(data['alttan'], dtype=float) >= float(masktype[6:]))
+                elif masktype.startswith('minsnr'):
+                    snr = radiance/np.asarray(data['sigma'], dtype=float)
+                    mask = mask & (snr > float(masktype[6:]))
+                elif masktype.startswith('siglimit'):
+                    sigmalimit = float(masktype[8:])
+                else:
+                    raise ValueError(f'masking = {masktype} not defined.')
+        return mask, sigmalimit
+
+    def determine_source_rate(self, scdata, use_weight=True):
+        """LOSResult.py:278-308: scale the model radiance to the data.  astropy's LinearLSQFitter
+        on a Multiply model is the weighted least-squares factor sum(w^2 x y) / sum(w^2 x^2) with
+        w = 1/sigma^2 (use_weight) or 1; with 'siglimit<n>' the spectra more than n sigma off the
+        first fit are dropped and the factor fitted again (the weights then follow the narrowed
+        mask; the reference passes the first mask's).  Sets radiance, sourcerate, mask."""
+        data = scdata.data
+        mask, sigmalimit = self.make_mask(data)
+        model = np.asarray(self.radiance, dtype=float)
+        observed = np.asarray(data['radiance'], dtype=float)
+        sigma = np.asarray(data['sigma'], dtype=float) if 'sigma' in data else None
+
+        def factor(m):
+            w = 1./sigma[m]**2 if use_weight else np.ones(int(m.sum()))
+            x, y = model[m], observed[m]
+            return np.sum(w*w*x*y)/np.sum(w*w*x*x)
+
+        if not np.all(model == 0):
+            best = factor(mask)
+            if sigmalimit is not None:
+                diff = np.abs((observed - best*model)/sigma)
+                mask = mask & (diff < sigmalimit)
+                best = factor(mask)
+            self.radiance *= best
+            self.sourcerate = Quantity(float(best), '1e23/s')
+        else:
+            self.sourcerate = Quantity(0., '1e23/s')
+        self.goodness_of_fit = None
+        self.mask = mask

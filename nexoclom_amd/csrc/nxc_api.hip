@@ -319,6 +319,24 @@ struct BlockPool {
     std::mutex lock;                         // stores are freed by whichever thread drops them
 };
 
+// A device list of (spectrum, row) pairs: what a line-of-sight pass found with weight > 0
+// (nxc_los_set_pairs), [2][cap] int64 as the kernels write them.  Owned by its creator.
+struct nxc_pairs {
+    int device = 0;
+    long long cap = 0, n = 0;        // n: pairs the last pass found (<= cap, or that pass failed)
+    long long *d = nullptr;
+};
+
+// LOSResultFitted's samples (nxc_fit_source*): a row range of a store or host columns uploaded
+struct FitSource {
+    bool set = false, f32 = false, index64 = true;
+    const nxc_rows *store = nullptr;
+    int64_t n = 0, shift = 0, stride = 0;    // rows, index shift, distance between columns
+    const void *col0 = nullptr;              // column 0 of row 0 (stores: all nine columns)
+    const void *cols[5] = {};                // x, y, z, vy, frac
+    const void *index = nullptr;
+};
+
 struct nxc_handle {
     int device = 0;
     int n_cu = 0;
@@ -423,6 +441,22 @@ struct nxc_handle {
     size_t dens_cell_cap = 0;
     double *d_dens_acc = nullptr;    // interleaved pair [Q][2], as the image's
     size_t dens_acc_cap = 0;
+
+    // LOSResultFitted: the pair list the line-of-sight passes fill (nxc_los_set_pairs); the fit's
+    // per-spectrum data, its sample source and per-packet sums (nxc_fit_*)
+    nxc_pairs *los_pairs = nullptr;
+    bool have_fit = false;
+    int64_t fit_S = 0, fit_np = -1;  // fit_np: packets whose multipliers are ready (nxc_fit_packets)
+    int fit_mode = 0;
+    FitSource fit_src;
+    double *d_fit_spec = nullptr;    // position [3][S] | ratio | weight | radiance sums | mask bytes
+    size_t fit_spec_cap = 0;
+    unsigned char *d_fit_pk = nullptr;   // num | den | mult (f64) | cnt | lengths (u32) per packet
+    size_t fit_pk_cap = 0;
+    unsigned char *d_fit_smp = nullptr;  // host columns of the fit on the device
+    size_t fit_smp_cap = 0;
+    unsigned char *d_fit_aux = nullptr;  // blob | counters | tile counts and offsets
+    size_t fit_aux_cap = 0;
 };
 
 static int order_on_device(nxc_handle *h, double k2max, const long long *d_lifetimes,
@@ -1061,17 +1095,12 @@ int rows_fetch(nxc_handle *h, void *rows_out, bool narrow)
     return NXC_OK;
 }
 
-// f-1 over stored samples that are already on the device (64-bit, or 32-bit as save() keeps them)
-template <typename T, typename I>
-int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, int64_t P,
-            const T *dx, const T *dy, const T *dz, const T *dvy, const T *dfrac, const I *d_index,
-            int64_t index_shift, int64_t n_index, double *radiance, int64_t *npackets, uint8_t *included,
-            int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
+// The pass constants and the LDS blob [header space | g-value tables] of a line-of-sight
+// descriptor (los_run, fit_radiance)
+int los_tables(nxc_handle *h, const nxc_los_desc *d, LosK &K, std::vector<unsigned char> &blob)
 {
-    // LDS block: [header space | g-value tables | spectra tile]
-    std::vector<unsigned char> blob((size_t)NXC_HEADER_BYTES, 0);
+    blob.assign((size_t)NXC_HEADER_BYTES, 0);
     std::memcpy(blob.data(), &h->header, sizeof(LdsHeader));      // nxc_log's table lives there
-    LosK K{};
     K.sin_dphi = d->sin_dphi;
     K.sin_2dphi = d->sin_2dphi;
     K.cos_thr = d->cos_threshold;
@@ -1082,16 +1111,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
     K.log1p_s_inv = 1.0 / std::log1p(d->sin_dphi);
     K.n_lines = d->n_lines;
     K.n_ladder = (int)d->n_ladder;
-    K.index_shift = index_shift;
     K.tan_dphi = std::tan(d->dphi);
-    // block culling measures distances along the boresights: they must be unit vectors (the
-    // reference's are); anything else switches the culling off, never the exact pair test
-    K.cull = (d->dphi > 0 && d->dphi < 1.5 && std::isfinite(K.tan_dphi)) ? 1 : 0;
-    for (int64_t i = 0; i < S && K.cull; i++) {
-        const double b2 = sc[3 * S + i] * sc[3 * S + i] + sc[4 * S + i] * sc[4 * S + i] +
-                          sc[5 * S + i] * sc[5 * S + i];
-        if (!(std::fabs(b2 - 1.0) <= 1e-9)) K.cull = 0;
-    }
     for (int l = 0; l < d->n_lines; l++) {
         // a run's Outputs share their g-value tables (one aplanet): the packed form of the last
         // call's tables is kept (packing places every cell by bisection: 0.5 ms a table, which for
@@ -1111,6 +1131,30 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
         }
         K.line[l] = placed_lut(c.lut.desc, blob.size());
         blob.insert(blob.end(), c.lut.bytes.begin(), c.lut.bytes.end());
+    }
+    return NXC_OK;
+}
+
+// f-1 over stored samples that are already on the device (64-bit, or 32-bit as save() keeps them)
+template <typename T, typename I>
+int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, int64_t P,
+            const T *dx, const T *dy, const T *dz, const T *dvy, const T *dfrac, const I *d_index,
+            int64_t index_shift, int64_t n_index, double *radiance, int64_t *npackets, uint8_t *included,
+            int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
+{
+    // LDS block: [header space | g-value tables | spectra tile]
+    std::vector<unsigned char> blob;
+    LosK K{};
+    int rc = los_tables(h, d, K, blob);
+    if (rc) return rc;
+    K.index_shift = index_shift;
+    // block culling measures distances along the boresights: they must be unit vectors (the
+    // reference's are); anything else switches the culling off, never the exact pair test
+    K.cull = (d->dphi > 0 && d->dphi < 1.5 && std::isfinite(K.tan_dphi)) ? 1 : 0;
+    for (int64_t i = 0; i < S && K.cull; i++) {
+        const double b2 = sc[3 * S + i] * sc[3 * S + i] + sc[4 * S + i] * sc[4 * S + i] +
+                          sc[5 * S + i] * sc[5 * S + i];
+        if (!(std::fabs(b2 - 1.0) <= 1e-9)) K.cull = 0;
     }
     const size_t stage_bytes = blob.size();
     K.tile_off = (int64_t)((stage_bytes + 31) & ~size_t(31));
@@ -1132,9 +1176,14 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
                  o_rad = take((size_t)S * 8), o_np = take((size_t)S * 8),
                  o_inc = take(included ? (size_t)n_index : 0),
                  o_used = take(used_pairs ? (size_t)used_cap * 16 : 0), o_nu = take(8);
-    int rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, off);
-    if (rc) return rc;
+    if ((rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, off))) return rc;
     unsigned char *base = reinterpret_cast<unsigned char *>(h->d_scratch);
+    // the used pairs go to the host copy (used_pairs) or stay on the device (nxc_los_set_pairs)
+    nxc_pairs *const sink = used_pairs ? nullptr : h->los_pairs;
+    long long *const d_used = used_pairs ? reinterpret_cast<long long *>(base + o_used)
+                                         : sink ? sink->d : nullptr;
+    const long long cap_used = used_pairs ? (long long)used_cap : sink ? sink->cap : 0;
+    if (sink) sink->n = 0;
     hipStream_t st = h->stream;
     HIPCHK(hipMemcpyAsync(base + o_blob, blob.data(), stage_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(base + o_sc, sc, (size_t)8 * S * 8, hipMemcpyHostToDevice, st));
@@ -1200,8 +1249,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
                                reinterpret_cast<const double *>(base + o_lad),
                                reinterpret_cast<double *>(base + o_rad),
                                reinterpret_cast<unsigned long long *>(base + o_np),
-                               included ? base + o_inc : nullptr, (long long)used_cap,
-                               used_pairs ? reinterpret_cast<long long *>(base + o_used) : nullptr,
+                               included ? base + o_inc : nullptr, cap_used, d_used,
                                reinterpret_cast<unsigned long long *>(base + o_nu), h->d_ctr);
             HIPCHK(hipGetLastError());
             hipLaunchKernelGGL((k_los_pairs<T, I>), dim3((unsigned)(h->n_cu * 2)), dim3(NXC_BLOCK),
@@ -1212,8 +1260,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
                                reinterpret_cast<const double *>(base + o_lad),
                                reinterpret_cast<double *>(base + o_rad),
                                reinterpret_cast<unsigned long long *>(base + o_np),
-                               included ? base + o_inc : nullptr, (long long)used_cap,
-                               used_pairs ? reinterpret_cast<long long *>(base + o_used) : nullptr,
+                               included ? base + o_inc : nullptr, cap_used, d_used,
                                reinterpret_cast<unsigned long long *>(base + o_nu), h->d_ctr);
             HIPCHK(hipGetLastError());
         }
@@ -1226,6 +1273,12 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
     HIPCHK(hipMemcpyAsync(&nu, base + o_nu, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (n_used) *n_used = (int64_t)nu;
+    if (sink) {
+        sink->n = (long long)std::min<unsigned long long>(nu, (unsigned long long)sink->cap);
+        if (nu > (unsigned long long)sink->cap)
+            return fail(NXC_ERR_OVERFLOW, "the pair list holds " + std::to_string(sink->cap) + " pairs, the pass found " +
+                                              std::to_string(nu));
+    }
     if (used_pairs) {
         const size_t got = (size_t)std::min<unsigned long long>(nu, (unsigned long long)used_cap);
         HIPCHK(hipMemcpy(used_pairs, base + o_used, got * 8, hipMemcpyDeviceToHost));
@@ -1245,6 +1298,7 @@ int los_check(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
         return fail(NXC_ERR_ARG, "bad nxc_los_desc");
     if (included && n_index < 1) return fail(NXC_ERR_ARG, "included needs n_index");
     if (used_pairs && (used_cap < 1 || !n_used)) return fail(NXC_ERR_ARG, "used_pairs needs a capacity");
+    if (used_pairs && h->los_pairs) return fail(NXC_ERR_ARG, "used_pairs with a device pair list set");
     HIPCHK(hipSetDevice(h->device));
     return NXC_OK;
 }
@@ -1474,6 +1528,196 @@ int density_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T
     return density_run<T>(h, p, d, d + p, d + 2 * p, d + 3 * p);
 }
 
+
+// ---- LOSResultFitted -------------------------------------------------------------------------
+// Calls f(T*, I*) with null pointers of the fit source's sample and index types.
+template <typename Fn>
+int fit_types(const FitSource &s, Fn &&f)
+{
+    if (s.f32 && !s.index64) return f((const float *)nullptr, (const int *)nullptr);
+    if (s.f32) return f((const float *)nullptr, (const long long *)nullptr);
+    return f((const double *)nullptr, (const long long *)nullptr);
+}
+
+int fit_check(nxc_handle *h, const nxc_pairs *p)
+{
+    if (!h || !h->have_fit) return fail(NXC_ERR_STATE, "nxc_fit_set has not been called");
+    if (!h->fit_src.set) return fail(NXC_ERR_STATE, "no fit source: call nxc_fit_source*");
+    if (!p || p->device != h->device || p->n < 0 || p->n > p->cap)
+        return fail(NXC_ERR_ARG, "bad pair list");
+    HIPCHK(hipSetDevice(h->device));
+    return NXC_OK;
+}
+
+FitK fit_consts(const nxc_handle *h, const nxc_pairs *p, int64_t n_packets)
+{
+    FitK F{};
+    F.S = h->fit_S;
+    F.n_pairs = p ? p->n : 0;
+    F.cap = p ? p->cap : 0;
+    F.n_rows = h->fit_src.n;
+    F.n_packets = n_packets;
+    F.index_shift = h->fit_src.shift;
+    F.mode = h->fit_mode;
+    return F;
+}
+
+// device scratch of the fit's small buffers: [blob | 4 counters | tile counts | tile offsets]
+int fit_aux(nxc_handle *h, size_t blob_bytes, int64_t tiles, unsigned char **blob,
+            unsigned long long **ctr, unsigned **tile_n, long long **tile_off)
+{
+    const size_t o_ctr = (blob_bytes + 255) & ~size_t(255), o_n = o_ctr + 256,
+                 o_off = o_n + (((size_t)tiles * 4 + 255) & ~size_t(255));
+    int rc = ensure(reinterpret_cast<void **>(&h->d_fit_aux), &h->fit_aux_cap, o_off + (size_t)tiles * 8 + 8);
+    if (rc) return rc;
+    *blob = h->d_fit_aux;
+    *ctr = reinterpret_cast<unsigned long long *>(h->d_fit_aux + o_ctr);
+    if (tile_n) *tile_n = reinterpret_cast<unsigned *>(h->d_fit_aux + o_n);
+    if (tile_off) *tile_off = reinterpret_cast<long long *>(h->d_fit_aux + o_off);
+    return NXC_OK;
+}
+
+double *fit_pos(nxc_handle *h) { return h->d_fit_spec; }
+double *fit_ratio(nxc_handle *h) { return h->d_fit_spec + 3 * h->fit_S; }
+double *fit_weight(nxc_handle *h) { return h->d_fit_spec + 4 * h->fit_S; }
+double *fit_rad(nxc_handle *h) { return h->d_fit_spec + 5 * h->fit_S; }
+unsigned char *fit_mask(nxc_handle *h) { return reinterpret_cast<unsigned char *>(h->d_fit_spec + 6 * h->fit_S); }
+
+// per-packet arrays of n packets: num | den | mult (f64) | cnt | lengths (u32)
+double *fit_num(nxc_handle *h, int64_t n) { return reinterpret_cast<double *>(h->d_fit_pk); }
+double *fit_den(nxc_handle *h, int64_t n) { return fit_num(h, n) + n; }
+double *fit_mult(nxc_handle *h, int64_t n) { return fit_num(h, n) + 2 * n; }
+unsigned *fit_cnt(nxc_handle *h, int64_t n) { return reinterpret_cast<unsigned *>(fit_num(h, n) + 3 * n); }
+unsigned *fit_len(nxc_handle *h, int64_t n) { return fit_cnt(h, n) + n; }
+
+int64_t fit_grid(const nxc_handle *h, int64_t work, int per_cu)
+{
+    return std::max<int64_t>(1, std::min<int64_t>((int64_t)h->n_cu * per_cu, (work + NXC_BLOCK - 1) / NXC_BLOCK));
+}
+
+template <typename T>
+int fit_source_columns(nxc_handle *h, int64_t P, const T *x, const T *y, const T *z, const T *vy,
+                       const T *frac, const int64_t *index)
+{
+    if (!h || !h->have_fit) return fail(NXC_ERR_STATE, "nxc_fit_set has not been called");
+    if (P < 0 || (P && (!x || !y || !z || !vy || !frac || !index))) return fail(NXC_ERR_ARG, "bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    h->fit_src = FitSource{};
+    h->fit_np = -1;
+    const size_t col = ((size_t)P * sizeof(T) + 255) & ~size_t(255);
+    int rc = ensure(reinterpret_cast<void **>(&h->d_fit_smp), &h->fit_smp_cap, 5 * col + (size_t)P * 8 + 8);
+    if (rc) return rc;
+    const T *src[5] = {x, y, z, vy, frac};
+    for (int c = 0; c < 5; c++) {
+        if (P) HIPCHK(hipMemcpyAsync(h->d_fit_smp + c * col, src[c], (size_t)P * sizeof(T),
+                                     hipMemcpyHostToDevice, h->stream));
+        h->fit_src.cols[c] = h->d_fit_smp + c * col;
+    }
+    if (P) HIPCHK(hipMemcpyAsync(h->d_fit_smp + 5 * col, index, (size_t)P * 8, hipMemcpyHostToDevice, h->stream));
+    h->fit_src.index = h->d_fit_smp + 5 * col;
+    h->fit_src.f32 = sizeof(T) == 4;
+    h->fit_src.index64 = true;
+    h->fit_src.n = P;
+    h->fit_src.set = true;
+    return NXC_OK;
+}
+
+template <typename T, typename I>
+int fit_packets_run(nxc_handle *h, const nxc_pairs *p, int64_t n_packets, unsigned long long *ctr)
+{
+    const FitSource &s = h->fit_src;
+    const FitK F = fit_consts(h, p, n_packets);
+    if (F.n_pairs > 0) {
+        hipLaunchKernelGGL((k_fit_packets<T, I>), dim3((unsigned)fit_grid(h, F.n_pairs, 8)), dim3(NXC_BLOCK), 0,
+                           h->stream, F, p->d, fit_pos(h), fit_ratio(h), fit_weight(h), fit_mask(h),
+                           static_cast<const T *>(s.cols[0]), static_cast<const T *>(s.cols[1]),
+                           static_cast<const T *>(s.cols[2]), static_cast<const I *>(s.index),
+                           fit_num(h, n_packets), fit_den(h, n_packets), fit_cnt(h, n_packets), ctr);
+        HIPCHK(hipGetLastError());
+    }
+    return NXC_OK;
+}
+
+template <typename T, typename I>
+int fit_radiance_run(nxc_handle *h, const nxc_pairs *p, const LosK &K, size_t stage_bytes,
+                     const unsigned char *d_blob, unsigned long long *ctr)
+{
+    const FitSource &s = h->fit_src;
+    const FitK F = fit_consts(h, p, h->fit_np);
+    if (F.n_pairs == 0) return NXC_OK;
+    size_t lds = (stage_bytes + 31) & ~size_t(31);
+    // the per-spectrum sums of a workgroup in LDS while they leave room for two workgroups per CU
+    const int lds_sums = lds + (size_t)F.S * 8 <= 64 * 1024 ? 1 : 0;
+    if (lds_sums) lds += (size_t)F.S * 8;
+    int rc;
+    if ((rc = prep_kernel(k_fit_radiance<T, I>, lds))) return rc;
+    hipLaunchKernelGGL((k_fit_radiance<T, I>), dim3((unsigned)fit_grid(h, F.n_pairs, 2)), dim3(NXC_BLOCK), lds,
+                       h->stream, K, d_blob, (int64_t)stage_bytes, F, lds_sums, p->d, fit_pos(h),
+                       fit_mult(h, h->fit_np), static_cast<const T *>(s.cols[0]),
+                       static_cast<const T *>(s.cols[1]), static_cast<const T *>(s.cols[2]),
+                       static_cast<const T *>(s.cols[3]), static_cast<const T *>(s.cols[4]),
+                       static_cast<const I *>(s.index), fit_rad(h), ctr, ctr + 1);
+    HIPCHK(hipGetLastError());
+    return NXC_OK;
+}
+
+template <typename T, typename I>
+int fit_rows_run(nxc_handle *h, int compress, nxc_rows **out, int64_t *lengths_out)
+{
+    const FitSource &s = h->fit_src;
+    const int64_t n = s.n, np = h->fit_np, tiles = (n + NXC_BLOCK - 1) / NXC_BLOCK;
+    FitK F = fit_consts(h, nullptr, np);
+    F.compress = compress ? 1 : 0;
+    unsigned char *blob;
+    unsigned long long *ctr;
+    unsigned *tile_n;
+    long long *tile_off;
+    int rc = fit_aux(h, 0, tiles, &blob, &ctr, &tile_n, &tile_off);
+    if (rc) return rc;
+    const T *frac = static_cast<const T *>(s.col0) + 7 * s.stride;
+    const I *index = static_cast<const I *>(s.index);
+    if (np) HIPCHK(hipMemsetAsync(fit_len(h, np), 0, (size_t)np * 4, h->stream));
+    std::vector<unsigned> kept((size_t)tiles);
+    std::vector<long long> offs((size_t)tiles);
+    long long total = 0;
+    if (tiles) {
+        hipLaunchKernelGGL((k_fit_rows_count<T, I>), dim3((unsigned)tiles), dim3(NXC_BLOCK), 0, h->stream, F,
+                           frac, index, fit_mult(h, np), tile_n, fit_len(h, np));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(kept.data(), tile_n, (size_t)tiles * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(stream_sync(h));
+        for (int64_t t = 0; t < tiles; t++) { offs[t] = total; total += kept[t]; }
+    }
+    nxc_rows *r = new (std::nothrow) nxc_rows();
+    if (!r) return fail(NXC_ERR_ARG, "out of host memory");
+    r->device = h->device; r->f32 = sizeof(T) == 4; r->total = total;
+    hipError_t e = hipSuccess;
+    if (total > 0) {
+        e = pool_take(h, (size_t)total * 9 * sizeof(T), &r->d_cols, &r->cols_cap);
+        if (e == hipSuccess) e = pool_take(h, (size_t)total * sizeof(I), &r->d_index, &r->index_cap);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(tile_off, offs.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL((k_fit_rows_write<T, I>), dim3((unsigned)tiles), dim3(NXC_BLOCK), 0, h->stream, F,
+                               static_cast<const T *>(s.col0), s.stride, index, fit_mult(h, np), tile_off,
+                               static_cast<T *>(r->d_cols), (int64_t)total, static_cast<I *>(r->d_index));
+            e = hipGetLastError();
+        }
+    }
+    std::vector<unsigned> len((size_t)np);
+    if (e == hipSuccess && np)
+        e = hipMemcpyAsync(len.data(), fit_len(h, np), (size_t)np * 4, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = stream_sync(h);
+    if (e != hipSuccess) {
+        nxc_rows_free(h, r);
+        return fail_hip("fitted rows", e);
+    }
+    if (lengths_out)
+        for (int64_t i = 0; i < np; i++) lengths_out[i] = len[i];
+    *out = r;
+    return NXC_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1553,7 +1797,7 @@ int nxc_destroy(nxc_handle *h)
                     h->d_steps, h->d_reduce, h->d_order, h->d_bounce, h->d_moonpos, h->d_offsets,
                     h->d_source, h->d_queue, h->d_samples, h->d_tiles, h->d_hist, h->d_rec, h->d_piece_hist,
                     h->d_blob_img, h->d_reduce_n, h->d_losblk, h->d_dens_pts, h->d_dens_cell,
-                    h->d_dens_acc};
+                    h->d_dens_acc, h->d_fit_spec, h->d_fit_pk, h->d_fit_smp, h->d_fit_aux};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     pool_flush(h);
@@ -2670,6 +2914,241 @@ int nxc_density_download(nxc_handle *h, double *sum_frac, double *count)
         sum_frac[j] = pair[2 * j];
         count[j] = pair[2 * j + 1];
     }
+    return NXC_OK;
+    });
+}
+
+int nxc_pairs_create(nxc_handle *h, int64_t capacity, nxc_pairs **out)
+{
+    return guarded([&]() -> int {
+    if (!h || !out) return fail(NXC_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (capacity < 1) return fail(NXC_ERR_ARG, "a pair list needs a capacity >= 1");
+    HIPCHK(hipSetDevice(h->device));
+    nxc_pairs *p = new (std::nothrow) nxc_pairs();
+    if (!p) return fail(NXC_ERR_ARG, "out of host memory");
+    p->device = h->device;
+    p->cap = capacity;
+    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->d), (size_t)capacity * 16);
+    if (e != hipSuccess) {
+        delete p;
+        return fail(NXC_ERR_NOMEM, "pair list of " + std::to_string(capacity) + " pairs");
+    }
+    *out = p;
+    return NXC_OK;
+    });
+}
+
+int nxc_pairs_free(nxc_handle *h, nxc_pairs *p)
+{
+    if (!p) return NXC_OK;
+    (void)hipSetDevice(p->device);
+    if (h && h->stream) (void)stream_sync(h);
+    if (h && h->los_pairs == p) h->los_pairs = nullptr;
+    if (p->d) (void)hipFree(p->d);
+    delete p;
+    return NXC_OK;
+}
+
+int nxc_pairs_count(const nxc_pairs *p, int64_t *n)
+{
+    if (!p || !n) return fail(NXC_ERR_ARG, "null argument");
+    *n = p->n;
+    return NXC_OK;
+}
+
+int nxc_pairs_download(nxc_handle *h, const nxc_pairs *p, int64_t *spectrum, int64_t *row)
+{
+    return guarded([&]() -> int {
+    if (!h || !p) return fail(NXC_ERR_ARG, "null argument");
+    if (p->device != h->device) return fail(NXC_ERR_ARG, "the pair list lives on another device");
+    if (p->n == 0) return NXC_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, p->d, (size_t)p->n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (row) HIPCHK(hipMemcpyAsync(row, p->d + p->cap, (size_t)p->n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+    });
+}
+
+int nxc_los_set_pairs(nxc_handle *h, nxc_pairs *p)
+{
+    if (!h) return fail(NXC_ERR_ARG, "null handle");
+    if (p && p->device != h->device) return fail(NXC_ERR_ARG, "the pair list lives on another device");
+    h->los_pairs = p;
+    return NXC_OK;
+}
+
+int nxc_fit_set(nxc_handle *h, const nxc_fit_desc *d)
+{
+    return guarded([&]() -> int {
+    if (!h || !d) return fail(NXC_ERR_ARG, "null argument");
+    const int64_t S = d->n_spectra;
+    if (S < 1 || d->weight_mode < 0 || d->weight_mode > 3 || !d->position || !d->ratio || !d->mask ||
+        (d->weight_mode == 3 && !d->weight))
+        return fail(NXC_ERR_ARG, "bad nxc_fit_desc");
+    HIPCHK(hipSetDevice(h->device));
+    h->have_fit = false;
+    h->fit_src = FitSource{};
+    h->fit_np = -1;
+    int rc = ensure(reinterpret_cast<void **>(&h->d_fit_spec), &h->fit_spec_cap, (size_t)S * 6 * 8 + (size_t)S);
+    if (rc) return rc;
+    h->fit_S = S;
+    std::vector<double> w((size_t)S, 1.0);
+    if (d->weight_mode == 3) w.assign(d->weight, d->weight + S);
+    HIPCHK(hipMemcpyAsync(fit_pos(h), d->position, (size_t)S * 24, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(fit_ratio(h), d->ratio, (size_t)S * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(fit_weight(h), w.data(), (size_t)S * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(fit_rad(h), 0, (size_t)S * 8, h->stream));
+    HIPCHK(hipMemcpyAsync(fit_mask(h), d->mask, (size_t)S, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(stream_sync(h));
+    h->fit_mode = d->weight_mode;
+    h->have_fit = true;
+    return NXC_OK;
+    });
+}
+
+int nxc_fit_source_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count, int64_t index_shift)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_fit) return fail(NXC_ERR_STATE, "nxc_fit_set has not been called");
+    int rc = rows_check(h, r, first, count);
+    if (rc) return rc;
+    h->fit_src = FitSource{};
+    h->fit_np = -1;
+    FitSource &s = h->fit_src;
+    const long long t = r->total;
+    const size_t vsz = r->f32 ? 4 : 8;
+    const char *c = static_cast<const char *>(r->d_cols) + (size_t)first * vsz;
+    const int which[5] = {1, 2, 3, 5, 7};           // x, y, z, vy, frac
+    for (int k = 0; k < 5; k++) s.cols[k] = c + (size_t)which[k] * t * vsz;
+    s.col0 = c;
+    s.stride = t;
+    s.index = static_cast<const char *>(r->d_index) + (size_t)first * vsz;
+    s.f32 = r->f32;
+    s.index64 = !r->f32;
+    s.store = r;
+    s.n = count;
+    s.shift = index_shift;
+    s.set = true;
+    return NXC_OK;
+    });
+}
+
+int nxc_fit_source(nxc_handle *h, int64_t P, const double *x, const double *y, const double *z,
+                   const double *vy, const double *frac, const int64_t *index)
+{
+    return guarded([&]() -> int { return fit_source_columns(h, P, x, y, z, vy, frac, index); });
+}
+
+int nxc_fit_source_f32(nxc_handle *h, int64_t P, const float *x, const float *y, const float *z,
+                       const float *vy, const float *frac, const int64_t *index)
+{
+    return guarded([&]() -> int { return fit_source_columns(h, P, x, y, z, vy, frac, index); });
+}
+
+int nxc_fit_packets(nxc_handle *h, const nxc_pairs *p, int64_t n_packets, double *num, double *den,
+                    int32_t *cnt, double *mult, double *stats)
+{
+    return guarded([&]() -> int {
+    int rc = fit_check(h, p);
+    if (rc) return rc;
+    if (n_packets < 0 || n_packets > INT32_MAX) return fail(NXC_ERR_ARG, "bad packet count");
+    h->fit_np = -1;
+    if ((rc = ensure(reinterpret_cast<void **>(&h->d_fit_pk), &h->fit_pk_cap, (size_t)n_packets * 32 + 16)))
+        return rc;
+    unsigned char *blob;
+    unsigned long long *ctr;
+    if ((rc = fit_aux(h, 16, 0, &blob, &ctr, nullptr, nullptr))) return rc;
+    double *d_stats = reinterpret_cast<double *>(blob);
+    HIPCHK(hipMemsetAsync(h->d_fit_pk, 0, (size_t)n_packets * 28, h->stream));   // num, den, mult, cnt
+    HIPCHK(hipMemsetAsync(blob, 0, 256 + 64, h->stream));                         // stats, counters
+    if ((rc = begin_timed(h))) return rc;
+    rc = fit_types(h->fit_src, [&](auto t, auto i) {
+        return fit_packets_run<std::remove_const_t<std::remove_pointer_t<decltype(t)>>,
+                               std::remove_const_t<std::remove_pointer_t<decltype(i)>>>(h, p, n_packets, ctr);
+    });
+    if (rc) return rc;
+    if (n_packets) {
+        hipLaunchKernelGGL(k_fit_norm, dim3(1), dim3(NXC_FIT_NORM_THREADS), 0, h->stream, n_packets,
+                           fit_num(h, n_packets), fit_den(h, n_packets), fit_mult(h, n_packets), d_stats);
+        HIPCHK(hipGetLastError());
+    }
+    if ((rc = end_timed(h))) return rc;
+    unsigned long long bad = 0;
+    double st[2] = {0.0, 0.0};
+    HIPCHK(hipMemcpyAsync(&bad, ctr, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(st, d_stats, 16, hipMemcpyDeviceToHost, h->stream));
+    const size_t n8 = (size_t)n_packets * 8;
+    if (num && n_packets) HIPCHK(hipMemcpyAsync(num, fit_num(h, n_packets), n8, hipMemcpyDeviceToHost, h->stream));
+    if (den && n_packets) HIPCHK(hipMemcpyAsync(den, fit_den(h, n_packets), n8, hipMemcpyDeviceToHost, h->stream));
+    if (mult && n_packets) HIPCHK(hipMemcpyAsync(mult, fit_mult(h, n_packets), n8, hipMemcpyDeviceToHost, h->stream));
+    if (cnt && n_packets)
+        HIPCHK(hipMemcpyAsync(cnt, fit_cnt(h, n_packets), (size_t)n_packets * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    if (stats) { stats[0] = st[0]; stats[1] = st[1]; }
+    if (bad) return fail(NXC_ERR_ARG, std::to_string(bad) + " pairs name a spectrum, row or packet outside the fit");
+    h->fit_np = n_packets;
+    return NXC_OK;
+    });
+}
+
+int nxc_fit_radiance(nxc_handle *h, const nxc_pairs *p, const nxc_los_desc *d)
+{
+    return guarded([&]() -> int {
+    int rc = fit_check(h, p);
+    if (rc) return rc;
+    if (h->fit_np < 0) return fail(NXC_ERR_STATE, "nxc_fit_radiance needs a preceding nxc_fit_packets");
+    if (!d || d->n_lines < 0 || d->n_lines > NXC_MAX_LINES || d->n_ladder < 1 || !d->ladder)
+        return fail(NXC_ERR_ARG, "bad nxc_los_desc");
+    std::vector<unsigned char> blob;
+    LosK K{};
+    if ((rc = los_tables(h, d, K, blob))) return rc;
+    if (((blob.size() + 31) & ~size_t(31)) > 160 * 1024) return fail(NXC_ERR_ARG, "g-value tables exceed the LDS");
+    unsigned char *d_blob;
+    unsigned long long *ctr;
+    if ((rc = fit_aux(h, blob.size(), 0, &d_blob, &ctr, nullptr, nullptr))) return rc;
+    HIPCHK(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(ctr, 0, 16, h->stream));
+    if ((rc = begin_timed(h))) return rc;
+    rc = fit_types(h->fit_src, [&](auto t, auto i) {
+        return fit_radiance_run<std::remove_const_t<std::remove_pointer_t<decltype(t)>>,
+                                std::remove_const_t<std::remove_pointer_t<decltype(i)>>>(h, p, K, blob.size(),
+                                                                                          d_blob, ctr);
+    });
+    if (rc) return rc;
+    if ((rc = end_timed(h))) return rc;
+    unsigned long long c[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(c, ctr, 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    if (c[0]) return fail(NXC_ERR_ARG, std::to_string(c[0]) + " pairs name a spectrum, row or packet outside the fit");
+    if (c[1]) return fail(NXC_ERR_ARG, std::to_string(c[1]) + " fitted pair weights are not finite");
+    return NXC_OK;
+    });
+}
+
+int nxc_fit_rows(nxc_handle *h, int compress, nxc_rows **out, int64_t *lengths_out)
+{
+    return guarded([&]() -> int {
+    if (!out) return fail(NXC_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (!h || !h->have_fit) return fail(NXC_ERR_STATE, "nxc_fit_set has not been called");
+    if (!h->fit_src.set || !h->fit_src.store) return fail(NXC_ERR_STATE, "nxc_fit_rows needs a row-store source");
+    if (h->fit_np < 0) return fail(NXC_ERR_STATE, "nxc_fit_rows needs a preceding nxc_fit_packets");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->fit_src.f32) return fit_rows_run<float, int>(h, compress, out, lengths_out);
+    return fit_rows_run<double, long long>(h, compress, out, lengths_out);
+    });
+}
+
+int nxc_fit_download(nxc_handle *h, double *radiance)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_fit) return fail(NXC_ERR_STATE, "nxc_fit_set has not been called");
+    if (!radiance) return fail(NXC_ERR_ARG, "radiance is null");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(radiance, fit_rad(h), (size_t)h->fit_S * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
     return NXC_OK;
     });
 }

@@ -1403,6 +1403,24 @@ NXC_DEV bool los_pair_maybe(const LosK &K, const double *__restrict__ sp, double
     return q * q >= K.cos_thr2_lo * d2;
 }
 
+// weight / Apix of a sample at distance `dist` from the spacecraft: the weight of
+// ModelResult.py:150-161 (out_of_shadow = 1) over the pixel area of compute_iteration.py:194-196.
+// Shared by los_pair and k_fit_radiance (LOSResultFitted.py:191-210), which must agree to the bit.
+NXC_DEV double los_wtemp(const LosK &K, double vy_p, double frac_p, double dist, double rs_1e6,
+                         unsigned long long &my_nonfinite)
+{
+    const double radvel = vy_p + K.vrplanet;
+    double gg = K.n_lines > 0 ? lut_interp(lut_view(K.line[0]), radvel) : 0.0;
+#pragma unroll
+    for (int l = 1; l < 4; l++)
+        if (l < K.n_lines) gg += lut_interp(lut_view(K.line[l]), radvel);
+    const double weight = nxc_div_const(frac_p * gg, 1e6, rs_1e6);   // 1e6 is mid-range
+    if (!(__builtin_fabs(weight) <= 1.7976931348623157e308) || radvel != radvel) my_nonfinite++;
+    const double ds = dist * K.sin_dphi;
+    const double apix = (3.141592653589793 * (ds * ds)) * K.unit_cm2;         // :194-195
+    return nxc_div(weight, apix);
+}
+
 // One (stored sample, spectrum) pair, exactly as the reference decides and weighs it
 // (compute_iteration.py:177-213).  sp: the spectrum's eight tile values.
 // (vy_p, frac_p, idx_p: the sample's radial velocity, fraction and slot in `included`, loaded by the
@@ -1442,18 +1460,9 @@ NXC_DEV void los_pair(const LosK &K, const double *__restrict__ sp, int64_t spec
         cand = cand || (((ex * ex + ey * ey) + ez * ez) <= r * r);
     }
     if (!cand) return;
-    // the weight of the sample (ModelResult.py:150-161, out_of_shadow = 1); pairs that get here
-    // are one in 1e4 of those tested, so it is formed per pair rather than kept per sample
-    const double radvel = vy_p + K.vrplanet;
-    double gg = K.n_lines > 0 ? lut_interp(lut_view(K.line[0]), radvel) : 0.0;
-#pragma unroll
-    for (int l = 1; l < 4; l++)
-        if (l < K.n_lines) gg += lut_interp(lut_view(K.line[l]), radvel);
-    const double weight = nxc_div_const(frac_p * gg, 1e6, rs_1e6);   // 1e6 is mid-range
-    if (!(__builtin_fabs(weight) <= 1.7976931348623157e308) || radvel != radvel) my_nonfinite++;
-    const double ds = dist * K.sin_dphi;
-    const double apix = (3.141592653589793 * (ds * ds)) * K.unit_cm2;         // :194-195
-    double wtemp = nxc_div(weight, apix);
+    // pairs that get here are one in 1e4 of those tested, so the weight is formed per pair
+    // rather than kept per sample
+    double wtemp = los_wtemp(K, vy_p, frac_p, dist, rs_1e6, my_nonfinite);
     const double hx = xs + bx * q, hy = ys + by * q, hz = zs + bz * q;          // :202-206
     const bool lit = ((hx * hx + hz * hz) > 0x1.0000000000001p+0) || (hy < 0.0);
     wtemp = lit ? wtemp : wtemp * 0.0;
@@ -2585,4 +2594,193 @@ k_density(DensityK K, int64_t n, const T *__restrict__ x, const T *__restrict__ 
             image_add_pairs(hit, q, w, acc2);
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// LOSResultFitted (data_simulation/LOSResultFitted.py:118-214): refit the packets of one Output to
+// observed radiances over the (spectrum, row) pairs its unfitted line-of-sight pass found with
+// weight > 0 (an nxc_pairs list, [2][cap] int64: spectrum, row of the launch's row range).
+//   k_fit_packets   per packet: num += ratio_j w, den += w, cnt += 1 over pairs with mask_j
+//   k_fit_norm      one workgroup: the mean of f = num / den over the packets with den > 0 in a
+//                   fixed order (bit-identical from call to call), then mult = f / mean
+//   k_fit_radiance  per spectrum: sum over its pairs of los_wtemp with frac' = frac mult[packet]
+//   k_fit_rows_*    frac' of every row, save()'s frac' > 0 filter as a stable compaction
+struct FitK {
+    int64_t S, n_pairs, cap, n_rows, n_packets, index_shift;
+    int mode;                      // 0: w = 1, 1: 1/d, 2: 1/d^2, 3: per spectrum (2/sigma)
+    int compress;
+};
+
+constexpr int NXC_FIT_NORM_THREADS = 1024;
+
+// packet of row r, or -1 (counted as bad) when the row or its index is outside the Output
+template <typename I>
+NXC_DEV int64_t fit_packet_of(const FitK &F, const I *__restrict__ index, int64_t r)
+{
+    if (r < 0 || r >= F.n_rows) return -1;
+    const int64_t pk = (int64_t)index[r] - F.index_shift;
+    return (pk >= 0 && pk < F.n_packets) ? pk : -1;
+}
+
+template <typename T, typename I>
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_fit_packets(FitK F, const long long *__restrict__ pairs, const double *__restrict__ pos,
+              const double *__restrict__ ratio, const double *__restrict__ wspec,
+              const unsigned char *__restrict__ mask, const T *__restrict__ x, const T *__restrict__ y,
+              const T *__restrict__ z, const I *__restrict__ index, double *__restrict__ num,
+              double *__restrict__ den, unsigned *__restrict__ cnt, unsigned long long *__restrict__ bad)
+{
+    unsigned long long my_bad = 0;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < F.n_pairs;
+         k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = pairs[k], r = pairs[F.cap + k];
+        if (j < 0 || j >= F.S) { my_bad++; continue; }
+        if (!mask[j]) continue;
+        const int64_t pk = fit_packet_of(F, index, r);
+        if (pk < 0) { my_bad++; continue; }
+        double w = 1.0;
+        if (F.mode == 1 || F.mode == 2) {
+            // sc_dist as the pair test forms `dist` (LOSResultFitted.py:152-161)
+            const double rx = (double)x[r] - pos[j], ry = (double)y[r] - pos[F.S + j],
+                         rz = (double)z[r] - pos[2 * F.S + j];
+            const double dist = nxc_sqrt((rx * rx + ry * ry) + rz * rz);
+            w = nxc_div(1.0, F.mode == 1 ? dist : dist * dist);
+        } else if (F.mode == 3) {
+            w = wspec[j];
+        }
+        unsafeAtomicAdd(&num[pk], ratio[j] * w);
+        unsafeAtomicAdd(&den[pk], w);
+        atomicAdd(&cnt[pk], 1u);
+    }
+    flush_counter(bad, my_bad);
+}
+
+// f = num / den where den > 0 (else 0); mean over den > 0; mult = f / mean (0 for every packet
+// when none was seen).  stats[0] = sum of f, stats[1] = packets with den > 0.
+__global__ void __launch_bounds__(NXC_FIT_NORM_THREADS)
+k_fit_norm(int64_t n, const double *__restrict__ num, const double *__restrict__ den,
+           double *__restrict__ mult, double *__restrict__ stats)
+{
+    __shared__ double s_sum[NXC_FIT_NORM_THREADS];
+    __shared__ double s_cnt[NXC_FIT_NORM_THREADS];
+    double sum = 0.0, c = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += NXC_FIT_NORM_THREADS) {
+        if (den[i] > 0.0) {
+            sum += nxc_div(num[i], den[i]);
+            c += 1.0;
+        }
+    }
+    s_sum[threadIdx.x] = sum;
+    s_cnt[threadIdx.x] = c;
+    __syncthreads();
+    for (int s = NXC_FIT_NORM_THREADS / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            s_sum[threadIdx.x] += s_sum[threadIdx.x + s];
+            s_cnt[threadIdx.x] += s_cnt[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    const double total = s_sum[0], seen = s_cnt[0];
+    const double mean = seen > 0.0 ? nxc_div(total, seen) : 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += NXC_FIT_NORM_THREADS) {
+        const double f = den[i] > 0.0 ? nxc_div(num[i], den[i]) : 0.0;
+        mult[i] = seen > 0.0 ? nxc_div(f, mean) : 0.0;
+    }
+    if (threadIdx.x == 0) { stats[0] = total; stats[1] = seen; }
+}
+
+// The fitted radiance of every spectrum (no mask, no shadow factor: LOSResultFitted.py:191-210).
+// Its per-spectrum sums are formed in LDS (lds_sums: S of them fit), as in k_los_pairs.
+template <typename T, typename I>
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_fit_radiance(LosK K, const unsigned char *__restrict__ blob, int64_t stage_bytes, FitK F,
+               int lds_sums, const long long *__restrict__ pairs, const double *__restrict__ pos,
+               const double *__restrict__ mult, const T *__restrict__ x, const T *__restrict__ y,
+               const T *__restrict__ z, const T *__restrict__ vy, const T *__restrict__ frac,
+               const I *__restrict__ index, double *__restrict__ radiance,
+               unsigned long long *__restrict__ bad, unsigned long long *__restrict__ nonfinite)
+{
+    stage_tables(blob, stage_bytes);                   // g-value tables; nxc_log's table in the header
+    double *const racc = reinterpret_cast<double *>(nxc_lds + ((stage_bytes + 31) & ~31ll));
+    if (lds_sums)
+        for (int64_t k = threadIdx.x; k < F.S; k += blockDim.x) racc[k] = 0.0;
+    __syncthreads();
+    const double rs_1e6 = nxc_recip_seed(1e6);
+    unsigned long long my_bad = 0, my_nonfinite = 0;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < F.n_pairs;
+         k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = pairs[k], r = pairs[F.cap + k];
+        const int64_t pk = (j < 0 || j >= F.S) ? -1 : fit_packet_of(F, index, r);
+        if (pk < 0) { my_bad++; continue; }
+        const double rx = (double)x[r] - pos[j], ry = (double)y[r] - pos[F.S + j],
+                     rz = (double)z[r] - pos[2 * F.S + j];
+        const double dist = nxc_sqrt((rx * rx + ry * ry) + rz * rz);
+        const double frac_fit = (double)frac[r] * mult[pk];
+        const double wtemp = los_wtemp(K, (double)vy[r], frac_fit, dist, rs_1e6, my_nonfinite);
+        unsafeAtomicAdd(lds_sums ? &racc[j] : &radiance[j], wtemp);
+    }
+    if (lds_sums) {
+        __syncthreads();
+        for (int64_t k = threadIdx.x; k < F.S; k += blockDim.x)
+            if (racc[k] != 0.0) unsafeAtomicAdd(&radiance[k], racc[k]);
+    }
+    flush_counter(bad, my_bad);
+    flush_counter(nonfinite, my_nonfinite);
+}
+
+// frac' of row r in fp64 and whether save() keeps it (frac' > 0 with compress)
+template <typename T, typename I>
+NXC_DEV bool fit_row(const FitK &F, const T *__restrict__ frac, const I *__restrict__ index,
+                     const double *__restrict__ mult, int64_t r, double &frac_fit, int64_t &pk)
+{
+    pk = fit_packet_of(F, index, r);
+    frac_fit = pk < 0 ? 0.0 : (double)frac[r] * mult[pk];
+    return pk >= 0 && (!F.compress || frac_fit > 0.0);
+}
+
+// pass 1: rows kept per tile of blockDim.x rows, and per packet
+template <typename T, typename I>
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_fit_rows_count(FitK F, const T *__restrict__ frac, const I *__restrict__ index,
+                 const double *__restrict__ mult, unsigned *__restrict__ tile_kept,
+                 unsigned *__restrict__ lengths)
+{
+    __shared__ unsigned kept;
+    if (threadIdx.x == 0) kept = 0;
+    __syncthreads();
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double f;
+    int64_t pk;
+    if (r < F.n_rows && fit_row(F, frac, index, mult, r, f, pk)) {
+        atomicAdd(&kept, 1u);
+        atomicAdd(&lengths[pk], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) tile_kept[blockIdx.x] = kept;
+}
+
+// pass 2: the kept rows of a tile in their order, from the tile's offset on (offsets: exclusive
+// sums of pass 1's counts).  Columns [9][n_rows] in (stride in_stride) -> [9][*] out (out_stride).
+template <typename T, typename I>
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_fit_rows_write(FitK F, const T *__restrict__ cols, int64_t in_stride, const I *__restrict__ index,
+                 const double *__restrict__ mult, const long long *__restrict__ tile_off,
+                 T *__restrict__ out, int64_t out_stride, I *__restrict__ out_index)
+{
+    __shared__ unsigned wave_kept[NXC_BLOCK / 64];
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double f = 0.0;
+    int64_t pk = -1;
+    const bool keep = r < F.n_rows && fit_row(F, cols + 7 * in_stride, index, mult, r, f, pk);
+    const unsigned long long m = __ballot(keep);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_kept[wave] = (unsigned)__popcll(m);
+    __syncthreads();
+    if (!keep) return;
+    long long at = tile_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; w++) at += wave_kept[w];
+#pragma unroll
+    for (int c = 0; c < 9; c++)
+        out[c * out_stride + at] = c == 7 ? (T)f : cols[c * in_stride + r];
+    out_index[at] = index[r];
 }

@@ -37,12 +37,17 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_comm_set_timeout', 'nxc_comm_abort', 'nxc_comm_request_abort',
            'nxc_comm_test_stall', 'nxc_packets_upload_pieces', 'nxc_density_set',
            'nxc_density_accumulate', 'nxc_density_accumulate_f32', 'nxc_density_accumulate_rows',
-           'nxc_density_download')
+           'nxc_density_download', 'nxc_pairs_create', 'nxc_pairs_free', 'nxc_pairs_count',
+           'nxc_pairs_download', 'nxc_los_set_pairs', 'nxc_fit_set', 'nxc_fit_source_rows',
+           'nxc_fit_source', 'nxc_fit_source_f32', 'nxc_fit_packets', 'nxc_fit_radiance',
+           'nxc_fit_rows', 'nxc_fit_download')
 ABI_VERSION = 3
 
 
 NXC_ERR_HIP, NXC_ERR_ARG, NXC_ERR_NO_DEVICE, NXC_ERR_RCCL, NXC_ERR_STATE, NXC_ERR_NOMEM, \
     NXC_ERR_INCOMPLETE = -1, -2, -3, -4, -5, -6, -7
+NXC_ERR_OVERFLOW = -8
+FIT_WEIGHT_MODES = {None: 0, 'dist': 1, 'dist2': 2, 'sigma': 3}
 
 
 class HipError(RuntimeError):
@@ -80,6 +85,12 @@ class nxc_density_desc(C.Structure):
     _fields_ = [('origin', C.c_double*3), ('h', C.c_double), ('dr', C.c_double),
                 ('dims', C.c_int64*3), ('n_points', C.c_int64), ('points', _dp),
                 ('cell_start', C.POINTER(C.c_int32))]
+
+
+class nxc_fit_desc(C.Structure):
+    _fields_ = [('n_spectra', C.c_int64), ('weight_mode', C.c_int32), ('reserved', C.c_int32),
+                ('position', _dp), ('ratio', _dp), ('weight', _dp),
+                ('mask', C.POINTER(C.c_uint8))]
 
 
 class nxc_source_desc(C.Structure):
@@ -214,6 +225,43 @@ class RowStore:
         for owner in list(self.owners):
             owner._spill()
         self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class PairList:
+    """A device list of (spectrum, row) pairs (an ``nxc_pairs``): what a line-of-sight pass found
+    with weight > 0, when it is passed as ``los_accumulate(..., pairs=...)``."""
+
+    def __init__(self, ctx, capacity):
+        self.ctx, self.capacity = ctx, int(capacity)
+        self._p = C.c_void_p()
+        ctx._check(ctx.lib.nxc_pairs_create(ctx._h, C.c_int64(self.capacity), C.byref(self._p)))
+
+    @property
+    def count(self):
+        n = C.c_int64(0)
+        self.ctx._check(self.ctx.lib.nxc_pairs_count(self._p, C.byref(n)))
+        return int(n.value)
+
+    def download(self):
+        """(2, n) int64: spectrum, row of every pair, in the order the pass wrote them."""
+        n = self.count
+        out = np.zeros((2, n), dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self.ctx._check(self.ctx.lib.nxc_pairs_download(self.ctx._h, self._p,
+                                                        out[0].ctypes.data_as(i64p),
+                                                        out[1].ctypes.data_as(i64p)))
+        return out
+
+    def free(self):
+        if self._p and getattr(self.ctx, '_h', None):
+            self.ctx.lib.nxc_pairs_free(self.ctx._h, self._p)
+        self._p = C.c_void_p()
 
     def __del__(self):
         try:
@@ -595,11 +643,29 @@ class Context:
     # -- f-1: spacecraft lines of sight ------------------------------------------------------
     def los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables,
                        ladder, sc, x=None, y=None, z=None, vy=None, frac=None, index=None,
-                       n_index=0, used_cap=0, rows=None):
+                       n_index=0, used_cap=0, rows=None, pairs=None):
         """sc: (8, S) array x,y,z,xbore,ybore,zbore,dist_from_plan,ladder_len.  Samples: five host
         columns (+ index), or ``rows = (RowStore, first, count, index_shift)`` for rows that are
         already in HBM.  Returns dict(radiance, npackets, included|None, used (2, m)|None,
-        n_used)."""
+        n_used).  ``pairs``: a PairList that receives the used pairs on the device instead of
+        ``used`` (HipError with code NXC_ERR_OVERFLOW when they do not fit)."""
+        if pairs is None:
+            return self._los_accumulate(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet,
+                                        unit_cm, g_tables, ladder, sc, x, y, z, vy, frac, index,
+                                        n_index, used_cap, rows)
+        if used_cap:
+            raise ValueError('used_cap and pairs exclude each other')
+        self._check(self.lib.nxc_los_set_pairs(self._h, pairs._p))
+        try:
+            return self._los_accumulate(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet,
+                                        unit_cm, g_tables, ladder, sc, x, y, z, vy, frac, index,
+                                        n_index, 0, rows)
+        finally:
+            self.lib.nxc_los_set_pairs(self._h, None)
+
+    @staticmethod
+    def _los_desc(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables, ladder):
+        """(nxc_los_desc, the arrays it points into)"""
         d = nxc_los_desc()
         d.dphi, d.sin_dphi, d.sin_2dphi, d.cos_threshold = dphi, sin_dphi, sin_2dphi, cos_threshold
         d.vrplanet, d.unit_cm = float(vrplanet), float(unit_cm)
@@ -610,7 +676,14 @@ class Context:
             keep += [v, g]
             d.line_n[k], d.line_v[k], d.line_g[k] = len(v), _p(v), _p(g)
         lad = _f64(ladder)
+        keep.append(lad)
         d.n_ladder, d.ladder = len(lad), _p(lad)
+        return d, keep
+
+    def _los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm,
+                        g_tables, ladder, sc, x, y, z, vy, frac, index, n_index, used_cap, rows):
+        d, keep = self._los_desc(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm,
+                                 g_tables, ladder)
         sc = _f64(sc)
         S = sc.shape[1]
         if rows is not None:
@@ -706,6 +779,89 @@ class Context:
         total, count = np.zeros(q), np.zeros(q)
         self._check(self.lib.nxc_density_download(self._h, _p(total), _p(count)))
         return total, count
+
+    # -- LOSResultFitted ----------------------------------------------------------------------
+    def pairs_create(self, capacity):
+        return PairList(self, capacity)
+
+    def fit_set(self, position, ratio, mask, weight_mode=None, weight=None):
+        """Per spectrum: spacecraft position (3, S), ratio = data / unfitted model, mask, and for
+        weight_mode 'sigma' the weight 1/sigma*2; zeroes the fitted radiance sums."""
+        pos = _f64(position).reshape(3, -1)
+        S = pos.shape[1]
+        ratio = _f64(ratio)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        if len(ratio) != S or len(mask) != S:
+            raise ValueError('position, ratio and mask must describe the same spectra')
+        d = nxc_fit_desc()
+        d.n_spectra, d.weight_mode = S, FIT_WEIGHT_MODES[weight_mode]
+        d.position, d.ratio = _p(pos), _p(ratio)
+        w = None
+        if weight_mode == 'sigma':
+            w = _f64(weight)
+            d.weight = _p(w)
+        d.mask = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._check(self.lib.nxc_fit_set(self._h, C.byref(d)))
+        self._fit_s = S
+
+    def fit_source(self, x=None, y=None, z=None, vy=None, frac=None, index=None, rows=None):
+        """The samples the pairs' rows index: five host columns with their packet index (float32
+        ones go over as they are), or ``rows = (RowStore, first, count, index_shift)``."""
+        if rows is not None:
+            store, first, count, shift = rows
+            if store._r is None:
+                raise HipError('the row store has been freed')
+            self._fit_store = store
+            self._check(self.lib.nxc_fit_source_rows(self._h, store._r, C.c_int64(first),
+                                                     C.c_int64(count), C.c_int64(shift)))
+            return
+        self._fit_store = None
+        cols = (x, y, z, vy, frac)
+        idx = np.ascontiguousarray(index, dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        if all(getattr(c, 'dtype', None) == np.float32 for c in cols):
+            cols = [np.ascontiguousarray(c) for c in cols]
+            ptrs = [c.ctypes.data_as(C.POINTER(C.c_float)) for c in cols]
+            entry = self.lib.nxc_fit_source_f32
+        else:
+            cols = [_f64(c) for c in cols]
+            ptrs = [_p(c) for c in cols]
+            entry = self.lib.nxc_fit_source
+        self._check(entry(self._h, C.c_int64(len(idx)), *ptrs, idx.ctypes.data_as(i64p)))
+
+    def fit_packets(self, pairs, n_packets):
+        """Per packet num, den, cnt and the multiplier mult over ``pairs`` (a PairList) and the
+        source; also the sum of f and the number of packets seen.  The multipliers stay on the
+        device for fit_radiance / fit_rows."""
+        n = int(n_packets)
+        num, den, mult = np.zeros(n), np.zeros(n), np.zeros(n)
+        cnt = np.zeros(n, dtype=np.int32)
+        stats = np.zeros(2)
+        self._check(self.lib.nxc_fit_packets(
+            self._h, pairs._p, C.c_int64(n), _p(num), _p(den),
+            cnt.ctypes.data_as(C.POINTER(C.c_int32)), _p(mult), _p(stats)))
+        return dict(num=num, den=den, cnt=cnt, mult=mult, f_sum=float(stats[0]),
+                    n_seen=int(stats[1]))
+
+    def fit_radiance(self, pairs, dphi, sin_dphi, vrplanet, unit_cm, g_tables):
+        """Add the fitted radiance of every pair to its spectrum's sum (Apix with ``dphi``)."""
+        d, keep = self._los_desc(dphi, sin_dphi, 0.0, 0.0, vrplanet, unit_cm, g_tables, [0.0])
+        self._check(self.lib.nxc_fit_radiance(self._h, pairs._p, C.byref(d)))
+
+    def fit_rows(self, n_packets, compress=True):
+        """(RowStore of the fitted rows, rows kept per packet) for a row-store source."""
+        lengths = np.zeros(int(n_packets), dtype=np.int64)
+        handle = C.c_void_p()
+        self._check(self.lib.nxc_fit_rows(self._h, C.c_int(int(bool(compress))), C.byref(handle),
+                                          lengths.ctypes.data_as(C.POINTER(C.c_int64))))
+        store = RowStore(self, handle)
+        self._stores.append(weakref.ref(store))
+        return store, lengths
+
+    def fit_download(self):
+        out = np.zeros(getattr(self, '_fit_s', 0))
+        self._check(self.lib.nxc_fit_download(self._h, _p(out)))
+        return out
 
     # -- RCCL -------------------------------------------------------------------------------
     def comm_unique_id(self):
