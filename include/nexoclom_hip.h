@@ -470,6 +470,55 @@ int nxc_density_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const f
 int nxc_density_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
 int nxc_density_download(nxc_handle *h, double *sum_frac, double *count);
 
+/* ---- Source maps: where the packets of fitted Outputs came from ---------------------------------
+ * data_simulation/make_source_map.py:11-174 per Output, summed over the Outputs of a result on the
+ * device.  Grid: nlon x nlat points at the bin centres point_lon[nlon], point_lat[nlat]; point p =
+ * i_lon * nlat + j_lat.  Packet q is in point p's ball iff (BallTree haversine query_radius, fp64,
+ * one rounding per operation in this order)
+ *     sin(0.5*(phi_p - phi_q))^2 + cos(phi_p)*cos(phi_q)*sin(0.5*(lam_p - lam_q))^2 <= threshold[j],
+ * with point_cos[j] = cos(phi_p) and threshold[j] = sin(0.5 * smear_radius * cos(phi_p))^2.  The
+ * host sorts each Output's packets by cell, lat-major (cell j * nlon + i of the bucket it files them
+ * in; cell_start[ncells] may be < n: packets after it are in no ball), and lists for every tile of
+ * `tile` consecutive longitudes of one latitude row (tile k covers row k / ceil(nlon / tile)) the
+ * cell runs [seg[2s], seg[2s + 1]] (inclusive, s in seg_off[k] .. seg_off[k + 1] - 1) that hold every
+ * packet of its points' balls.  Histograms follow np.histogram with `range=`: bins between
+ * np.linspace edges, the right edge inclusive, values outside dropped.
+ * Map per point: [nvel speed | nalt altitude | naz azimuth | n_total | n_included | weight sum],
+ * then hist2d[npoints]: the unsmeared lon/lat histogram (np.histogram2d of the included packets).
+ * Included: frac > 0; weight: frac, or 1 when `available`.
+ *   nxc_source_map_set         uploads the grid and segments and zeroes the resident map
+ *   nxc_source_map_accumulate  adds one Output: n packets' lat, lon, v [R/s], altitude, azimuth,
+ *                              frac (sorted), cell_start[ncells + 1], its speed edges [nvel + 1]
+ *                              (speed = v * r_km); the speed histograms of the map are added times
+ *                              `factor`.  small[nvel + nalt + naz + nvel] receives the Output's
+ *                              whole-planet speed, altitude and azimuth histograms and its speed
+ *                              map summed over the grid (unscaled)
+ *   nxc_source_map_download    map[npoints][nvel + nalt + naz + 3], hist2d[npoints] */
+typedef struct nxc_source_map_desc {
+    int64_t nlon, nlat, nvel, nalt, naz;
+    int64_t tile;             /* grid points per workgroup (<= nlon)                              */
+    double r_km;              /* planet radius [km]                                              */
+    const double *alt_edges;  /* host [nalt + 1]; az_edges [naz + 1]; lon_edges [nlon + 1];      */
+    const double *az_edges;   /* lat_edges [nlat + 1]                                            */
+    const double *lon_edges;
+    const double *lat_edges;
+    const double *point_lon;  /* host [nlon]                                                     */
+    const double *point_lat;  /* host [nlat]                                                     */
+    const double *point_cos;  /* host [nlat]                                                     */
+    const double *threshold;  /* host [nlat]                                                     */
+    int64_t n_seg;
+    const int32_t *seg;       /* host [n_seg][2]                                                 */
+    const int32_t *seg_off;   /* host [ntiles + 1]                                               */
+} nxc_source_map_desc;
+
+int nxc_source_map_set(nxc_handle *h, const nxc_source_map_desc *d);
+int nxc_source_map_accumulate(nxc_handle *h, int64_t n, const double *lat, const double *lon,
+                              const double *v, const double *alt, const double *az,
+                              const double *frac, const int32_t *cell_start,
+                              const double *vel_edges, int32_t available, double factor,
+                              double *small);
+int nxc_source_map_download(nxc_handle *h, double *map, double *hist2d);
+
 /* ---- LOSResultFitted: packet weights refitted to observed radiances ------------------------------
  * data_simulation/LOSResultFitted.py:118-214 per Output, over the (spectrum, row) pairs its UNFITTED
  * line-of-sight pass found with weight > 0 (compute_iteration.py:210's `used`).

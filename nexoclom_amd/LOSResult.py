@@ -15,8 +15,9 @@ reference's own doubles; every (sample, spectrum) pair test runs in the HIP kern
 
 ``make_mask`` and ``determine_source_rate`` restate LOSResult.py:171-200,278-308; the source-rate
 fit is NOT called by ``simulate_data_from_inputs`` here (the reference calls it at the end): call it
-explicitly before handing the result to ``LOSResultFitted`` (LOSResultFitted.py).  Source maps and
-the PostgreSQL caching of iterations are out of scope.
+explicitly before handing the result to ``LOSResultFitted`` (LOSResultFitted.py).
+``make_source_map`` restates LOSResult.py:310-458 with make_source_map.py on the GPU (sourcemap.py).
+The PostgreSQL caching of iterations is out of scope.
 """
 import numpy as np
 import pandas as pd
@@ -287,3 +288,94 @@ class LOSResult(ModelResult):
             self.sourcerate = Quantity(0., '1e23/s')
         self.goodness_of_fit = None
         self.mask = mask
+
+    def make_source_map(self, grid_params=None, normalize=True, do_source=True, do_available=True,
+                        *, cp=None, reduce='rccl'):
+        """LOSResult.py:310-458 with make_source_map.py:11-174 per Output (see sourcemap.py):
+        returns (sourcemap, availablemap), each a SourceMap or None.  Works on the Outputs
+        catalogued under ``self.inputs`` -- for a LOSResultFitted the fitted ones, whose X0.frac
+        carries the multipliers.  ``normalize`` uses ``self.sourcerate`` (determine_source_rate).
+        ``cp``: the control plane of a shared run: one small all-reduce agrees on the global vmax
+        (each rank fills its slot of a world-length vector), each rank sums its own Outputs on
+        that axis, one all-reduce sums the combined arrays.  The reference's ``distribute`` is
+        not ported."""
+        from . import sourcemap as SM
+        todo = [t for t, on in (('source', do_source), ('available', do_available)) if on]
+        grid = SM.SourceMapGrid(grid_params, self.unit_km)
+        runs = []
+        for run in self.inputs._catalogue:
+            cols = SM.x0_columns(run)
+            if cols is not None:
+                runs.append((cols, SM.output_vmax(cols, grid.r_km)))
+        shared = cp is not None and cp.world > 1
+        ctx = self.context()
+        vmax = max([v for _, v in runs], default=-np.inf)
+        if shared:
+            from .distributed import allreduce_small, guarded
+            slots = np.zeros(cp.world)
+            slots[cp.rank] = vmax if runs else np.nan
+            with guarded(cp, ctx):
+                slots = allreduce_small(slots, cp, ctx, reduce)
+            vmax = float(np.nanmax(slots)) if np.isfinite(slots).any() else -np.inf
+        if not np.isfinite(vmax):
+            raise RuntimeError('make_source_map: no Output has an X0 packet')
+        # the Outputs of this rank, sorted by cell once for both passes
+        sorted_runs = []
+        for cols, v in runs:
+            order, cell_start = grid.bucket(cols['latitude'], cols['longitude'])
+            sorted_runs.append(({c: cols[c][order] for c in SM.X0_COLUMNS}, cell_start, v))
+        results = []
+        for todo_ in todo:
+            results.append(self._source_map_pass(grid, sorted_runs, vmax, todo_ == 'available',
+                                                 normalize, ctx, cp if shared else None, reduce))
+        out = dict(zip(todo, results))
+        return out.get('source'), out.get('available')
+
+    def _source_map_pass(self, grid, sorted_runs, vmax, available, normalize, ctx, cp, reduce):
+        from . import sourcemap as SM
+        nvel, nalt, naz = grid.nvel, grid.nalt, grid.naz
+        top = SM.centres(SM.speed_edges(vmax, nvel)).max()
+        ctx.source_map_set(grid)
+        pieces, vmaxes = [], []
+        for cols, cell_start, v in sorted_runs:
+            factor = 2.0 if SM.centres(SM.speed_edges(v, nvel)).max() == top else 1.0
+            pieces.append(ctx.source_map_accumulate(
+                cols['latitude'], cols['longitude'], cols['v'], cols['altitude'], cols['azimuth'],
+                cols['frac'], cell_start, SM.speed_edges(v, nvel), available, factor))
+            vmaxes.append(v)
+        acc, hist2d = ctx.source_map_download()
+        if pieces:
+            small, _ = SM.combine_small(pieces, vmaxes, nvel, vmax)
+        else:
+            small = dict(speed_dist=np.zeros(nvel), broadcast=np.zeros(nvel),
+                         altitude_dist=np.zeros(nalt), azimuth_dist=np.zeros(naz))
+        small['speed'] = SM.centres(SM.speed_edges(vmax, nvel))
+        if cp is not None:
+            from .distributed import allreduce_small, guarded
+            flat = np.concatenate([acc.ravel(), hist2d, small['speed_dist'], small['broadcast'],
+                                   small['altitude_dist'], small['azimuth_dist']])
+            with guarded(cp, ctx):
+                flat = allreduce_small(flat, cp, ctx, reduce)
+            k = acc.size
+            acc = flat[:k].reshape(acc.shape)
+            hist2d = flat[k:k + hist2d.size]
+            k += hist2d.size
+            for key, n in (('speed_dist', nvel), ('broadcast', nvel), ('altitude_dist', nalt),
+                           ('azimuth_dist', naz)):
+                small[key] = flat[k:k + n].copy()
+                k += n
+        shape = (grid.nlon, grid.nlat)
+        nb = nvel + nalt + naz
+        d = dict(longitude=grid.lon.copy(), latitude=grid.lat.copy(), speed=small['speed'],
+                 altitude=grid.altitude.copy(), azimuth=grid.azimuth.copy(),
+                 speed_dist=small['speed_dist'], altitude_dist=small['altitude_dist'],
+                 azimuth_dist=small['azimuth_dist'])
+        d['speed_dist_map'] = (acc[:, :nvel] + small['broadcast']).reshape(shape + (nvel,))
+        d['altitude_dist_map'] = acc[:, nvel:nvel + nalt].reshape(shape + (nalt,))
+        d['azimuth_dist_map'] = acc[:, nvel + nalt:nb].reshape(shape + (naz,))
+        d['n_total'] = acc[:, nb].reshape(shape)
+        d['n_included'] = acc[:, nb + 1].reshape(shape)
+        d['abundance_uncor'] = (acc[:, nb + 2] if grid.smear_abundance else hist2d).reshape(shape)
+        d = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in d.items()}
+        SM.finish(d, normalize, getattr(self, 'sourcerate', 0.), self.unit_km)
+        return SM.SourceMap(d, normalized=normalize)

@@ -14,6 +14,7 @@ from .ModelImage import ModelImage, ModelResult   # noqa: F401
 from .LOSResult import LOSResult, SpacecraftData   # noqa: F401
 from .ModelDensity import ModelDensity        # noqa: F401
 from .LOSResultFitted import LOSResultFitted  # noqa: F401
+from .sourcemap import SourceMap              # noqa: F401
 from .solarsystem import SSObject, planet_dist    # noqa: F401
 from .atomicdata import gValue, RadPresConst, PhotoRate, atomicmass   # noqa: F401
 from .input_classes import InputError       # noqa: F401

@@ -457,6 +457,19 @@ struct nxc_handle {
     size_t fit_smp_cap = 0;
     unsigned char *d_fit_aux = nullptr;  // blob | counters | tile counts and offsets
     size_t fit_aux_cap = 0;
+
+    // source maps (nxc_source_map_*): the grid and tile segments, the resident map and unsmeared
+    // histogram, and one Output's packets
+    bool have_smap = false;
+    SmapK smap{};
+    int64_t smap_ntiles = 0, smap_ncells = 0;
+    std::vector<double> smap_edges;  // alt | az | lon | lat edges (the speed edges come per Output)
+    unsigned char *d_smap_grid = nullptr;  // pt_lon | pt_lat | pt_cos | thr | seg_off | seg
+    size_t smap_grid_cap = 0;
+    double *d_smap_acc = nullptr;    // map [npoints][stride] | hist2d [npoints]
+    size_t smap_acc_cap = 0;
+    unsigned char *d_smap_pk = nullptr;    // columns | geo | bins | cell starts | edges | small
+    size_t smap_pk_cap = 0;
 };
 
 static int order_on_device(nxc_handle *h, double k2max, const long long *d_lifetimes,
@@ -1797,7 +1810,8 @@ int nxc_destroy(nxc_handle *h)
                     h->d_steps, h->d_reduce, h->d_order, h->d_bounce, h->d_moonpos, h->d_offsets,
                     h->d_source, h->d_queue, h->d_samples, h->d_tiles, h->d_hist, h->d_rec, h->d_piece_hist,
                     h->d_blob_img, h->d_reduce_n, h->d_losblk, h->d_dens_pts, h->d_dens_cell,
-                    h->d_dens_acc, h->d_fit_spec, h->d_fit_pk, h->d_fit_smp, h->d_fit_aux};
+                    h->d_dens_acc, h->d_fit_spec, h->d_fit_pk, h->d_fit_smp, h->d_fit_aux,
+                    h->d_smap_grid, h->d_smap_acc, h->d_smap_pk};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     pool_flush(h);
@@ -2914,6 +2928,213 @@ int nxc_density_download(nxc_handle *h, double *sum_frac, double *count)
         sum_frac[j] = pair[2 * j];
         count[j] = pair[2 * j + 1];
     }
+    return NXC_OK;
+    });
+}
+
+// ---- source maps ---------------------------------------------------------------------------------
+namespace {
+size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+
+bool linspace_ok(const double *e, int64_t n)
+{
+    if (!e || n < 1) return false;
+    for (int64_t k = 0; k <= n; k++)
+        if (!std::isfinite(e[k]) || (k && !(e[k] >= e[k - 1]))) return false;
+    return e[n] > e[0];
+}
+
+void set_axis(const double *e, int64_t n, double &lo, double &hi, double &inv)
+{
+    lo = e[0];
+    hi = e[n];
+    inv = (double)n / (hi - lo);
+}
+
+size_t smap_points_lds(const SmapK &K)
+{
+    return (size_t)8 * K.tile * smap_stride(K) + (size_t)4 * 2 * (K.nseg_max + 1);
+}
+}  // namespace
+
+int nxc_source_map_set(nxc_handle *h, const nxc_source_map_desc *d)
+{
+    return guarded([&]() -> int {
+    if (!h || !d) return fail(NXC_ERR_ARG, "null argument");
+    const int64_t nlon = d->nlon, nlat = d->nlat;
+    if (nlon < 1 || nlat < 1 || d->nvel < 1 || d->nalt < 1 || d->naz < 1 || nlon * nlat > (1 << 24) ||
+        d->nvel + d->nalt + d->naz > (1 << 16) || d->tile < 1 || d->tile > nlon ||
+        !(d->r_km > 0.0) || !std::isfinite(d->r_km))
+        return fail(NXC_ERR_ARG, "bad nxc_source_map_desc grid");
+    if (!linspace_ok(d->alt_edges, d->nalt) || !linspace_ok(d->az_edges, d->naz) ||
+        !linspace_ok(d->lon_edges, nlon) || !linspace_ok(d->lat_edges, nlat))
+        return fail(NXC_ERR_ARG, "nxc_source_map_desc: edges must be finite and increasing");
+    if (!d->point_lon || !d->point_lat || !d->point_cos || !d->threshold || !d->seg_off ||
+        (d->n_seg && !d->seg))
+        return fail(NXC_ERR_ARG, "nxc_source_map_desc: null table");
+    const int64_t tpr = (nlon + d->tile - 1) / d->tile, ntiles = tpr * nlat, ncells = nlon * nlat;
+    // every segment is a run of existing cells, and the tiles' lists tile the segment array
+    if (d->seg_off[0] != 0 || d->seg_off[ntiles] != d->n_seg || d->n_seg > INT32_MAX)
+        return fail(NXC_ERR_ARG, "nxc_source_map_desc: segment offsets do not span the segments");
+    int64_t nseg_max = 0;
+    for (int64_t t = 0; t < ntiles; t++) {
+        const int64_t c = d->seg_off[t + 1] - d->seg_off[t];
+        if (c < 0) return fail(NXC_ERR_ARG, "nxc_source_map_desc: segment offsets are not sorted");
+        nseg_max = std::max(nseg_max, c);
+    }
+    for (int64_t s = 0; s < d->n_seg; s++)
+        if (d->seg[2 * s] < 0 || d->seg[2 * s] > d->seg[2 * s + 1] || d->seg[2 * s + 1] >= ncells)
+            return fail(NXC_ERR_ARG, "nxc_source_map_desc: segment outside the grid");
+    SmapK K{};
+    K.r_km = d->r_km;
+    K.nlon = (int)nlon; K.nlat = (int)nlat;
+    K.nvel = (int)d->nvel; K.nalt = (int)d->nalt; K.naz = (int)d->naz;
+    K.tile = (int)d->tile; K.tiles_per_row = (int)tpr; K.nseg_max = (int)nseg_max;
+    set_axis(d->alt_edges, d->nalt, K.alt_lo, K.alt_hi, K.alt_inv);
+    set_axis(d->az_edges, d->naz, K.az_lo, K.az_hi, K.az_inv);
+    set_axis(d->lon_edges, nlon, K.lon_lo, K.lon_hi, K.lon_inv);
+    set_axis(d->lat_edges, nlat, K.lat_lo, K.lat_hi, K.lat_inv);
+    if (smap_points_lds(K) > 64 * 1024)
+        return fail(NXC_ERR_ARG, "nxc_source_map_desc: a tile's histograms exceed 64 KiB of LDS");
+    HIPCHK(hipSetDevice(h->device));
+    h->have_smap = false;
+    const int64_t npoints = ncells, stride = smap_stride(K);
+    const size_t grid_bytes = align256(8 * (size_t)(2 * nlat + nlon + nlat)) +
+                              align256(4 * (size_t)(ntiles + 1)) + 8 * (size_t)std::max<int64_t>(d->n_seg, 1);
+    std::vector<unsigned char> grid(grid_bytes, 0);
+    double *g = reinterpret_cast<double *>(grid.data());
+    std::copy(d->point_lon, d->point_lon + nlon, g);
+    std::copy(d->point_lat, d->point_lat + nlat, g + nlon);
+    std::copy(d->point_cos, d->point_cos + nlat, g + nlon + nlat);
+    std::copy(d->threshold, d->threshold + nlat, g + nlon + 2 * nlat);
+    const size_t off_segoff = align256(8 * (size_t)(2 * nlat + nlon + nlat));
+    const size_t off_seg = off_segoff + align256(4 * (size_t)(ntiles + 1));
+    std::copy(d->seg_off, d->seg_off + ntiles + 1, reinterpret_cast<int32_t *>(grid.data() + off_segoff));
+    if (d->n_seg)
+        std::copy(d->seg, d->seg + 2 * d->n_seg, reinterpret_cast<int32_t *>(grid.data() + off_seg));
+    const size_t acc_bytes = 8 * (size_t)npoints * (size_t)(stride + 1);
+    int rc;
+    if ((rc = ensure(reinterpret_cast<void **>(&h->d_smap_grid), &h->smap_grid_cap, grid_bytes)) ||
+        (rc = ensure(reinterpret_cast<void **>(&h->d_smap_acc), &h->smap_acc_cap, acc_bytes)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(h->d_smap_grid, grid.data(), grid_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_smap_acc, 0, acc_bytes, h->stream));
+    HIPCHK(stream_sync(h));
+    h->smap_edges.clear();
+    for (auto [e, n] : {std::pair<const double *, int64_t>{d->alt_edges, d->nalt}, {d->az_edges, d->naz},
+                        {d->lon_edges, nlon}, {d->lat_edges, nlat}})
+        h->smap_edges.insert(h->smap_edges.end(), e, e + n + 1);
+    h->smap = K;
+    h->smap_ntiles = ntiles;
+    h->smap_ncells = ncells;
+    h->have_smap = true;
+    return NXC_OK;
+    });
+}
+
+int nxc_source_map_accumulate(nxc_handle *h, int64_t n, const double *lat, const double *lon,
+                              const double *v, const double *alt, const double *az,
+                              const double *frac, const int32_t *cell_start,
+                              const double *vel_edges, int32_t available, double factor,
+                              double *small)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_smap) return fail(NXC_ERR_STATE, "nxc_source_map_set has not been called");
+    SmapK K = h->smap;
+    if (n < 0 || n > INT32_MAX || !cell_start || !small ||
+        (n && (!lat || !lon || !v || !alt || !az || !frac)) || !std::isfinite(factor))
+        return fail(NXC_ERR_ARG, "bad arguments");
+    if (!linspace_ok(vel_edges, K.nvel))
+        return fail(NXC_ERR_ARG, "speed edges must be finite and increasing");
+    const int64_t nc = h->smap_ncells;
+    if (cell_start[0] != 0 || cell_start[nc] > n)
+        return fail(NXC_ERR_ARG, "cell starts do not lie within the packets");
+    for (int64_t c = 0; c < nc; c++)
+        if (cell_start[c + 1] < cell_start[c]) return fail(NXC_ERR_ARG, "cell starts are not sorted");
+    set_axis(vel_edges, K.nvel, K.vel_lo, K.vel_hi, K.vel_inv);
+    K.available = available ? 1 : 0;
+    HIPCHK(hipSetDevice(h->device));
+    const int nh = K.nvel + K.nalt + K.naz;
+    const size_t col = align256(8 * (size_t)std::max<int64_t>(n, 1));
+    const size_t geo_b = align256(32 * (size_t)std::max<int64_t>(n, 1));
+    const size_t bins_b = align256(16 * (size_t)std::max<int64_t>(n, 1));
+    const size_t cs_b = align256(4 * (size_t)(nc + 1));
+    const size_t ne = (size_t)(K.nvel + 1) + h->smap_edges.size();
+    const size_t edges_b = align256(8 * ne);
+    const size_t small_b = align256(8 * (size_t)(nh + K.nvel));
+    const size_t part_b = 8 * (size_t)h->smap_ntiles * K.nvel;
+    int rc = ensure(reinterpret_cast<void **>(&h->d_smap_pk), &h->smap_pk_cap,
+                    6 * col + geo_b + bins_b + cs_b + edges_b + small_b + part_b);
+    if (rc) return rc;
+    unsigned char *base = h->d_smap_pk;
+    double *dcol = reinterpret_cast<double *>(base);
+    double4 *geo = reinterpret_cast<double4 *>(base + 6 * col);
+    int4 *bins = reinterpret_cast<int4 *>(base + 6 * col + geo_b);
+    int *dcs = reinterpret_cast<int *>(base + 6 * col + geo_b + bins_b);
+    double *dedges = reinterpret_cast<double *>(base + 6 * col + geo_b + bins_b + cs_b);
+    double *dsmall = reinterpret_cast<double *>(base + 6 * col + geo_b + bins_b + cs_b + edges_b);
+    double *dpart = reinterpret_cast<double *>(base + 6 * col + geo_b + bins_b + cs_b + edges_b + small_b);
+    const double *src[6] = {lat, lon, v, alt, az, frac};
+    if (n)
+        for (int c = 0; c < 6; c++)
+            HIPCHK(hipMemcpyAsync(reinterpret_cast<unsigned char *>(dcol) + c * col, src[c], 8 * (size_t)n,
+                                  hipMemcpyHostToDevice, h->stream));
+    std::vector<double> edges(ne);
+    std::copy(vel_edges, vel_edges + K.nvel + 1, edges.begin());
+    std::copy(h->smap_edges.begin(), h->smap_edges.end(), edges.begin() + K.nvel + 1);
+    HIPCHK(hipMemcpyAsync(dedges, edges.data(), 8 * ne, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(dcs, cell_start, 4 * (size_t)(nc + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(dsmall, 0, 8 * (size_t)(nh + K.nvel), h->stream));
+    const int64_t npoints = (int64_t)K.nlon * K.nlat;
+    double *acc = h->d_smap_acc, *hist2d = h->d_smap_acc + npoints * smap_stride(K);
+    const unsigned char *gb = h->d_smap_grid;
+    const int nlon = K.nlon, nlat = K.nlat;
+    const size_t off_segoff = align256(8 * (size_t)(2 * nlat + nlon + nlat));
+    const size_t off_seg = off_segoff + align256(4 * (size_t)(h->smap_ntiles + 1));
+    const double *pt_lon = reinterpret_cast<const double *>(gb);
+    const int *seg_off = reinterpret_cast<const int *>(gb + off_segoff);
+    const int2 *seg = reinterpret_cast<const int2 *>(gb + off_seg);
+    if ((rc = begin_timed(h))) return rc;
+    if (n) {
+        const size_t lds = 8 * (ne + (size_t)nh);
+        const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((n + NXC_BLOCK - 1) / NXC_BLOCK,
+                                                                    (int64_t)h->n_cu * 8));
+        hipLaunchKernelGGL(k_smap_prep, dim3((unsigned)grid), dim3(NXC_BLOCK), lds, h->stream, K, (int)n,
+                           dcol, reinterpret_cast<const double *>(reinterpret_cast<unsigned char *>(dcol) + col),
+                           reinterpret_cast<const double *>(reinterpret_cast<unsigned char *>(dcol) + 2 * col),
+                           reinterpret_cast<const double *>(reinterpret_cast<unsigned char *>(dcol) + 3 * col),
+                           reinterpret_cast<const double *>(reinterpret_cast<unsigned char *>(dcol) + 4 * col),
+                           reinterpret_cast<const double *>(reinterpret_cast<unsigned char *>(dcol) + 5 * col),
+                           dedges, geo, bins, dsmall, hist2d);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_smap_points, dim3((unsigned)h->smap_ntiles), dim3(NXC_BLOCK), smap_points_lds(K),
+                       h->stream, K, geo, bins, dcs, seg, seg_off, pt_lon, pt_lon + nlon,
+                       pt_lon + nlon + nlat, pt_lon + nlon + 2 * nlat, factor, acc, dpart);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_smap_gridsum, dim3((unsigned)K.nvel), dim3(NXC_BLOCK), 8 * NXC_BLOCK, h->stream,
+                       (int)h->smap_ntiles,
+                       K.nvel, dpart, dsmall + nh);
+    HIPCHK(hipGetLastError());
+    if ((rc = end_timed(h))) return rc;
+    HIPCHK(hipMemcpyAsync(small, dsmall, 8 * (size_t)(nh + K.nvel), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+    });
+}
+
+int nxc_source_map_download(nxc_handle *h, double *map, double *hist2d)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_smap) return fail(NXC_ERR_STATE, "nxc_source_map_set has not been called");
+    if (!map || !hist2d) return fail(NXC_ERR_ARG, "bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    const int64_t npoints = (int64_t)h->smap.nlon * h->smap.nlat;
+    const size_t mb = 8 * (size_t)npoints * smap_stride(h->smap);
+    HIPCHK(hipMemcpyAsync(map, h->d_smap_acc, mb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(hist2d, h->d_smap_acc + npoints * smap_stride(h->smap), 8 * (size_t)npoints,
+                          hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
     return NXC_OK;
     });
 }

@@ -2784,3 +2784,181 @@ k_fit_rows_write(FitK F, const T *__restrict__ cols, int64_t in_stride, const I 
         out[c * out_stride + at] = c == 7 ? (T)f : cols[c * in_stride + r];
     out_index[at] = index[r];
 }
+
+// ---------------------------------------------------------------------------------------------
+// Source maps (data_simulation/make_source_map.py:11-174): per grid point p of an nlon x nlat
+// lon/lat grid, over the X0 packets q in its haversine ball (BallTree.query_radius):
+//   sin(0.5*(phi_p - phi_q))^2 + cos(phi_p)*cos(phi_q)*sin(0.5*(lam_p - lam_q))^2 <= thr_p,
+// thr_p = sin(0.5 * smear_radius * cos(phi_p))^2 (host, NumPy), evaluated here in fp64 with one
+// rounding per operation in that order: n_total, n_included, the weight sum, and the speed /
+// altitude / azimuth histograms of the included packets.  Map layout: point p = i_lon * nlat +
+// j_lat, SMAP_STRIDE(K) doubles each: [nvel speed | nalt altitude | naz azimuth | n_total |
+// n_included | weight sum].
+//
+// The packets come sorted by grid cell, lat-major (cell j * nlon + i, i = floor(mod(lon, 2 pi) /
+// dlon), j = floor((lat + pi/2) / dlat), both clamped to the grid); packets with a non-finite
+// lon/lat sit after cell_start[ncells] and are never walked (they are in no ball).  A workgroup
+// owns a tile of `tile` consecutive longitudes of one latitude row and walks the candidate cells
+// the host listed for it (segments of consecutive cells: the latitude band |dphi| <= r_p and a
+// longitude window that wraps at 0 / 2 pi and opens to the whole row near the poles, each grown
+// by one cell).  The tile's histograms live in LDS (ds_add_f64) and are added once to the
+// resident map with plain loads and stores: no other workgroup touches those points in a launch.
+struct SmapK {
+    double r_km;             // speed = v * r_km
+    double vel_lo, vel_hi, vel_inv;      // speed edges (staged in LDS by k_smap_prep)
+    double alt_lo, alt_hi, alt_inv;
+    double az_lo, az_hi, az_inv;
+    double lon_lo, lon_hi, lon_inv;
+    double lat_lo, lat_hi, lat_inv;
+    int nlon, nlat, nvel, nalt, naz;
+    int available;           // 1: weight 1 ('available'); 0: weight frac ('source')
+    int tile, tiles_per_row;
+    int nseg_max;
+    int reserved;
+};
+
+__host__ __device__ inline int smap_stride(const SmapK &K) { return K.nvel + K.nalt + K.naz + 3; }
+
+// LDS of k_smap_prep: edges (speed, altitude, azimuth, longitude, latitude), then the
+// whole-planet histograms [nvel | nalt | naz].
+NXC_DEV int smap_edges_bytes(const SmapK &K)
+{
+    return 8 * (K.nvel + K.nalt + K.naz + K.nlon + K.nlat + 5);
+}
+
+// Per packet: {lat, lon, cos(lat), weight} and {speed bin, altitude bin, azimuth bin, included};
+// a bin is -1 for an excluded packet or a value outside the histogram's range.  The same bins
+// (bin_index: np.histogram's linspace edges, right edge inclusive) feed the whole-planet
+// histograms (LDS, then one global add per bin and workgroup) and the unsmeared lon/lat histogram
+// of the included packets (global fp64 atomics on the resident hist2d).
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_smap_prep(SmapK K, int n, const double *__restrict__ lat, const double *__restrict__ lon,
+            const double *__restrict__ v, const double *__restrict__ alt,
+            const double *__restrict__ az, const double *__restrict__ frac,
+            const double *__restrict__ edges, double4 *__restrict__ geo, int4 *__restrict__ bins,
+            double *__restrict__ planet, double *__restrict__ hist2d)
+{
+    const int ne = K.nvel + K.nalt + K.naz + K.nlon + K.nlat + 5;
+    const int nh = K.nvel + K.nalt + K.naz;
+    double *lds = reinterpret_cast<double *>(nxc_lds);
+    for (int e = threadIdx.x; e < ne; e += blockDim.x) lds[e] = edges[e];
+    for (int e = threadIdx.x; e < nh; e += blockDim.x) lds[ne + e] = 0.0;
+    __syncthreads();
+    const int e_vel = 0, e_alt = 8 * (K.nvel + 1), e_az = e_alt + 8 * (K.nalt + 1);
+    const int e_lon = e_az + 8 * (K.naz + 1), e_lat = e_lon + 8 * (K.nlon + 1);
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < n; q += gridDim.x * blockDim.x) {
+        const double f = frac[q];
+        const double w = K.available ? 1.0 : f;
+        const bool incl = f > 0.0;
+        int vb = -1, ab = -1, zb = -1;
+        if (incl) {
+            vb = bin_index(v[q] * K.r_km, e_vel, K.nvel, K.vel_lo, K.vel_hi, K.vel_inv);
+            ab = bin_index(alt[q], e_alt, K.nalt, K.alt_lo, K.alt_hi, K.alt_inv);
+            zb = bin_index(az[q], e_az, K.naz, K.az_lo, K.az_hi, K.az_inv);
+            if (vb >= 0) atomicAdd(&lds[ne + vb], w);
+            if (ab >= 0) atomicAdd(&lds[ne + K.nvel + ab], w);
+            if (zb >= 0) atomicAdd(&lds[ne + K.nvel + K.nalt + zb], w);
+            const int ib = bin_index(lon[q], e_lon, K.nlon, K.lon_lo, K.lon_hi, K.lon_inv);
+            const int jb = bin_index(lat[q], e_lat, K.nlat, K.lat_lo, K.lat_hi, K.lat_inv);
+            if (ib >= 0 && jb >= 0) unsafeAtomicAdd(&hist2d[(int64_t)ib * K.nlat + jb], w);
+        }
+        const double phi = lat[q];
+        geo[q] = make_double4(phi, lon[q], cos(phi), w);
+        bins[q] = make_int4(vb, ab, zb, incl ? 1 : 0);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < nh; e += blockDim.x) {
+        const double s = lds[ne + e];
+        if (s != 0.0) unsafeAtomicAdd(&planet[e], s);
+    }
+}
+
+// One workgroup per tile.  LDS: the tile's map [tile][stride] doubles, then the segment starts
+// (packet index) and their exclusive prefix lengths (nseg_max + 1 ints each).
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_smap_points(SmapK K, const double4 *__restrict__ geo, const int4 *__restrict__ bins,
+              const int *__restrict__ cell_start, const int2 *__restrict__ seg,
+              const int *__restrict__ seg_off, const double *__restrict__ pt_lon,
+              const double *__restrict__ pt_lat, const double *__restrict__ pt_cos,
+              const double *__restrict__ thr, double factor, double *__restrict__ acc,
+              double *__restrict__ partial)
+{
+    const int stride = smap_stride(K);
+    const int t = blockIdx.x;
+    const int j = t / K.tiles_per_row;
+    const int i0 = (t - j * K.tiles_per_row) * K.tile;
+    const int nt = min(K.tile, K.nlon - i0);
+    double *h = reinterpret_cast<double *>(nxc_lds);
+    int *sbeg = reinterpret_cast<int *>(nxc_lds + 8 * K.tile * stride);
+    int *spre = sbeg + K.nseg_max + 1;
+    for (int e = threadIdx.x; e < K.tile * stride; e += blockDim.x) h[e] = 0.0;
+    const int s0 = seg_off[t], ns = seg_off[t + 1] - s0;
+    for (int s = threadIdx.x; s < ns; s += blockDim.x) {
+        const int2 c = seg[s0 + s];
+        sbeg[s] = cell_start[c.x];
+        spre[s + 1] = cell_start[c.y + 1] - cell_start[c.x];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        spre[0] = 0;
+        for (int s = 0; s < ns; s++) spre[s + 1] += spre[s];
+    }
+    __syncthreads();
+    const int total = spre[ns];
+    const double phi_p = pt_lat[j], cos_p = pt_cos[j], th = thr[j];
+    const int nb = K.nvel + K.nalt + K.naz;
+    int s = 0;
+    for (int k = threadIdx.x; k < total; k += blockDim.x) {
+        while (spre[s + 1] <= k) ++s;                   // k only grows: s only moves forward
+        const int q = sbeg[s] + (k - spre[s]);
+        const double4 g = geo[q];
+        const int4 b = bins[q];
+        const double s_lat = sin(0.5 * (phi_p - g.x));
+        const double a = s_lat * s_lat;
+        const double cc = cos_p * g.z;
+        for (int u = 0; u < nt; u++) {
+            const double s_lon = sin(0.5 * (pt_lon[i0 + u] - g.y));
+            const double hav = a + cc * s_lon * s_lon;
+            if (hav <= th) {
+                double *hp = h + u * stride;
+                atomicAdd(&hp[nb], 1.0);
+                if (b.w) atomicAdd(&hp[nb + 1], 1.0);
+                atomicAdd(&hp[nb + 2], g.w);
+                if (b.x >= 0) atomicAdd(&hp[b.x], g.w);
+                if (b.y >= 0) atomicAdd(&hp[K.nvel + b.y], g.w);
+                if (b.z >= 0) atomicAdd(&hp[K.nvel + K.nalt + b.z], g.w);
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < nt * stride; e += blockDim.x) {
+        const int u = e / stride, c = e - u * stride;
+        const int64_t p = (int64_t)(i0 + u) * K.nlat + j;
+        const double add = c < K.nvel ? factor * h[e] : h[e];
+        acc[p * stride + c] += add;
+    }
+    // this tile's share of the Output's grid-summed speed histograms (the interp term)
+    for (int c = threadIdx.x; c < K.nvel; c += blockDim.x) {
+        double sum = 0.0;
+        for (int u = 0; u < nt; u++) sum += h[u * stride + c];
+        partial[(int64_t)t * K.nvel + c] = sum;
+    }
+}
+
+// The grid-summed speed histogram of one Output: workgroup c sums bin c over the tiles, thread k
+// the tiles k, k + 256, ... in order, then a fixed tree in LDS (the same sum on every call).
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_smap_gridsum(int ntiles, int nvel, const double *__restrict__ partial, double *__restrict__ out)
+{
+    double *red = reinterpret_cast<double *>(nxc_lds);
+    const int c = blockIdx.x;
+    double sum = 0.0;
+    for (int t = threadIdx.x; t < ntiles; t += NXC_BLOCK) sum += partial[(int64_t)t * nvel + c];
+    red[threadIdx.x] = sum;
+    __syncthreads();
+    for (int half = NXC_BLOCK / 2; half > 0; half >>= 1) {
+        if (threadIdx.x < half) red[threadIdx.x] += red[threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[c] = red[0];
+}

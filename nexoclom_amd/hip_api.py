@@ -40,7 +40,8 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_density_download', 'nxc_pairs_create', 'nxc_pairs_free', 'nxc_pairs_count',
            'nxc_pairs_download', 'nxc_los_set_pairs', 'nxc_fit_set', 'nxc_fit_source_rows',
            'nxc_fit_source', 'nxc_fit_source_f32', 'nxc_fit_packets', 'nxc_fit_radiance',
-           'nxc_fit_rows', 'nxc_fit_download')
+           'nxc_fit_rows', 'nxc_fit_download', 'nxc_source_map_set', 'nxc_source_map_accumulate',
+           'nxc_source_map_download')
 ABI_VERSION = 3
 
 
@@ -85,6 +86,15 @@ class nxc_density_desc(C.Structure):
     _fields_ = [('origin', C.c_double*3), ('h', C.c_double), ('dr', C.c_double),
                 ('dims', C.c_int64*3), ('n_points', C.c_int64), ('points', _dp),
                 ('cell_start', C.POINTER(C.c_int32))]
+
+
+class nxc_source_map_desc(C.Structure):
+    _fields_ = [('nlon', C.c_int64), ('nlat', C.c_int64), ('nvel', C.c_int64),
+                ('nalt', C.c_int64), ('naz', C.c_int64), ('tile', C.c_int64), ('r_km', C.c_double),
+                ('alt_edges', _dp), ('az_edges', _dp), ('lon_edges', _dp), ('lat_edges', _dp),
+                ('point_lon', _dp), ('point_lat', _dp), ('point_cos', _dp), ('threshold', _dp),
+                ('n_seg', C.c_int64), ('seg', C.POINTER(C.c_int32)),
+                ('seg_off', C.POINTER(C.c_int32))]
 
 
 class nxc_fit_desc(C.Structure):
@@ -862,6 +872,57 @@ class Context:
         out = np.zeros(getattr(self, '_fit_s', 0))
         self._check(self.lib.nxc_fit_download(self._h, _p(out)))
         return out
+
+    # -- source maps ------------------------------------------------------------------------
+    def source_map_set(self, grid):
+        """Upload a source-map grid (sourcemap.SourceMapGrid: edges, point centres, cos and
+        thresholds per latitude row, tile segments) and zero the resident map."""
+        keep = [_f64(a) for a in (grid.alt_edges, grid.az_edges, grid.lon_edges, grid.lat_edges,
+                                  grid.lon, grid.lat, grid.cos_lat, grid.threshold)]
+        seg = np.ascontiguousarray(grid.seg, dtype=np.int32).reshape(-1, 2)
+        seg_off = np.ascontiguousarray(grid.seg_off, dtype=np.int32)
+        d = nxc_source_map_desc()
+        d.nlon, d.nlat, d.nvel, d.nalt, d.naz = (int(v) for v in (
+            grid.nlon, grid.nlat, grid.nvel, grid.nalt, grid.naz))
+        d.tile, d.r_km = int(grid.tile), float(grid.r_km)
+        (d.alt_edges, d.az_edges, d.lon_edges, d.lat_edges, d.point_lon, d.point_lat,
+         d.point_cos, d.threshold) = (_p(a) for a in keep)
+        d.n_seg = len(seg)
+        d.seg = seg.ctypes.data_as(C.POINTER(C.c_int32)) if len(seg) else None
+        d.seg_off = seg_off.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self.lib.nxc_source_map_set(self._h, C.byref(d)))
+        self._smap = (int(grid.nlon)*int(grid.nlat), int(grid.nvel), int(grid.nalt), int(grid.naz))
+
+    def source_map_accumulate(self, lat, lon, v, alt, az, frac, cell_start, vel_edges,
+                              available, factor):
+        """Add one Output's packets (sorted by cell) to the resident map, its speed histograms
+        times ``factor``.  Returns the Output's whole-planet speed, altitude and azimuth histograms
+        and its speed map summed over the grid."""
+        _, nvel, nalt, naz = self._smap
+        cols = [_f64(c) for c in (lat, lon, v, alt, az, frac)]
+        starts = np.ascontiguousarray(cell_start, dtype=np.int32)
+        edges = _f64(vel_edges)
+        small = np.zeros(nvel + nalt + naz + nvel)
+        n = len(cols[0])
+        if any(len(c) != n for c in cols) or len(starts) != self._smap[0] + 1 or \
+                len(edges) != nvel + 1:
+            raise ValueError('source_map_accumulate: column, cell-start or edge lengths differ '
+                             'from the grid')
+        ptr = [(_p(c) if n else None) for c in cols]
+        self._check(self.lib.nxc_source_map_accumulate(
+            self._h, C.c_int64(n), *ptr, starts.ctypes.data_as(C.POINTER(C.c_int32)), _p(edges),
+            C.c_int32(int(bool(available))), C.c_double(float(factor)), _p(small)))
+        return dict(speed_dist=small[:nvel], altitude_dist=small[nvel:nvel + nalt],
+                    azimuth_dist=small[nvel + nalt:nvel + nalt + naz],
+                    speed_gridsum=small[nvel + nalt + naz:])
+
+    def source_map_download(self):
+        """(map [npoints, nvel + nalt + naz + 3], unsmeared histogram [npoints])."""
+        npoints, nvel, nalt, naz = self._smap
+        out = np.zeros((npoints, nvel + nalt + naz + 3))
+        hist2d = np.zeros(npoints)
+        self._check(self.lib.nxc_source_map_download(self._h, _p(out), _p(hist2d)))
+        return out, hist2d
 
     # -- RCCL -------------------------------------------------------------------------------
     def comm_unique_id(self):
