@@ -182,10 +182,7 @@ class LOSResult(ModelResult):
                                                 rows=(store, first, count, packet0), **extra)
         else:
             samples = output.X
-            if 'Index' in samples.columns:
-                index = samples['Index'].values
-            else:
-                index = np.arange(len(samples))
+            index = Output.packet_index(samples)
             n_index = int(len(output.X0)) if len(output.X0) else int(index.max()) + 1
             res = self.context().los_accumulate(
                 *setup, *(samples[c].values for c in ('x', 'y', 'z', 'vy', 'frac')),

@@ -142,7 +142,7 @@ class LOSResultFitted(LOSResult):
             ctx.fit_source(rows=view)
         else:
             X = run.X
-            index = X['Index'].values if 'Index' in X.columns else np.arange(len(X))
+            index = Output.packet_index(X)
             ctx.fit_source(*(X[c].values for c in ('x', 'y', 'z', 'vy', 'frac')), index=index)
         # 2. the multipliers
         res = ctx.fit_packets(pairs, n_packets)
@@ -166,6 +166,7 @@ class LOSResultFitted(LOSResult):
 
     def _fitted_output(self, run, ctx, view, mult):
         """A new Output: ``run`` with frac' = frac * mult[packet] in its rows and X0."""
+        from .Output import Output
         fitted = copy.copy(run)
         fitted.inputs = self.inputs
         fitted.filename, fitted.idnum = None, None
@@ -189,7 +190,7 @@ class LOSResultFitted(LOSResult):
         else:
             X = run.X
             if len(X) and 'frac' in X:
-                index = X['Index'].values if 'Index' in X.columns else np.arange(len(X))
+                index = Output.packet_index(X)
                 frac = X['frac'].values
                 new = frac.astype(np.float64)*mult[index]
                 X = X.copy()

@@ -652,6 +652,12 @@ class Output:
 
     IMAGE_COLS = ('x', 'y', 'z', 'vy', 'frac')
 
+    @staticmethod
+    def packet_index(frame):
+        """The packet of every row of a host frame: its Index column, or the row number when it
+        has none."""
+        return frame['Index'].values if 'Index' in frame.columns else np.arange(len(frame))
+
     @classmethod
     def image_columns(cls, source):
         """What create_image needs of a stored Output, without restoring the rest: the five

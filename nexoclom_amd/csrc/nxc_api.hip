@@ -327,14 +327,18 @@ struct nxc_pairs {
     long long *d = nullptr;
 };
 
-// LOSResultFitted's samples (nxc_fit_source*): a row range of a store or host columns uploaded
-struct FitSource {
-    bool set = false, f32 = false, index64 = true;
-    const nxc_rows *store = nullptr;
-    int64_t n = 0, shift = 0, stride = 0;    // rows, index shift, distance between columns
-    const void *col0 = nullptr;              // column 0 of row 0 (stores: all nine columns)
-    const void *cols[5] = {};                // x, y, z, vy, frac
-    const void *index = nullptr;
+// Stored samples on the device, as every consumer (image, line of sight, density, fit) reads them:
+// a row range of a store (samples_from_rows) or host columns uploaded (samples_upload)
+struct Samples {
+    bool f32 = false, index64 = true;
+    int64_t n = 0, shift = 0;                // rows, index shift
+    const void *cols[5] = {};                // x, y, z, vy, frac (vy null where nobody reads it)
+    const void *index = nullptr;             // null where the entry allows it
+    const nxc_rows *store = nullptr;         // stores: the store, column 0 of row 0 and the
+    const void *col0 = nullptr;              // distance between columns (the fit's rows copy
+    int64_t stride = 0;                      // all nine columns)
+    template <typename T> const T *col(int c) const { return static_cast<const T *>(cols[c]); }
+    template <typename I> const I *idx() const { return static_cast<const I *>(index); }
 };
 
 struct nxc_handle {
@@ -448,7 +452,8 @@ struct nxc_handle {
     bool have_fit = false;
     int64_t fit_S = 0, fit_np = -1;  // fit_np: packets whose multipliers are ready (nxc_fit_packets)
     int fit_mode = 0;
-    FitSource fit_src;
+    bool have_fit_src = false;
+    Samples fit_src;
     double *d_fit_spec = nullptr;    // position [3][S] | ratio | weight | radiance sums | mask bytes
     size_t fit_spec_cap = 0;
     unsigned char *d_fit_pk = nullptr;   // num | den | mult (f64) | cnt | lengths (u32) per packet
@@ -1087,6 +1092,59 @@ int rows_check(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
     return NXC_OK;
 }
 
+// ---- sample views ------------------------------------------------------------------------------
+constexpr int ROW_SAMPLE_COLS[5] = {1, 2, 3, 5, 7};   // the store columns of x, y, z, vy, frac
+
+// rows [first, first + count) of a store (its index is int32 beside float32 rows, else int64)
+int samples_from_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count, int64_t shift,
+                      Samples *s)
+{
+    int rc = rows_check(h, r, first, count);
+    if (rc) return rc;
+    const size_t vsz = r->f32 ? 4 : 8;
+    const char *c = static_cast<const char *>(r->d_cols) + (size_t)first * vsz;
+    *s = Samples{};
+    for (int k = 0; k < 5; k++) s->cols[k] = c + (size_t)ROW_SAMPLE_COLS[k] * r->total * vsz;
+    s->index = static_cast<const char *>(r->d_index) + (size_t)first * vsz;
+    s->f32 = r->f32; s->index64 = !r->f32; s->n = count; s->shift = shift;
+    s->store = r; s->col0 = c; s->stride = r->total;
+    return NXC_OK;
+}
+
+// P samples in host memory, 64-bit or as save() keeps them (32-bit), to the device buffer *buf:
+// each column (null ones are skipped) 256-byte aligned, then the int64 index if there is one
+template <typename T>
+int samples_upload(nxc_handle *h, unsigned char **buf, size_t *cap, int64_t P, const T *const cols[5],
+                   const int64_t *index, Samples *s)
+{
+    const size_t bytes = (size_t)P * sizeof(T), col = (bytes + 255) & ~size_t(255);
+    const size_t n_cols = 5 - std::count(cols, cols + 5, nullptr);
+    int rc = ensure(reinterpret_cast<void **>(buf), cap, n_cols * col + (index ? (size_t)P * 8 : 0));
+    if (rc) return rc;
+    *s = Samples{};
+    s->f32 = sizeof(T) == 4; s->n = P;
+    unsigned char *d = *buf;
+    for (int c = 0; c < 5; c++) {
+        if (!cols[c]) continue;
+        if (P) HIPCHK(hipMemcpyAsync(d, cols[c], bytes, hipMemcpyHostToDevice, h->stream));
+        s->cols[c] = d;
+        d += col;
+    }
+    if (index && P) HIPCHK(hipMemcpyAsync(d, index, (size_t)P * 8, hipMemcpyHostToDevice, h->stream));
+    s->index = index ? d : nullptr;
+    return NXC_OK;
+}
+
+// Calls f(T(), I()) with the value and index types of s: (double, long long), (float, int) for
+// float32 stores or (float, long long) for float32 host columns -- the only instantiations
+template <typename Fn>
+int with_sample_types(const Samples &s, Fn &&f)
+{
+    if (!s.f32) return f(double(), (long long)0);
+    if (s.index64) return f(float(), (long long)0);
+    return f(float(), int());
+}
+
 // nxc_rows_fetch / nxc_rows_fetch_f32: build, copy out, free
 int rows_fetch(nxc_handle *h, void *rows_out, bool narrow)
 {
@@ -1316,6 +1374,19 @@ int los_check(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
     return NXC_OK;
 }
 
+// ... over a sample view
+int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, const Samples &s,
+            int64_t n_index, double *radiance, int64_t *npackets, uint8_t *included, int64_t used_cap,
+            int64_t *used_pairs, int64_t *n_used)
+{
+    return with_sample_types(s, [&](auto t, auto i) {
+        using T = decltype(t);
+        return los_run(h, d, S, sc, s.n, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3), s.col<T>(4),
+                       s.idx<decltype(i)>(), s.shift, n_index, radiance, npackets, included, used_cap,
+                       used_pairs, n_used);
+    });
+}
+
 // ... over samples in host memory: five columns (+ the index column) go to the device first
 template <typename T>
 int los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, int64_t P,
@@ -1327,21 +1398,10 @@ int los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double
                        n_used);
     if (rc) return rc;
     if (P && (!x || !y || !z || !vy || !frac)) return fail(NXC_ERR_ARG, "bad arguments");
-    const size_t colP = ((size_t)P * sizeof(T) + 255) & ~size_t(255);
-    const size_t idx_bytes = index ? (size_t)P * 8 : 0;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_samples), &h->samples_cap, 5 * colP + idx_bytes)))
-        return rc;
     const T *cols[5] = {x, y, z, vy, frac};
-    for (int c = 0; c < 5 && P; c++)
-        HIPCHK(hipMemcpyAsync(h->d_samples + c * colP, cols[c], (size_t)P * sizeof(T),
-                              hipMemcpyHostToDevice, h->stream));
-    if (index && P)
-        HIPCHK(hipMemcpyAsync(h->d_samples + 5 * colP, index, idx_bytes, hipMemcpyHostToDevice, h->stream));
-    auto col = [&](int c) { return reinterpret_cast<const T *>(h->d_samples + c * colP); };
-    return los_run<T, long long>(h, d, S, sc, P, col(0), col(1), col(2), col(3), col(4),
-                                 index ? reinterpret_cast<const long long *>(h->d_samples + 5 * colP)
-                                       : (const long long *)nullptr,
-                                 0, n_index, radiance, npackets, included, used_cap, used_pairs, n_used);
+    Samples s;
+    if ((rc = samples_upload(h, &h->d_samples, &h->samples_cap, P, cols, index, &s))) return rc;
+    return los_run(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs, n_used);
 }
 
 // Geometry of the tiled image: tile b = image rows ix = b (mod nb), nb a power of two; a tile's
@@ -1484,6 +1544,15 @@ int image_run(nxc_handle *h, int64_t p, const T *dx, const T *dy, const T *dz, c
     return NXC_OK;
 }
 
+// ... over a sample view
+int image_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) {
+        using T = decltype(t);
+        return image_run(h, s.n, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3), s.col<T>(4));
+    });
+}
+
 // ... over samples in host memory, 64-bit or as save() keeps them (32-bit)
 template <typename T>
 int image_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T *z, const T *vy,
@@ -1494,14 +1563,10 @@ int image_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T *
     if (p < 0 || (p && (!x || !y || !z || !vy || !frac))) return fail(NXC_ERR_ARG, "bad arguments");
     HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
     if (p == 0) return NXC_OK;
-    const size_t col = (size_t)p * sizeof(T);
-    int rc = ensure(reinterpret_cast<void **>(&h->d_samples), &h->samples_cap, 5 * col);
-    if (rc) return rc;
-    T *d = reinterpret_cast<T *>(h->d_samples);
-    const T *src[5] = {x, y, z, vy, frac};
-    for (int c = 0; c < 5; c++)
-        HIPCHK(hipMemcpyAsync(d + c * p, src[c], col, hipMemcpyHostToDevice, h->stream));
-    return image_run<T>(h, p, d, d + p, d + 2 * p, d + 3 * p, d + 4 * p);
+    const T *cols[5] = {x, y, z, vy, frac};
+    Samples s;
+    int rc = samples_upload(h, &h->d_samples, &h->samples_cap, p, cols, nullptr, &s);
+    return rc ? rc : image_run(h, s);
 }
 
 // ModelDensity over samples on the device (k_density)
@@ -1523,6 +1588,15 @@ int density_run(nxc_handle *h, int64_t p, const T *dx, const T *dy, const T *dz,
     return NXC_OK;
 }
 
+// ... over a sample view (vy is not read)
+int density_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) {
+        using T = decltype(t);
+        return density_run(h, s.n, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(4));
+    });
+}
+
 // ... over samples in host memory, 64-bit or as save() keeps them (32-bit)
 template <typename T>
 int density_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T *z, const T *frac)
@@ -1531,31 +1605,18 @@ int density_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T
     if (p < 0 || (p && (!x || !y || !z || !frac))) return fail(NXC_ERR_ARG, "bad arguments");
     HIPCHK(hipSetDevice(h->device));
     if (p == 0 || h->dens_q == 0) return NXC_OK;
-    const size_t col = (size_t)p * sizeof(T);
-    int rc = ensure(reinterpret_cast<void **>(&h->d_samples), &h->samples_cap, 4 * col);
-    if (rc) return rc;
-    T *d = reinterpret_cast<T *>(h->d_samples);
-    const T *src[4] = {x, y, z, frac};
-    for (int c = 0; c < 4; c++)
-        HIPCHK(hipMemcpyAsync(d + c * p, src[c], col, hipMemcpyHostToDevice, h->stream));
-    return density_run<T>(h, p, d, d + p, d + 2 * p, d + 3 * p);
+    const T *cols[5] = {x, y, z, nullptr, frac};
+    Samples s;
+    int rc = samples_upload(h, &h->d_samples, &h->samples_cap, p, cols, nullptr, &s);
+    return rc ? rc : density_run(h, s);
 }
 
 
 // ---- LOSResultFitted -------------------------------------------------------------------------
-// Calls f(T*, I*) with null pointers of the fit source's sample and index types.
-template <typename Fn>
-int fit_types(const FitSource &s, Fn &&f)
-{
-    if (s.f32 && !s.index64) return f((const float *)nullptr, (const int *)nullptr);
-    if (s.f32) return f((const float *)nullptr, (const long long *)nullptr);
-    return f((const double *)nullptr, (const long long *)nullptr);
-}
-
 int fit_check(nxc_handle *h, const nxc_pairs *p)
 {
     if (!h || !h->have_fit) return fail(NXC_ERR_STATE, "nxc_fit_set has not been called");
-    if (!h->fit_src.set) return fail(NXC_ERR_STATE, "no fit source: call nxc_fit_source*");
+    if (!h->have_fit_src) return fail(NXC_ERR_STATE, "no fit source: call nxc_fit_source*");
     if (!p || p->device != h->device || p->n < 0 || p->n > p->cap)
         return fail(NXC_ERR_ARG, "bad pair list");
     HIPCHK(hipSetDevice(h->device));
@@ -1608,6 +1669,8 @@ int64_t fit_grid(const nxc_handle *h, int64_t work, int per_cu)
     return std::max<int64_t>(1, std::min<int64_t>((int64_t)h->n_cu * per_cu, (work + NXC_BLOCK - 1) / NXC_BLOCK));
 }
 
+// host columns go to a buffer of their own: the source outlives the image and line-of-sight calls,
+// which stage theirs in d_samples
 template <typename T>
 int fit_source_columns(nxc_handle *h, int64_t P, const T *x, const T *y, const T *z, const T *vy,
                        const T *frac, const int64_t *index)
@@ -1615,36 +1678,23 @@ int fit_source_columns(nxc_handle *h, int64_t P, const T *x, const T *y, const T
     if (!h || !h->have_fit) return fail(NXC_ERR_STATE, "nxc_fit_set has not been called");
     if (P < 0 || (P && (!x || !y || !z || !vy || !frac || !index))) return fail(NXC_ERR_ARG, "bad arguments");
     HIPCHK(hipSetDevice(h->device));
-    h->fit_src = FitSource{};
+    h->have_fit_src = false;
     h->fit_np = -1;
-    const size_t col = ((size_t)P * sizeof(T) + 255) & ~size_t(255);
-    int rc = ensure(reinterpret_cast<void **>(&h->d_fit_smp), &h->fit_smp_cap, 5 * col + (size_t)P * 8 + 8);
-    if (rc) return rc;
-    const T *src[5] = {x, y, z, vy, frac};
-    for (int c = 0; c < 5; c++) {
-        if (P) HIPCHK(hipMemcpyAsync(h->d_fit_smp + c * col, src[c], (size_t)P * sizeof(T),
-                                     hipMemcpyHostToDevice, h->stream));
-        h->fit_src.cols[c] = h->d_fit_smp + c * col;
-    }
-    if (P) HIPCHK(hipMemcpyAsync(h->d_fit_smp + 5 * col, index, (size_t)P * 8, hipMemcpyHostToDevice, h->stream));
-    h->fit_src.index = h->d_fit_smp + 5 * col;
-    h->fit_src.f32 = sizeof(T) == 4;
-    h->fit_src.index64 = true;
-    h->fit_src.n = P;
-    h->fit_src.set = true;
-    return NXC_OK;
+    const T *cols[5] = {x, y, z, vy, frac};
+    int rc = samples_upload(h, &h->d_fit_smp, &h->fit_smp_cap, P, cols, index, &h->fit_src);
+    h->have_fit_src = rc == NXC_OK;
+    return rc;
 }
 
 template <typename T, typename I>
 int fit_packets_run(nxc_handle *h, const nxc_pairs *p, int64_t n_packets, unsigned long long *ctr)
 {
-    const FitSource &s = h->fit_src;
+    const Samples &s = h->fit_src;
     const FitK F = fit_consts(h, p, n_packets);
     if (F.n_pairs > 0) {
         hipLaunchKernelGGL((k_fit_packets<T, I>), dim3((unsigned)fit_grid(h, F.n_pairs, 8)), dim3(NXC_BLOCK), 0,
                            h->stream, F, p->d, fit_pos(h), fit_ratio(h), fit_weight(h), fit_mask(h),
-                           static_cast<const T *>(s.cols[0]), static_cast<const T *>(s.cols[1]),
-                           static_cast<const T *>(s.cols[2]), static_cast<const I *>(s.index),
+                           s.col<T>(0), s.col<T>(1), s.col<T>(2), s.idx<I>(),
                            fit_num(h, n_packets), fit_den(h, n_packets), fit_cnt(h, n_packets), ctr);
         HIPCHK(hipGetLastError());
     }
@@ -1655,7 +1705,7 @@ template <typename T, typename I>
 int fit_radiance_run(nxc_handle *h, const nxc_pairs *p, const LosK &K, size_t stage_bytes,
                      const unsigned char *d_blob, unsigned long long *ctr)
 {
-    const FitSource &s = h->fit_src;
+    const Samples &s = h->fit_src;
     const FitK F = fit_consts(h, p, h->fit_np);
     if (F.n_pairs == 0) return NXC_OK;
     size_t lds = (stage_bytes + 31) & ~size_t(31);
@@ -1666,10 +1716,8 @@ int fit_radiance_run(nxc_handle *h, const nxc_pairs *p, const LosK &K, size_t st
     if ((rc = prep_kernel(k_fit_radiance<T, I>, lds))) return rc;
     hipLaunchKernelGGL((k_fit_radiance<T, I>), dim3((unsigned)fit_grid(h, F.n_pairs, 2)), dim3(NXC_BLOCK), lds,
                        h->stream, K, d_blob, (int64_t)stage_bytes, F, lds_sums, p->d, fit_pos(h),
-                       fit_mult(h, h->fit_np), static_cast<const T *>(s.cols[0]),
-                       static_cast<const T *>(s.cols[1]), static_cast<const T *>(s.cols[2]),
-                       static_cast<const T *>(s.cols[3]), static_cast<const T *>(s.cols[4]),
-                       static_cast<const I *>(s.index), fit_rad(h), ctr, ctr + 1);
+                       fit_mult(h, h->fit_np), s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3),
+                       s.col<T>(4), s.idx<I>(), fit_rad(h), ctr, ctr + 1);
     HIPCHK(hipGetLastError());
     return NXC_OK;
 }
@@ -1677,7 +1725,7 @@ int fit_radiance_run(nxc_handle *h, const nxc_pairs *p, const LosK &K, size_t st
 template <typename T, typename I>
 int fit_rows_run(nxc_handle *h, int compress, nxc_rows **out, int64_t *lengths_out)
 {
-    const FitSource &s = h->fit_src;
+    const Samples &s = h->fit_src;
     const int64_t n = s.n, np = h->fit_np, tiles = (n + NXC_BLOCK - 1) / NXC_BLOCK;
     FitK F = fit_consts(h, nullptr, np);
     F.compress = compress ? 1 : 0;
@@ -1687,8 +1735,8 @@ int fit_rows_run(nxc_handle *h, int compress, nxc_rows **out, int64_t *lengths_o
     long long *tile_off;
     int rc = fit_aux(h, 0, tiles, &blob, &ctr, &tile_n, &tile_off);
     if (rc) return rc;
-    const T *frac = static_cast<const T *>(s.col0) + 7 * s.stride;
-    const I *index = static_cast<const I *>(s.index);
+    const T *frac = s.col<T>(4);
+    const I *index = s.idx<I>();
     if (np) HIPCHK(hipMemsetAsync(fit_len(h, np), 0, (size_t)np * 4, h->stream));
     std::vector<unsigned> kept((size_t)tiles);
     std::vector<long long> offs((size_t)tiles);
@@ -2788,20 +2836,12 @@ int nxc_image_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, i
 {
     return guarded([&]() -> int {
     if (!h || !h->have_image) return fail(NXC_ERR_STATE, "nxc_set_image has not been called");
-    int rc = rows_check(h, r, first, count);
+    Samples s;
+    int rc = samples_from_rows(h, r, first, count, 0, &s);
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
-    if (count == 0) return NXC_OK;
-    // columns 1, 2, 3, 5, 7 of the store = x, y, z, vy, frac
-    if (r->f32) {
-        const float *c = static_cast<const float *>(r->d_cols) + first;
-        const long long t = r->total;
-        return image_run<float>(h, count, c + t, c + 2 * t, c + 3 * t, c + 5 * t, c + 7 * t);
-    }
-    const double *c = static_cast<const double *>(r->d_cols) + first;
-    const long long t = r->total;
-    return image_run<double>(h, count, c + t, c + 2 * t, c + 3 * t, c + 5 * t, c + 7 * t);
+    return count ? image_run(h, s) : NXC_OK;
     });
 }
 
@@ -2815,20 +2855,9 @@ int nxc_los_accumulate_rows(nxc_handle *h, const nxc_los_desc *d, int64_t S, con
     int rc = los_check(h, d, S, sc, count, radiance, npackets, included, n_index, used_cap,
                        used_pairs, n_used);
     if (rc) return rc;
-    if ((rc = rows_check(h, r, first, count))) return rc;
-    const long long t = r->total;
-    if (r->f32) {
-        const float *c = static_cast<const float *>(r->d_cols) + first;
-        return los_run<float, int>(h, d, S, sc, count, c + t, c + 2 * t, c + 3 * t, c + 5 * t,
-                                   c + 7 * t, static_cast<const int *>(r->d_index) + first, index_shift,
-                                   n_index,
-                                   radiance, npackets, included, used_cap, used_pairs, n_used);
-    }
-    const double *c = static_cast<const double *>(r->d_cols) + first;
-    return los_run<double, long long>(h, d, S, sc, count, c + t, c + 2 * t, c + 3 * t, c + 5 * t,
-                                      c + 7 * t, static_cast<const long long *>(r->d_index) + first,
-                                      index_shift, n_index, radiance, npackets, included, used_cap, used_pairs,
-                                      n_used);
+    Samples s;
+    if ((rc = samples_from_rows(h, r, first, count, index_shift, &s))) return rc;
+    return los_run(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs, n_used);
     });
 }
 
@@ -2899,17 +2928,11 @@ int nxc_density_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first,
 {
     return guarded([&]() -> int {
     if (!h || !h->have_density) return fail(NXC_ERR_STATE, "nxc_density_set has not been called");
-    int rc = rows_check(h, r, first, count);
+    Samples s;
+    int rc = samples_from_rows(h, r, first, count, 0, &s);
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    // columns 1, 2, 3, 7 of the store = x, y, z, frac
-    const long long t = r->total;
-    if (r->f32) {
-        const float *c = static_cast<const float *>(r->d_cols) + first;
-        return density_run<float>(h, count, c + t, c + 2 * t, c + 3 * t, c + 7 * t);
-    }
-    const double *c = static_cast<const double *>(r->d_cols) + first;
-    return density_run<double>(h, count, c + t, c + 2 * t, c + 3 * t, c + 7 * t);
+    return density_run(h, s);
     });
 }
 
@@ -3210,7 +3233,7 @@ int nxc_fit_set(nxc_handle *h, const nxc_fit_desc *d)
         return fail(NXC_ERR_ARG, "bad nxc_fit_desc");
     HIPCHK(hipSetDevice(h->device));
     h->have_fit = false;
-    h->fit_src = FitSource{};
+    h->have_fit_src = false;
     h->fit_np = -1;
     int rc = ensure(reinterpret_cast<void **>(&h->d_fit_spec), &h->fit_spec_cap, (size_t)S * 6 * 8 + (size_t)S);
     if (rc) return rc;
@@ -3233,25 +3256,12 @@ int nxc_fit_source_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t
 {
     return guarded([&]() -> int {
     if (!h || !h->have_fit) return fail(NXC_ERR_STATE, "nxc_fit_set has not been called");
-    int rc = rows_check(h, r, first, count);
+    Samples s;
+    int rc = samples_from_rows(h, r, first, count, index_shift, &s);
     if (rc) return rc;
-    h->fit_src = FitSource{};
+    h->fit_src = s;
+    h->have_fit_src = true;
     h->fit_np = -1;
-    FitSource &s = h->fit_src;
-    const long long t = r->total;
-    const size_t vsz = r->f32 ? 4 : 8;
-    const char *c = static_cast<const char *>(r->d_cols) + (size_t)first * vsz;
-    const int which[5] = {1, 2, 3, 5, 7};           // x, y, z, vy, frac
-    for (int k = 0; k < 5; k++) s.cols[k] = c + (size_t)which[k] * t * vsz;
-    s.col0 = c;
-    s.stride = t;
-    s.index = static_cast<const char *>(r->d_index) + (size_t)first * vsz;
-    s.f32 = r->f32;
-    s.index64 = !r->f32;
-    s.store = r;
-    s.n = count;
-    s.shift = index_shift;
-    s.set = true;
     return NXC_OK;
     });
 }
@@ -3285,9 +3295,8 @@ int nxc_fit_packets(nxc_handle *h, const nxc_pairs *p, int64_t n_packets, double
     HIPCHK(hipMemsetAsync(h->d_fit_pk, 0, (size_t)n_packets * 28, h->stream));   // num, den, mult, cnt
     HIPCHK(hipMemsetAsync(blob, 0, 256 + 64, h->stream));                         // stats, counters
     if ((rc = begin_timed(h))) return rc;
-    rc = fit_types(h->fit_src, [&](auto t, auto i) {
-        return fit_packets_run<std::remove_const_t<std::remove_pointer_t<decltype(t)>>,
-                               std::remove_const_t<std::remove_pointer_t<decltype(i)>>>(h, p, n_packets, ctr);
+    rc = with_sample_types(h->fit_src, [&](auto t, auto i) {
+        return fit_packets_run<decltype(t), decltype(i)>(h, p, n_packets, ctr);
     });
     if (rc) return rc;
     if (n_packets) {
@@ -3332,10 +3341,8 @@ int nxc_fit_radiance(nxc_handle *h, const nxc_pairs *p, const nxc_los_desc *d)
     HIPCHK(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(ctr, 0, 16, h->stream));
     if ((rc = begin_timed(h))) return rc;
-    rc = fit_types(h->fit_src, [&](auto t, auto i) {
-        return fit_radiance_run<std::remove_const_t<std::remove_pointer_t<decltype(t)>>,
-                                std::remove_const_t<std::remove_pointer_t<decltype(i)>>>(h, p, K, blob.size(),
-                                                                                          d_blob, ctr);
+    rc = with_sample_types(h->fit_src, [&](auto t, auto i) {
+        return fit_radiance_run<decltype(t), decltype(i)>(h, p, K, blob.size(), d_blob, ctr);
     });
     if (rc) return rc;
     if ((rc = end_timed(h))) return rc;
@@ -3354,9 +3361,10 @@ int nxc_fit_rows(nxc_handle *h, int compress, nxc_rows **out, int64_t *lengths_o
     if (!out) return fail(NXC_ERR_ARG, "out is null");
     *out = nullptr;
     if (!h || !h->have_fit) return fail(NXC_ERR_STATE, "nxc_fit_set has not been called");
-    if (!h->fit_src.set || !h->fit_src.store) return fail(NXC_ERR_STATE, "nxc_fit_rows needs a row-store source");
+    if (!h->have_fit_src || !h->fit_src.store) return fail(NXC_ERR_STATE, "nxc_fit_rows needs a row-store source");
     if (h->fit_np < 0) return fail(NXC_ERR_STATE, "nxc_fit_rows needs a preceding nxc_fit_packets");
     HIPCHK(hipSetDevice(h->device));
+    // a store's types: (float, int) or (double, long long)
     if (h->fit_src.f32) return fit_rows_run<float, int>(h, compress, out, lengths_out);
     return fit_rows_run<double, long long>(h, compress, out, lengths_out);
     });

@@ -618,19 +618,31 @@ class Context:
                                                _p(final), _p(hs)))
         return np.ascontiguousarray(final.T), hs
 
-    # -- a-6..a-8 ---------------------------------------------------------------------------
-    def image_accumulate(self, x, y, z, vy, frac):
-        """Bin stored samples.  Five float32 columns (an Output as save() keeps it) go to the
-        device as they are and are widened there; anything else is taken as float64."""
-        cols = (x, y, z, vy, frac)
+    # -- stored samples: host columns or a RowStore's rows ----------------------------------
+    @staticmethod
+    def _columns(cols):
+        """(entry suffix, ctypes pointers, arrays to keep alive) of host sample columns: float32
+        ones (an Output as save() keeps it) go to the device as they are and are widened there
+        (suffix '_f32'); anything else is taken as float64 (suffix '')."""
         if all(getattr(c, 'dtype', None) == np.float32 for c in cols):
             cols = [np.ascontiguousarray(c) for c in cols]
-            ptr = [c.ctypes.data_as(C.POINTER(C.c_float)) for c in cols]
-            self._check(self.lib.nxc_image_accumulate_f32(self._h, C.c_int64(len(cols[0])), *ptr))
-            return
-        x, y, z, vy, frac = map(_f64, cols)
-        self._check(self.lib.nxc_image_accumulate(self._h, C.c_int64(len(x)), _p(x), _p(y), _p(z),
-                                                  _p(vy), _p(frac)))
+            return '_f32', [c.ctypes.data_as(C.POINTER(C.c_float)) for c in cols], cols
+        cols = [_f64(c) for c in cols]
+        return '', [_p(c) for c in cols], cols
+
+    @staticmethod
+    def _rows_handle(store):
+        """The nxc_rows of a RowStore that is still in HBM."""
+        if store._r is None:
+            raise HipError('the row store has been freed')
+        return store._r
+
+    # -- a-6..a-8 ---------------------------------------------------------------------------
+    def image_accumulate(self, x, y, z, vy, frac):
+        """Bin stored samples given as host columns (float32 ones go over as they are)."""
+        suffix, ptrs, cols = self._columns((x, y, z, vy, frac))
+        self._check(getattr(self.lib, 'nxc_image_accumulate' + suffix)(
+            self._h, C.c_int64(len(cols[0])), *ptrs))
 
     IMAGE_MODES = {'auto': 0, 'atomics': 1, 'tiles': 2}
 
@@ -645,10 +657,8 @@ class Context:
     def image_accumulate_rows(self, store, first=0, count=None):
         """Bin rows [first, first + count) of a RowStore: no host round trip."""
         count = store.total - first if count is None else int(count)
-        if store._r is None:
-            raise HipError('the row store has been freed')
-        self._check(self.lib.nxc_image_accumulate_rows(self._h, store._r, C.c_int64(first),
-                                                       C.c_int64(count)))
+        self._check(self.lib.nxc_image_accumulate_rows(self._h, self._rows_handle(store),
+                                                       C.c_int64(first), C.c_int64(count)))
 
     # -- f-1: spacecraft lines of sight ------------------------------------------------------
     def los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables,
@@ -696,48 +706,24 @@ class Context:
                                  g_tables, ladder)
         sc = _f64(sc)
         S = sc.shape[1]
+        i64p = C.POINTER(C.c_int64)
         if rows is not None:
             store, first, count, shift = rows
-            if store._r is None:
-                raise HipError('the row store has been freed')
-            radiance = np.zeros(S)
-            npackets = np.zeros(S, dtype=np.int64)
-            included = np.zeros(n_index, dtype=np.uint8) if n_index else None
-            used = np.zeros((2, used_cap), dtype=np.int64) if used_cap else None
-            n_used = C.c_int64(0)
-            i64p = C.POINTER(C.c_int64)
-            self._check(self.lib.nxc_los_accumulate_rows(
-                self._h, C.byref(d), C.c_int64(S), _p(sc), store._r, C.c_int64(first),
-                C.c_int64(count), C.c_int64(shift), C.c_int64(n_index), _p(radiance),
-                npackets.ctypes.data_as(i64p),
-                included.ctypes.data_as(C.POINTER(C.c_uint8)) if included is not None else None,
-                C.c_int64(used_cap), used.ctypes.data_as(i64p) if used is not None else None,
-                C.byref(n_used)))
-            m = min(int(n_used.value), used_cap)
-            return dict(radiance=radiance, npackets=npackets,
-                        included=None if included is None else included.astype(bool),
-                        used=None if used is None else used[:, :m], n_used=int(n_used.value))
-        cols = (x, y, z, vy, frac)
-        narrow = all(getattr(c, 'dtype', None) == np.float32 for c in cols)
-        if narrow:          # stored float32 samples go over as they are; the device widens them
-            cols = [np.ascontiguousarray(c) for c in cols]
-            ptrs = [c.ctypes.data_as(C.POINTER(C.c_float)) for c in cols]
-            entry = self.lib.nxc_los_accumulate_f32
+            entry = self.lib.nxc_los_accumulate_rows
+            samples = (self._rows_handle(store), C.c_int64(first), C.c_int64(count), C.c_int64(shift))
         else:
-            cols = [_f64(c) for c in cols]
-            ptrs = [_p(c) for c in cols]
-            entry = self.lib.nxc_los_accumulate
-        P = len(cols[0])
+            suffix, ptrs, cols = self._columns((x, y, z, vy, frac))
+            idx = None if index is None else np.ascontiguousarray(index, dtype=np.int64)
+            entry = getattr(self.lib, 'nxc_los_accumulate' + suffix)
+            samples = (C.c_int64(len(cols[0])), *ptrs,
+                       idx.ctypes.data_as(i64p) if idx is not None else None)
         radiance = np.zeros(S)
         npackets = np.zeros(S, dtype=np.int64)
-        idx = None if index is None else np.ascontiguousarray(index, dtype=np.int64)
         included = np.zeros(n_index, dtype=np.uint8) if n_index else None
         used = np.zeros((2, used_cap), dtype=np.int64) if used_cap else None
         n_used = C.c_int64(0)
-        i64p = C.POINTER(C.c_int64)
         self._check(entry(
-            self._h, C.byref(d), C.c_int64(S), _p(sc), C.c_int64(P), *ptrs,
-            idx.ctypes.data_as(i64p) if idx is not None else None, C.c_int64(n_index),
+            self._h, C.byref(d), C.c_int64(S), _p(sc), *samples, C.c_int64(n_index),
             _p(radiance), npackets.ctypes.data_as(i64p),
             included.ctypes.data_as(C.POINTER(C.c_uint8)) if included is not None else None,
             C.c_int64(used_cap), used.ctypes.data_as(i64p) if used is not None else None,
@@ -768,20 +754,12 @@ class Context:
         are and are widened on the device), or ``rows = (RowStore, first, count)``."""
         if rows is not None:
             store, first, count = rows
-            if store._r is None:
-                raise HipError('the row store has been freed')
-            self._check(self.lib.nxc_density_accumulate_rows(self._h, store._r, C.c_int64(first),
-                                                             C.c_int64(count)))
+            self._check(self.lib.nxc_density_accumulate_rows(
+                self._h, self._rows_handle(store), C.c_int64(first), C.c_int64(count)))
             return
-        cols = (x, y, z, frac)
-        if all(getattr(c, 'dtype', None) == np.float32 for c in cols):
-            cols = [np.ascontiguousarray(c) for c in cols]
-            ptr = [c.ctypes.data_as(C.POINTER(C.c_float)) for c in cols]
-            self._check(self.lib.nxc_density_accumulate_f32(self._h, C.c_int64(len(cols[0])), *ptr))
-            return
-        cols = [_f64(c) for c in cols]
-        self._check(self.lib.nxc_density_accumulate(self._h, C.c_int64(len(cols[0])),
-                                                    *(_p(c) for c in cols)))
+        suffix, ptrs, cols = self._columns((x, y, z, frac))
+        self._check(getattr(self.lib, 'nxc_density_accumulate' + suffix)(
+            self._h, C.c_int64(len(cols[0])), *ptrs))
 
     def density_download(self):
         """(frac sums, counts) per indexed point, float64, in the index's point order."""
@@ -819,25 +797,16 @@ class Context:
         ones go over as they are), or ``rows = (RowStore, first, count, index_shift)``."""
         if rows is not None:
             store, first, count, shift = rows
-            if store._r is None:
-                raise HipError('the row store has been freed')
+            r = self._rows_handle(store)
             self._fit_store = store
-            self._check(self.lib.nxc_fit_source_rows(self._h, store._r, C.c_int64(first),
+            self._check(self.lib.nxc_fit_source_rows(self._h, r, C.c_int64(first),
                                                      C.c_int64(count), C.c_int64(shift)))
             return
         self._fit_store = None
-        cols = (x, y, z, vy, frac)
+        suffix, ptrs, cols = self._columns((x, y, z, vy, frac))
         idx = np.ascontiguousarray(index, dtype=np.int64)
-        i64p = C.POINTER(C.c_int64)
-        if all(getattr(c, 'dtype', None) == np.float32 for c in cols):
-            cols = [np.ascontiguousarray(c) for c in cols]
-            ptrs = [c.ctypes.data_as(C.POINTER(C.c_float)) for c in cols]
-            entry = self.lib.nxc_fit_source_f32
-        else:
-            cols = [_f64(c) for c in cols]
-            ptrs = [_p(c) for c in cols]
-            entry = self.lib.nxc_fit_source
-        self._check(entry(self._h, C.c_int64(len(idx)), *ptrs, idx.ctypes.data_as(i64p)))
+        self._check(getattr(self.lib, 'nxc_fit_source' + suffix)(
+            self._h, C.c_int64(len(idx)), *ptrs, idx.ctypes.data_as(C.POINTER(C.c_int64))))
 
     def fit_packets(self, pairs, n_packets):
         """Per packet num, den, cnt and the multiplier mult over ``pairs`` (a PairList) and the

@@ -86,7 +86,8 @@ def test_ctypes_structs_match_the_compiled_header(tmp_path):
     import subprocess
     import sys
     structs = ['nxc_forces', 'nxc_image_desc', 'nxc_counters', 'nxc_bounce_desc',
-               'nxc_bodies_desc', 'nxc_source_desc', 'nxc_los_desc']
+               'nxc_bodies_desc', 'nxc_source_desc', 'nxc_los_desc', 'nxc_density_desc',
+               'nxc_source_map_desc', 'nxc_fit_desc']
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', 'int main(void){']
     for name in structs:
         ct = getattr(hip_api, name)
