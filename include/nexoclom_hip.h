@@ -230,6 +230,18 @@ int nxc_last_kernel_ms(nxc_handle *h, float *ms);  /* HIP-event time of the last
  *                             on linspace(0, 2 pi, map_nlon) x linspace(-pi/2, pi/2, map_nlat),
  *                             bilinear between nodes (math/randomdeviates.py:36-83); the device
  *                             runs the trials per packet instead of in rounds of n candidates
+ *             spatial_type 2  'surface map' (:63-83), 2-D: the density that is bilinear between
+ *                             the nodes map[map_nlon][map_nlat] on linspace(map_lon0, map_lon1) x
+ *                             linspace(map_s0, map_s1) in (longitude, sin latitude) -- the law
+ *                             random_deviates_2d accepts against -- drawn exactly from three
+ *                             uniforms, without a loop: the cell from map_cdf (the cells' masses
+ *                             (a + b) + (c + d) of their corner values, cumulated in the order
+ *                             i_lon * (map_nlat - 1) + j_lat and divided by the total), then the
+ *                             point within the cell by inverting two linear densities.  Every
+ *                             packet gets a launch point (no `unfinished`)
+ *             spatial_type 3  'surface map', 1-D (:73-77): latitude 0, longitude =
+ *                             interp(u, map_cdf, map) with map the even longitude grid [map_nlon]
+ *                             and map_cdf its cdf (math/randomdeviates.py:29-33)
  *   speed     speed_type 0/1  flat, gaussian (:141-147,169-171)
  *             speed_type 2    inverse CDF of a tabulated flux density (maxwellian, sputtering;
  *                             :148-168, math/randomdeviates.py:8-33): v = interp(u, speed_cdf,
@@ -249,13 +261,13 @@ typedef struct nxc_source_desc {
     int32_t is_planet;     /* longitude convention (source_distribution.py:13-28)               */
     uint64_t seed;
     int64_t first_index;
-    int32_t spatial_type;  /* 0 uniform, 1 surface spot                                         */
+    int32_t spatial_type;  /* 0 uniform, 1 surface spot, 2 surface map, 3 1-D surface map       */
     int32_t reserved;
     int64_t n_speed;       /* speed_type 2: table length (>= 2)                                 */
     const double *speed_cdf;   /* [n_speed] non-decreasing, first 0, last 1                     */
     const double *speed_v;     /* [n_speed] km/s                                                */
-    int64_t map_nlon, map_nlat;   /* spatial_type 1: density map dims (>= 2 each)               */
-    const double *map;     /* [map_nlon][map_nlat], >= 0                                        */
+    int64_t map_nlon, map_nlat;   /* spatial_type 1, 2: map dims (2..8192 each); 3: map_nlon    */
+    const double *map;     /* [map_nlon][map_nlat], >= 0 (3: the longitude grid [map_nlon])     */
     /* generator 1: the reference's own seeded stream, numpy.random.default_rng(seed) = PCG64
      * (Output.py:92), reproduced on the device: the packets are rows pcg_row0 .. pcg_row0 + n - 1
      * of the pcg_n-packet vectors the reference would draw one after the other ([launch time,]
@@ -271,6 +283,11 @@ typedef struct nxc_source_desc {
      * dest_total packets that several calls fill (pieces in ascending order, the first with
      * dest_offset 0; the set is usable once the last piece is in).  0: they are the whole set.    */
     int64_t dest_offset, dest_total;
+    /* spatial_type 2: [(map_nlon - 1) * (map_nlat - 1)] cumulated cell masses, non-decreasing,
+     * last = 1; spatial_type 3: [map_nlon] cdf of the longitude grid, from 0 to 1               */
+    const double *map_cdf;
+    double map_lon0, map_lon1;   /* spatial_type 2: first and last longitude node, rad          */
+    double map_s0, map_s1;       /* spatial_type 2: first and last sin(latitude) node           */
 } nxc_source_desc;
 
 int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, double *soa_out);

@@ -256,16 +256,23 @@ class Output:
         """Keyword arguments of hip_api.Context.sample_packets for these inputs: the scalar fields
         of nxc_source_desc plus, where the source needs them, ``speed_table`` (maxwellian /
         sputtering: the inverse-CDF table the host sampler interpolates in,
-        math/randomdeviates.py:29-33) and ``surface_map`` (surface spot: the 361 x 181 density map
-        the host sampler rejects against, source_distribution.py:96-113)."""
-        from .source_distribution import density_cdf, spot_density_map, tabulated_speed_density
+        math/randomdeviates.py:29-33; user defined: the same table of the file's speed_dist) and
+        ``surface_map`` (surface spot: the 361 x 181 density map the host sampler rejects against,
+        source_distribution.py:96-113).  A 'surface map' source adds ``map_nodes``, ``map_cdf`` and
+        (2-D) ``map_lon0``, ``map_lon1``, ``map_s0``, ``map_s1``: the file's abundance with the
+        cumulated masses of its cells (source_distribution.surface_map_cells), or for a 1-D map the
+        even longitude grid with its cdf."""
+        from .source_distribution import (density_cdf, speed_file_density, spot_density_map,
+                                          surface_map_cells, surface_map_density,
+                                          tabulated_speed_density)
         sd, vd, ad = self.inputs.spatialdist, self.inputs.speeddist, self.inputs.angulardist
-        if sd.type not in ('uniform', 'surface spot') \
-                or vd.type not in ('flat', 'gaussian', 'maxwellian', 'sputtering') \
+        if sd.type not in ('uniform', 'surface spot', 'surface map') \
+                or vd.type not in ('flat', 'gaussian', 'maxwellian', 'sputtering',
+                                   'user defined') \
                 or ad.type not in ('isotropic', 'radial'):
-            raise NotImplementedError("sampler='device' supports uniform|surface spot / "
-                                      "flat|gaussian|maxwellian|sputtering / isotropic|radial "
-                                      "sources")
+            raise NotImplementedError("sampler='device' supports uniform|surface spot|surface map "
+                                      "/ flat|gaussian|maxwellian|sputtering|user defined / "
+                                      "isotropic|radial sources")
         d = dict(endtime=self.inputs.options.endtime.value, exobase=float(sd.exobase),
                  unit_km=self.unit_km, random_time=int(self.inputs.options.step_size == 0),
                  angular_type=0 if ad.type == 'radial' else 1,
@@ -276,15 +283,25 @@ class Output:
             lon0, lon1 = (float(v) for v in sd.longitude)
             d.update(spatial_type=0, lon0=lon0, lon1=lon1 + 2*np.pi if lon0 > lon1 else lon1,
                      sinlat0=float(np.sin(sd.latitude[0])), sinlat1=float(np.sin(sd.latitude[1])))
-        else:
+        elif sd.type == 'surface spot':
             _, _, density = spot_density_map(float(sd.longitude), float(sd.latitude),
                                              float(sd.sigma))
             d.update(spatial_type=1, surface_map=density)
+        else:
+            longitude, latitude, abundance, sd.coordinate_system = surface_map_density(sd)
+            if latitude is None:
+                cdf, grid = density_cdf(longitude, abundance)
+                d.update(spatial_type=3, map_nodes=grid, map_cdf=cdf)
+            else:
+                cdf, (lon0, lon1, s0, s1) = surface_map_cells(longitude, latitude, abundance)
+                d.update(spatial_type=2, map_nodes=abundance, map_cdf=cdf, map_lon0=lon0,
+                         map_lon1=lon1, map_s0=s0, map_s1=s1)
         if vd.type in ('flat', 'gaussian'):
             d.update(speed_type=0 if vd.type == 'flat' else 1, vprob=vd.vprob.value,
                      vwidth=vd.delv.value if vd.type == 'flat' else vd.sigma.value)
         else:
-            grid, density = tabulated_speed_density(vd, self.inputs.options.species)
+            grid, density = speed_file_density(vd) if vd.type == 'user defined' else \
+                tabulated_speed_density(vd, self.inputs.options.species)
             d.update(speed_type=2, speed_table=density_cdf(grid, density))
         if ad.type == 'isotropic':
             az0, az1 = (float(v) for v in ad.azimuth)

@@ -2408,9 +2408,10 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
     return guarded([&]() -> int {
     if (!h || !d || n < 1) return fail(NXC_ERR_ARG, "bad arguments");
     if (d->speed_type < 0 || d->speed_type > 2 || d->angular_type < 0 || d->angular_type > 1 ||
-        d->spatial_type < 0 || d->spatial_type > 1 || !(d->unit_km > 0) || !(d->exobase > 0))
+        d->spatial_type < 0 || d->spatial_type > 3 || !(d->unit_km > 0) || !(d->exobase > 0))
         return fail(NXC_ERR_ARG, "bad nxc_source_desc");
     const bool tab_speed = d->speed_type == 2, spot = d->spatial_type == 1;
+    const bool map2d = d->spatial_type == 2, map1d = d->spatial_type == 3;
     const bool pcg = d->generator == 1;
     if (d->generator != 0 && d->generator != 1) return fail(NXC_ERR_ARG, "nxc_source_desc: generator must be 0 or 1");
     if (pcg) {
@@ -2442,6 +2443,37 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
         }
         if (!(map_max > 0.0)) return fail(NXC_ERR_ARG, "nxc_source_desc: density map is all zero");
     }
+    // surface map: node values [map_nlon][map_nlat] with the cumulated masses of the
+    // (map_nlon - 1) x (map_nlat - 1) cells; 1-D map: longitude grid [map_nlon] with its cdf
+    const int64_t n_nodes = map2d ? d->map_nlon * d->map_nlat : d->map_nlon;
+    const int64_t n_cdf = map2d ? (d->map_nlon - 1) * (d->map_nlat - 1) : d->map_nlon;
+    if (map2d || map1d) {
+        if (d->map_nlon < 2 || d->map_nlon > 8192 || (map2d && (d->map_nlat < 2 || d->map_nlat > 8192)) ||
+            !d->map || !d->map_cdf)
+            return fail(NXC_ERR_ARG, "nxc_source_desc: a surface map needs 2..8192 nodes per axis, "
+                                     "map and map_cdf");
+        double node_max = 0.0;
+        for (int64_t k = 0; k < n_nodes; k++) {
+            // (a 1-D map's `map` is its longitude grid: finite is all it has to be)
+            if (!std::isfinite(d->map[k]) || (map2d && !(d->map[k] >= 0.0)))
+                return fail(NXC_ERR_ARG, "nxc_source_desc: surface map values must be finite and >= 0 "
+                                         "(node " + std::to_string(k) + ")");
+            node_max = std::max(node_max, d->map[k]);
+        }
+        if (map2d && !(node_max > 0.0)) return fail(NXC_ERR_ARG, "nxc_source_desc: surface map is all zero");
+        if (!(d->map_cdf[0] >= 0.0) || !(d->map_cdf[n_cdf - 1] == 1.0))
+            return fail(NXC_ERR_ARG, "nxc_source_desc: map_cdf must run from >= 0 to 1 (is the map all zero?)");
+        for (int64_t k = 0; k + 1 < n_cdf; k++)
+            if (!(d->map_cdf[k + 1] >= d->map_cdf[k]))
+                return fail(NXC_ERR_ARG, "nxc_source_desc: map_cdf must be non-decreasing");
+        if (map1d && !(d->map_cdf[n_cdf - 1] > d->map_cdf[0]))
+            return fail(NXC_ERR_ARG, "nxc_source_desc: map_cdf is flat");
+        if (map2d && (!std::isfinite(d->map_lon0) || !std::isfinite(d->map_lon1) ||
+                      !(d->map_lon0 < d->map_lon1) || !(d->map_s0 >= -1.0) || !(d->map_s1 <= 1.0) ||
+                      !(d->map_s0 < d->map_s1)))
+            return fail(NXC_ERR_ARG, "nxc_source_desc: surface map needs map_lon0 < map_lon1 and "
+                                     "-1 <= map_s0 < map_s1 <= 1");
+    }
     HIPCHK(hipSetDevice(h->device));
     const int64_t total = d->dest_total > 0 ? d->dest_total : n;
     const int64_t offset = d->dest_total > 0 ? d->dest_offset : 0;
@@ -2452,11 +2484,13 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
     int rc = ensure(reinterpret_cast<void **>(&h->d_packets), &h->packets_cap, bytes);
     if (rc) return rc;
     const size_t n_sp = tab_speed ? (size_t)d->n_speed : 0;
-    const size_t n_map = spot ? (size_t)(d->map_nlon * d->map_nlat) : 0;
+    const size_t n_map = spot ? (size_t)(d->map_nlon * d->map_nlat)
+                              : (map2d || map1d ? (size_t)n_nodes : 0);
+    const size_t n_mcdf = map2d || map1d ? (size_t)n_cdf : 0;
     const size_t n_pcg = pcg ? (size_t)4 * (NXC_PCG_BITS + NXC_PCG_VECS) : 0;   // doubles' worth
     if (n_sp + n_map + n_pcg) {
         if ((rc = ensure(reinterpret_cast<void **>(&h->d_source), &h->source_cap,
-                         (2 * n_sp + n_map + n_pcg) * sizeof(double))))
+                         (2 * n_sp + n_map + n_mcdf + n_pcg) * sizeof(double))))
             return rc;
         if (pcg) {
             const u128 inc = ((u128)d->pcg_inc[0] << 64) | d->pcg_inc[1];
@@ -2471,6 +2505,9 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
         }
         if (n_map)
             HIPCHK(hipMemcpyAsync(h->d_source + 2 * n_sp, d->map, n_map * 8, hipMemcpyHostToDevice, h->stream));
+        if (n_mcdf)
+            HIPCHK(hipMemcpyAsync(h->d_source + 2 * n_sp + n_map, d->map_cdf, n_mcdf * 8,
+                                  hipMemcpyHostToDevice, h->stream));
     }
     SourceK K{};
     K.endtime = d->endtime; K.exobase = d->exobase; K.sinlat0 = d->sinlat0; K.sinlat1 = d->sinlat1;
@@ -2480,7 +2517,13 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
     K.angular_type = d->angular_type; K.is_planet = d->is_planet; K.seed = d->seed;
     K.first_index = d->first_index;
     K.spatial_type = d->spatial_type; K.n_speed = (int)n_sp;
-    K.map_nlon = spot ? (int)d->map_nlon : 0; K.map_nlat = spot ? (int)d->map_nlat : 0;
+    K.map_nlon = spot || map2d || map1d ? (int)d->map_nlon : 0;
+    K.map_nlat = spot || map2d ? (int)d->map_nlat : 0;
+    if (map2d) {
+        K.map_lon0 = d->map_lon0; K.map_dlon = (d->map_lon1 - d->map_lon0) / (double)(d->map_nlon - 1);
+        K.map_s0 = d->map_s0; K.map_ds = (d->map_s1 - d->map_s0) / (double)(d->map_nlat - 1);
+        K.map_s1 = d->map_s1;
+    }
     K.map_max = map_max;
     K.max_trials = NXC_SPOT_MIN_TRIALS;
     if (spot && map_sum > 0) {
@@ -2492,6 +2535,7 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
                        : (want < (double)NXC_SPOT_MIN_TRIALS ? NXC_SPOT_MIN_TRIALS : (int)want);
     }
     K.speed_cdf = h->d_source; K.speed_v = h->d_source + n_sp; K.map = h->d_source + 2 * n_sp;
+    K.map_cdf = K.map + n_map;
     K.generator = d->generator;
     if (pcg) {       // (pcg excludes the tabulated sources, so the maps sit at the buffer's start)
         K.pcg.state = ((u128)d->pcg_state[0] << 64) | d->pcg_state[1];

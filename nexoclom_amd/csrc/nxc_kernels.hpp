@@ -2185,6 +2185,10 @@ struct SourceK {
     int spatial_type, n_speed, map_nlon, map_nlat;
     double map_max;                      // accept/reject ceiling = max of the density map
     const double *speed_cdf, *speed_v, *map;
+    // surface map (spatial_type 2: node values [map_nlon][map_nlat] in `map`, cell cdf in map_cdf;
+    // 3: longitude grid in `map`, its cdf in map_cdf): first node and node spacing of each axis
+    const double *map_cdf;
+    double map_lon0, map_dlon, map_s0, map_ds, map_s1;
     int generator, max_trials;                 // 0 = Philox-4x32-10, 1 = NumPy's PCG64 stream
     PcgK pcg;
     long long stride, offset;            // the packets go to soa[c * stride + offset + i]
@@ -2235,6 +2239,43 @@ NXC_DEV double map_bilinear(const SourceK &K, double lon, double lat)
            (tx * (1.0 - ty) * row1[0] + tx * ty * row1[1]);
 }
 
+// Inverse CDF of the density f0 + (f1 - f0) t on [0, 1] at u: the root of
+// (f1 - f0) t^2 + 2 f0 t - u (f0 + f1) = 0 in the form that does not cancel.  u = 0 gives 0 (0/0
+// otherwise when f0 = 0); a density that is zero at both ends (a cell edge of zeros) is taken flat.
+NXC_DEV double linear_inverse_cdf(double f0, double f1, double u)
+{
+    const double s = f0 + f1;
+    if (!(u > 0.0)) return 0.0;
+    if (!(s > 0.0)) return u;
+    const double t = u * s / (f0 + sqrt(f0 * f0 + u * s * (f1 - f0)));
+    return t < 1.0 ? t : 1.0;
+}
+
+// 'surface map' (source_distribution.py:63-83): a point of the density that is bilinear between the
+// nodes of linspace(lon) x linspace(sin lat) -- what random_deviates_2d accepts against -- drawn
+// without a loop: the cell by bisection of the cells' cumulated masses (first cell with cdf > u, so
+// a cell without mass is never chosen), then the longitude within the cell from its marginal, which
+// is linear, then sin(latitude) from the conditional, linear as well.
+NXC_DEV void map_point(const SourceK &K, double u_cell, double u_x, double u_y, double &lon,
+                       double &lat)
+{
+    const int ny = K.map_nlat - 1;
+    int lo = 0, hi = (K.map_nlon - 1) * ny - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (K.map_cdf[mid] > u_cell) hi = mid; else lo = mid + 1;
+    }
+    const int i = lo / ny, j = lo - i * ny;
+    const double *row0 = K.map + (long long)i * K.map_nlat + j, *row1 = row0 + K.map_nlat;
+    const double a = row0[0], b = row0[1], c = row1[0], d = row1[1];
+    const double tx = linear_inverse_cdf(a + b, c + d, u_x);
+    const double f0 = (1.0 - tx) * a + tx * c, f1 = (1.0 - tx) * b + tx * d;
+    const double ty = linear_inverse_cdf(f0, f1, u_y);
+    lon = K.map_lon0 + ((double)i + tx) * K.map_dlon;
+    const double s = K.map_s0 + ((double)j + ty) * K.map_ds;
+    lat = asin(s < K.map_s1 ? s : K.map_s1);
+}
+
 // Rejection trials per packet: the host sizes the budget to the map (32 / acceptance rate, so that
 // a packet fails to find a launch point with probability e^-32) between these bounds; a packet
 // that never passes is reported, and the call fails.
@@ -2273,6 +2314,15 @@ k_sample(SourceK K, int64_t n, double *__restrict__ soa, DevCounters *__restrict
         if (K.spatial_type == 0) {                                             // uniform :51-62
             lat = asin(K.sinlat0 + (K.sinlat1 - K.sinlat0) * ulat);
             lon = fmod(K.lon0 + (K.lon1 - K.lon0) * ulon, TWO_PI);
+        } else if (K.spatial_type == 2) {                                      // surface map :63-83
+            // (the spot's trial blocks: the two types exclude each other)
+            double u_cell, u_x, u_y, unused;
+            philox_pair(gi, NXC_SPOT_BLOCK0, NXC_STREAM_SOURCE, K.seed, u_cell, u_x);
+            philox_pair(gi, NXC_SPOT_BLOCK0 + 1u, NXC_STREAM_SOURCE, K.seed, u_y, unused);
+            map_point(K, u_cell, u_x, u_y, lon, lat);
+        } else if (K.spatial_type == 3) {                                      // 1-D map :73-77
+            lat = 0.0;
+            lon = interp_global(K.map_cdf, K.map, K.map_nlon, ulon);
         } else {                                                               // surface spot :96-118
             bool accepted = false;
             lon = 0.0; lat = 0.0;

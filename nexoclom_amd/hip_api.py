@@ -113,7 +113,8 @@ class nxc_source_desc(C.Structure):
                 ('speed_v', _dp), ('map_nlon', C.c_int64), ('map_nlat', C.c_int64), ('map', _dp),
                 ('generator', C.c_int32), ('reserved2', C.c_int32), ('pcg_state', C.c_uint64*2),
                 ('pcg_inc', C.c_uint64*2), ('pcg_n', C.c_int64), ('pcg_row0', C.c_int64),
-                ('dest_offset', C.c_int64), ('dest_total', C.c_int64)]
+                ('dest_offset', C.c_int64), ('dest_total', C.c_int64), ('map_cdf', _dp)] + \
+               [(k, C.c_double) for k in ('map_lon0', 'map_lon1', 'map_s0', 'map_s1')]
 
 
 class nxc_bounce_desc(C.Structure):
@@ -481,11 +482,14 @@ class Context:
         self.n_packets = int(sum(p.shape[1] for p in pieces))
 
     def sample_packets(self, n, seed, first_index=0, download=False, speed_table=None,
-                       surface_map=None, pcg64=None, piece=None, **src):
+                       surface_map=None, pcg64=None, piece=None, map_nodes=None, map_cdf=None,
+                       **src):
         """Draw n initial states on the device (nxc_packets_sample).  ``src``: the scalar fields
         of nxc_source_desc except seed/first_index; ``speed_table`` = (cdf, speeds [km/s]) for
         speed_type 2; ``surface_map`` = density array [nlon, nlat] for spatial_type 1 (see
-        Output.source_desc).  ``pcg64 = (npackets, row0)``: the reference's own seeded stream --
+        Output.source_desc); ``map_nodes`` / ``map_cdf`` = node values [nlon, nlat] and cumulated
+        cell masses for spatial_type 2 (with map_lon0, map_lon1, map_s0, map_s1 among ``src``), the
+        longitude grid and its cdf for spatial_type 3.  ``pcg64 = (npackets, row0)``: the reference's own seeded stream --
         rows row0 .. row0 + n - 1 of the npackets-long vectors default_rng(seed) would draw.
         ``piece = (offset, total)``: the n packets are part of a resident set of ``total`` that
         several calls fill in ascending order."""
@@ -510,6 +514,18 @@ class Context:
             dens = _f64(surface_map)
             keep.append(dens)
             d.map_nlon, d.map_nlat, d.map = dens.shape[0], dens.shape[1], _p(dens)
+        if map_nodes is not None or map_cdf is not None:
+            if surface_map is not None or map_nodes is None or map_cdf is None:
+                raise ValueError('a surface map source takes map_nodes and map_cdf, and no '
+                                 'surface_map')
+            nodes, cdf = _f64(map_nodes), _f64(map_cdf)
+            cells = (nodes.shape[0] - 1)*(nodes.shape[1] - 1) if nodes.ndim == 2 else len(nodes)
+            if nodes.ndim not in (1, 2) or cdf.ndim != 1 or len(cdf) != cells:
+                raise ValueError('map_cdf must hold one entry per cell of map_nodes (2-D) or per '
+                                 'node (1-D)')
+            keep += [nodes, cdf]
+            d.map_nlon, d.map_nlat = nodes.shape[0], nodes.shape[1] if nodes.ndim == 2 else 0
+            d.map, d.map_cdf = _p(nodes), _p(cdf)
         out = np.empty((8, int(n))) if download else None
         self._check(self.lib.nxc_packets_sample(self._h, C.byref(d), C.c_int64(int(n)),
                                                 _p(out) if download else None))

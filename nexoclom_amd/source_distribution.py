@@ -14,9 +14,12 @@ tests/test_host.py::test_x0_sampling_is_seed_deterministic_and_in_reference_orde
 Like the reference, the tabulated-density samplers ('maxwellian', 'sputtering', 'surface spot')
 draw from the UNSEEDED process-global ``numpy.random`` (randomdeviates.py:33,63-65), so they are
 statistically but not bitwise reproducible; the device sampler (nxc_packets_sample) covers them
-with counter-based draws.  Sources that need the reference's pickled map files ('surface map',
-'user defined') are out of scope.
+with counter-based draws.  So do the sources read from a file, 'surface map' (``mapfile``) and 'user
+defined' speeds (``vdistfile``): the file is a SourceMap written by ``SourceMap.save`` (.npz) -- what
+``LOSResult.make_source_map`` returns -- not the reference's pickled astropy quantities.
 """
+import os
+
 import numpy as np
 import numpy.random as unseeded
 from scipy.interpolate import interpn
@@ -221,9 +224,95 @@ def _surface_spot(out, sd):
     return random_deviates_2d(density, lon, lat, out.npackets)
 
 
+def source_file(parameter, path):
+    """The SourceMap file an input parameter (``mapfile``, ``vdistfile``) names.  'default' stands
+    for data files the reference does not ship either; a file that is not there is an InputError
+    (source_distribution.py:173-176)."""
+    from .sourcemap import SourceMap
+    if path == 'default':
+        raise InputError(parameter, f'{parameter} = default: there is no default file; name an '
+                                    '.npz written by SourceMap.save')
+    if not os.path.exists(path):
+        raise InputError(parameter, f'{path} not found.')
+    return SourceMap(path)
+
+
+def _first_bad(values):
+    """Index (as a tuple) and value of the first entry that is not a finite number >= 0."""
+    bad = np.argwhere(~(np.isfinite(values) & (values >= 0)))
+    return (None, None) if len(bad) == 0 else (tuple(int(k) for k in bad[0]), values[tuple(bad[0])])
+
+
+def surface_map_density(sd):
+    """(longitude, latitude or None, abundance, coordinate_system) of ``spatialdist.mapfile``, or
+    the reason it cannot be launched from.  The reference's rejection loop would not end on a map
+    without positive entries and draws nonsense from negative or non-finite ones
+    (math/randomdeviates.py:59-78): those are ValueErrors here.  Planet-fixed maps are refused as
+    in the reference (source_distribution.py:85-93)."""
+    smap = source_file('mapfile', sd.mapfile)
+    if smap.abundance is None or smap.longitude is None:
+        raise ValueError(f'{sd.mapfile} holds no abundance map')
+    abundance = np.asarray(smap.abundance, dtype=np.float64)
+    longitude = np.asarray(smap.longitude, dtype=np.float64)
+    latitude = None if smap.latitude is None else np.asarray(smap.latitude, dtype=np.float64)
+    shape = (len(longitude),) if latitude is None else (len(longitude), len(latitude))
+    if abundance.shape != shape or min(shape) < 2:
+        raise ValueError(f'{sd.mapfile}: abundance{abundance.shape} does not fit its axes {shape} '
+                         '(at least two nodes each)')
+    where, value = _first_bad(abundance)
+    if where is not None:
+        raise ValueError(f'{sd.mapfile}: abundance{list(where)} = {value}; a source map must be '
+                         'finite and >= 0 (make_source_map gives inf where no packet of a grid '
+                         "point's ball was observed)")
+    if not abundance.max() > 0:
+        raise ValueError(f'{sd.mapfile}: abundance is zero everywhere')
+    if 'planet' in smap.coordinate_system:
+        if sd.subsolarlon is None:
+            raise ValueError('inputs.spatialdist.subsolarlon is None')
+        raise NotImplementedError('planet-fixed source maps: the reference stops here as well '
+                                  "('Need to verify this works')")
+    return longitude, latitude, abundance, smap.coordinate_system
+
+
+def speed_file_density(vd):
+    """(speed [km/s], speed_dist) of ``speeddist.vdistfile``."""
+    smap = source_file('vdistfile', vd.vdistfile)
+    if smap.speed is None or smap.speed_dist is None:
+        raise ValueError(f'{vd.vdistfile} holds no speed distribution')
+    speed = np.asarray(smap.speed, dtype=np.float64)
+    density = np.asarray(smap.speed_dist, dtype=np.float64)
+    if speed.ndim != 1 or speed.shape != density.shape or len(speed) < 2:
+        raise ValueError(f'{vd.vdistfile}: speed and speed_dist must be 1-D and equally long')
+    where, value = _first_bad(density)
+    if where is not None or not np.all(np.isfinite(speed)):
+        raise ValueError(f'{vd.vdistfile}: speed_dist{list(where or ())} = {value}; speed and '
+                         'speed_dist must be finite, speed_dist >= 0')
+    if not density.max() > 0:
+        raise ValueError(f'{vd.vdistfile}: speed_dist is zero everywhere')
+    return speed, density
+
+
+def surface_map_cells(longitude, latitude, abundance):
+    """What the device draws a 2-D map's launch points from (k_sample, spatial_type 2).  The law
+    random_deviates_2d samples has its density proportional to the bilinear interpolant of
+    ``abundance`` on the even node grid linspace(lon) x linspace(sin lat); the mass of a cell of
+    that grid is its area (the same for all) times the mean of its four corners.  Returns the
+    cumulated corner sums (a + b) + (c + d), lon-major, divided by their total, and the limits
+    (lon0, lon1, s0, s1) of the two axes."""
+    s = np.sin(latitude)
+    corners = (abundance[:-1, :-1] + abundance[:-1, 1:]) + (abundance[1:, :-1] + abundance[1:, 1:])
+    cdf = np.cumsum(corners.ravel())
+    cdf /= cdf[-1]
+    return cdf, (float(longitude.min()), float(longitude.max()), float(s.min()), float(s.max()))
+
+
 def _surface_map(out, sd):
-    raise NotImplementedError("surface-map sources need the reference's pickled map files; "
-                              'out of scope (SURVEY.md section 2)')
+    longitude, latitude, abundance, system = surface_map_density(sd)
+    out.inputs.spatialdist.coordinate_system = system                      # :71
+    if latitude is None:
+        return random_deviates_1d(longitude, abundance, out.npackets), np.zeros(out.npackets)
+    lon, s = random_deviates_2d(abundance, longitude, np.sin(latitude), out.npackets)
+    return lon, np.arcsin(s)
 
 
 SURFACES = {'uniform': _surface_uniform, 'surface spot': _surface_spot,
@@ -273,7 +362,7 @@ def _speed_tabulated(out, vd, species):
 
 
 def _speed_from_file(out, vd, species):
-    raise InputError('speed_distribution', 'user-defined speed files are out of scope')
+    return random_deviates_1d(*speed_file_density(vd), out.npackets)
 
 
 SPEEDS = {'gaussian': _speed_gaussian, 'flat': _speed_flat, 'sputtering': _speed_tabulated,

@@ -37,8 +37,12 @@ Quirks of the reference kept as written:
 Deviations: Outputs with no X0 packet are skipped (the reference fails on ceil(NaN)); Outputs
 whose X0 was not kept (device sampler) raise NotImplementedError; the two speed adds of a
 max-vmax Output are one add of twice the value on the device (same value to one rounding); the
-LDS sums are not in a fixed order (weighted sums agree to rounding, counts exactly).  Loading .pkl
-/ .sav map files is out of scope.
+LDS sums are not in a fixed order (weighted sums agree to rounding, counts exactly).
+
+Files: ``SourceMap.save(path)`` writes an .npz of plain float64 arrays and strings, ``SourceMap(path)``
+reads it back exactly; that file is what ``spatialdist.mapfile`` / ``speeddist.vdistfile`` of an
+input file name (source_distribution.py launches packets from it).  The reference's .pkl / .sav
+files hold pickled astropy quantities and stay out of scope.
 
 Units (``SourceMap.units``): the arrays are plain float64; with ``normalize`` abundance and
 abundance_uncor are in '1/(cm2 s)', speed_dist in '1/(km/s)/s', speed_dist_map in
@@ -47,6 +51,7 @@ abundance_uncor are in '1/(cm2 s)', speed_dist in '1/(km/s)/s', speed_dist_map i
 before that.  Without ``normalize`` the histograms are unitless, as in the reference.
 """
 import math
+import os
 
 import numpy as np
 
@@ -263,7 +268,10 @@ class SourceMap:
     """initial_state/SourceMap.py's attributes (abundance, longitude, latitude, speed, speed_dist,
     azimuth, azimuth_dist, altitude, altitude_dist, fraction_observed, coordinate_system) plus
     abundance_uncor, n_included, n_total and the three *_dist_map arrays; ``units`` names the
-    unit of each array.  Built from a dict (load_dict); map files are not read."""
+    unit of each array.  Built from a dict (load_dict) or from an .npz file written by ``save``."""
+
+    ARRAYS = ('abundance', 'longitude', 'latitude', 'speed', 'speed_dist', 'azimuth',
+              'azimuth_dist', 'altitude', 'altitude_dist', 'fraction_observed')
 
     EXTRA = ('abundance_uncor', 'n_included', 'n_total', 'speed_dist_map', 'altitude_dist_map',
              'azimuth_dist_map')
@@ -279,11 +287,36 @@ class SourceMap:
         self.units = dict(UNITS_NORMALIZED if normalized else UNITS_RAW)
         if isinstance(sourcemap, dict):
             self.load_dict(sourcemap)
+        elif isinstance(sourcemap, (str, os.PathLike)) and os.fspath(sourcemap).endswith('.npz'):
+            self.load_npz(sourcemap)
         elif sourcemap is not None:
-            raise NotImplementedError('loading .pkl / .sav source map files is not supported')
+            raise NotImplementedError(
+                'loading .pkl / .sav source map files (pickled astropy quantities) is not '
+                'supported: write the map with SourceMap.save to an .npz file and name that')
 
     def load_dict(self, sourcemap):
-        for key in ('abundance', 'longitude', 'latitude', 'speed', 'speed_dist', 'azimuth',
-                    'azimuth_dist', 'altitude', 'altitude_dist', 'fraction_observed') + self.EXTRA:
+        for key in self.ARRAYS + self.EXTRA:
             setattr(self, key, sourcemap.get(key, None))
         self.coordinate_system = sourcemap.get('coordinate_system', 'solar-fixed')
+
+    def save(self, path):
+        """Write every attribute that is not None to ``path`` (.npz): the arrays as float64,
+        coordinate_system as a string, ``units`` as two string arrays.  ``SourceMap(path)`` reads
+        it back exactly."""
+        if not os.fspath(path).endswith('.npz'):
+            raise ValueError('SourceMap.save writes .npz files: the path must end in .npz')
+        contents = {key: np.asarray(getattr(self, key), dtype=np.float64)
+                    for key in self.ARRAYS + self.EXTRA if getattr(self, key) is not None}
+        contents['coordinate_system'] = np.array(str(self.coordinate_system))
+        contents['units_keys'] = np.array(list(self.units), dtype=str)
+        contents['units_values'] = np.array([self.units[k] for k in self.units], dtype=str)
+        with open(path, 'wb') as file:          # (np.savez would add a second .npz to a bare name)
+            np.savez(file, **contents)
+
+    def load_npz(self, path):
+        with np.load(path, allow_pickle=False) as file:
+            for key in self.ARRAYS + self.EXTRA:
+                setattr(self, key, np.array(file[key]) if key in file.files else None)
+            self.coordinate_system = str(file['coordinate_system'])
+            self.units = dict(zip((str(k) for k in file['units_keys']),
+                                  (str(v) for v in file['units_values'])))
