@@ -246,6 +246,15 @@ int nxc_last_kernel_ms(nxc_handle *h, float *ms);  /* HIP-event time of the last
  *             speed_type 2    inverse CDF of a tabulated flux density (maxwellian, sputtering;
  *                             :148-168, math/randomdeviates.py:8-33): v = interp(u, speed_cdf,
  *                             speed_v), speed_cdf non-decreasing from 0 to 1
+ *             speed_type 3    thermal: a Maxwellian flux at the launch point's surface temperature
+ *                             ('maxwellian' at temperature 0, which the reference documents but
+ *                             stops at, :165-168).  T = t0 on the night side, t0 + t1
+ *                             sqrt(sqrt(|cos lon cos lat|)) within 90 degrees of the sub-solar
+ *                             longitude (surface_temperature.py:4-19); v = max(S(T, u), 0) with S
+ *                             the bicubic spline (tx[nx], ty[ny], coef[nx-4][ny-4], the
+ *                             nxc_bounce_desc layout) of SurfaceInteraction.py:28-61, u the speed
+ *                             uniform.  Speed bound of the queue: max |coef| (B-spline bases are
+ *                             >= 0 and sum to 1)
  *   direction angular_type 0  radial, 1 isotropic (:198-252) */
 typedef struct nxc_source_desc {
     double endtime;        /* s                                                                 */
@@ -256,7 +265,7 @@ typedef struct nxc_source_desc {
     double unit_km;        /* planet radius                                                     */
     double sinalt0, sinalt1, az0, az1;   /* isotropic launch cone                               */
     int32_t random_time;   /* 1: t = u*endtime (variable-step runs, Output.py:138-139)          */
-    int32_t speed_type;    /* 0 flat, 1 gaussian, 2 tabulated                                   */
+    int32_t speed_type;    /* 0 flat, 1 gaussian, 2 tabulated, 3 thermal                        */
     int32_t angular_type;  /* 0 radial, 1 isotropic                                             */
     int32_t is_planet;     /* longitude convention (source_distribution.py:13-28)               */
     uint64_t seed;
@@ -273,8 +282,9 @@ typedef struct nxc_source_desc {
      * of the pcg_n-packet vectors the reference would draw one after the other ([launch time,]
      * sin latitude, longitude, speed, [sin altitude, azimuth]); the uniforms are bit-identical
      * to Generator.random(pcg_n), the states equal the host sampler's to libm rounding.  Only
-     * sources whose every draw is such a vector: spatial_type 0, speed_type 0 (flat), any
-     * angular_type.  pcg_state / pcg_inc: PCG64(seed).state['state'] as {high, low} words.      */
+     * sources whose every draw is such a vector: spatial_type 0, speed_type 0 (flat) or 3
+     * (thermal), any angular_type.  pcg_state / pcg_inc: PCG64(seed).state['state'] as {high,
+     * low} words.                                                                                */
     int32_t generator;     /* 0 Philox-4x32-10 (counter-based, statistical parity), 1 PCG64     */
     int32_t reserved2;
     uint64_t pcg_state[2], pcg_inc[2];
@@ -288,6 +298,13 @@ typedef struct nxc_source_desc {
     const double *map_cdf;
     double map_lon0, map_lon1;   /* spatial_type 2: first and last longitude node, rad          */
     double map_s0, map_s1;       /* spatial_type 2: first and last sin(latitude) node           */
+    /* speed_type 3: night-side temperature t0 > 0 and sub-solar excess t1 >= 0, K; the v(T, p)
+     * spline [km/s] as in nxc_bounce_desc: knots tx[nx], ty[ny] (non-decreasing, strictly
+     * increasing between tx[3] .. tx[nx-4] and ty[3] .. ty[ny-4], nx, ny >= 8), finite
+     * coefficients coef[(nx-4) * (ny-4)] row-major                                               */
+    double t0, t1;
+    int64_t nx, ny;
+    const double *tx, *ty, *coef;
 } nxc_source_desc;
 
 int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, double *soa_out);

@@ -21,8 +21,8 @@ loss_info, randgen, compress, inputs, planet) and the same column order of ``X``
   ``materialize_x0`` (False: leave the device-sampled states on the GPU), ``window``
   ((n, a, b): only rows [a, b) of the n packets the seed would draw, bit-identical to slicing)
   and ``generator`` ('pcg64': the device sampler follows the seeded HOST stream -- NumPy's PCG64,
-  the uniforms bit for bit -- instead of its own Philox counters; uniform / flat / isotropic |
-  radial sources).
+  the uniforms bit for bit -- instead of its own Philox counters; uniform / flat or thermal /
+  isotropic | radial sources).
 * the trajectory rows of a constant-step run stay in HBM (hip_api.RowStore) in exactly the form
   save() would store them -- frac > 0 rows, float32 / int32 -- and ``X`` is built from them on
   first access; ModelImage and LOSResult read the resident rows directly.  ``Output.integrate_batch``
@@ -36,7 +36,7 @@ import pandas as pd
 from .atomicdata import LossInfo, RadPresConst
 from .solarsystem import planet_dist
 from .source_distribution import (LaunchTable, angular_distribution, speed_distribution,
-                                  surface_distribution)
+                                  surface_distribution, thermal_source)
 from .units import Quantity, register_unit
 
 STATE_COLS = ['time', 'x', 'y', 'z', 'vx', 'vy', 'vz', 'frac']
@@ -139,6 +139,11 @@ class Output:
             from .surface import bounce_config
             self._bounce = bounce_config(inputs, self.GM, self.unit_km, self.device_key)
             self._first_index = first_index
+            if thermal_source(inputs):
+                # thermal launch speeds: the v(T, p) table, built once per Input; off Mercury this
+                # raises NotImplementedError before anything is drawn
+                from .surface import thermal_launch_spline
+                thermal_launch_spline(inputs)
 
             self.npackets = npackets
             # the host sampler fills a table of plain columns; the frame is built once at the end
@@ -261,7 +266,9 @@ class Output:
         source_distribution.py:96-113).  A 'surface map' source adds ``map_nodes``, ``map_cdf`` and
         (2-D) ``map_lon0``, ``map_lon1``, ``map_s0``, ``map_s1``: the file's abundance with the
         cumulated masses of its cells (source_distribution.surface_map_cells), or for a 1-D map the
-        even longitude grid with its cdf."""
+        even longitude grid with its cdf.  Thermal speeds ('maxwellian' at temperature 0) are
+        speed_type 3 with the surface temperature's ``t0`` / ``t1`` and ``thermal_spline``, the
+        (tx, ty, coef) of the v(T, p) spline the host sampler evaluates."""
         from .source_distribution import (density_cdf, speed_file_density, spot_density_map,
                                           surface_map_cells, surface_map_density,
                                           tabulated_speed_density)
@@ -299,6 +306,10 @@ class Output:
         if vd.type in ('flat', 'gaussian'):
             d.update(speed_type=0 if vd.type == 'flat' else 1, vprob=vd.vprob.value,
                      vwidth=vd.delv.value if vd.type == 'flat' else vd.sigma.value)
+        elif thermal_source(self.inputs):
+            from .surface import NIGHT_SIDE_K, day_side_t1, spline_tables, thermal_launch_spline
+            d.update(speed_type=3, t0=NIGHT_SIDE_K, t1=float(day_side_t1(self.inputs.geometry)),
+                     thermal_spline=spline_tables(thermal_launch_spline(self.inputs)))
         else:
             grid, density = speed_file_density(vd) if vd.type == 'user defined' else \
                 tabulated_speed_density(vd, self.inputs.options.species)

@@ -2407,17 +2407,18 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
 {
     return guarded([&]() -> int {
     if (!h || !d || n < 1) return fail(NXC_ERR_ARG, "bad arguments");
-    if (d->speed_type < 0 || d->speed_type > 2 || d->angular_type < 0 || d->angular_type > 1 ||
+    if (d->speed_type < 0 || d->speed_type > 3 || d->angular_type < 0 || d->angular_type > 1 ||
         d->spatial_type < 0 || d->spatial_type > 3 || !(d->unit_km > 0) || !(d->exobase > 0))
         return fail(NXC_ERR_ARG, "bad nxc_source_desc");
     const bool tab_speed = d->speed_type == 2, spot = d->spatial_type == 1;
     const bool map2d = d->spatial_type == 2, map1d = d->spatial_type == 3;
+    const bool thermal = d->speed_type == 3;
     const bool pcg = d->generator == 1;
     if (d->generator != 0 && d->generator != 1) return fail(NXC_ERR_ARG, "nxc_source_desc: generator must be 0 or 1");
     if (pcg) {
-        if (d->spatial_type != 0 || d->speed_type != 0)
+        if (d->spatial_type != 0 || (d->speed_type != 0 && !thermal))
             return fail(NXC_ERR_ARG, "generator 1 (PCG64) covers the sources whose every draw is a "
-                                     "random(npackets) vector: uniform surface, flat speeds");
+                                     "random(npackets) vector: uniform surface, flat or thermal speeds");
         if (d->pcg_n < 1 || d->pcg_row0 < 0 || d->pcg_row0 + n > d->pcg_n ||
             d->pcg_n >= ((int64_t)1 << (NXC_PCG_BITS - 1)) || !(d->pcg_inc[1] & 1ull))
             return fail(NXC_ERR_ARG, "nxc_source_desc: PCG64 window outside its draw vectors");
@@ -2430,6 +2431,35 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
                 return fail(NXC_ERR_ARG, "nxc_source_desc: speed_cdf must be non-decreasing");
         if (!(d->speed_cdf[d->n_speed - 1] > d->speed_cdf[0]))
             return fail(NXC_ERR_ARG, "nxc_source_desc: speed_cdf is flat");
+    }
+    // thermal speeds: the surface temperature's constants and the v(T, p) spline, checked like
+    // nxc_set_bounce's table would have to be for bispev3 to stay finite (a zero-width knot
+    // interval inside [t[3], t[n-4]] would divide by zero)
+    const int64_t n_coef = thermal ? (d->nx - 4) * (d->ny - 4) : 0;
+    double coef_max = 0.0;
+    if (thermal) {
+        if (!(d->t0 > 0.0) || !std::isfinite(d->t0) || !(d->t1 >= 0.0) || !std::isfinite(d->t1))
+            return fail(NXC_ERR_ARG, "nxc_source_desc: thermal speeds need finite t0 > 0 and t1 >= 0");
+        if (d->nx < 8 || d->ny < 8 || d->nx > (1 << 16) || d->ny > (1 << 16) || !d->tx || !d->ty ||
+            !d->coef)
+            return fail(NXC_ERR_ARG, "nxc_source_desc: thermal speeds need a spline with 8..65536 "
+                                     "knots per axis, tx, ty and coef");
+        for (int axis = 0; axis < 2; axis++) {
+            const double *t = axis ? d->ty : d->tx;
+            const int64_t nk = axis ? d->ny : d->nx;
+            for (int64_t k = 0; k < nk; k++)
+                if (!std::isfinite(t[k]) || (k > 0 && !(t[k] >= t[k - 1])) ||
+                    (k > 3 && k <= nk - 4 && !(t[k] > t[k - 1])))
+                    return fail(NXC_ERR_ARG, std::string("nxc_source_desc: thermal spline knots ") +
+                                             (axis ? "ty" : "tx") + " must be finite, non-decreasing "
+                                             "and increasing inside [t[3], t[n-4]]");
+        }
+        for (int64_t k = 0; k < n_coef; k++) {
+            if (!std::isfinite(d->coef[k]))
+                return fail(NXC_ERR_ARG, "nxc_source_desc: thermal spline coefficients must be finite "
+                                         "(coef " + std::to_string(k) + ")");
+            coef_max = std::max(coef_max, std::fabs(d->coef[k]));
+        }
     }
     double map_max = 0.0, map_sum = 0.0;
     if (spot) {
@@ -2488,9 +2518,12 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
                               : (map2d || map1d ? (size_t)n_nodes : 0);
     const size_t n_mcdf = map2d || map1d ? (size_t)n_cdf : 0;
     const size_t n_pcg = pcg ? (size_t)4 * (NXC_PCG_BITS + NXC_PCG_VECS) : 0;   // doubles' worth
-    if (n_sp + n_map + n_pcg) {
+    // the spline's knots and coefficients go behind every other table (the PCG64 maps included)
+    const size_t n_spl = thermal ? (size_t)(d->nx + d->ny + n_coef) : 0;
+    const size_t at_spl = 2 * n_sp + n_map + n_mcdf + n_pcg;
+    if (n_sp + n_map + n_pcg + n_spl) {
         if ((rc = ensure(reinterpret_cast<void **>(&h->d_source), &h->source_cap,
-                         (2 * n_sp + n_map + n_mcdf + n_pcg) * sizeof(double))))
+                         (at_spl + n_spl) * sizeof(double))))
             return rc;
         if (pcg) {
             const u128 inc = ((u128)d->pcg_inc[0] << 64) | d->pcg_inc[1];
@@ -2508,6 +2541,13 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
         if (n_mcdf)
             HIPCHK(hipMemcpyAsync(h->d_source + 2 * n_sp + n_map, d->map_cdf, n_mcdf * 8,
                                   hipMemcpyHostToDevice, h->stream));
+        if (n_spl) {
+            HIPCHK(hipMemcpyAsync(h->d_source + at_spl, d->tx, (size_t)d->nx * 8, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->d_source + at_spl + d->nx, d->ty, (size_t)d->ny * 8,
+                                  hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->d_source + at_spl + d->nx + d->ny, d->coef, (size_t)n_coef * 8,
+                                  hipMemcpyHostToDevice, h->stream));
+        }
     }
     SourceK K{};
     K.endtime = d->endtime; K.exobase = d->exobase; K.sinlat0 = d->sinlat0; K.sinlat1 = d->sinlat1;
@@ -2544,10 +2584,19 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
     }
     K.stride = total;
     K.offset = offset;
+    if (thermal) {
+        K.t0 = d->t0; K.t1 = d->t1;
+        K.spl.tx = h->d_source + at_spl; K.spl.ty = K.spl.tx + d->nx; K.spl.coef = K.spl.ty + d->ny;
+        K.spl.nx = (int)d->nx; K.spl.ny = (int)d->ny;
+    }
     HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
     if ((rc = begin_timed(h))) return rc;
-    hipLaunchKernelGGL(k_sample, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0, h->stream, K,
-                       n, h->d_packets, h->d_ctr);
+    if (thermal)
+        hipLaunchKernelGGL(k_sample<true>, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0, h->stream,
+                           K, n, h->d_packets, h->d_ctr);
+    else
+        hipLaunchKernelGGL(k_sample<false>, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0, h->stream,
+                           K, n, h->d_packets, h->d_ctr);
     HIPCHK(hipGetLastError());
     if ((rc = end_timed(h))) return rc;
     DevCounters c;
@@ -2576,6 +2625,8 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
         vmax = 0.0;
         for (size_t k = 0; k < n_sp; k++) vmax = std::max(vmax, std::fabs(d->speed_v[k]));
         vmax /= d->unit_km;
+    } else if (thermal) {
+        vmax = coef_max / d->unit_km;      // |S| <= max |coef|: the bases are >= 0 and sum to 1
     } else {
         vmax = (d->speed_type == 0 ? std::fabs(d->vprob) + std::fabs(d->vwidth)
                                    : std::fabs(d->vprob) + 6 * std::fabs(d->vwidth)) / d->unit_km;

@@ -583,8 +583,11 @@ NXC_DEV int knot_interval(const double *__restrict__ t, int n, double x)
     return lo;
 }
 
-// scipy RectBivariateSpline(...).ev(x, y) for kx = ky = 3 (FITPACK bispev)
-NXC_DEV double bispev3(const BounceK &B, double x, double y)
+// scipy RectBivariateSpline(...).ev(x, y) for kx = ky = 3 (FITPACK bispev).  B: any struct with
+// the spline's knots tx[nx], ty[ny] and coefficients coef[(nx-4) x (ny-4)] (BounceK for
+// re-emission, SplineK for thermal launch speeds)
+template <class Spline>
+NXC_DEV double bispev3(const Spline &B, double x, double y)
 {
     x = __builtin_fmin(__builtin_fmax(x, B.tx[3]), B.tx[B.nx - 4]);
     y = __builtin_fmin(__builtin_fmax(y, B.ty[3]), B.ty[B.ny - 4]);

@@ -2176,6 +2176,13 @@ NXC_DEV double pcg_uniform(const PcgK &P, nxc_u128 s, int vec)
     return (double)(r >> 11) * 0x1p-53;
 }
 
+// The bicubic v(T, p) spline of thermal launch speeds (speed_type 3), in global memory: the
+// fields bispev3 reads, named as in BounceK
+struct SplineK {
+    const double *tx, *ty, *coef;
+    int nx, ny;
+};
+
 struct SourceK {
     double endtime, exobase, sinlat0, sinlat1, lon0, lon1, vprob, vwidth, unit_km;
     double sinalt0, sinalt1, az0, az1;
@@ -2192,6 +2199,10 @@ struct SourceK {
     int generator, max_trials;                 // 0 = Philox-4x32-10, 1 = NumPy's PCG64 stream
     PcgK pcg;
     long long stride, offset;            // the packets go to soa[c * stride + offset + i]
+    // thermal speeds (speed_type 3): surface temperature t0 (night), t0 + t1 |cos lon cos lat|^1/4
+    // (day), and the v(T, p) spline
+    double t0, t1;
+    SplineK spl;
 };
 
 // diagnostics: out[vec][i] = uniform of draw `vec` for row i (the parity test compares them with
@@ -2282,6 +2293,10 @@ NXC_DEV void map_point(const SourceK &K, double u_cell, double u_x, double u_y, 
 constexpr int NXC_SPOT_MIN_TRIALS = 4096, NXC_SPOT_MAX_TRIALS = 1 << 18;
 constexpr unsigned NXC_SPOT_BLOCK0 = 16;    // Philox draw blocks 16 + 2t, 17 + 2t of trial t
 
+// THERMAL: the instantiation for speed_type 3 (thermal speeds).  The temperature and the bicubic
+// spline take 122 VGPRs against 97; kept out of the instantiation every other source runs, whose code
+// is that of the kernel before thermal speeds existed.
+template <bool THERMAL>
 __global__ void __launch_bounds__(NXC_BLOCK)
 k_sample(SourceK K, int64_t n, double *__restrict__ soa, DevCounters *__restrict__ ctr)
 {
@@ -2349,6 +2364,14 @@ k_sample(SourceK K, int64_t n, double *__restrict__ soa, DevCounters *__restrict
             philox_pair(gi, 3, NXC_STREAM_SOURCE, K.seed, g0, g1);
             const double zn = sqrt(-2.0 * log(1.0 - g0)) * cos(TWO_PI * g1);
             v = K.vwidth == 0.0 ? K.vprob : zn * K.vwidth + K.vprob;
+        } else if (THERMAL) {                                                  // thermal (:165-168)
+            // the temperature as bounce_packet forms it (surface_temperature.py:12-17), then the
+            // speed of re-emission's table at probability uspd (bouncepackets.py:71-74)
+            double tsurf = K.t0;
+            if (lon <= 1.5707963267948966 || lon >= 4.71238898038469)
+                tsurf = K.t0 + K.t1 * nxc_sqrt(nxc_sqrt(__builtin_fabs(cos(lon) * cos(lat))));
+            const double s = bispev3(K.spl, tsurf, uspd);
+            v = s > 0.0 ? s : 0.0;
         } else {                                                               // tabulated :148-168
             v = interp_global(K.speed_cdf, K.speed_v, K.n_speed, uspd);
         }

@@ -114,7 +114,8 @@ class nxc_source_desc(C.Structure):
                 ('generator', C.c_int32), ('reserved2', C.c_int32), ('pcg_state', C.c_uint64*2),
                 ('pcg_inc', C.c_uint64*2), ('pcg_n', C.c_int64), ('pcg_row0', C.c_int64),
                 ('dest_offset', C.c_int64), ('dest_total', C.c_int64), ('map_cdf', _dp)] + \
-               [(k, C.c_double) for k in ('map_lon0', 'map_lon1', 'map_s0', 'map_s1')]
+               [(k, C.c_double) for k in ('map_lon0', 'map_lon1', 'map_s0', 'map_s1', 't0', 't1')] + \
+               [('nx', C.c_int64), ('ny', C.c_int64), ('tx', _dp), ('ty', _dp), ('coef', _dp)]
 
 
 class nxc_bounce_desc(C.Structure):
@@ -483,13 +484,15 @@ class Context:
 
     def sample_packets(self, n, seed, first_index=0, download=False, speed_table=None,
                        surface_map=None, pcg64=None, piece=None, map_nodes=None, map_cdf=None,
-                       **src):
+                       thermal_spline=None, **src):
         """Draw n initial states on the device (nxc_packets_sample).  ``src``: the scalar fields
         of nxc_source_desc except seed/first_index; ``speed_table`` = (cdf, speeds [km/s]) for
         speed_type 2; ``surface_map`` = density array [nlon, nlat] for spatial_type 1 (see
         Output.source_desc); ``map_nodes`` / ``map_cdf`` = node values [nlon, nlat] and cumulated
         cell masses for spatial_type 2 (with map_lon0, map_lon1, map_s0, map_s1 among ``src``), the
-        longitude grid and its cdf for spatial_type 3.  ``pcg64 = (npackets, row0)``: the reference's own seeded stream --
+        longitude grid and its cdf for spatial_type 3; ``thermal_spline`` = (tx, ty, coef[nx-4,
+        ny-4]) of the v(T, p) spline for speed_type 3 (with t0, t1 among ``src``).
+        ``pcg64 = (npackets, row0)``: the reference's own seeded stream --
         rows row0 .. row0 + n - 1 of the npackets-long vectors default_rng(seed) would draw.
         ``piece = (offset, total)``: the n packets are part of a resident set of ``total`` that
         several calls fill in ascending order."""
@@ -526,6 +529,13 @@ class Context:
             keep += [nodes, cdf]
             d.map_nlon, d.map_nlat = nodes.shape[0], nodes.shape[1] if nodes.ndim == 2 else 0
             d.map, d.map_cdf = _p(nodes), _p(cdf)
+        if thermal_spline is not None:
+            tx, ty, coef = (_f64(a) for a in thermal_spline)
+            if tx.ndim != 1 or ty.ndim != 1 or coef.shape != (len(tx) - 4, len(ty) - 4):
+                raise ValueError('thermal_spline must be (tx, ty, coef) with coef of shape '
+                                 '(len(tx) - 4, len(ty) - 4)')
+            keep += [tx, ty, coef]
+            d.nx, d.ny, d.tx, d.ty, d.coef = len(tx), len(ty), _p(tx), _p(ty), _p(coef)
         out = np.empty((8, int(n))) if download else None
         self._check(self.lib.nxc_packets_sample(self._h, C.byref(d), C.c_int64(int(n)),
                                                 _p(out) if download else None))

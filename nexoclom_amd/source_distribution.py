@@ -14,7 +14,10 @@ tests/test_host.py::test_x0_sampling_is_seed_deterministic_and_in_reference_orde
 Like the reference, the tabulated-density samplers ('maxwellian', 'sputtering', 'surface spot')
 draw from the UNSEEDED process-global ``numpy.random`` (randomdeviates.py:33,63-65), so they are
 statistically but not bitwise reproducible; the device sampler (nxc_packets_sample) covers them
-with counter-based draws.  So do the sources read from a file, 'surface map' (``mapfile``) and 'user
+with counter-based draws.  A 'maxwellian' at temperature 0 -- thermal speeds at the local surface
+temperature, which the reference documents but never wrote -- is the exception: its one draw is a
+seeded ``random(npackets)`` vector in the speed slot, where 'flat' draws, so it is reproducible
+draw for draw and can be windowed.  So do the sources read from a file, 'surface map' (``mapfile``) and 'user
 defined' speeds (``vdistfile``): the file is a SourceMap written by ``SourceMap.save`` (.npz) -- what
 ``LOSResult.make_source_map`` returns -- not the reference's pickled astropy quantities.
 """
@@ -361,12 +364,38 @@ def _speed_tabulated(out, vd, species):
     return random_deviates_1d(*tabulated_speed_density(vd, species), out.npackets)
 
 
+def thermal_source(inputs):
+    """Whether the launch speeds are thermal: 'maxwellian' at temperature 0, a Maxwellian flux at
+    the local surface temperature (what the reference documents but stops at, :165-168)."""
+    vd = inputs.speeddist
+    return vd.type == 'maxwellian' and vd.temperature == 0
+
+
+def _speed_thermal(out, vd, species):
+    """The speed below which a fraction u of a Maxwellian flux at the launch point's surface
+    temperature leaves the surface: v = max(S(T, u), 0) with S the v(T, p) spline of thermally
+    accommodated re-emission (surface.tabulate_thermal_speeds; bouncepackets.py:71-74 draws from
+    it the same way), T from the longitude / latitude already drawn, u one seeded vector in the
+    speed slot.  The clamp matters only at u = 0, where S is a few 1e-18 below zero at some T."""
+    from .surface import surface_temperature, thermal_launch_spline
+    spline = thermal_launch_spline(out.inputs)
+    temperature = surface_temperature(out.inputs.geometry, out.X0['longitude'],
+                                      out.X0['latitude'])
+    return np.maximum(spline.ev(temperature, out.randgen.random(out.npackets)), 0.0)
+
+
+def _speed_maxwellian(out, vd, species):
+    if thermal_source(out.inputs):
+        return _speed_thermal(out, vd, species)
+    return _speed_tabulated(out, vd, species)
+
+
 def _speed_from_file(out, vd, species):
     return random_deviates_1d(*speed_file_density(vd), out.npackets)
 
 
 SPEEDS = {'gaussian': _speed_gaussian, 'flat': _speed_flat, 'sputtering': _speed_tabulated,
-          'maxwellian': _speed_tabulated, 'user defined': _speed_from_file}
+          'maxwellian': _speed_maxwellian, 'user defined': _speed_from_file}
 
 
 def speed_distribution(outputs):
