@@ -108,7 +108,9 @@ typedef struct nxc_counters {
     uint64_t particle_steps; /* rk5 steps taken = sum over iterations of active packets          */
     uint64_t samples;        /* packet samples offered to the image (frac > 0 records)           */
     uint64_t samples_binned; /* of those, inside the image range                                 */
-    uint64_t nonfinite;      /* non-finite state / errmax / weight events                        */
+    uint64_t nonfinite;      /* non-finite state / errmax / weight events; impacts without a finite
+                                re-emission (on the polar axis, at rest inside the planet), whose
+                                packets are absorbed where they are (nxc_set_bounce)              */
     uint64_t bad_step;       /* step size <= 0 or not finite (variable driver)                   */
     uint64_t neg_frac;       /* accepted step with frac < 0 (variable driver, Output.py:287)     */
     uint64_t unfinished;     /* packets stopped by max_steps before reaching their end time      */
@@ -156,6 +158,12 @@ typedef struct nxc_bounce_desc {
     uint64_t seed;
 } nxc_bounce_desc;
 
+/* NULL: back to perfect sticking.  With accomfactor != 0 the spline is checked as for
+ * nxc_packets_sample speed_type 3 (finite, non-decreasing knots that increase inside
+ * [t[3], t[n-4]], finite coefficients: NXC_ERR_ARG otherwise, the handle's description unchanged);
+ * with accomfactor == 0 it is never evaluated and zero-filled tables of 8 knots will do.
+ * Re-emission belongs to the constant-step driver: nxc_integrate_var, nxc_integrate_const_streamed
+ * and any launch with bodies set return NXC_ERR_STATE while a description is set. */
 int nxc_set_bounce(nxc_handle *h, const nxc_bounce_desc *d);
 int nxc_set_first_index(nxc_handle *h, int64_t first_index);  /* RNG counter of resident packet 0 */
 
@@ -400,7 +408,9 @@ int nxc_integrate_const_streamed(nxc_handle *h, int64_t n, const double *soa0, i
  * packets per lane (4.7e6 packets) the waves of a SIMD take turns at issue priority and, once the
  * queue is drained, sparse waves hand their live packets to one wave per SIMD; above it the plain
  * form: same arithmetic, same bits (the environment variable NXC_TEST_VAR_VARIANT = "fair" /
- * "plain" forces either, for tests). */
+ * "plain" forces either, for tests).  Returns NXC_ERR_STATE, leaving the handle usable, while
+ * bodies (nxc_set_bodies) or surface re-emission (nxc_set_bounce) are set: the reference has
+ * neither in this driver (Output.py:312-315). */
 int nxc_integrate_var(nxc_handle *h, double resolution, double outeredge, int64_t max_steps,
                       double *final_out, double *hstore_out);
 

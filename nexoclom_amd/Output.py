@@ -399,7 +399,7 @@ class Output:
 
     def _raise_on_counters(self, ctr):
         self.counters = ctr
-        assert ctr.get('nonfinite', 0) == 0, '\n\tInfinite values of emax'
+        assert ctr.get('nonfinite', 0) == 0, '\n\tInfinite values of emax or a non-finite impact'
         assert ctr.get('neg_frac', 0) == 0, 'Found new values of frac that are negative'
         assert ctr.get('bad_step', 0) == 0, 'Bad step size'
 
@@ -533,6 +533,7 @@ class Output:
         assert self._bounce is None, 'Not set up'            # Output.py:312-315
         ctx = self.context()
         ctx.set_forces(**self.forces_kwargs())
+        ctx.set_bounce(None)                 # nxc_integrate_var refuses a handle with re-emission set
         ctx.set_bodies(None)
         ctx.upload_soa(np.ascontiguousarray(self.X[STATE_COLS].values.T, dtype=np.float64))
         final, hs = ctx.integrate_var(float(opt.resolution), opt.outeredge)

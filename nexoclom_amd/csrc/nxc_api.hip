@@ -2039,6 +2039,41 @@ int nxc_set_image(nxc_handle *h, const nxc_image_desc *d)
     });
 }
 
+namespace {
+// What bispev3 needs of a bicubic spline (FITPACK layout) to stay finite: 8..65536 finite,
+// non-decreasing knots per axis that increase inside [t[3], t[n-4]] (a zero-width interval there
+// would divide by zero) and finite coefficients.  One check for every entry that takes such a
+// spline (nxc_set_bounce with accommodation, nxc_packets_sample speed_type 3).  `who` starts the
+// error text; *coef_max receives max |coef|.
+int check_bicubic_spline(const char *who, int64_t nx, int64_t ny, const double *tx, const double *ty,
+                         const double *coef, double *coef_max)
+{
+    if (nx < 8 || ny < 8 || nx > (1 << 16) || ny > (1 << 16) || !tx || !ty || !coef)
+        return fail(NXC_ERR_ARG, std::string(who) + " speeds need a spline with 8..65536 knots per "
+                                 "axis, tx, ty and coef");
+    for (int axis = 0; axis < 2; axis++) {
+        const double *t = axis ? ty : tx;
+        const int64_t nk = axis ? ny : nx;
+        for (int64_t k = 0; k < nk; k++)
+            if (!std::isfinite(t[k]) || (k > 0 && !(t[k] >= t[k - 1])) ||
+                (k > 3 && k <= nk - 4 && !(t[k] > t[k - 1])))
+                return fail(NXC_ERR_ARG, std::string(who) + " spline knots " + (axis ? "ty" : "tx") +
+                                         " must be finite, non-decreasing and increasing inside "
+                                         "[t[3], t[n-4]]");
+    }
+    double big = 0.0;
+    const int64_t n_coef = (nx - 4) * (ny - 4);
+    for (int64_t k = 0; k < n_coef; k++) {
+        if (!std::isfinite(coef[k]))
+            return fail(NXC_ERR_ARG, std::string(who) + " spline coefficients must be finite (coef " +
+                                     std::to_string(k) + ")");
+        big = std::max(big, std::fabs(coef[k]));
+    }
+    if (coef_max) *coef_max = big;
+    return NXC_OK;
+}
+}  // namespace
+
 int nxc_set_bounce(nxc_handle *h, const nxc_bounce_desc *d)
 {
     return guarded([&]() -> int {
@@ -2051,6 +2086,12 @@ int nxc_set_bounce(nxc_handle *h, const nxc_bounce_desc *d)
     if (d->nx < 8 || d->ny < 8 || !d->tx || !d->ty || !d->coef || !(d->unit_km > 0) ||
         d->accomfactor < 0 || d->accomfactor > 1 || d->stickcoef < 0 || d->stickcoef > 1)
         return fail(NXC_ERR_ARG, "bad nxc_bounce_desc");
+    // the spline is evaluated only with accommodation: without it the tables may be dummies
+    if (d->accomfactor != 0) {
+        if (int rc = check_bicubic_spline("nxc_bounce_desc: accommodated", d->nx, d->ny, d->tx, d->ty,
+                                          d->coef, nullptr))
+            return rc;
+    }
     const size_t ncoef = (size_t)(d->nx - 4) * (size_t)(d->ny - 4);
     const size_t total = (size_t)d->nx + (size_t)d->ny + ncoef;
     int rc = ensure(reinterpret_cast<void **>(&h->d_bounce), &h->bounce_cap, total * sizeof(double));
@@ -2432,34 +2473,15 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
         if (!(d->speed_cdf[d->n_speed - 1] > d->speed_cdf[0]))
             return fail(NXC_ERR_ARG, "nxc_source_desc: speed_cdf is flat");
     }
-    // thermal speeds: the surface temperature's constants and the v(T, p) spline, checked like
-    // nxc_set_bounce's table would have to be for bispev3 to stay finite (a zero-width knot
-    // interval inside [t[3], t[n-4]] would divide by zero)
+    // thermal speeds: the surface temperature's constants and the v(T, p) spline
     const int64_t n_coef = thermal ? (d->nx - 4) * (d->ny - 4) : 0;
     double coef_max = 0.0;
     if (thermal) {
         if (!(d->t0 > 0.0) || !std::isfinite(d->t0) || !(d->t1 >= 0.0) || !std::isfinite(d->t1))
             return fail(NXC_ERR_ARG, "nxc_source_desc: thermal speeds need finite t0 > 0 and t1 >= 0");
-        if (d->nx < 8 || d->ny < 8 || d->nx > (1 << 16) || d->ny > (1 << 16) || !d->tx || !d->ty ||
-            !d->coef)
-            return fail(NXC_ERR_ARG, "nxc_source_desc: thermal speeds need a spline with 8..65536 "
-                                     "knots per axis, tx, ty and coef");
-        for (int axis = 0; axis < 2; axis++) {
-            const double *t = axis ? d->ty : d->tx;
-            const int64_t nk = axis ? d->ny : d->nx;
-            for (int64_t k = 0; k < nk; k++)
-                if (!std::isfinite(t[k]) || (k > 0 && !(t[k] >= t[k - 1])) ||
-                    (k > 3 && k <= nk - 4 && !(t[k] > t[k - 1])))
-                    return fail(NXC_ERR_ARG, std::string("nxc_source_desc: thermal spline knots ") +
-                                             (axis ? "ty" : "tx") + " must be finite, non-decreasing "
-                                             "and increasing inside [t[3], t[n-4]]");
-        }
-        for (int64_t k = 0; k < n_coef; k++) {
-            if (!std::isfinite(d->coef[k]))
-                return fail(NXC_ERR_ARG, "nxc_source_desc: thermal spline coefficients must be finite "
-                                         "(coef " + std::to_string(k) + ")");
-            coef_max = std::max(coef_max, std::fabs(d->coef[k]));
-        }
+        if (int rc = check_bicubic_spline("nxc_source_desc: thermal", d->nx, d->ny, d->tx, d->ty,
+                                          d->coef, &coef_max))
+            return rc;
     }
     double map_max = 0.0, map_sum = 0.0;
     if (spot) {
@@ -3498,6 +3520,9 @@ int nxc_integrate_var(nxc_handle *h, double resolution, double outeredge, int64_
     if (!(resolution > 0) || !final_out || max_steps < 1) return fail(NXC_ERR_ARG, "bad arguments");
     if (h->have_bodies)
         return fail(NXC_ERR_STATE, "nxc_integrate_var: moons need the constant-step driver");
+    if (h->have_bounce)
+        return fail(NXC_ERR_STATE, "nxc_integrate_var: surface re-emission needs the constant-step "
+                                   "driver (nxc_set_bounce(h, NULL) for perfect sticking)");
     const size_t col = (size_t)n * sizeof(double);
     if ((rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, 9 * col)))
         return rc;

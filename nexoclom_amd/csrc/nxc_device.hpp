@@ -604,8 +604,11 @@ NXC_DEV double bispev3(const Spline &B, double x, double y)
     return s;
 }
 
-// One impact: move the packet back to the surface along its velocity, re-emit it.
-NXC_DEV void bounce_packet(const BounceK &B, double (&s)[8], double r2, unsigned long long id,
+// One impact: move the packet back to the surface along its velocity, re-emit it.  Returns false,
+// leaving s untouched, when the impact has no finite re-emission: exactly on the polar axis (the
+// east vector is 0/0), at rest inside the planet (the way back is 0/0), or with |z| rounded above
+// 1 on the day side (asin).  The reference asserts on the first two; apply_fate absorbs the packet.
+NXC_DEV bool bounce_packet(const BounceK &B, double (&s)[8], double r2, unsigned long long id,
                            int &nbounce)
 {
     const double TWO_PI = 6.283185307179586;
@@ -645,15 +648,22 @@ NXC_DEV void bounce_packet(const BounceK &B, double (&s)[8], double r2, unsigned
         const double v_emit = bispev3(B, tsurf, u_p) / B.unit_km;       // :71-75
         v_new = nxc_sqrt(v_emit * v_emit * B.accom + v_old2 * (1 - B.accom));   // :77-78
     }
-    s[1] = x; s[2] = y; s[3] = z;
-    s[4] = dx * v_new; s[5] = dy * v_new; s[6] = dz * v_new;            // :80
+    const double wx = dx * v_new, wy = dy * v_new, wz = dz * v_new;     // :80
+    double frac = s[7];
     if (B.temp_dependent) {                                             // :83-89, SurfaceInteraction.py:13-20
         double st = B.A0 * exp(B.A1 * tsurf) + B.A2;
         st = st > 1. ? 1. : (st < 0. ? 0. : st);
-        s[7] *= (1 - st);
+        frac *= (1 - st);
     } else if (B.stickcoef > 0) {
-        s[7] *= (1 - B.stickcoef);                                      // :92-93
+        frac *= (1 - B.stickcoef);                                      // :92-93
     }
+    // v * 0 is 0 for a finite v and NaN otherwise
+    const double zero = ((x * 0.0 + y * 0.0) + (z * 0.0 + frac * 0.0)) + ((wx * 0.0 + wy * 0.0) + wz * 0.0);
+    if (zero != 0.0) return false;
+    s[1] = x; s[2] = y; s[3] = z;
+    s[4] = wx; s[5] = wy; s[6] = wz;
+    s[7] = frac;
+    return true;
 }
 
 // Post-step tests with stickcoef == 1.  Constant driver: Output.py:395-416 (r = |x|); variable
@@ -663,15 +673,18 @@ NXC_DEV void bounce_packet(const BounceK &B, double (&s)[8], double r2, unsigned
 // correctly rounded square root is <= outeredge (so r2 > edge2  <=>  sqrt(r2) > outeredge), for
 // the variable driver outeredge itself.
 // With BOUNCE a packet that hits the surface is re-emitted instead of absorbed (Output.py:398-402);
-// the escape test still uses the pre-impact radius, as the reference's tempR does.
+// the escape test still uses the pre-impact radius, as the reference's tempR does.  An impact
+// without a finite re-emission (bounce_packet) is absorbed where it is and counted in `nonfinite`.
 template <bool BOUNCE, bool NBODY = false>
 NXC_DEV void apply_fate(double (&s)[8], double edge2, unsigned long long id, int &nbounce,
-                        const BodyK *Bd = nullptr, const double *__restrict__ base = nullptr)
+                        unsigned long long &nonfinite, const BodyK *Bd = nullptr,
+                        const double *__restrict__ base = nullptr)
 {
     const double r2 = (s[1] * s[1] + s[2] * s[2]) + s[3] * s[3];
     if (r2 < 1.0) {
-        if (BOUNCE) bounce_packet(lds_header().B, s, r2, id, nbounce);
-        else s[7] = 0.0;
+        if (BOUNCE) {
+            if (!bounce_packet(lds_header().B, s, r2, id, nbounce)) { s[7] = 0.0; nonfinite++; }
+        } else s[7] = 0.0;
     }
     if (r2 > edge2) s[7] = 0.0;
     if (NBODY) {                    // absorbed by a moon (positions at the end of the step)

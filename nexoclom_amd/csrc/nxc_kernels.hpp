@@ -534,10 +534,10 @@ k_const_fused(ForceK F, const unsigned char *__restrict__ blob,
                     const BodyK *Bd = &lds_header().Bd;
                     const double *mp = moon_pos + (long long)k * (2 * Bd->n_moons);
                     rk5_step<false, true, FULL, true>(F, T, s, 0.0, lds_header().W, d, Bd, mp);
-                    apply_fate<false, true>(s, edge2, 0ull, nbounce, Bd, mp);
+                    apply_fate<false, true>(s, edge2, 0ull, nbounce, my_nonfinite, Bd, mp);
                 } else {
                     rk5_step<false, true, FULL>(F, T, s, 0.0, lds_header().W, d);
-                    apply_fate<BOUNCE>(s, edge2, (unsigned long long)(first_id + id), nbounce);
+                    apply_fate<BOUNCE>(s, edge2, (unsigned long long)(first_id + id), nbounce, my_nonfinite);
                 }
 #ifdef NXC_PROBE_VMOV      /* what binds the loop? N independent cheap / fp64 instructions per trip */
                 {
@@ -639,8 +639,8 @@ k_const_fused(ForceK F, const unsigned char *__restrict__ blob,
     if (IMAGE) {
         flush_counter(&ctr->samples, my_samples);
         flush_counter(&ctr->samples_binned, my_binned);
-        flush_counter(&ctr->nonfinite, my_nonfinite);
     }
+    if (IMAGE || BOUNCE) flush_counter(&ctr->nonfinite, my_nonfinite);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -899,7 +899,7 @@ k_var(ForceK F, const unsigned char *__restrict__ blob, int64_t stage_bytes, int
                         double hold = h;
                         if (e < 1e-7) { e = 1.0; hold = h * 10; }
                         if (e < 1.0) {
-                            { int nb_ = 0; apply_fate<false>(t, outeredge, 0ull, nb_); }
+                            { int nb_ = 0; apply_fate<false>(t, outeredge, 0ull, nb_, my_nonfinite); }
 #pragma unroll
                             for (int c = 0; c < 8; c++) s[c] = t[c];
                         } else {
