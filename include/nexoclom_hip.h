@@ -143,15 +143,20 @@ int nxc_set_image(nxc_handle *h, const nxc_image_desc *d);   /* also zeroes the 
  * (Output.py:398-402).  NULL restores perfect sticking.  Random numbers are Philox draws keyed
  * by (seed; first_index + packet row, bounce number): statistically the reference's process.
  * tx[nx], ty[ny], coef[(nx-4)*(ny-4)]: knots/coefficients of scipy's RectBivariateSpline
- * (SurfaceInteraction.py:56) in km/s; ignored when accomfactor == 0. */
+ * (SurfaceInteraction.py:56) in km/s; ignored when accomfactor == 0.
+ * Sticking law (temp_dependent): 0 the constant stickcoef, 1 clip(A0 exp(A1 T) + A2, 0, 1) at the
+ * local surface temperature, 2 the surface map of nxc_set_stick_map at the impact point (the
+ * inputfiles' sticktype = surface map, which the reference documents and never wrote); frac is
+ * multiplied by 1 - coefficient.  The two calls may come in either order; a launch with law 2 and
+ * no map returns NXC_ERR_STATE and leaves the handle usable. */
 typedef struct nxc_bounce_desc {
     double GM;            /* R^3/s^2 (negative), for the impact speed (bouncepackets.py:59)      */
     double unit_km;
     double accomfactor;   /* 0 = elastic rebound at the impact speed                            */
-    double stickcoef;     /* constant sticking (used when !temp_dependent)                      */
+    double stickcoef;     /* constant sticking (used when temp_dependent == 0)                  */
     double A[3];          /* temperature-dependent sticking A0 exp(A1 T) + A2                   */
     double t0, t1;        /* surface temperature: t0 night, t0 + t1 |cos lon cos lat|^0.25 day  */
-    int32_t temp_dependent;
+    int32_t temp_dependent; /* sticking law: 0 constant, 1 temperature, 2 surface map            */
     int32_t reserved;
     int64_t nx, ny;
     const double *tx, *ty, *coef;
@@ -166,6 +171,24 @@ typedef struct nxc_bounce_desc {
  * and any launch with bodies set return NXC_ERR_STATE while a description is set. */
 int nxc_set_bounce(nxc_handle *h, const nxc_bounce_desc *d);
 int nxc_set_first_index(nxc_handle *h, int64_t first_index);  /* RNG counter of resident packet 0 */
+
+/* Sticking coefficient from a surface map (sticking law 2 of nxc_bounce_desc): coef[nlon * nlat],
+ * longitude-major, in [0, 1], on the nodes lon[nlon] (rad, strictly increasing within [0, 2 pi);
+ * 0 at the sub-solar point, pi/2 at dusk: the solar-fixed longitude atan2(x, -y) of the impact)
+ * and lat[nlat] (rad, strictly increasing within [-pi/2, pi/2]); nlat = 0: coef[nlon], a function
+ * of longitude only.  At an impact the map is interpolated bilinearly: periodic in longitude (the
+ * interval from lon[nlon-1] to lon[0] + 2 pi closes the circle), clamped to the end nodes in
+ * latitude; with wl, wt the fractions of the cell (i, j),
+ *   S = (S[i][j] (1 - wl) + S[i+1][j] wl) (1 - wt) + (S[i][j+1] (1 - wl) + S[i+1][j+1] wl) wt,
+ * evaluated in that order, one rounding per operation.  The arrays are copied to the device.
+ * NULL clears the map.  Fewer than 2 (or more than 65536) nodes on an axis, nodes out of order or
+ * range, or a coefficient that is not a number in [0, 1]: NXC_ERR_ARG, the handle unchanged.
+ * nxc_set_bounce(h, NULL) does not clear the map, and a map without law 2 is ignored. */
+typedef struct nxc_stick_map_desc {
+    int64_t nlon, nlat;
+    const double *lon, *lat, *coef;
+} nxc_stick_map_desc;
+int nxc_set_stick_map(nxc_handle *h, const nxc_stick_map_desc *d);
 
 /* ---- f-4 (tail): moons and plasma-torus loss ---------------------------------------------------
  * EXTENSION -- no reference implementation exists: particle_tracking/state.py:5-10 documents

@@ -388,6 +388,9 @@ struct nxc_handle {
     bool have_bounce = false;
     double *d_bounce = nullptr;      // spline knots + coefficients of the accommodation table
     size_t bounce_cap = 0;
+    bool have_stick_map = false;
+    double *d_stick_map = nullptr;   // sticking map: longitude nodes, latitude nodes, coefficients
+    size_t stick_map_cap = 0;
     double *d_source = nullptr;      // sampler tables: speed CDF + speeds, surface density map
     size_t source_cap = 0;
     DevCounters *d_ctr = nullptr;
@@ -905,6 +908,15 @@ int speed_order_for_const(nxc_handle *h)
     return order_on_device(h, -1.0, nullptr, 0);
 }
 
+// Sticking law 2 reads the map at every impact: no launch without one.
+int need_stick_map(nxc_handle *h)
+{
+    if (h->have_bounce && h->header.B.temp_dependent == 2 && !h->have_stick_map)
+        return fail(NXC_ERR_STATE, "the bounce description asks for sticking from a surface map "
+                                   "(temp_dependent = 2) and no map is set (nxc_set_stick_map)");
+    return NXC_OK;
+}
+
 int launch_const(nxc_handle *h, double step, int64_t n_iter, double outeredge, bool image,
                  double *d_final, long long *d_steps)
 {
@@ -919,6 +931,7 @@ int launch_const(nxc_handle *h, double step, int64_t n_iter, double outeredge, b
             return fail(NXC_ERR_STATE, "surface re-emission is not available with moons set");
         if ((rc = upload_moon_table(h, step, n_iter))) return rc;
     }
+    if ((rc = need_stick_map(h))) return rc;
     return pick_fused(h, tables, lds, n_iter, edge2, image, d_final, d_steps, whole_set(h));
 }
 
@@ -1023,6 +1036,7 @@ int write_records(nxc_handle *h, bool narrow, size_t reserve)
             return fail(NXC_ERR_STATE, "surface re-emission is not available with moons set");
         if ((rc = upload_moon_table(h, h->rows_step, h->rows_n_iter))) return rc;
     }
+    if ((rc = need_stick_map(h))) return rc;
     if ((rc = upload_step(h, h->rows_step))) return rc;
     HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
     const double edge2 = sqrt_threshold(h->rows_edge);
@@ -1855,7 +1869,7 @@ int nxc_destroy(nxc_handle *h)
     g_coll_failure.clear();
     if (h->comm && g_rccl.ok) g_rccl.CommDestroy(h->comm);
     void *ptrs[] = {h->d_blob, h->d_image, h->d_packets, h->d_ctr, h->d_scratch,
-                    h->d_steps, h->d_reduce, h->d_order, h->d_bounce, h->d_moonpos, h->d_offsets,
+                    h->d_steps, h->d_reduce, h->d_order, h->d_bounce, h->d_stick_map, h->d_moonpos, h->d_offsets,
                     h->d_source, h->d_queue, h->d_samples, h->d_tiles, h->d_hist, h->d_rec, h->d_piece_hist,
                     h->d_blob_img, h->d_reduce_n, h->d_losblk, h->d_dens_pts, h->d_dens_cell,
                     h->d_dens_acc, h->d_fit_spec, h->d_fit_pk, h->d_fit_smp, h->d_fit_aux,
@@ -2102,10 +2116,61 @@ int nxc_set_bounce(nxc_handle *h, const nxc_bounce_desc *d)
     BounceK &B = h->header.B;
     B.GM = d->GM; B.unit_km = d->unit_km; B.accom = d->accomfactor; B.stickcoef = d->stickcoef;
     B.A0 = d->A[0]; B.A1 = d->A[1]; B.A2 = d->A[2]; B.t0 = d->t0; B.t1 = d->t1;
-    B.temp_dependent = d->temp_dependent ? 1 : 0; B.nx = (int)d->nx; B.ny = (int)d->ny;
+    B.temp_dependent = d->temp_dependent == 2 ? 2 : (d->temp_dependent ? 1 : 0); B.nx = (int)d->nx; B.ny = (int)d->ny;
     B.seed = d->seed;
     B.tx = h->d_bounce; B.ty = h->d_bounce + d->nx; B.coef = h->d_bounce + d->nx + d->ny;
     h->have_bounce = true;
+    if (h->d_blob)
+        HIPCHK(hipMemcpyAsync(h->d_blob + offsetof(LdsHeader, B), &h->header.B, sizeof(BounceK),
+                              hipMemcpyHostToDevice, h->stream));
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+    });
+}
+
+int nxc_set_stick_map(nxc_handle *h, const nxc_stick_map_desc *d)
+{
+    return guarded([&]() -> int {
+    if (!h) return fail(NXC_ERR_ARG, "null handle");
+    HIPCHK(hipSetDevice(h->device));
+    BounceK &B = h->header.B;
+    if (d) {
+        const double TWO_PI = 6.283185307179586, HALF_PI = 1.5707963267948966;
+        const int64_t nlon = d->nlon, nlat = d->nlat;
+        if (nlon < 2 || nlon > (1 << 16) || nlat < 0 || nlat == 1 || nlat > (1 << 16) || !d->lon ||
+            !d->coef || (nlat && !d->lat))
+            return fail(NXC_ERR_ARG, "nxc_stick_map_desc: 2..65536 longitude nodes, 0 or 2..65536 "
+                                     "latitude nodes, lon, coef (and lat)");
+        for (int64_t k = 0; k < nlon; k++)
+            if (!(d->lon[k] >= 0 && d->lon[k] < TWO_PI) || (k > 0 && !(d->lon[k] > d->lon[k - 1])))
+                return fail(NXC_ERR_ARG, "nxc_stick_map_desc: longitude nodes must increase within "
+                                         "[0, 2 pi) (lon " + std::to_string(k) + ")");
+        for (int64_t k = 0; k < nlat; k++)
+            if (!(d->lat[k] >= -HALF_PI && d->lat[k] <= HALF_PI) || (k > 0 && !(d->lat[k] > d->lat[k - 1])))
+                return fail(NXC_ERR_ARG, "nxc_stick_map_desc: latitude nodes must increase within "
+                                         "[-pi/2, pi/2] (lat " + std::to_string(k) + ")");
+        const int64_t ncoef = nlon * (nlat ? nlat : 1);
+        for (int64_t k = 0; k < ncoef; k++)
+            if (!(d->coef[k] >= 0 && d->coef[k] <= 1))
+                return fail(NXC_ERR_ARG, "nxc_stick_map_desc: coefficients must lie in [0, 1] (coef " +
+                                         std::to_string(k) + " = " + std::to_string(d->coef[k]) + ")");
+        const size_t total = (size_t)(nlon + nlat + ncoef);
+        // (a launch that reads the previous map has ended: every launch is followed by a sync or is
+        // ordered before these copies on the handle's stream)
+        int rc = ensure(reinterpret_cast<void **>(&h->d_stick_map), &h->stick_map_cap, total * sizeof(double));
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(h->d_stick_map, d->lon, (size_t)nlon * 8, hipMemcpyHostToDevice, h->stream));
+        if (nlat)
+            HIPCHK(hipMemcpyAsync(h->d_stick_map + nlon, d->lat, (size_t)nlat * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_stick_map + nlon + nlat, d->coef, (size_t)ncoef * 8, hipMemcpyHostToDevice, h->stream));
+        B.mlon = h->d_stick_map; B.mlat = h->d_stick_map + nlon; B.mcoef = h->d_stick_map + nlon + nlat;
+        B.mlon_n = (int)nlon; B.mlat_n = (int)nlat;
+        h->have_stick_map = true;
+    } else {
+        B.mlon = B.mlat = B.mcoef = nullptr;
+        B.mlon_n = B.mlat_n = 0;
+        h->have_stick_map = false;
+    }
     if (h->d_blob)
         HIPCHK(hipMemcpyAsync(h->d_blob + offsetof(LdsHeader, B), &h->header.B, sizeof(BounceK),
                               hipMemcpyHostToDevice, h->stream));

@@ -416,12 +416,16 @@ struct ImageK {            // kernel-argument scalars of nxc_image_desc
 // VALU-bound kernel.  (StepW is defined above; ImageK here.)
 // Surface re-emission constants (particle_tracking/bouncepackets.py; read only when a packet
 // hits the surface).  tx/ty/coef: knots and coefficients of the bicubic spline v(T, p) in global
-// memory (FITPACK layout: coef[(nx-4) x (ny-4)] row-major).
+// memory (FITPACK layout: coef[(nx-4) x (ny-4)] row-major).  temp_dependent selects the sticking
+// law: 0 constant, 1 temperature, 2 the map mcoef[mlon_n x mlat_n] (lon-major; mlat_n = 0: a
+// function of longitude only) on the nodes mlon, mlat, in global memory as well (nxc_set_stick_map).
 struct BounceK {
     double GM, unit_km, accom, stickcoef, A0, A1, A2, t0, t1;
     int temp_dependent, nx, ny, pad_;
     unsigned long long seed;
     const double *tx, *ty, *coef;
+    const double *mlon, *mlat, *mcoef;
+    int mlon_n, mlat_n;
 };
 
 // Kernel arguments the persistent loop touches only rarely (a chunk claim per 64 packets, a final
@@ -604,6 +608,43 @@ NXC_DEV double bispev3(const Spline &B, double x, double y)
     return s;
 }
 
+// Largest k in [0, n-1] with t[k] <= x (0 when there is none): never outside the array, whatever x.
+NXC_DEV int node_below(const double *__restrict__ t, int n, double x)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (x >= t[mid]) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Sticking coefficient of the map at an impact point (surface.py, SurfaceInteraction.stickcoef: the
+// same operations in the same order).  Bilinear on the file's nodes; longitude is periodic -- the
+// interval from the last node to the first + 2 pi serves lon >= L[n-1] and lon < L[0], the latter
+// shifted by 2 pi -- and latitude is clamped to the end nodes.  A NaN (|z| rounded above 1) stays a
+// NaN: bounce_packet then absorbs the packet.  Not clamped to [0, 1] here.
+NXC_DEV double stick_map_at(const BounceK &B, double lon, double lat)
+{
+    const double TWO_PI = 6.283185307179586;
+    const double *__restrict__ L = B.mlon, *__restrict__ S = B.mcoef;
+    const int n = B.mlon_n, m = B.mlat_n;
+    int i;
+    if (lon < L[0]) { lon = lon + TWO_PI; i = n - 1; }
+    else i = node_below(L, n, lon);
+    const int i1 = i == n - 1 ? 0 : i + 1;
+    const double l0 = L[i], l1 = i == n - 1 ? L[0] + TWO_PI : L[i + 1];
+    const double wl = (lon - l0) / (l1 - l0);
+    if (m == 0) return S[i] * (1 - wl) + S[i1] * wl;
+    const double *__restrict__ T = B.mlat;
+    lat = lat < T[0] ? T[0] : (lat > T[m - 1] ? T[m - 1] : lat);
+    int j = node_below(T, m, lat);
+    j = j > m - 2 ? m - 2 : j;
+    const double wt = (lat - T[j]) / (T[j + 1] - T[j]);
+    return (S[i * m + j] * (1 - wl) + S[i1 * m + j] * wl) * (1 - wt) +
+           (S[i * m + j + 1] * (1 - wl) + S[i1 * m + j + 1] * wl) * wt;
+}
+
 // One impact: move the packet back to the surface along its velocity, re-emit it.  Returns false,
 // leaving s untouched, when the impact has no finite re-emission: exactly on the polar axis (the
 // east vector is 0/0), at rest inside the planet (the way back is 0/0), or with |z| rounded above
@@ -650,7 +691,11 @@ NXC_DEV bool bounce_packet(const BounceK &B, double (&s)[8], double r2, unsigned
     }
     const double wx = dx * v_new, wy = dy * v_new, wz = dz * v_new;     // :80
     double frac = s[7];
-    if (B.temp_dependent) {                                             // :83-89, SurfaceInteraction.py:13-20
+    if (B.temp_dependent == 2) {                                        // the documented surface map
+        double st = stick_map_at(B, lonhit, lathit);
+        st = st > 1. ? 1. : (st < 0. ? 0. : st);
+        frac *= (1 - st);
+    } else if (B.temp_dependent) {                                      // :83-89, SurfaceInteraction.py:13-20
         double st = B.A0 * exp(B.A1 * tsurf) + B.A2;
         st = st > 1. ? 1. : (st < 0. ? 0. : st);
         frac *= (1 - st);

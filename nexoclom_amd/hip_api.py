@@ -41,7 +41,7 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_pairs_download', 'nxc_los_set_pairs', 'nxc_fit_set', 'nxc_fit_source_rows',
            'nxc_fit_source', 'nxc_fit_source_f32', 'nxc_fit_packets', 'nxc_fit_radiance',
            'nxc_fit_rows', 'nxc_fit_download', 'nxc_source_map_set', 'nxc_source_map_accumulate',
-           'nxc_source_map_download')
+           'nxc_source_map_download', 'nxc_set_stick_map')
 ABI_VERSION = 3
 
 
@@ -124,6 +124,10 @@ class nxc_bounce_desc(C.Structure):
                 ('t1', C.c_double), ('temp_dependent', C.c_int32), ('reserved', C.c_int32),
                 ('nx', C.c_int64), ('ny', C.c_int64), ('tx', _dp), ('ty', _dp), ('coef', _dp),
                 ('seed', C.c_uint64)]
+
+
+class nxc_stick_map_desc(C.Structure):
+    _fields_ = [('nlon', C.c_int64), ('nlat', C.c_int64), ('lon', _dp), ('lat', _dp), ('coef', _dp)]
 
 
 class nxc_bodies_desc(C.Structure):
@@ -397,10 +401,15 @@ class Context:
         self.image_shape = (int(d.nx), int(d.nz))
 
     def set_bounce(self, cfg):
-        """cfg: dict from nexoclom_amd.surface.bounce_config, or None for perfect sticking."""
+        """cfg: dict from nexoclom_amd.surface.bounce_config, or None for perfect sticking.
+        ``temp_dependent`` is the sticking law (0 constant, 1 temperature, 2 surface map); with
+        ``stick_map`` = (longitude nodes, latitude nodes or None, coefficients) the map is set
+        first, so that a refused map leaves the description as it was."""
         if cfg is None:
             self._check(self.lib.nxc_set_bounce(self._h, None))
             return
+        if cfg.get('stick_map') is not None:
+            self.set_stick_map(*cfg['stick_map'])
         d = nxc_bounce_desc()
         d.GM, d.unit_km = cfg['GM'], cfg['unit_km']
         d.accomfactor, d.stickcoef = cfg['accomfactor'], cfg['stickcoef']
@@ -412,6 +421,25 @@ class Context:
         d.tx, d.ty, d.coef = _p(tx), _p(ty), _p(coef)
         d.seed = int(cfg['seed']) & 0xffffffffffffffff
         self._check(self.lib.nxc_set_bounce(self._h, C.byref(d)))
+
+    def set_stick_map(self, longitude, latitude=None, coef=None):
+        """The surface map of sticking law 2 (nxc_set_stick_map): coef[nlon, nlat] on the nodes
+        ``longitude``, ``latitude`` [rad], or coef[nlon] with ``latitude`` None; ``longitude``
+        None clears the map."""
+        if longitude is None:
+            self._check(self.lib.nxc_set_stick_map(self._h, None))
+            return
+        lon, val = _f64(longitude), _f64(coef)
+        lat = None if latitude is None else _f64(latitude)
+        shape = (len(lon),) if lat is None else (len(lon), len(lat))
+        if val.shape != shape:
+            raise ValueError(f'stick_map: coef{val.shape} does not fit its axes {shape}')
+        d = nxc_stick_map_desc()
+        d.nlon, d.nlat = len(lon), 0 if lat is None else len(lat)
+        d.lon, d.coef = _p(lon), _p(val)
+        if lat is not None:
+            d.lat = _p(lat)
+        self._check(self.lib.nxc_set_stick_map(self._h, C.byref(d)))
 
     def set_bodies(self, cfg):
         """cfg: dict(moons=[dict(gm, radius, a, omega, phi), ...], t0, chx=dict(k0, rho0, width,

@@ -9,6 +9,13 @@ FITPACK).  ``bounce_tables()`` exports the spline's knots and coefficients so th
 evaluates the very same spline (de Boor) at every impact.  The same table gives thermal launch
 speeds ('maxwellian' at temperature 0): ``thermal_launch_spline`` builds it once per Input, whatever
 the surface interaction.
+
+Sticking from a surface map (``sticktype = surface map``; docs/nexoclom/inputfiles.rst, "Sticking
+Coefficient from a Surface Map"; the reference stops at ``assert 0``, SurfaceInteraction.py:23-24 and
+bouncepackets.py:90-91): ``stick_mapfile`` names a SourceMap .npz whose ``abundance`` holds the
+coefficient on the nodes ``longitude`` (x ``latitude``), solar-fixed.  ``load_sticking_map`` reads
+and checks it, ``sticking_map_callable`` is the interpolation rule the kernel follows operation
+for operation (nxc_device.hpp, stick_map_at).
 """
 import threading
 
@@ -94,18 +101,124 @@ def thermal_launch_spline(inputs):
         return spline
 
 
+TWO_PI = 6.283185307179586
+DEFAULT_A = (1.57014, -0.006262, 0.1614157)      # the inputfiles' default coefficients of the law
+
+
+def _first_not_a_coefficient(values):
+    """Index (as a tuple) and value of the first entry that is not a finite number in [0, 1]."""
+    bad = np.argwhere(~(np.isfinite(values) & (values >= 0) & (values <= 1)))
+    return (None, None) if len(bad) == 0 else (tuple(int(k) for k in bad[0]), values[tuple(bad[0])])
+
+
+def check_sticking_map(longitude, latitude, coef, name='sticking map'):
+    """(longitude, latitude or None, coef) as contiguous float64, or the ValueError that says why
+    the map cannot be interpolated: what nxc_set_stick_map checks, with names."""
+    if coef is None or longitude is None:
+        raise ValueError(f'{name} holds no abundance map (the sticking coefficient)')
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    longitude = np.ascontiguousarray(longitude, dtype=np.float64)
+    latitude = None if latitude is None else np.ascontiguousarray(latitude, dtype=np.float64)
+    if longitude.ndim != 1 or (latitude is not None and latitude.ndim != 1):
+        raise ValueError(f'{name}: longitude and latitude must be 1-D')
+    shape = (len(longitude),) if latitude is None else (len(longitude), len(latitude))
+    if coef.shape != shape or min(shape) < 2:
+        raise ValueError(f'{name}: abundance{coef.shape} does not fit its axes {shape} (at least '
+                         'two nodes each)')
+    if not (np.all(np.diff(longitude) > 0) and longitude[0] >= 0 and longitude[-1] < TWO_PI):
+        raise ValueError(f'{name}: longitude nodes must increase strictly within [0, 2 pi)')
+    if latitude is not None and not (np.all(np.diff(latitude) > 0) and latitude[0] >= -np.pi/2
+                                     and latitude[-1] <= np.pi/2):
+        raise ValueError(f'{name}: latitude nodes must increase strictly within [-pi/2, pi/2]')
+    where, value = _first_not_a_coefficient(coef)
+    if where is not None:
+        raise ValueError(f'{name}: abundance{list(where)} = {value}; a sticking coefficient must be '
+                         'finite and in [0, 1]')
+    return longitude, latitude, coef
+
+
+def load_sticking_map(spec):
+    """(longitude, latitude or None, coef) of ``surfaceinteraction.stick_mapfile``, or the reason
+    it cannot be used.  Planet-fixed maps are refused as the reference refuses them for sources
+    ('Need to verify this works', source_distribution.py:85-93)."""
+    from .source_distribution import source_file
+    smap = source_file('stick_mapfile', spec.stick_mapfile)
+    checked = check_sticking_map(smap.longitude, smap.latitude, smap.abundance, spec.stick_mapfile)
+    if 'planet' in smap.coordinate_system:
+        if spec.subsolarlon is None:
+            raise ValueError('inputs.surfaceinteraction.subsolarlon is None')
+        raise NotImplementedError('planet-fixed sticking maps: the reference stops here for source '
+                                  "maps as well ('Need to verify this works')")
+    return checked
+
+
+def sticking_map_callable(longitude, latitude, coef):
+    """stickcoef(lon, lat) of a checked map.  Bilinear on the map's own nodes.  Longitude is
+    periodic: the interval from the last node to the first + 2 pi serves lon >= L[n-1] and
+    lon < L[0], the latter shifted by 2 pi.  Latitude is clamped to the end nodes.  i is the
+    largest index with L[i] <= lon, j likewise, capped at m - 2; wl = (lon - L[i])/(L[i+1] - L[i]),
+    wt likewise, and
+        S = (S[i,j] (1 - wl) + S[i+1,j] wl) (1 - wt) + (S[i,j+1] (1 - wl) + S[i+1,j+1] wl) wt,
+    every operation rounded once, in that order (the kernel's stick_map_at), then clipped to
+    [0, 1].  A 1-D map (``latitude`` None) uses the longitude part only."""
+    L, T, S = longitude, latitude, coef
+    n = len(L)
+
+    def stickcoef(lon, lat):
+        lon = np.array(lon, dtype=np.float64, ndmin=1)
+        low = lon < L[0]
+        lon[low] = lon[low] + TWO_PI
+        i = np.clip(np.searchsorted(L, lon, side='right') - 1, 0, n - 1)
+        i[low] = n - 1
+        last = i == n - 1
+        i1 = np.where(last, 0, i + 1)
+        l1 = np.where(last, L[0] + TWO_PI, L[i1])
+        wl = (lon - L[i])/(l1 - L[i])
+        if T is None:
+            return np.clip(S[i]*(1 - wl) + S[i1]*wl, 0., 1.)
+        lat = np.array(lat, dtype=np.float64, ndmin=1)
+        lat = np.where(lat < T[0], T[0], np.where(lat > T[-1], T[-1], lat))
+        j = np.clip(np.searchsorted(T, lat, side='right') - 1, 0, len(T) - 2)
+        wt = (lat - T[j])/(T[j + 1] - T[j])
+        return np.clip((S[i, j]*(1 - wl) + S[i1, j]*wl)*(1 - wt) +
+                       (S[i, j + 1]*(1 - wl) + S[i1, j + 1]*wl)*wt, 0., 1.)
+    return stickcoef
+
+
+def sticking_map_from_law(inputs, longitude, latitude):
+    """The Yakshinskiy-Madey law clip(A0 exp(A1 T) + A2, 0, 1) of these inputs
+    (``surfaceinteraction.A``, or the inputfiles' default coefficients when the inputs name no
+    ``A``) on the nodes ``longitude`` x ``latitude`` [rad], as a SourceMap ready for ``.save()``:
+    the file a ``sticktype = surface map`` run reads back."""
+    from .sourcemap import SourceMap
+    longitude = np.asarray(longitude, dtype=np.float64)
+    latitude = np.asarray(latitude, dtype=np.float64)
+    A = getattr(inputs.surfaceinteraction, 'A', None) or DEFAULT_A
+    law = SurfaceInteraction._sticking_law(inputs.geometry, A)
+    lon, lat = np.meshgrid(longitude, latitude, indexing='ij')
+    coef = law(lon.ravel(), lat.ravel()).reshape(lon.shape)
+    smap = SourceMap(dict(abundance=coef, longitude=longitude, latitude=latitude,
+                          coordinate_system='solar-fixed'))
+    smap.units = {'longitude': 'rad', 'latitude': 'rad', 'abundance': ''}
+    return smap
+
+
+
 class SurfaceInteraction:
     """SurfaceInteraction.py:10-61: ``stickcoef(lon, lat)`` for temperature-dependent sticking
-    and ``v_interp(T, p)`` [km/s] for accommodation (when accomfactor != 0): the speed below which
+    and for sticking from a surface map (``stick_map``: its nodes and coefficients), and ``v_interp(T, p)`` [km/s] for accommodation (when accomfactor != 0): the speed below which
     a fraction p of a Maxwellian flux at temperature T is emitted, tabulated on ``nt``
     temperatures spanning the planet's surface and ``nprob`` probabilities."""
 
     def __init__(self, inputs, nt=201, nv=101, nprob=101):
         spec = inputs.surfaceinteraction
         self.inputs = inputs
-        assert spec.sticktype != 'surface map', 'sticking maps are out of scope'
+        self.stick_map = None
         if spec.sticktype == 'temperature dependent':
             self.stickcoef = self._sticking_law(inputs.geometry, spec.A)
+        elif spec.sticktype == 'surface map':
+            self.stick_map = load_sticking_map(spec)
+            self.stickcoef = sticking_map_callable(*self.stick_map)
         self.spline = None
         if spec.accomfactor != 0:
             self._tabulate(inputs, nt, nv, nprob)
@@ -132,17 +245,19 @@ class SurfaceInteraction:
 
 def bounce_config(inputs, GM, unit_km, seed):
     """Keyword arguments of hip_api.Context.set_bounce for these inputs; None when packets simply
-    stick (stickcoef == 1)."""
+    stick (stickcoef == 1).  ``temp_dependent`` is the sticking law: 0 constant, 1 temperature,
+    2 the surface map ``stick_map`` = (longitude, latitude or None, coef)."""
     spec = inputs.surfaceinteraction
     if spec.sticktype == 'constant' and spec.stickcoef == 1.:
         return None
     surf = SurfaceInteraction(inputs)
     tx, ty, coef = surf.bounce_tables()
     by_temperature = spec.sticktype == 'temperature dependent'
+    by_map = spec.sticktype == 'surface map'
     return dict(GM=float(GM), unit_km=float(unit_km),
                 accomfactor=float(spec.accomfactor or 0.0),
-                temp_dependent=int(by_temperature),
-                stickcoef=0.0 if by_temperature else float(spec.stickcoef),
+                temp_dependent=2 if by_map else int(by_temperature), stick_map=surf.stick_map,
+                stickcoef=0.0 if by_temperature or by_map else float(spec.stickcoef),
                 A=tuple(spec.A) if by_temperature else (0., 0., 0.),
                 t0=NIGHT_SIDE_K, t1=float(day_side_t1(inputs.geometry)), tpow=0.25,
                 tx=tx, ty=ty, coef=coef, seed=0 if seed is None else int(seed),
