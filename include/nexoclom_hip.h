@@ -286,7 +286,26 @@ int nxc_last_kernel_ms(nxc_handle *h, float *ms);  /* HIP-event time of the last
  *                             nxc_bounce_desc layout) of SurfaceInteraction.py:28-61, u the speed
  *                             uniform.  Speed bound of the queue: max |coef| (B-spline bases are
  *                             >= 0 and sum to 1)
- *   direction angular_type 0  radial, 1 isotropic (:198-252) */
+ *             speed_type 4    per-node tables of a 2-D surface map (needs spatial_type 2): the
+ *                             packet comes from one corner node c of its launch cell (i, j), drawn
+ *                             with probability w_c A_c / sum w A -- w the bilinear hat weights at
+ *                             the launch point's in-cell coordinates (tx, ty), A the node values
+ *                             `map` -- so that the joint law is sum_c w_c A_c p_c and the launch
+ *                             points keep the law of spatial_type 2.  Corners in the order (i, j),
+ *                             (i, j+1), (i+1, j), (i+1, j+1) with weights (1-tx)(1-ty) a,
+ *                             (1-tx) ty b, tx (1-ty) c, tx ty d: the first whose running sum
+ *                             exceeds u_corner * total; if rounding leaves none, the last with a
+ *                             positive weight; if total is not > 0 (a point on a zero edge), the
+ *                             corner with the largest A.  u_corner is the second uniform of Philox
+ *                             block 17.  Then v = interp(u, node_speed_cdf[c], node_speed_v), u the
+ *                             speed uniform.  Speed bound of the queue: max |node_speed_v|
+ *   direction angular_type 0  radial, 1 isotropic (:198-252)
+ *             angular_type 2  per-node tables (needs spatial_type 2): altitude =
+ *                             interp(u_alt, node_alt_cdf[c], node_alt) and azimuth = interp(u_az,
+ *                             node_az_cdf[c], node_az) at the same corner node c as speed_type 4
+ *                             (one corner serves all of a packet's per-node draws).  Goes with
+ *                             speed_type 0, 1, 2 and 4; with thermal speeds (speed_type 3) it is
+ *                             refused (NXC_ERR_ARG): no kernel holds both laws */
 typedef struct nxc_source_desc {
     double endtime;        /* s                                                                 */
     double exobase;        /* R                                                                 */
@@ -296,8 +315,8 @@ typedef struct nxc_source_desc {
     double unit_km;        /* planet radius                                                     */
     double sinalt0, sinalt1, az0, az1;   /* isotropic launch cone                               */
     int32_t random_time;   /* 1: t = u*endtime (variable-step runs, Output.py:138-139)          */
-    int32_t speed_type;    /* 0 flat, 1 gaussian, 2 tabulated, 3 thermal                        */
-    int32_t angular_type;  /* 0 radial, 1 isotropic                                             */
+    int32_t speed_type;    /* 0 flat, 1 gaussian, 2 tabulated, 3 thermal, 4 per-node tables  */
+    int32_t angular_type;  /* 0 radial, 1 isotropic, 2 per-node tables                       */
     int32_t is_planet;     /* longitude convention (source_distribution.py:13-28)               */
     uint64_t seed;
     int64_t first_index;
@@ -336,6 +355,17 @@ typedef struct nxc_source_desc {
     double t0, t1;
     int64_t nx, ny;
     const double *tx, *ty, *coef;
+    /* speed_type 4 / angular_type 2: one cdf row per node of the 2-D map, [map_nlon * map_nlat][n]
+     * row-major with the nodes lon-major (node = i_lon * map_nlat + j_lat), and the axis [n] all
+     * rows share (n >= 2, finite).  A row is non-decreasing from 0 to 1; where the node's value in
+     * `map` is 0 -- such a node is never drawn -- it may instead be the placeholder of all zeros.
+     * Generator 0 only.  The tables are copied to device memory owned by the handle.             */
+    int64_t n_node_speed;
+    const double *node_speed_cdf, *node_speed_v;     /* speed_type 4; km/s                       */
+    int64_t n_node_alt;
+    const double *node_alt_cdf, *node_alt;           /* angular_type 2; rad above the horizon    */
+    int64_t n_node_az;
+    const double *node_az_cdf, *node_az;             /* angular_type 2; rad from north via east  */
 } nxc_source_desc;
 
 int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, double *soa_out);

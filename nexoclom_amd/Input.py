@@ -53,6 +53,7 @@ class Input:
         table = read_inputfile(infile)
         for name, cls in SECTIONS:
             setattr(self, name, cls(table.get(name, {})))
+        spec.check_map_laws(self.spatialdist, self.speeddist, self.angulardist)
 
     def _sections(self):
         return [getattr(self, name) for name, _ in SECTIONS]

@@ -268,21 +268,30 @@ class Output:
         cumulated masses of its cells (source_distribution.surface_map_cells), or for a 1-D map the
         even longitude grid with its cdf.  Thermal speeds ('maxwellian' at temperature 0) are
         speed_type 3 with the surface temperature's ``t0`` / ``t1`` and ``thermal_spline``, the
-        (tx, ty, coef) of the v(T, p) spline the host sampler evaluates."""
-        from .source_distribution import (density_cdf, speed_file_density, spot_density_map,
-                                          surface_map_cells, surface_map_density,
-                                          tabulated_speed_density)
+        (tx, ty, coef) of the v(T, p) spline the host sampler evaluates.  The per-point laws of a
+        map ('surface map' speeds / directions) are speed_type 4 with ``node_speed_table`` and
+        angular_type 2 with ``node_altitude_table`` and ``node_azimuth_table``: (cdf per node,
+        shared axis) of source_distribution.node_law_tables, which keeps them per map file, so
+        the chunks of a run share one set.  Thermal speeds with directions from a map have no
+        kernel: NotImplementedError."""
+        from .source_distribution import (density_cdf, node_law_tables, speed_file_density,
+                                          spot_density_map, surface_map_cells,
+                                          surface_map_density, tabulated_speed_density)
         sd, vd, ad = self.inputs.spatialdist, self.inputs.speeddist, self.inputs.angulardist
         if sd.type not in ('uniform', 'surface spot', 'surface map') \
                 or vd.type not in ('flat', 'gaussian', 'maxwellian', 'sputtering',
-                                   'user defined') \
-                or ad.type not in ('isotropic', 'radial'):
+                                   'user defined', 'surface map') \
+                or ad.type not in ('isotropic', 'radial', 'surface map'):
             raise NotImplementedError("sampler='device' supports uniform|surface spot|surface map "
-                                      "/ flat|gaussian|maxwellian|sputtering|user defined / "
-                                      "isotropic|radial sources")
+                                      "/ flat|gaussian|maxwellian|sputtering|user defined|surface "
+                                      "map / isotropic|radial|surface map sources")
+        if thermal_source(self.inputs) and ad.type == 'surface map':
+            raise NotImplementedError("sampler='device' has no kernel for thermal speeds "
+                                      "(maxwellian at temperature 0) together with directions "
+                                      "from a surface map; use sampler='numpy'")
         d = dict(endtime=self.inputs.options.endtime.value, exobase=float(sd.exobase),
                  unit_km=self.unit_km, random_time=int(self.inputs.options.step_size == 0),
-                 angular_type=0 if ad.type == 'radial' else 1,
+                 angular_type={'radial': 0, 'isotropic': 1, 'surface map': 2}[ad.type],
                  is_planet=int(self.planet.type == 'Planet'),
                  sinlat0=-1.0, sinlat1=1.0, lon0=0.0, lon1=2*np.pi, vprob=0.0, vwidth=0.0,
                  sinalt0=0.0, sinalt1=1.0, az0=0.0, az1=2*np.pi)
@@ -306,6 +315,8 @@ class Output:
         if vd.type in ('flat', 'gaussian'):
             d.update(speed_type=0 if vd.type == 'flat' else 1, vprob=vd.vprob.value,
                      vwidth=vd.delv.value if vd.type == 'flat' else vd.sigma.value)
+        elif vd.type == 'surface map':
+            d.update(speed_type=4, node_speed_table=node_law_tables(sd, 'speed'))
         elif thermal_source(self.inputs):
             from .surface import NIGHT_SIDE_K, day_side_t1, spline_tables, thermal_launch_spline
             d.update(speed_type=3, t0=NIGHT_SIDE_K, t1=float(day_side_t1(self.inputs.geometry)),
@@ -320,6 +331,9 @@ class Output:
                 az0, az1 = az1, az0 + 2*np.pi
             d.update(sinalt0=float(np.sin(ad.altitude[0])), sinalt1=float(np.sin(ad.altitude[1])),
                      az0=az0, az1=az1)
+        elif ad.type == 'surface map':
+            d.update(node_altitude_table=node_law_tables(sd, 'altitude'),
+                     node_azimuth_table=node_law_tables(sd, 'azimuth'))
         return d
 
     def _bodies_config(self):

@@ -25,6 +25,7 @@
 #include "../../include/nexoclom_hip.h"
 #include "nxc_kernels.hpp"
 #include "nxc_log_table.hpp"
+#include "nxc_source_check.hpp"
 
 namespace {
 
@@ -2513,12 +2514,13 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
 {
     return guarded([&]() -> int {
     if (!h || !d || n < 1) return fail(NXC_ERR_ARG, "bad arguments");
-    if (d->speed_type < 0 || d->speed_type > 3 || d->angular_type < 0 || d->angular_type > 1 ||
+    if (d->speed_type < 0 || d->speed_type > 4 || d->angular_type < 0 || d->angular_type > 2 ||
         d->spatial_type < 0 || d->spatial_type > 3 || !(d->unit_km > 0) || !(d->exobase > 0))
         return fail(NXC_ERR_ARG, "bad nxc_source_desc");
     const bool tab_speed = d->speed_type == 2, spot = d->spatial_type == 1;
     const bool map2d = d->spatial_type == 2, map1d = d->spatial_type == 3;
     const bool thermal = d->speed_type == 3;
+    const bool node_tables = d->speed_type == 4 || d->angular_type == 2;
     const bool pcg = d->generator == 1;
     if (d->generator != 0 && d->generator != 1) return fail(NXC_ERR_ARG, "nxc_source_desc: generator must be 0 or 1");
     if (pcg) {
@@ -2591,6 +2593,11 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
             return fail(NXC_ERR_ARG, "nxc_source_desc: surface map needs map_lon0 < map_lon1 and "
                                      "-1 <= map_s0 < map_s1 <= 1");
     }
+    // per-node tables of the map (speed_type 4, angular_type 2): nxc_source_check.hpp
+    if (node_tables) {
+        const std::string why = check_node_tables(d);
+        if (!why.empty()) return fail(NXC_ERR_ARG, why);
+    }
     HIPCHK(hipSetDevice(h->device));
     const int64_t total = d->dest_total > 0 ? d->dest_total : n;
     const int64_t offset = d->dest_total > 0 ? d->dest_offset : 0;
@@ -2608,9 +2615,12 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
     // the spline's knots and coefficients go behind every other table (the PCG64 maps included)
     const size_t n_spl = thermal ? (size_t)(d->nx + d->ny + n_coef) : 0;
     const size_t at_spl = 2 * n_sp + n_map + n_mcdf + n_pcg;
-    if (n_sp + n_map + n_pcg + n_spl) {
+    // ... and the per-node tables behind the spline
+    NodeTableLayout nodes{};
+    if (node_tables) nodes = node_table_layout(d, at_spl + n_spl);
+    if (n_sp + n_map + n_pcg + n_spl + nodes.total) {
         if ((rc = ensure(reinterpret_cast<void **>(&h->d_source), &h->source_cap,
-                         (at_spl + n_spl) * sizeof(double))))
+                         (at_spl + n_spl + nodes.total) * sizeof(double))))
             return rc;
         if (pcg) {
             const u128 inc = ((u128)d->pcg_inc[0] << 64) | d->pcg_inc[1];
@@ -2635,6 +2645,10 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
             HIPCHK(hipMemcpyAsync(h->d_source + at_spl + d->nx + d->ny, d->coef, (size_t)n_coef * 8,
                                   hipMemcpyHostToDevice, h->stream));
         }
+        for (const NodeTableCopy &c : nodes.copy)
+            if (c.count)
+                HIPCHK(hipMemcpyAsync(h->d_source + c.at, c.from, c.count * 8, hipMemcpyHostToDevice,
+                                      h->stream));
     }
     SourceK K{};
     K.endtime = d->endtime; K.exobase = d->exobase; K.sinlat0 = d->sinlat0; K.sinlat1 = d->sinlat1;
@@ -2676,13 +2690,23 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
         K.spl.tx = h->d_source + at_spl; K.spl.ty = K.spl.tx + d->nx; K.spl.coef = K.spl.ty + d->ny;
         K.spl.nx = (int)d->nx; K.spl.ny = (int)d->ny;
     }
+    if (node_tables) {
+        K.node_speed_cdf = h->d_source + nodes.copy[0].at; K.node_speed_v = h->d_source + nodes.copy[1].at;
+        K.node_alt_cdf = h->d_source + nodes.copy[2].at; K.node_alt = h->d_source + nodes.copy[3].at;
+        K.node_az_cdf = h->d_source + nodes.copy[4].at; K.node_az = h->d_source + nodes.copy[5].at;
+        K.n_node_speed = (int)nodes.copy[1].count; K.n_node_alt = (int)nodes.copy[3].count;
+        K.n_node_az = (int)nodes.copy[5].count;
+    }
     HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
     if ((rc = begin_timed(h))) return rc;
-    if (thermal)
-        hipLaunchKernelGGL(k_sample<true>, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0, h->stream,
-                           K, n, h->d_packets, h->d_ctr);
+    if (node_tables)
+        hipLaunchKernelGGL(k_sample<NXC_LAW_NODES>, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0,
+                           h->stream, K, n, h->d_packets, h->d_ctr);
+    else if (thermal)
+        hipLaunchKernelGGL(k_sample<NXC_LAW_THERMAL>, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0,
+                           h->stream, K, n, h->d_packets, h->d_ctr);
     else
-        hipLaunchKernelGGL(k_sample<false>, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0, h->stream,
+        hipLaunchKernelGGL(k_sample<NXC_LAW_PLAIN>, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0, h->stream,
                            K, n, h->d_packets, h->d_ctr);
     HIPCHK(hipGetLastError());
     if ((rc = end_timed(h))) return rc;
@@ -2714,6 +2738,10 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
         vmax /= d->unit_km;
     } else if (thermal) {
         vmax = coef_max / d->unit_km;      // |S| <= max |coef|: the bases are >= 0 and sum to 1
+    } else if (d->speed_type == 4) {
+        vmax = 0.0;
+        for (int64_t k = 0; k < d->n_node_speed; k++) vmax = std::max(vmax, std::fabs(d->node_speed_v[k]));
+        vmax /= d->unit_km;
     } else {
         vmax = (d->speed_type == 0 ? std::fabs(d->vprob) + std::fabs(d->vwidth)
                                    : std::fabs(d->vprob) + 6 * std::fabs(d->vwidth)) / d->unit_km;

@@ -2203,6 +2203,10 @@ struct SourceK {
     // (day), and the v(T, p) spline
     double t0, t1;
     SplineK spl;
+    // per-node tables (speed_type 4, angular_type 2): one cdf row of n_node_* entries per node of
+    // the 2-D map (node = i_lon * map_nlat + j_lat) and the axis all rows share
+    const double *node_speed_cdf, *node_speed_v, *node_alt_cdf, *node_alt, *node_az_cdf, *node_az;
+    int n_node_speed, n_node_alt, n_node_az;
 };
 
 // diagnostics: out[vec][i] = uniform of draw `vec` for row i (the parity test compares them with
@@ -2267,8 +2271,9 @@ NXC_DEV double linear_inverse_cdf(double f0, double f1, double u)
 // without a loop: the cell by bisection of the cells' cumulated masses (first cell with cdf > u, so
 // a cell without mass is never chosen), then the longitude within the cell from its marginal, which
 // is linear, then sin(latitude) from the conditional, linear as well.
+// Also returns the cell (i, j) and the point's in-cell coordinates (tx, ty), for map_corner.
 NXC_DEV void map_point(const SourceK &K, double u_cell, double u_x, double u_y, double &lon,
-                       double &lat)
+                       double &lat, int &cell_i, int &cell_j, double &cell_tx, double &cell_ty)
 {
     const int ny = K.map_nlat - 1;
     int lo = 0, hi = (K.map_nlon - 1) * ny - 1;
@@ -2285,6 +2290,46 @@ NXC_DEV void map_point(const SourceK &K, double u_cell, double u_x, double u_y, 
     lon = K.map_lon0 + ((double)i + tx) * K.map_dlon;
     const double s = K.map_s0 + ((double)j + ty) * K.map_ds;
     lat = asin(s < K.map_s1 ? s : K.map_s1);
+    cell_i = i; cell_j = j; cell_tx = tx; cell_ty = ty;
+}
+
+// The node whose tabulated laws a packet launched at (tx, ty) of cell (i, j) draws from: the joint
+// density of point and law is sum_c w_c A_c p_c over the cell's corners (w the bilinear hat
+// weights, A the node values, p the node's law), so given the point the packet comes from corner c
+// with probability w_c A_c / sum w A.  Corners in the order (i, j), (i, j+1), (i+1, j), (i+1, j+1):
+// the first whose running sum exceeds u * total; the last with a positive weight if rounding
+// leaves none; the corner with the largest A when the total is not > 0 (a point on a zero edge of
+// a cell that has mass).  Never a node without mass: its row may be the placeholder.
+NXC_DEV int map_corner(const SourceK &K, int i, int j, double tx, double ty, double u)
+{
+    const double *row0 = K.map + (long long)i * K.map_nlat + j, *row1 = row0 + K.map_nlat;
+    const double a = row0[0], b = row0[1], c = row1[0], d = row1[1];
+    const double w0 = (1.0 - tx) * (1.0 - ty) * a, w1 = (1.0 - tx) * ty * b;
+    const double w2 = tx * (1.0 - ty) * c, w3 = tx * ty * d;
+    const double r1 = w0 + w1, r2 = r1 + w2, total = r2 + w3;
+    int k;
+    if (total > 0.0) {
+        const double target = u * total;
+        if (w0 > target) k = 0;
+        else if (r1 > target) k = 1;
+        else if (r2 > target) k = 2;
+        else if (total > target) k = 3;
+        else k = w3 > 0.0 ? 3 : (w2 > 0.0 ? 2 : (w1 > 0.0 ? 1 : 0));
+    } else {
+        k = 0;
+        double best = a;
+        if (b > best) { best = b; k = 1; }
+        if (c > best) { best = c; k = 2; }
+        if (d > best) { best = d; k = 3; }
+    }
+    return (i + (k >> 1)) * K.map_nlat + (j + (k & 1));
+}
+
+// interp_global on row `node` of a per-node cdf table [nodes][n] with the axis all rows share
+NXC_DEV double interp_node(const double *__restrict__ cdf, const double *__restrict__ axis, int n,
+                           int node, double u)
+{
+    return interp_global(cdf + (long long)node * n, axis, n, u);
 }
 
 // Rejection trials per packet: the host sizes the budget to the map (32 / acceptance rate, so that
@@ -2293,13 +2338,19 @@ NXC_DEV void map_point(const SourceK &K, double u_cell, double u_x, double u_y, 
 constexpr int NXC_SPOT_MIN_TRIALS = 4096, NXC_SPOT_MAX_TRIALS = 1 << 18;
 constexpr unsigned NXC_SPOT_BLOCK0 = 16;    // Philox draw blocks 16 + 2t, 17 + 2t of trial t
 
-// THERMAL: the instantiation for speed_type 3 (thermal speeds).  The temperature and the bicubic
-// spline take 122 VGPRs against 97; kept out of the instantiation every other source runs, whose code
-// is that of the kernel before thermal speeds existed.
-template <bool THERMAL>
+// LAW: which instantiation.  NXC_LAW_THERMAL is the one for speed_type 3 (thermal speeds): the
+// temperature and the bicubic spline take 122 VGPRs against 97.  NXC_LAW_NODES is the one for the
+// per-node tables of a surface map (speed_type 4, angular_type 2): the corner choice and up to
+// three more bisections.  Both are kept out of NXC_LAW_PLAIN, which every other source runs and
+// whose code is that of the kernel before either existed.  No instantiation holds both laws:
+// speed_type 3 with angular_type 2 is refused before the launch (check_node_tables).
+constexpr int NXC_LAW_PLAIN = 0, NXC_LAW_THERMAL = 1, NXC_LAW_NODES = 2;
+
+template <int LAW>
 __global__ void __launch_bounds__(NXC_BLOCK)
 k_sample(SourceK K, int64_t n, double *__restrict__ soa, DevCounters *__restrict__ ctr)
 {
+    constexpr bool THERMAL = LAW == NXC_LAW_THERMAL, NODES = LAW == NXC_LAW_NODES;
     const double TWO_PI = 6.283185307179586;
     unsigned long long my_unfinished = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
@@ -2326,15 +2377,18 @@ k_sample(SourceK K, int64_t n, double *__restrict__ soa, DevCounters *__restrict
         }
         const double time = K.random_time ? ut * K.endtime : K.endtime;       // Output.py:136-139
         double lat, lon;
+        int node = 0;                          // NODES: the corner node the packet's laws come from
         if (K.spatial_type == 0) {                                             // uniform :51-62
             lat = asin(K.sinlat0 + (K.sinlat1 - K.sinlat0) * ulat);
             lon = fmod(K.lon0 + (K.lon1 - K.lon0) * ulon, TWO_PI);
         } else if (K.spatial_type == 2) {                                      // surface map :63-83
             // (the spot's trial blocks: the two types exclude each other)
-            double u_cell, u_x, u_y, unused;
+            double u_cell, u_x, u_y, u_corner, tx, ty;
+            int ci, cj;
             philox_pair(gi, NXC_SPOT_BLOCK0, NXC_STREAM_SOURCE, K.seed, u_cell, u_x);
-            philox_pair(gi, NXC_SPOT_BLOCK0 + 1u, NXC_STREAM_SOURCE, K.seed, u_y, unused);
-            map_point(K, u_cell, u_x, u_y, lon, lat);
+            philox_pair(gi, NXC_SPOT_BLOCK0 + 1u, NXC_STREAM_SOURCE, K.seed, u_y, u_corner);
+            map_point(K, u_cell, u_x, u_y, lon, lat, ci, cj, tx, ty);
+            if (NODES) node = map_corner(K, ci, cj, tx, ty, u_corner);
         } else if (K.spatial_type == 3) {                                      // 1-D map :73-77
             lat = 0.0;
             lon = interp_global(K.map_cdf, K.map, K.map_nlon, ulon);
@@ -2372,12 +2426,17 @@ k_sample(SourceK K, int64_t n, double *__restrict__ soa, DevCounters *__restrict
                 tsurf = K.t0 + K.t1 * nxc_sqrt(nxc_sqrt(__builtin_fabs(cos(lon) * cos(lat))));
             const double s = bispev3(K.spl, tsurf, uspd);
             v = s > 0.0 ? s : 0.0;
+        } else if (NODES && K.speed_type == 4) {                               // the node's table
+            v = interp_node(K.node_speed_cdf, K.node_speed_v, K.n_node_speed, node, uspd);
         } else {                                                               // tabulated :148-168
             v = interp_global(K.speed_cdf, K.speed_v, K.n_speed, uspd);
         }
         v = v / K.unit_km;                                                     // :184
         double alt, az;
-        if (K.angular_type == 0) {                                             // radial :198-201
+        if (NODES && K.angular_type == 2) {                                    // the node's tables
+            alt = interp_node(K.node_alt_cdf, K.node_alt, K.n_node_alt, node, ualt);
+            az = interp_node(K.node_az_cdf, K.node_az, K.n_node_az, node, uaz);
+        } else if (K.angular_type == 0) {                                             // radial :198-201
             alt = 1.5707963267948966; az = 0.0;
         } else {                                                               // isotropic :202-212
             alt = asin(ualt * (K.sinalt1 - K.sinalt0) + K.sinalt0);

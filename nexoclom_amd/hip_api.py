@@ -115,7 +115,10 @@ class nxc_source_desc(C.Structure):
                 ('pcg_inc', C.c_uint64*2), ('pcg_n', C.c_int64), ('pcg_row0', C.c_int64),
                 ('dest_offset', C.c_int64), ('dest_total', C.c_int64), ('map_cdf', _dp)] + \
                [(k, C.c_double) for k in ('map_lon0', 'map_lon1', 'map_s0', 'map_s1', 't0', 't1')] + \
-               [('nx', C.c_int64), ('ny', C.c_int64), ('tx', _dp), ('ty', _dp), ('coef', _dp)]
+               [('nx', C.c_int64), ('ny', C.c_int64), ('tx', _dp), ('ty', _dp), ('coef', _dp),
+                ('n_node_speed', C.c_int64), ('node_speed_cdf', _dp), ('node_speed_v', _dp),
+                ('n_node_alt', C.c_int64), ('node_alt_cdf', _dp), ('node_alt', _dp),
+                ('n_node_az', C.c_int64), ('node_az_cdf', _dp), ('node_az', _dp)]
 
 
 class nxc_bounce_desc(C.Structure):
@@ -512,14 +515,18 @@ class Context:
 
     def sample_packets(self, n, seed, first_index=0, download=False, speed_table=None,
                        surface_map=None, pcg64=None, piece=None, map_nodes=None, map_cdf=None,
-                       thermal_spline=None, **src):
+                       thermal_spline=None, node_speed_table=None, node_altitude_table=None,
+                       node_azimuth_table=None, **src):
         """Draw n initial states on the device (nxc_packets_sample).  ``src``: the scalar fields
         of nxc_source_desc except seed/first_index; ``speed_table`` = (cdf, speeds [km/s]) for
         speed_type 2; ``surface_map`` = density array [nlon, nlat] for spatial_type 1 (see
         Output.source_desc); ``map_nodes`` / ``map_cdf`` = node values [nlon, nlat] and cumulated
         cell masses for spatial_type 2 (with map_lon0, map_lon1, map_s0, map_s1 among ``src``), the
         longitude grid and its cdf for spatial_type 3; ``thermal_spline`` = (tx, ty, coef[nx-4,
-        ny-4]) of the v(T, p) spline for speed_type 3 (with t0, t1 among ``src``).
+        ny-4]) of the v(T, p) spline for speed_type 3 (with t0, t1 among ``src``);
+        ``node_speed_table`` = (cdf[nlon * nlat, nv], speeds[nv] [km/s]) for speed_type 4,
+        ``node_altitude_table`` / ``node_azimuth_table`` = (cdf[nlon * nlat, n], axis[n] [rad]) for
+        angular_type 2: one cdf row per node of ``map_nodes`` (spatial_type 2), lon-major.
         ``pcg64 = (npackets, row0)``: the reference's own seeded stream --
         rows row0 .. row0 + n - 1 of the npackets-long vectors default_rng(seed) would draw.
         ``piece = (offset, total)``: the n packets are part of a resident set of ``total`` that
@@ -564,6 +571,19 @@ class Context:
                                  '(len(tx) - 4, len(ty) - 4)')
             keep += [tx, ty, coef]
             d.nx, d.ny, d.tx, d.ty, d.coef = len(tx), len(ty), _p(tx), _p(ty), _p(coef)
+        for name, table in (('speed', node_speed_table), ('alt', node_altitude_table),
+                            ('az', node_azimuth_table)):
+            if table is None:
+                continue
+            cdf, axis = _f64(table[0]), _f64(table[1])
+            if map_nodes is None or cdf.ndim != 2 or axis.ndim != 1 or \
+                    cdf.shape != (np.size(map_nodes), len(axis)):
+                raise ValueError(f'node_{name} table must be (cdf[nodes, n], axis[n]) with one row '
+                                 'per node of map_nodes')
+            keep += [cdf, axis]
+            setattr(d, f'n_node_{name}', len(axis))
+            setattr(d, f'node_{name}_cdf', _p(cdf))
+            setattr(d, 'node_speed_v' if name == 'speed' else f'node_{name}', _p(axis))
         out = np.empty((8, int(n))) if download else None
         self._check(self.lib.nxc_packets_sample(self._h, C.byref(d), C.c_int64(int(n)),
                                                 _p(out) if download else None))

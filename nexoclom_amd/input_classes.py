@@ -313,6 +313,9 @@ class SpeedDist(Section):
         'maxwellian': (_speed('temperature', measured('K')),),
         'flat': (_speed('vprob', measured('km/s')), _speed('delv', measured('km/s'))),
         'user defined': (Field('vdistfile', default='default'),),
+        # EXTENSION: each packet's speed from speed_dist_map at its launch point, in the SourceMap
+        # file that SpatialDist.mapfile names as well (check_map_laws)
+        'surface map': (Field('vdistfile', default='default'),),
         'fitted output': (Constant('unfit_outid', -1), Constant('query', None)),
     }
 
@@ -334,6 +337,9 @@ class AngularDist(Section):
         'isotropic': (Field('azimuth', angle_pair(0., TWO_PI), default=radians(0, TWO_PI)),
                       _altitude(HALF_PI)),
         '2d': (_altitude(math.pi),),
+        # EXTENSION: altitude and azimuth from altitude_dist_map / azimuth_dist_map at the launch
+        # point, in the SourceMap file that SpatialDist.mapfile names as well (check_map_laws)
+        'surface map': (Field('mapfile', default='default'),),
     }
 
     def layout(self, params):
@@ -350,6 +356,25 @@ class AngularDist(Section):
         if alt is not None and alt[0] > alt[1]:
             raise InputError('AngularDist.__init__',
                              'AngularDist.altitude[0] > AngularDist.altitude[1]')
+
+
+def check_map_laws(spatialdist, speeddist, angulardist):
+    """SpeedDist.type = surface map and AngularDist.type = surface map take a launch point's laws
+    from the per-point arrays of a source map: the packets must be launched from that very map,
+    SpatialDist.type = surface map naming the same file."""
+    for section, name, attr in ((speeddist, 'SpeedDist', 'vdistfile'),
+                                (angulardist, 'AngularDist', 'mapfile')):
+        if section.type != 'surface map':
+            continue
+        if spatialdist.type != 'surface map':
+            raise InputError(f'{name}.__init__',
+                             f'{name}.type = surface map needs SpatialDist.type = surface map '
+                             f'(it is {spatialdist.type})')
+        mine, theirs = getattr(section, attr), spatialdist.mapfile
+        if os.path.abspath(mine) != os.path.abspath(theirs):
+            raise InputError(f'{name}.__init__',
+                             f'{name}.{attr} = {mine} must name the file of SpatialDist.mapfile = '
+                             f'{theirs}: per-point laws belong to the map the points come from')
 
 
 # ---- options ------------------------------------------------------------------------------------------

@@ -20,6 +20,15 @@ seeded ``random(npackets)`` vector in the speed slot, where 'flat' draws, so it 
 draw for draw and can be windowed.  So do the sources read from a file, 'surface map' (``mapfile``) and 'user
 defined' speeds (``vdistfile``): the file is a SourceMap written by ``SourceMap.save`` (.npz) -- what
 ``LOSResult.make_source_map`` returns -- not the reference's pickled astropy quantities.
+
+EXTENSION (the reference stops before it): ``SpeedDist.type = surface map`` and ``AngularDist.type =
+surface map`` draw a packet's speed, altitude and azimuth from the per-point ``speed_dist_map``,
+``altitude_dist_map`` and ``azimuth_dist_map`` of the map its launch point came from.  The joint
+density is sum_c w_c A_c p_c over the four corner nodes c of the launch point's cell (w the bilinear
+hat weights in (longitude, sin latitude), A the node's abundance, p its normalised 1-D tabulated
+law), whose marginal is the launch-point law: given the point, the packet takes ONE corner with
+probability w_c A_c / sum w A (``corner_nodes``) and all its per-point draws come from that node's
+laws (``random_deviates_1d``'s law, row by row).  Unseeded, like the other map laws.
 """
 import os
 
@@ -246,13 +255,15 @@ def _first_bad(values):
     return (None, None) if len(bad) == 0 else (tuple(int(k) for k in bad[0]), values[tuple(bad[0])])
 
 
-def surface_map_density(sd):
-    """(longitude, latitude or None, abundance, coordinate_system) of ``spatialdist.mapfile``, or
+def surface_map_density(sd, smap=None):
+    """(longitude, latitude or None, abundance, coordinate_system) of ``spatialdist.mapfile``
+    (``smap``: the file, where it has been read already), or
     the reason it cannot be launched from.  The reference's rejection loop would not end on a map
     without positive entries and draws nonsense from negative or non-finite ones
     (math/randomdeviates.py:59-78): those are ValueErrors here.  Planet-fixed maps are refused as
     in the reference (source_distribution.py:85-93)."""
-    smap = source_file('mapfile', sd.mapfile)
+    if smap is None:
+        smap = source_file('mapfile', sd.mapfile)
     if smap.abundance is None or smap.longitude is None:
         raise ValueError(f'{sd.mapfile} holds no abundance map')
     abundance = np.asarray(smap.abundance, dtype=np.float64)
@@ -307,6 +318,147 @@ def surface_map_cells(longitude, latitude, abundance):
     cdf = np.cumsum(corners.ravel())
     cdf /= cdf[-1]
     return cdf, (float(longitude.min()), float(longitude.max()), float(s.min()), float(s.max()))
+
+
+# ---- per-point laws of a source map ------------------------------------------------------------------
+NODE_LAWS = {'speed': 'speed_dist_map', 'altitude': 'altitude_dist_map',
+             'azimuth': 'azimuth_dist_map'}
+
+
+_NODE_LAWS_OF = {}       # the last map file's: {'stamp', 'map', 'density', law: (table, grid)}
+
+
+def _node_laws_of(sd):
+    """What `node_law_tables` keeps of ``spatialdist.mapfile``: the file as read once, its
+    checked abundance, and the tables made from it so far.  One file at a time (a default map's
+    tables take 22 MB); a file that changed on disk is read again."""
+    path = os.path.abspath(sd.mapfile)
+    stamp = None
+    if os.path.exists(path):
+        stat = os.stat(path)
+        stamp = (path, stat.st_mtime_ns, stat.st_size)
+    if stamp is None or _NODE_LAWS_OF.get('stamp') != stamp:
+        _NODE_LAWS_OF.clear()
+        smap = source_file('mapfile', sd.mapfile)
+        _NODE_LAWS_OF.update(map=smap, density=surface_map_density(sd, smap), stamp=stamp)
+    return _NODE_LAWS_OF
+
+
+def node_law_tables(sd, law):
+    """(cdf [nlon * nlat, n], grid [n]) of one per-point law (``law``: a key of NODE_LAWS) of
+    ``spatialdist.mapfile``: row c = i_lon * nlat + j_lat holds density_cdf of node c's row of the
+    *_dist_map, ``grid`` the even axis all rows share -- what random_deviates_1d interpolates in.
+    The speed axis is the file's ``speed``; the angle axes are rebuilt from the map's last
+    dimension (the centres of linspace(0, pi/2 | 2 pi, n + 1)), since a normalised map overwrites
+    ``altitude`` / ``azimuth`` with distributions (sourcemap.py).  Rows of nodes without abundance
+    are never drawn from (make_source_map(normalize=True) leaves NaN there): they become rows of
+    zeros.  Any other row must be finite, >= 0 and not all zero -- beyond its first entry, whose
+    mass density_cdf drops; else ValueError naming file, array and node.
+    The file is read once for all three laws, and the tables (read-only arrays) are kept until
+    another file is asked for or this one changes: every chunk of a run asks for them again."""
+    kept = _node_laws_of(sd)
+    if law not in kept:
+        kept[law] = _node_law_table(sd.mapfile, kept['map'], kept['density'], law)
+    return kept[law]
+
+
+def _node_law_table(path, smap, density, law):
+    from .sourcemap import centres
+    name = NODE_LAWS[law]
+    _, latitude, abundance, _ = density
+    if latitude is None:
+        raise ValueError(f'{path}: {name} launches need a 2-D map (longitude and latitude); this '
+                         'one has no latitudes')
+    values = getattr(smap, name)
+    if values is None:
+        raise ValueError(f'{path} holds no {name}')
+    values = np.asarray(values, dtype=np.float64)
+    if values.ndim != 3 or values.shape[:2] != abundance.shape:
+        raise ValueError(f'{path}: {name}{values.shape} does not fit abundance{abundance.shape}: '
+                         'its leading dimensions must be the map\'s')
+    n = values.shape[2]
+    if law == 'speed':
+        axis = None if smap.speed is None else np.asarray(smap.speed, dtype=np.float64)
+        if axis is None or axis.ndim != 1 or len(axis) != n or n < 2 \
+                or not np.all(np.isfinite(axis)):
+            raise ValueError(f'{path}: speed must be 1-D, finite and as long as the last dimension '
+                             f'of speed_dist_map{values.shape} (at least 2)')
+    else:
+        if n < 2:
+            raise ValueError(f'{path}: {name}{values.shape} needs at least 2 bins')
+        axis = centres(np.linspace(0, np.pi/2 if law == 'altitude' else TWO_PI, n + 1))
+    live = abundance > 0
+    rows = values[live]
+    where, value = _first_bad(rows)
+    if where is not None:
+        i, j = (int(k) for k in np.argwhere(live)[where[0]])
+        raise ValueError(f'{path}: {name}[{i}, {j}, {where[1]}] = {value}; the law of a node with '
+                         'abundance > 0 must be finite and >= 0')
+    cdf = rows.cumsum(axis=1)
+    cdf -= cdf[:, :1].copy()
+    empty = np.flatnonzero(~(cdf[:, -1] > 0))
+    if len(empty):
+        i, j = (int(k) for k in np.argwhere(live)[empty[0]])
+        raise ValueError(f'{path}: {name}[{i}, {j}] is zero everywhere (beyond its first entry, '
+                         'whose mass the tabulated law drops) at a node with abundance > 0')
+    cdf /= cdf[:, -1:].copy()
+    table = np.zeros((abundance.size, n))
+    table[live.ravel()] = cdf
+    grid = np.linspace(axis.min(), axis.max(), n)
+    table.setflags(write=False)
+    grid.setflags(write=False)
+    return table, grid
+
+
+def corner_nodes(abundance, i, j, tx, ty, u):
+    """The node (i_lon * nlat + j_lat) each packet's per-point laws come from: a corner of its
+    cell (i, j), in the order (i, j), (i, j+1), (i+1, j), (i+1, j+1) with weights (1-tx)(1-ty) a,
+    (1-tx) ty b, tx (1-ty) c, tx ty d -- the first whose running sum exceeds u * total; the last
+    with a positive weight if rounding leaves none; the corner with the largest abundance where the
+    total is not > 0 (a point on a zero edge of its cell)."""
+    a, b, c, d = abundance[i, j], abundance[i, j + 1], abundance[i + 1, j], abundance[i + 1, j + 1]
+    w = np.array([(1.0 - tx)*(1.0 - ty)*a, (1.0 - tx)*ty*b, tx*(1.0 - ty)*c, tx*ty*d])
+    running = np.cumsum(w, axis=0)
+    total = running[3]
+    over = running > u*total
+    first = np.argmax(over, axis=0)
+    last_positive = 3 - np.argmax(w[::-1] > 0, axis=0)
+    k = np.where(over.any(axis=0), first, last_positive)
+    k = np.where(total > 0, k, np.argmax(np.array([a, b, c, d]), axis=0))
+    return (i + (k >> 1))*abundance.shape[1] + (j + (k & 1))
+
+
+def node_deviates(cdf, grid, node, u):
+    """np.interp(u, cdf[node], grid) packet by packet: random_deviates_1d's inversion on each
+    packet's own row of a per-node cdf table."""
+    order = np.argsort(node, kind='stable')
+    ranked = node[order]
+    starts = np.flatnonzero(np.r_[True, ranked[1:] != ranked[:-1]])
+    out = np.empty(len(node))
+    for first, last in zip(starts, np.r_[starts[1:], len(node)]):
+        rows = order[first:last]
+        out[rows] = np.interp(u[rows], cdf[ranked[first]], grid)
+    return out
+
+
+def _map_law_nodes(out):
+    """The corner node of every packet of ``out``, drawn once (one corner serves all of a packet's
+    per-point draws): cell and in-cell coordinates of the launch points already in X0 on the map's
+    even node grid in (longitude, sin latitude), then `corner_nodes`."""
+    if getattr(out, '_map_nodes', None) is None:
+        sd = out.inputs.spatialdist
+        longitude, latitude, abundance, _ = _node_laws_of(sd)['density']
+        if latitude is None:
+            raise ValueError(f'{sd.mapfile}: per-point laws need a 2-D map (longitude and latitude)')
+        _, (lon0, lon1, s0, s1) = surface_map_cells(longitude, latitude, abundance)
+        nlon, nlat = abundance.shape
+        gx = (np.asarray(out.X0['longitude']) - lon0)/((lon1 - lon0)/(nlon - 1))
+        gy = (np.sin(np.asarray(out.X0['latitude'])) - s0)/((s1 - s0)/(nlat - 1))
+        i = np.clip(np.floor(gx), 0, nlon - 2).astype(np.int64)
+        j = np.clip(np.floor(gy), 0, nlat - 2).astype(np.int64)
+        tx, ty = np.clip(gx - i, 0.0, 1.0), np.clip(gy - j, 0.0, 1.0)
+        out._map_nodes = corner_nodes(abundance, i, j, tx, ty, unseeded.rand(out.npackets))
+    return out._map_nodes
 
 
 def _surface_map(out, sd):
@@ -394,8 +546,14 @@ def _speed_from_file(out, vd, species):
     return random_deviates_1d(*speed_file_density(vd), out.npackets)
 
 
+def _speed_from_map(out, vd, species):
+    cdf, grid = node_law_tables(out.inputs.spatialdist, 'speed')
+    return node_deviates(cdf, grid, _map_law_nodes(out), unseeded.rand(out.npackets))
+
+
 SPEEDS = {'gaussian': _speed_gaussian, 'flat': _speed_flat, 'sputtering': _speed_tabulated,
-          'maxwellian': _speed_maxwellian, 'user defined': _speed_from_file}
+          'maxwellian': _speed_maxwellian, 'user defined': _speed_from_file,
+          'surface map': _speed_from_map}
 
 
 def speed_distribution(outputs):
@@ -429,8 +587,14 @@ def _direction_planar(out, ad):
     return np.arccos(out.randgen.random(out.npackets) * (c1 - c0) + c0), None
 
 
+def _direction_from_map(out, ad):
+    nodes, n = _map_law_nodes(out), out.npackets
+    return tuple(node_deviates(*node_law_tables(out.inputs.spatialdist, law), nodes,
+                               unseeded.rand(n)) for law in ('altitude', 'azimuth'))
+
+
 DIRECTIONS = {'radial': _direction_radial, 'isotropic': _direction_isotropic,
-              '2d': _direction_planar}
+              '2d': _direction_planar, 'surface map': _direction_from_map}
 
 
 def angular_distribution(outputs):

@@ -1,0 +1,427 @@
+"""Launching speeds and directions from a source map's per-point laws, without a GPU: the parser,
+the descriptor, what is refused, and the law -- of the NumPy restatement of the device's draw
+(tests/distmap_launch_restatement.py) and of the host sampler -- against its analytic form.
+
+The seed and size of the statistical tests are tests/test_sourcemap_launch_cpu.py's LAW_SEED and
+LAW_N, fixed there before this file existed; nothing here was tried at another seed."""
+import os
+
+import numpy as np
+import pytest
+from scipy import stats
+
+from nexoclom_amd import Input, Output
+from nexoclom_amd.input_classes import InputError
+from nexoclom_amd.source_distribution import (corner_nodes, node_law_tables, surface_map_cells)
+from nexoclom_amd.sourcemap import SourceMap
+
+from . import distmap_launch_restatement as R
+from .test_sourcemap_launch_cpu import (BENCH_INPUT, LAW_N, LAW_SEED, P_MIN, SCALARS, bare_output)
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+INPUTFILES = os.path.join(ROOT, 'nexoclom_amd', 'inputfiles')
+HOST_SEED, HOST_N = 515, 100000        # the host sampler's unseeded stream, seeded for the test
+
+
+def save_map(tmp_path, content, **changes):
+    content = dict(content)
+    content.update(changes)
+    content = {k: v for k, v in content.items() if v is not None}
+    path = str(tmp_path / f'distmap{len(list(tmp_path.iterdir()))}.npz')
+    SourceMap(content).save(path)
+    return path
+
+
+def distmap_input(tmp_path, mapfile, speeds=True, angles=True, spatial=None, vdistfile=None,
+                  angle_file=None, speed_lines=None):
+    """The bench input launched from ``mapfile``, with per-point speeds and / or directions
+    (``speed_lines``: another speed distribution in place of either)."""
+    lines = []
+    for line in open(BENCH_INPUT):
+        key = line.split('=')[0].strip().casefold()
+        if key.startswith('spatialdist.') \
+                or ((speeds or speed_lines) and key.startswith('speeddist.')) \
+                or (angles and key.startswith('angulardist.')):
+            continue
+        lines.append(line)
+    lines += spatial or ['SpatialDist.type = surface map\n', f'SpatialDist.mapfile = {mapfile}\n']
+    if speed_lines:
+        lines += speed_lines
+    elif speeds:
+        lines += ['SpeedDist.type = surface map\n', f'SpeedDist.vdistfile = {vdistfile or mapfile}\n']
+    if angles:
+        lines += ['AngularDist.type = surface map\n',
+                  f'AngularDist.mapfile = {angle_file or mapfile}\n']
+    path = tmp_path / f'distmap{len(list(tmp_path.iterdir()))}.input'
+    path.write_text(''.join(lines))
+    return Input(str(path))
+
+
+def descriptor(tmp_path, content, **kw):
+    return bare_output(distmap_input(tmp_path, save_map(tmp_path, content), **kw)).source_desc()
+
+
+@pytest.fixture(scope='module')
+def coded(tmp_path_factory):
+    content, code = R.coded_map()
+    src = descriptor(tmp_path_factory.mktemp('coded'), content)
+    return content, code, src
+
+
+@pytest.fixture(scope='module')
+def smooth(tmp_path_factory):
+    content = R.smooth_map()
+    tmp = tmp_path_factory.mktemp('smooth')
+    path = save_map(tmp, content)
+    return content, path, bare_output(distmap_input(tmp, path)).source_desc()
+
+
+# ---- parser --------------------------------------------------------------------------------------------
+def test_parser_accepts_the_new_types_each_on_its_own(tmp_path):
+    path = save_map(tmp_path, R.coded_map()[0])
+    both = distmap_input(tmp_path, path)
+    assert both.speeddist.type == 'surface map' and both.speeddist.vdistfile == path
+    assert both.angulardist.type == 'surface map' and both.angulardist.mapfile == path
+    speeds = distmap_input(tmp_path, path, angles=False)
+    assert speeds.speeddist.type == 'surface map' and speeds.angulardist.type == 'isotropic'
+    angles = distmap_input(tmp_path, path, speeds=False)
+    assert angles.angulardist.type == 'surface map' and angles.speeddist.type == 'flat'
+    # the same file named another way
+    relative = os.path.relpath(path)
+    assert distmap_input(tmp_path, path, vdistfile=relative).speeddist.vdistfile == relative
+
+
+def test_parser_refuses_laws_without_their_map(tmp_path):
+    path = save_map(tmp_path, R.coded_map()[0])
+    other = save_map(tmp_path, R.coded_map()[0])
+    uniform = ['SpatialDist.type = uniform\n']
+    spot = ['SpatialDist.type = surface spot\n', 'SpatialDist.longitude = 1\n',
+            'SpatialDist.latitude = 0\n', 'SpatialDist.sigma = 0.3\n']
+    for kw, word in ((dict(spatial=uniform, angles=False), 'SpeedDist'),
+                     (dict(spatial=uniform, speeds=False), 'AngularDist'),
+                     (dict(spatial=spot), 'SpatialDist.type = surface map'),
+                     (dict(vdistfile=other, angles=False), 'vdistfile'),
+                     (dict(angle_file=other, speeds=False), 'mapfile')):
+        with pytest.raises(InputError) as err:
+            distmap_input(tmp_path, path, **kw)
+        assert word in str(err.value), str(err.value)
+
+
+def test_old_inputfiles_parse_as_before():
+    """Sections of every shipped inputfile that does not use the new types hold exactly the
+    attributes they held (names and values written down from the parent commit's parser)."""
+    bench = Input(os.path.join(INPUTFILES, 'Na.mercury.bench.input'))
+    assert set(bench.speeddist.__dict__) == {'type', 'vprob', 'delv'}
+    assert set(bench.angulardist.__dict__) == {'type', 'azimuth', 'altitude'}
+    assert set(bench.spatialdist.__dict__) == {'type', 'exobase', 'longitude', 'latitude'}
+    mapped = Input(os.path.join(INPUTFILES, 'Na.mercury.sourcemap.input'))
+    assert mapped.speeddist.__dict__ == {'type': 'user defined', 'vdistfile': 'map.npz'}
+    assert mapped.spatialdist.__dict__ == {'type': 'surface map', 'exobase': 1.0,
+                                           'mapfile': 'map.npz', 'subsolarlon': None,
+                                           'coordinate_system': 'solar-fixed'}
+    assert set(mapped.angulardist.__dict__) == {'type', 'azimuth', 'altitude'}
+    for name in os.listdir(INPUTFILES):
+        if name != 'Na.mercury.distmap.input':
+            inputs = Input(os.path.join(INPUTFILES, name))
+            assert inputs.speeddist.type != 'surface map'
+            assert inputs.angulardist.type != 'surface map'
+    new = Input(os.path.join(INPUTFILES, 'Na.mercury.distmap.input'))
+    assert (new.spatialdist.type, new.speeddist.type, new.angulardist.type) == ('surface map',)*3
+
+
+# ---- descriptor ----------------------------------------------------------------------------------------
+MAP_KEYS = {'map_nodes', 'map_cdf', 'map_lon0', 'map_lon1', 'map_s0', 'map_s1'}
+
+
+def test_source_desc_of_the_new_sources(tmp_path, coded):
+    content, _, both = coded
+    assert set(both) == SCALARS | MAP_KEYS | {'node_speed_table', 'node_altitude_table',
+                                              'node_azimuth_table'}
+    assert (both['spatial_type'], both['speed_type'], both['angular_type']) == (2, 4, 2)
+    cdf, grid = both['node_speed_table']
+    assert cdf.shape == (20, R.NV) and np.array_equal(grid, np.linspace(0.25, 3.25, R.NV))
+    cdf, grid = both['node_altitude_table']
+    assert cdf.shape == (20, R.NA)
+    np.testing.assert_allclose(grid, R.angle_centres(np.pi/2, R.NA), rtol=1e-15)
+    cdf, grid = both['node_azimuth_table']
+    assert cdf.shape == (20, R.NZ)
+    np.testing.assert_allclose(grid, R.angle_centres(2*np.pi, R.NZ), rtol=1e-15)
+    speeds = descriptor(tmp_path, content, angles=False)
+    assert set(speeds) == SCALARS | MAP_KEYS | {'node_speed_table'}
+    assert (speeds['speed_type'], speeds['angular_type']) == (4, 1)
+    angles = descriptor(tmp_path, content, speeds=False)
+    assert set(angles) == SCALARS | MAP_KEYS | {'node_altitude_table', 'node_azimuth_table'}
+    assert (angles['speed_type'], angles['angular_type']) == (0, 2)
+
+
+THERMAL_SPEEDS = ['SpeedDist.type = maxwellian\n', 'SpeedDist.temperature = 0\n']
+
+
+def test_thermal_speeds_with_map_directions_have_no_device_descriptor(tmp_path, coded):
+    """No k_sample instantiation holds both laws: the device sampler says so before anything is
+    drawn; the host sampler draws the pair.  Thermal speeds with per-point speeds' map (isotropic
+    directions) and tabulated speeds with map directions keep their descriptors."""
+    path = save_map(tmp_path, coded[0])
+    both = distmap_input(tmp_path, path, speed_lines=THERMAL_SPEEDS)
+    assert both.speeddist.type == 'maxwellian' and both.angulardist.type == 'surface map'
+    with pytest.raises(NotImplementedError, match='thermal speeds'):
+        bare_output(both).source_desc()
+    np.random.seed(HOST_SEED)
+    X0 = Output(both, 2000, seed=3, integrate=False, save=False).X0
+    assert np.all(np.isfinite(X0[['v', 'altitude', 'azimuth']].values))
+    grid = coded[2]['node_altitude_table'][1]
+    assert X0.altitude.min() >= grid[0] and X0.altitude.max() <= grid[-1]
+    thermal = bare_output(distmap_input(tmp_path, path, angles=False,
+                                        speed_lines=THERMAL_SPEEDS)).source_desc()
+    assert (thermal['spatial_type'], thermal['speed_type'], thermal['angular_type']) == (2, 3, 1)
+    tabulated = bare_output(distmap_input(tmp_path, path, speed_lines=[
+        'SpeedDist.type = maxwellian\n', 'SpeedDist.temperature = 1200\n'])).source_desc()
+    assert (tabulated['speed_type'], tabulated['angular_type']) == (2, 2)
+
+
+def test_node_tables_are_read_once_per_file(tmp_path, monkeypatch):
+    """Every chunk of a run asks for the tables again: they are kept per file (one read for all
+    three laws), read-only, and made anew when the file changes or another one is named."""
+    from nexoclom_amd import source_distribution as sdist
+    reads = []
+    source_file = sdist.source_file
+    monkeypatch.setattr(sdist, 'source_file',
+                        lambda parameter, path: reads.append(path) or source_file(parameter, path))
+    content = R.coded_map()[0]
+    path = save_map(tmp_path, content)
+    sd = distmap_input(tmp_path, path).spatialdist
+    first = {law: node_law_tables(sd, law) for law in ('speed', 'altitude', 'azimuth')}
+    again = {law: node_law_tables(sd, law) for law in ('speed', 'altitude', 'azimuth')}
+    assert reads == [path]
+    for law in first:
+        assert first[law][0] is again[law][0] and first[law][1] is again[law][1]
+        assert not first[law][0].flags.writeable and not first[law][1].flags.writeable
+    changed = content['speed_dist_map'].copy()
+    changed[0, 0] = changed[0, 1]
+    SourceMap(dict(content, speed_dist_map=changed, speed=content['speed'] + 1.0)).save(path)
+    assert np.array_equal(node_law_tables(sd, 'speed')[1], first['speed'][1] + 1.0)
+    other = distmap_input(tmp_path, save_map(tmp_path, content)).spatialdist
+    assert np.array_equal(node_law_tables(other, 'speed')[0], first['speed'][0])
+    assert len(reads) == 3
+
+
+def test_per_node_inversion_is_np_interp_packet_by_packet(coded, smooth):
+    """The grouped inversions -- the host sampler's node_deviates and the restatement's
+    interp_node -- against the law as the issue writes it, one packet at a time:
+    v = interp(u, cdf_c, grid)."""
+    from nexoclom_amd.source_distribution import node_deviates
+    rng = np.random.default_rng(77)
+    for src in (coded[2], smooth[2]):
+        live = np.flatnonzero(np.asarray(src['map_nodes']).ravel() > 0)
+        node = rng.choice(live, 400)
+        u = rng.random(400)
+        u[:4] = 0.0, 1.0 - 2.0**-53, 0.5, 2.0**-53
+        for key in ('node_speed_table', 'node_altitude_table', 'node_azimuth_table'):
+            cdf, grid = src[key]
+            want = np.array([np.interp(u[k], cdf[node[k]], grid) for k in range(400)])
+            assert np.array_equal(node_deviates(cdf, grid, node, u), want)
+            assert np.array_equal(R.interp_node(cdf, grid, node, u), want)
+
+
+def test_source_desc_of_existing_inputfiles_keeps_its_keys(tmp_path):
+    assert set(bare_output(Input(BENCH_INPUT)).source_desc()) == SCALARS
+    content = R.coded_map()[0]
+    path = save_map(tmp_path, content, speed_dist=np.ones(R.NV))
+    lines = open(os.path.join(INPUTFILES, 'Na.mercury.sourcemap.input')).read()
+    infile = tmp_path / 'sourcemap.input'
+    infile.write_text(lines.replace('map.npz', path))
+    assert set(bare_output(Input(str(infile))).source_desc()) == SCALARS | MAP_KEYS | {'speed_table'}
+
+
+def test_node_tables_are_the_reference_law_row_by_row(coded):
+    """Every row with abundance is density_cdf of that node's row; the others are zeros."""
+    from nexoclom_amd.source_distribution import density_cdf
+    content, _, src = coded
+    live = (content['abundance'] > 0).ravel()
+    for key, name, axis in (('node_speed_table', 'speed_dist_map', content['speed']),
+                            ('node_altitude_table', 'altitude_dist_map',
+                             R.angle_centres(np.pi/2, R.NA)),
+                            ('node_azimuth_table', 'azimuth_dist_map',
+                             R.angle_centres(2*np.pi, R.NZ))):
+        table, grid = src[key]
+        rows = content[name].reshape(20, -1)
+        for n in range(20):
+            if live[n]:
+                cdf, want_grid = density_cdf(axis, rows[n])
+                assert np.array_equal(table[n], cdf) and np.array_equal(grid, want_grid)
+                assert table[n, 0] == 0 and table[n, -1] == 1 and np.all(np.diff(table[n]) >= 0)
+            else:
+                assert np.all(table[n] == 0)
+
+
+# ---- refusals ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('sampler', ['numpy', 'device'])
+def test_unusable_maps_are_refused_by_name(tmp_path, sampler):
+    content = R.coded_map()[0]
+
+    def attempt(**changes):
+        inputs = distmap_input(tmp_path, save_map(tmp_path, content, **changes))
+        if sampler == 'numpy':
+            np.random.seed(1)
+            return Output(inputs, 50, seed=1, integrate=False, save=False)
+        return bare_output(inputs).source_desc()
+
+    for name in ('speed_dist_map', 'altitude_dist_map', 'azimuth_dist_map'):
+        for bad, word in ((np.nan, 'nan'), (-1.0, '-1')):
+            values = content[name].copy()
+            values[1, 2, 1] = bad
+            with pytest.raises(ValueError, match=name + r'\[1, 2, 1\] = ' + word) as err:
+                attempt(**{name: values})
+            assert '.npz' in str(err.value)
+        values = content[name].copy()
+        values[2, 1] = 0.0
+        with pytest.raises(ValueError, match=name + r'\[2, 1\] is zero everywhere'):
+            attempt(**{name: values})
+        with pytest.raises(ValueError, match=name + r'.*does not fit abundance'):
+            attempt(**{name: content[name][:4]})
+        with pytest.raises(ValueError, match='holds no ' + name):
+            attempt(**{name: None})
+    with pytest.raises(ValueError, match='speed must be 1-D'):              # nv < 2
+        attempt(speed=content['speed'][:1], speed_dist_map=content['speed_dist_map'][:, :, 1:2])
+    with pytest.raises(ValueError, match='speed must be 1-D'):
+        attempt(speed=content['speed'][:-1])
+    values = content['speed'].copy()
+    values[3] = np.inf
+    with pytest.raises(ValueError, match='speed must be 1-D, finite'):
+        attempt(speed=values)
+    with pytest.raises(ValueError, match='altitude_dist_map.*at least 2 bins'):
+        attempt(altitude_dist_map=content['altitude_dist_map'][:, :, 1:2])
+    with pytest.raises(ValueError, match='2-D map'):                          # a 1-D map
+        attempt(latitude=None, abundance=content['abundance'][:, 0])
+    # NaN rows where there is no abundance are what make_source_map(normalize=True) leaves: fine
+    assert np.isnan(content['speed_dist_map'][3, 3]).all()
+    assert attempt() is not None
+
+
+# ---- the corner law, exact --------------------------------------------------------------------------------
+def coded_grids(src):
+    return (src['node_speed_table'][1], src['node_altitude_table'][1], src['node_azimuth_table'][1])
+
+
+def test_restated_corner_choice_follows_the_node_law(coded):
+    content, code, src = coded
+    got = R.draw(LAW_N, LAW_SEED, **src)
+    decoded = R.decode_nodes(code, *coded_grids(src), got['speed'], got['altitude'], got['azimuth'])
+    # the three draws of a packet come from one node, the one map_corner chose
+    assert np.array_equal(decoded, got['node'])
+    assert np.all(content['abundance'].ravel()[got['node']] > 0)
+    p_nodes = R.node_goodness_of_fit(got['node'], content['abundance'])
+    print(f'coded map: nodes p={p_nodes:.4f}')
+    assert p_nodes > P_MIN
+    # the launch points are those of the map source without per-point laws
+    lon, lat = R.S.launch_points(LAW_N, LAW_SEED, **src)
+    assert np.array_equal(lon, got['lon']) and np.array_equal(lat, got['lat'])
+
+
+def test_corner_choice_at_its_edges():
+    nodes = np.array([[0.0, 2.0, 0.0], [3.0, 0.0, 5.0]])
+    one = np.ones(1)
+    i, j = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    for pick in (R.map_corner, corner_nodes):
+        # cell (0, 0): corners 0, 2, 3, 0.  On the edge tx = 0 only (0, 1) has weight
+        assert pick(nodes, i, j, 0*one, 0.5*one, 0.999*one)[0] == 1
+        # a point where every weight vanishes (tx = 0, ty = 0): the largest abundance, (1, 0)
+        assert pick(nodes, i, j, 0*one, 0*one, 0.3*one)[0] == 3
+        # rounding leaves no running sum above u * total: the last corner with weight, (1, 0)
+        assert pick(nodes, i, j, 0.5*one, 0.5*one, one)[0] == 3
+        # cell (0, 1): corners 2, 0, 0, 5 in the middle: 2 / 7 for (0, 1), else (1, 2)
+        assert pick(nodes, i, j + 1, 0.5*one, 0.5*one, 0.28*one)[0] == 1
+        assert pick(nodes, i, j + 1, 0.5*one, 0.5*one, 0.29*one)[0] == 5
+    rng = np.random.default_rng(8)
+    n = 20000
+    a = rng.random((6, 5))*(rng.random((6, 5)) > 0.3)
+    i, j = rng.integers(0, 5, n), rng.integers(0, 4, n)
+    tx, ty, u = rng.random(n), rng.random(n), rng.random(n)
+    tx[:50], ty[50:100] = 0.0, 1.0
+    assert np.array_equal(R.map_corner(a, i, j, tx, ty, u), corner_nodes(a, i, j, tx, ty, u))
+
+
+# ---- marginal laws on a smooth map ----------------------------------------------------------------------
+def marginal_p_values(content, src, speed, altitude, azimuth):
+    return [stats.kstest(sample, R.mixture_cdf(content['abundance'], src[key])).pvalue
+            for key, sample in (('node_speed_table', speed), ('node_altitude_table', altitude),
+                                ('node_azimuth_table', azimuth))]
+
+
+def test_restated_draw_follows_the_mixture_laws(smooth):
+    content, _, src = smooth
+    got = R.draw(LAW_N, LAW_SEED, **src)
+    p = marginal_p_values(content, src, got['speed'], got['altitude'], got['azimuth'])
+    p_nodes = R.node_goodness_of_fit(got['node'], content['abundance'])
+    print('smooth map: KS speed p=%.4f altitude p=%.4f azimuth p=%.4f' % tuple(p),
+          f'nodes p={p_nodes:.4f}')
+    assert min(p) > P_MIN and p_nodes > P_MIN
+    # the restatement's own inverse: launch_angles recovers what went into the velocities
+    speed, altitude, azimuth = R.launch_angles(got['X'][:1000].T)
+    np.testing.assert_allclose(speed*src['unit_km'], got['speed'][:1000], rtol=1e-12)
+    np.testing.assert_allclose(altitude, got['altitude'][:1000], rtol=1e-9)
+    np.testing.assert_allclose(azimuth, got['azimuth'][:1000], rtol=1e-9)
+
+
+def test_host_sampler_follows_the_mixture_laws(smooth, tmp_path):
+    content, path, src = smooth
+    np.random.seed(HOST_SEED)
+    out = Output(distmap_input(tmp_path, path), HOST_N, seed=3, integrate=False, save=False)
+    X0 = out.X0
+    assert list(X0.columns[:8]) == ['time', 'x', 'y', 'z', 'vx', 'vy', 'vz', 'frac']
+    p = marginal_p_values(content, src, X0.v.values*out.unit_km, X0.altitude.values,
+                          X0.azimuth.values)
+    print('host, smooth map: KS speed p=%.4f altitude p=%.4f azimuth p=%.4f' % tuple(p))
+    assert min(p) > P_MIN
+    speed, altitude, azimuth = R.launch_angles(X0[['time', 'x', 'y', 'z', 'vx', 'vy', 'vz',
+                                                   'frac']].values.T)
+    np.testing.assert_allclose(altitude, X0.altitude.values, atol=1e-9)
+    np.testing.assert_allclose(azimuth, X0.azimuth.values, atol=1e-7)
+
+
+def test_host_sampler_follows_the_node_law(coded, tmp_path):
+    content, code, src = coded
+    np.random.seed(HOST_SEED)
+    out = Output(distmap_input(tmp_path, save_map(tmp_path, content)), HOST_N, seed=3,
+                 integrate=False, save=False)
+    X0 = out.X0
+    decoded = R.decode_nodes(code, *coded_grids(src), X0.v.values*out.unit_km, X0.altitude.values,
+                             X0.azimuth.values)
+    assert np.array_equal(decoded, out._map_nodes)
+    p_nodes = R.node_goodness_of_fit(decoded, content['abundance'])
+    print(f'host, coded map: nodes p={p_nodes:.4f}')
+    assert p_nodes > P_MIN
+    # the corner is one of the launch point's own cell
+    _, limits = surface_map_cells(content['longitude'], content['latitude'], content['abundance'])
+    i, j = R.S.cell_of(X0.longitude.values, np.sin(X0.latitude.values), limits, (5, 4))
+    di, dj = decoded//4 - i, decoded % 4 - j
+    assert np.all((di >= 0) & (di <= 1) & (dj >= 0) & (dj <= 1))
+
+
+def test_node_law_tables_rebuild_the_angle_axes_of_a_normalised_map(tmp_path):
+    """A normalised map overwrites `altitude` / `azimuth` with distributions; the axes come from
+    the maps' last dimension."""
+    content = R.coded_map()[0]
+    path = save_map(tmp_path, content, altitude=np.array([5.0, 1.0, 9.0]),
+                    azimuth=np.array([3.0, 3.0, 1.0, 0.0]))
+    sd = distmap_input(tmp_path, path).spatialdist
+    assert np.allclose(node_law_tables(sd, 'altitude')[1], R.angle_centres(np.pi/2, R.NA))
+    assert np.allclose(node_law_tables(sd, 'azimuth')[1], R.angle_centres(2*np.pi, R.NZ))
+
+
+# ---- the C side's refusals, without a GPU ---------------------------------------------------------------
+def test_descriptor_validation_and_staging_as_a_host_program(tmp_path):
+    """nxc_packets_sample's validation and staging of the per-node tables are host-only code
+    (nxc_source_check.hpp); tests/tools/node_tables_check.cpp feeds them good and bad descriptors
+    up to the first device call.  Built plainly here; the same file is what is built with
+    -fsanitize=address,undefined to check the host code's memory accesses."""
+    import subprocess
+    exe = tmp_path / 'node_tables_check'
+    subprocess.check_call(['g++', '-std=c++17', '-O1', '-Wall', '-Werror',
+                           os.path.join(HERE, 'tools', 'node_tables_check.cpp'), '-o', str(exe)])
+    done = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert done.returncode == 0, done.stdout
+    assert '0 unexpected' in done.stdout and done.stdout.count('refused') >= 16
+    refused = [line for line in done.stdout.splitlines() if ' refused: ' in line]
+    assert any(line.startswith('thermal speeds with per-node directions') for line in refused)
