@@ -23,9 +23,9 @@
 #include <vector>
 
 #include "../../include/nexoclom_hip.h"
+#include "nxc_desc_check.hpp"
 #include "nxc_kernels.hpp"
 #include "nxc_log_table.hpp"
-#include "nxc_source_check.hpp"
 
 namespace {
 
@@ -238,38 +238,6 @@ LutDesc placed_lut(LutDesc d, size_t base)
 {
     d.rec += (int)base; d.fs += (int)base; d.cell += (int)base;
     return d;
-}
-
-// Affine maps of NumPy's PCG64 for the device sampler (nxc_kernels.hpp: PcgK): entry b <
-// NXC_PCG_BITS advances 2^b steps, entry NXC_PCG_BITS + v advances v*n steps (the start of draw
-// vector v).  state' = mult^d state + inc (mult^d - 1)/(mult - 1), accumulated by squaring like
-// pcg_advance_lcg_128 (numpy/random/src/pcg64/pcg64.c).
-typedef unsigned __int128 u128;
-const u128 PCG_MULT = ((u128)2549297995355413924ULL << 64) | 4865540595714422341ULL;
-
-void pcg_advance_map(u128 delta, u128 inc, u128 *a_out, u128 *c_out)
-{
-    u128 acc_mult = 1, acc_plus = 0, cur_mult = PCG_MULT, cur_plus = inc;
-    while (delta > 0) {
-        if (delta & 1) {
-            acc_mult *= cur_mult;
-            acc_plus = acc_plus * cur_mult + cur_plus;
-        }
-        cur_plus = (cur_mult + 1) * cur_plus;
-        cur_mult *= cur_mult;
-        delta >>= 1;
-    }
-    *a_out = acc_mult;
-    *c_out = acc_plus;
-}
-
-std::vector<u128> pcg_tables(u128 inc, int64_t n)
-{
-    std::vector<u128> t((size_t)2 * (NXC_PCG_BITS + NXC_PCG_VECS));
-    for (int b = 0; b < NXC_PCG_BITS; b++) pcg_advance_map((u128)1 << b, inc, &t[2 * b], &t[2 * b + 1]);
-    for (int v = 0; v < NXC_PCG_VECS; v++)
-        pcg_advance_map((u128)v * (u128)n, inc, &t[2 * (NXC_PCG_BITS + v)], &t[2 * (NXC_PCG_BITS + v) + 1]);
-    return t;
 }
 
 // Largest double x with sqrt(x) <= e (host sqrt is correctly rounded): r2 > x <=> sqrt(r2) > e,
@@ -2054,41 +2022,6 @@ int nxc_set_image(nxc_handle *h, const nxc_image_desc *d)
     });
 }
 
-namespace {
-// What bispev3 needs of a bicubic spline (FITPACK layout) to stay finite: 8..65536 finite,
-// non-decreasing knots per axis that increase inside [t[3], t[n-4]] (a zero-width interval there
-// would divide by zero) and finite coefficients.  One check for every entry that takes such a
-// spline (nxc_set_bounce with accommodation, nxc_packets_sample speed_type 3).  `who` starts the
-// error text; *coef_max receives max |coef|.
-int check_bicubic_spline(const char *who, int64_t nx, int64_t ny, const double *tx, const double *ty,
-                         const double *coef, double *coef_max)
-{
-    if (nx < 8 || ny < 8 || nx > (1 << 16) || ny > (1 << 16) || !tx || !ty || !coef)
-        return fail(NXC_ERR_ARG, std::string(who) + " speeds need a spline with 8..65536 knots per "
-                                 "axis, tx, ty and coef");
-    for (int axis = 0; axis < 2; axis++) {
-        const double *t = axis ? ty : tx;
-        const int64_t nk = axis ? ny : nx;
-        for (int64_t k = 0; k < nk; k++)
-            if (!std::isfinite(t[k]) || (k > 0 && !(t[k] >= t[k - 1])) ||
-                (k > 3 && k <= nk - 4 && !(t[k] > t[k - 1])))
-                return fail(NXC_ERR_ARG, std::string(who) + " spline knots " + (axis ? "ty" : "tx") +
-                                         " must be finite, non-decreasing and increasing inside "
-                                         "[t[3], t[n-4]]");
-    }
-    double big = 0.0;
-    const int64_t n_coef = (nx - 4) * (ny - 4);
-    for (int64_t k = 0; k < n_coef; k++) {
-        if (!std::isfinite(coef[k]))
-            return fail(NXC_ERR_ARG, std::string(who) + " spline coefficients must be finite (coef " +
-                                     std::to_string(k) + ")");
-        big = std::max(big, std::fabs(coef[k]));
-    }
-    if (coef_max) *coef_max = big;
-    return NXC_OK;
-}
-}  // namespace
-
 int nxc_set_bounce(nxc_handle *h, const nxc_bounce_desc *d)
 {
     return guarded([&]() -> int {
@@ -2103,9 +2036,9 @@ int nxc_set_bounce(nxc_handle *h, const nxc_bounce_desc *d)
         return fail(NXC_ERR_ARG, "bad nxc_bounce_desc");
     // the spline is evaluated only with accommodation: without it the tables may be dummies
     if (d->accomfactor != 0) {
-        if (int rc = check_bicubic_spline("nxc_bounce_desc: accommodated", d->nx, d->ny, d->tx, d->ty,
-                                          d->coef, nullptr))
-            return rc;
+        const std::string why = check_bicubic_spline("nxc_bounce_desc: accommodated", d->nx, d->ny, d->tx,
+                                                     d->ty, d->coef, nullptr);
+        if (!why.empty()) return fail(NXC_ERR_ARG, why);
     }
     const size_t ncoef = (size_t)(d->nx - 4) * (size_t)(d->ny - 4);
     const size_t total = (size_t)d->nx + (size_t)d->ny + ncoef;
@@ -2136,25 +2069,9 @@ int nxc_set_stick_map(nxc_handle *h, const nxc_stick_map_desc *d)
     HIPCHK(hipSetDevice(h->device));
     BounceK &B = h->header.B;
     if (d) {
-        const double TWO_PI = 6.283185307179586, HALF_PI = 1.5707963267948966;
-        const int64_t nlon = d->nlon, nlat = d->nlat;
-        if (nlon < 2 || nlon > (1 << 16) || nlat < 0 || nlat == 1 || nlat > (1 << 16) || !d->lon ||
-            !d->coef || (nlat && !d->lat))
-            return fail(NXC_ERR_ARG, "nxc_stick_map_desc: 2..65536 longitude nodes, 0 or 2..65536 "
-                                     "latitude nodes, lon, coef (and lat)");
-        for (int64_t k = 0; k < nlon; k++)
-            if (!(d->lon[k] >= 0 && d->lon[k] < TWO_PI) || (k > 0 && !(d->lon[k] > d->lon[k - 1])))
-                return fail(NXC_ERR_ARG, "nxc_stick_map_desc: longitude nodes must increase within "
-                                         "[0, 2 pi) (lon " + std::to_string(k) + ")");
-        for (int64_t k = 0; k < nlat; k++)
-            if (!(d->lat[k] >= -HALF_PI && d->lat[k] <= HALF_PI) || (k > 0 && !(d->lat[k] > d->lat[k - 1])))
-                return fail(NXC_ERR_ARG, "nxc_stick_map_desc: latitude nodes must increase within "
-                                         "[-pi/2, pi/2] (lat " + std::to_string(k) + ")");
-        const int64_t ncoef = nlon * (nlat ? nlat : 1);
-        for (int64_t k = 0; k < ncoef; k++)
-            if (!(d->coef[k] >= 0 && d->coef[k] <= 1))
-                return fail(NXC_ERR_ARG, "nxc_stick_map_desc: coefficients must lie in [0, 1] (coef " +
-                                         std::to_string(k) + " = " + std::to_string(d->coef[k]) + ")");
+        const std::string why = check_stick_map(d);
+        if (!why.empty()) return fail(NXC_ERR_ARG, why);
+        const int64_t nlon = d->nlon, nlat = d->nlat, ncoef = nlon * (nlat ? nlat : 1);
         const size_t total = (size_t)(nlon + nlat + ncoef);
         // (a launch that reads the previous map has ended: every launch is followed by a sync or is
         // ordered before these copies on the handle's stream)
@@ -2510,146 +2427,32 @@ int nxc_packets_upload_pieces(nxc_handle *h, int32_t n_pieces, const int64_t *co
     });
 }
 
+// (what the descriptor must satisfy, where its tables go and what the launch derives from them:
+// plan_source, nxc_desc_check.hpp)
 int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, double *soa_out)
 {
     return guarded([&]() -> int {
-    if (!h || !d || n < 1) return fail(NXC_ERR_ARG, "bad arguments");
-    if (d->speed_type < 0 || d->speed_type > 4 || d->angular_type < 0 || d->angular_type > 2 ||
-        d->spatial_type < 0 || d->spatial_type > 3 || !(d->unit_km > 0) || !(d->exobase > 0))
-        return fail(NXC_ERR_ARG, "bad nxc_source_desc");
-    const bool tab_speed = d->speed_type == 2, spot = d->spatial_type == 1;
-    const bool map2d = d->spatial_type == 2, map1d = d->spatial_type == 3;
-    const bool thermal = d->speed_type == 3;
-    const bool node_tables = d->speed_type == 4 || d->angular_type == 2;
-    const bool pcg = d->generator == 1;
-    if (d->generator != 0 && d->generator != 1) return fail(NXC_ERR_ARG, "nxc_source_desc: generator must be 0 or 1");
-    if (pcg) {
-        if (d->spatial_type != 0 || (d->speed_type != 0 && !thermal))
-            return fail(NXC_ERR_ARG, "generator 1 (PCG64) covers the sources whose every draw is a "
-                                     "random(npackets) vector: uniform surface, flat or thermal speeds");
-        if (d->pcg_n < 1 || d->pcg_row0 < 0 || d->pcg_row0 + n > d->pcg_n ||
-            d->pcg_n >= ((int64_t)1 << (NXC_PCG_BITS - 1)) || !(d->pcg_inc[1] & 1ull))
-            return fail(NXC_ERR_ARG, "nxc_source_desc: PCG64 window outside its draw vectors");
-    }
-    if (tab_speed) {
-        if (d->n_speed < 2 || d->n_speed > (1 << 24) || !d->speed_cdf || !d->speed_v)
-            return fail(NXC_ERR_ARG, "nxc_source_desc: tabulated speeds need n_speed >= 2 and both tables");
-        for (int64_t k = 0; k + 1 < d->n_speed; k++)
-            if (!(d->speed_cdf[k + 1] >= d->speed_cdf[k]))
-                return fail(NXC_ERR_ARG, "nxc_source_desc: speed_cdf must be non-decreasing");
-        if (!(d->speed_cdf[d->n_speed - 1] > d->speed_cdf[0]))
-            return fail(NXC_ERR_ARG, "nxc_source_desc: speed_cdf is flat");
-    }
-    // thermal speeds: the surface temperature's constants and the v(T, p) spline
-    const int64_t n_coef = thermal ? (d->nx - 4) * (d->ny - 4) : 0;
-    double coef_max = 0.0;
-    if (thermal) {
-        if (!(d->t0 > 0.0) || !std::isfinite(d->t0) || !(d->t1 >= 0.0) || !std::isfinite(d->t1))
-            return fail(NXC_ERR_ARG, "nxc_source_desc: thermal speeds need finite t0 > 0 and t1 >= 0");
-        if (int rc = check_bicubic_spline("nxc_source_desc: thermal", d->nx, d->ny, d->tx, d->ty,
-                                          d->coef, &coef_max))
-            return rc;
-    }
-    double map_max = 0.0, map_sum = 0.0;
-    if (spot) {
-        if (d->map_nlon < 2 || d->map_nlat < 2 || d->map_nlon > 8192 || d->map_nlat > 8192 || !d->map)
-            return fail(NXC_ERR_ARG, "nxc_source_desc: surface spot needs a density map");
-        for (int64_t k = 0; k < d->map_nlon * d->map_nlat; k++) {
-            if (!(d->map[k] >= 0.0) || !std::isfinite(d->map[k]))
-                return fail(NXC_ERR_ARG, "nxc_source_desc: density map values must be finite and >= 0");
-            map_max = std::max(map_max, d->map[k]);
-            map_sum += d->map[k];
-        }
-        if (!(map_max > 0.0)) return fail(NXC_ERR_ARG, "nxc_source_desc: density map is all zero");
-    }
-    // surface map: node values [map_nlon][map_nlat] with the cumulated masses of the
-    // (map_nlon - 1) x (map_nlat - 1) cells; 1-D map: longitude grid [map_nlon] with its cdf
-    const int64_t n_nodes = map2d ? d->map_nlon * d->map_nlat : d->map_nlon;
-    const int64_t n_cdf = map2d ? (d->map_nlon - 1) * (d->map_nlat - 1) : d->map_nlon;
-    if (map2d || map1d) {
-        if (d->map_nlon < 2 || d->map_nlon > 8192 || (map2d && (d->map_nlat < 2 || d->map_nlat > 8192)) ||
-            !d->map || !d->map_cdf)
-            return fail(NXC_ERR_ARG, "nxc_source_desc: a surface map needs 2..8192 nodes per axis, "
-                                     "map and map_cdf");
-        double node_max = 0.0;
-        for (int64_t k = 0; k < n_nodes; k++) {
-            // (a 1-D map's `map` is its longitude grid: finite is all it has to be)
-            if (!std::isfinite(d->map[k]) || (map2d && !(d->map[k] >= 0.0)))
-                return fail(NXC_ERR_ARG, "nxc_source_desc: surface map values must be finite and >= 0 "
-                                         "(node " + std::to_string(k) + ")");
-            node_max = std::max(node_max, d->map[k]);
-        }
-        if (map2d && !(node_max > 0.0)) return fail(NXC_ERR_ARG, "nxc_source_desc: surface map is all zero");
-        if (!(d->map_cdf[0] >= 0.0) || !(d->map_cdf[n_cdf - 1] == 1.0))
-            return fail(NXC_ERR_ARG, "nxc_source_desc: map_cdf must run from >= 0 to 1 (is the map all zero?)");
-        for (int64_t k = 0; k + 1 < n_cdf; k++)
-            if (!(d->map_cdf[k + 1] >= d->map_cdf[k]))
-                return fail(NXC_ERR_ARG, "nxc_source_desc: map_cdf must be non-decreasing");
-        if (map1d && !(d->map_cdf[n_cdf - 1] > d->map_cdf[0]))
-            return fail(NXC_ERR_ARG, "nxc_source_desc: map_cdf is flat");
-        if (map2d && (!std::isfinite(d->map_lon0) || !std::isfinite(d->map_lon1) ||
-                      !(d->map_lon0 < d->map_lon1) || !(d->map_s0 >= -1.0) || !(d->map_s1 <= 1.0) ||
-                      !(d->map_s0 < d->map_s1)))
-            return fail(NXC_ERR_ARG, "nxc_source_desc: surface map needs map_lon0 < map_lon1 and "
-                                     "-1 <= map_s0 < map_s1 <= 1");
-    }
-    // per-node tables of the map (speed_type 4, angular_type 2): nxc_source_check.hpp
-    if (node_tables) {
-        const std::string why = check_node_tables(d);
-        if (!why.empty()) return fail(NXC_ERR_ARG, why);
-    }
+    if (!h) return fail(NXC_ERR_ARG, "bad arguments");
+    const SourcePlan plan = plan_source(d, n);
+    if (!plan.why.empty()) return fail(NXC_ERR_ARG, plan.why);
     HIPCHK(hipSetDevice(h->device));
-    const int64_t total = d->dest_total > 0 ? d->dest_total : n;
-    const int64_t offset = d->dest_total > 0 ? d->dest_offset : 0;
-    if (offset < 0 || offset + n > total) return fail(NXC_ERR_ARG, "nxc_source_desc: piece outside its set");
+    const int64_t total = plan.stride, offset = plan.offset;
     const size_t bytes = (size_t)8 * total * sizeof(double);
     if (offset > 0 && (h->packets_cap < bytes || h->n_packets != total))
         return fail(NXC_ERR_STATE, "nxc_packets_sample: pieces of a set must start with dest_offset 0");
     int rc = ensure(reinterpret_cast<void **>(&h->d_packets), &h->packets_cap, bytes);
     if (rc) return rc;
-    const size_t n_sp = tab_speed ? (size_t)d->n_speed : 0;
-    const size_t n_map = spot ? (size_t)(d->map_nlon * d->map_nlat)
-                              : (map2d || map1d ? (size_t)n_nodes : 0);
-    const size_t n_mcdf = map2d || map1d ? (size_t)n_cdf : 0;
-    const size_t n_pcg = pcg ? (size_t)4 * (NXC_PCG_BITS + NXC_PCG_VECS) : 0;   // doubles' worth
-    // the spline's knots and coefficients go behind every other table (the PCG64 maps included)
-    const size_t n_spl = thermal ? (size_t)(d->nx + d->ny + n_coef) : 0;
-    const size_t at_spl = 2 * n_sp + n_map + n_mcdf + n_pcg;
-    // ... and the per-node tables behind the spline
-    NodeTableLayout nodes{};
-    if (node_tables) nodes = node_table_layout(d, at_spl + n_spl);
-    if (n_sp + n_map + n_pcg + n_spl + nodes.total) {
-        if ((rc = ensure(reinterpret_cast<void **>(&h->d_source), &h->source_cap,
-                         (at_spl + n_spl + nodes.total) * sizeof(double))))
-            return rc;
-        if (pcg) {
-            const u128 inc = ((u128)d->pcg_inc[0] << 64) | d->pcg_inc[1];
-            const std::vector<u128> maps = pcg_tables(inc, d->pcg_n);
-            HIPCHK(hipMemcpyAsync(h->d_source, maps.data(), maps.size() * sizeof(u128),
-                                  hipMemcpyHostToDevice, h->stream));
-            HIPCHK(stream_sync(h));      // the table is a local
-        }
-        if (n_sp) {
-            HIPCHK(hipMemcpyAsync(h->d_source, d->speed_cdf, n_sp * 8, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_source + n_sp, d->speed_v, n_sp * 8, hipMemcpyHostToDevice, h->stream));
-        }
-        if (n_map)
-            HIPCHK(hipMemcpyAsync(h->d_source + 2 * n_sp, d->map, n_map * 8, hipMemcpyHostToDevice, h->stream));
-        if (n_mcdf)
-            HIPCHK(hipMemcpyAsync(h->d_source + 2 * n_sp + n_map, d->map_cdf, n_mcdf * 8,
-                                  hipMemcpyHostToDevice, h->stream));
-        if (n_spl) {
-            HIPCHK(hipMemcpyAsync(h->d_source + at_spl, d->tx, (size_t)d->nx * 8, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_source + at_spl + d->nx, d->ty, (size_t)d->ny * 8,
-                                  hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->d_source + at_spl + d->nx + d->ny, d->coef, (size_t)n_coef * 8,
-                                  hipMemcpyHostToDevice, h->stream));
-        }
-        for (const NodeTableCopy &c : nodes.copy)
-            if (c.count)
-                HIPCHK(hipMemcpyAsync(h->d_source + c.at, c.from, c.count * 8, hipMemcpyHostToDevice,
-                                      h->stream));
+    if (plan.total &&
+        (rc = ensure(reinterpret_cast<void **>(&h->d_source), &h->source_cap, plan.total * sizeof(double))))
+        return rc;
+    for (const TableCopy &c : plan.copy) {
+        if (!c.count) continue;
+        HIPCHK(hipMemcpyAsync(h->d_source + c.at, c.from, c.count * 8, hipMemcpyHostToDevice, h->stream));
+        if (c.from == plan.pcg_maps.data()) HIPCHK(stream_sync(h));      // the table is the plan's
     }
+    const auto table = [&](SourceTable t) { return h->d_source + plan.copy[t].at; };
+    const auto rows = [&](SourceTable t) { return (int)plan.copy[t].count; };
+    const bool map2d = d->spatial_type == 2;
     SourceK K{};
     K.endtime = d->endtime; K.exobase = d->exobase; K.sinlat0 = d->sinlat0; K.sinlat1 = d->sinlat1;
     K.lon0 = d->lon0; K.lon1 = d->lon1; K.vprob = d->vprob; K.vwidth = d->vwidth;
@@ -2657,57 +2460,39 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
     K.az1 = d->az1; K.random_time = d->random_time; K.speed_type = d->speed_type;
     K.angular_type = d->angular_type; K.is_planet = d->is_planet; K.seed = d->seed;
     K.first_index = d->first_index;
-    K.spatial_type = d->spatial_type; K.n_speed = (int)n_sp;
-    K.map_nlon = spot || map2d || map1d ? (int)d->map_nlon : 0;
-    K.map_nlat = spot || map2d ? (int)d->map_nlat : 0;
-    if (map2d) {
-        K.map_lon0 = d->map_lon0; K.map_dlon = (d->map_lon1 - d->map_lon0) / (double)(d->map_nlon - 1);
-        K.map_s0 = d->map_s0; K.map_ds = (d->map_s1 - d->map_s0) / (double)(d->map_nlat - 1);
-        K.map_s1 = d->map_s1;
-    }
-    K.map_max = map_max;
-    K.max_trials = NXC_SPOT_MIN_TRIALS;
-    if (spot && map_sum > 0) {
-        // acceptance rate of the uniform (lon, lat) proposal = mean / max of the map: a narrow spot
-        // (sigma 0.05 rad: 8e-4) needs tens of thousands of trials for the unluckiest of 1e6 packets
-        const double accept = map_sum / (double)(d->map_nlon * d->map_nlat) / map_max;
-        const double want = 32.0 / accept;
-        K.max_trials = want > (double)NXC_SPOT_MAX_TRIALS ? NXC_SPOT_MAX_TRIALS
-                       : (want < (double)NXC_SPOT_MIN_TRIALS ? NXC_SPOT_MIN_TRIALS : (int)want);
-    }
-    K.speed_cdf = h->d_source; K.speed_v = h->d_source + n_sp; K.map = h->d_source + 2 * n_sp;
-    K.map_cdf = K.map + n_map;
+    K.spatial_type = d->spatial_type; K.n_speed = rows(ST_SPEED_V);
+    K.map_nlon = d->spatial_type != 0 ? (int)d->map_nlon : 0;
+    K.map_nlat = d->spatial_type == 1 || map2d ? (int)d->map_nlat : 0;
+    if (map2d) { K.map_lon0 = d->map_lon0; K.map_s0 = d->map_s0; K.map_s1 = d->map_s1; }
+    K.map_dlon = plan.map_dlon; K.map_ds = plan.map_ds; K.map_max = plan.map_max;
+    K.max_trials = plan.max_trials;
+    K.speed_cdf = table(ST_SPEED_CDF); K.speed_v = table(ST_SPEED_V);
+    K.map = table(ST_MAP); K.map_cdf = table(ST_MAP_CDF);
     K.generator = d->generator;
-    if (pcg) {       // (pcg excludes the tabulated sources, so the maps sit at the buffer's start)
+    if (d->generator == 1) {
         K.pcg.state = ((u128)d->pcg_state[0] << 64) | d->pcg_state[1];
         K.pcg.row0 = d->pcg_row0;
-        K.pcg.maps = reinterpret_cast<const nxc_u128 *>(h->d_source);
+        K.pcg.maps = reinterpret_cast<const nxc_u128 *>(table(ST_PCG));
     }
-    K.stride = total;
-    K.offset = offset;
-    if (thermal) {
+    K.stride = total; K.offset = offset;
+    if (plan.law == NXC_LAW_THERMAL) {
         K.t0 = d->t0; K.t1 = d->t1;
-        K.spl.tx = h->d_source + at_spl; K.spl.ty = K.spl.tx + d->nx; K.spl.coef = K.spl.ty + d->ny;
-        K.spl.nx = (int)d->nx; K.spl.ny = (int)d->ny;
+        K.spl.tx = table(ST_TX); K.spl.ty = table(ST_TY); K.spl.coef = table(ST_COEF);
+        K.spl.nx = rows(ST_TX); K.spl.ny = rows(ST_TY);
     }
-    if (node_tables) {
-        K.node_speed_cdf = h->d_source + nodes.copy[0].at; K.node_speed_v = h->d_source + nodes.copy[1].at;
-        K.node_alt_cdf = h->d_source + nodes.copy[2].at; K.node_alt = h->d_source + nodes.copy[3].at;
-        K.node_az_cdf = h->d_source + nodes.copy[4].at; K.node_az = h->d_source + nodes.copy[5].at;
-        K.n_node_speed = (int)nodes.copy[1].count; K.n_node_alt = (int)nodes.copy[3].count;
-        K.n_node_az = (int)nodes.copy[5].count;
+    if (plan.law == NXC_LAW_NODES) {
+        K.node_speed_cdf = table(ST_NODE_SPEED_CDF); K.node_speed_v = table(ST_NODE_SPEED_V);
+        K.node_alt_cdf = table(ST_NODE_ALT_CDF); K.node_alt = table(ST_NODE_ALT);
+        K.node_az_cdf = table(ST_NODE_AZ_CDF); K.node_az = table(ST_NODE_AZ);
+        K.n_node_speed = rows(ST_NODE_SPEED_V); K.n_node_alt = rows(ST_NODE_ALT);
+        K.n_node_az = rows(ST_NODE_AZ);
     }
     HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
     if ((rc = begin_timed(h))) return rc;
-    if (node_tables)
-        hipLaunchKernelGGL(k_sample<NXC_LAW_NODES>, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0,
-                           h->stream, K, n, h->d_packets, h->d_ctr);
-    else if (thermal)
-        hipLaunchKernelGGL(k_sample<NXC_LAW_THERMAL>, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0,
-                           h->stream, K, n, h->d_packets, h->d_ctr);
-    else
-        hipLaunchKernelGGL(k_sample<NXC_LAW_PLAIN>, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0, h->stream,
-                           K, n, h->d_packets, h->d_ctr);
+    const auto kernel = plan.law == NXC_LAW_NODES ? k_sample<NXC_LAW_NODES>
+                        : (plan.law == NXC_LAW_THERMAL ? k_sample<NXC_LAW_THERMAL> : k_sample<NXC_LAW_PLAIN>);
+    hipLaunchKernelGGL(kernel, dim3(flat_grid(h, n, NXC_BLOCK)), dim3(NXC_BLOCK), 0, h->stream, K, n,
+                       h->d_packets, h->d_ctr);
     HIPCHK(hipGetLastError());
     if ((rc = end_timed(h))) return rc;
     DevCounters c;
@@ -2731,23 +2516,7 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
         HIPCHK(stream_sync(h));
         return NXC_OK;
     }
-    double vmax;
-    if (tab_speed) {
-        vmax = 0.0;
-        for (size_t k = 0; k < n_sp; k++) vmax = std::max(vmax, std::fabs(d->speed_v[k]));
-        vmax /= d->unit_km;
-    } else if (thermal) {
-        vmax = coef_max / d->unit_km;      // |S| <= max |coef|: the bases are >= 0 and sum to 1
-    } else if (d->speed_type == 4) {
-        vmax = 0.0;
-        for (int64_t k = 0; k < d->n_node_speed; k++) vmax = std::max(vmax, std::fabs(d->node_speed_v[k]));
-        vmax /= d->unit_km;
-    } else {
-        vmax = (d->speed_type == 0 ? std::fabs(d->vprob) + std::fabs(d->vwidth)
-                                   : std::fabs(d->vprob) + 6 * std::fabs(d->vwidth)) / d->unit_km;
-    }
-    // (a set made of pieces may mix sources: let the device find its largest launch speed)
-    if ((rc = order_on_device(h, d->dest_total > 0 ? -1.0 : vmax * vmax, nullptr, 0))) return rc;
+    if ((rc = order_on_device(h, plan.k2max, nullptr, 0))) return rc;
     HIPCHK(stream_sync(h));
     return NXC_OK;
     });

@@ -17,6 +17,7 @@
 // into LDS from one packed blob.
 #pragma once
 #include "nxc_device.hpp"
+#include "nxc_source_limits.hpp"
 
 struct DevCounters {
     unsigned long long particle_steps, samples, samples_binned, nonfinite, bad_step, neg_frac,
@@ -2145,10 +2146,9 @@ k_los_pairs(LosK K, const unsigned char *__restrict__ blob, int64_t stage_bytes,
 // so element `row` of draw `vec` of a chunk of `n` packets is output number vec*n + row of the
 // stream, i.e. the state after vec*n + row + 1 steps.  A thread jumps there in two moves: to
 // row + 1 with the precomputed affine maps of 2^b steps (one 128-bit multiply-add per set bit),
-// then by vec*n with that vector's map.  All maps come from the host (nxc_api.hip: pcg_tables).
+// then by vec*n with that vector's map.  All maps come from the host (nxc_desc_check.hpp: pcg_tables;
+// NXC_PCG_BITS, NXC_PCG_VECS: nxc_source_limits.hpp).
 typedef unsigned __int128 nxc_u128;
-constexpr int NXC_PCG_BITS = 40;       // rows below 2^40
-constexpr int NXC_PCG_VECS = 8;        // draws per packet
 struct PcgK {
     nxc_u128 state;                    // after seeding: PCG64(seed).state['state']['state']
     long long row0;                    // row of this call's first packet inside its chunk's draws
@@ -2332,10 +2332,7 @@ NXC_DEV double interp_node(const double *__restrict__ cdf, const double *__restr
     return interp_global(cdf + (long long)node * n, axis, n, u);
 }
 
-// Rejection trials per packet: the host sizes the budget to the map (32 / acceptance rate, so that
-// a packet fails to find a launch point with probability e^-32) between these bounds; a packet
-// that never passes is reported, and the call fails.
-constexpr int NXC_SPOT_MIN_TRIALS = 4096, NXC_SPOT_MAX_TRIALS = 1 << 18;
+// (the rejection trials per packet, NXC_SPOT_MIN_TRIALS .. NXC_SPOT_MAX_TRIALS: nxc_source_limits.hpp)
 constexpr unsigned NXC_SPOT_BLOCK0 = 16;    // Philox draw blocks 16 + 2t, 17 + 2t of trial t
 
 // LAW: which instantiation.  NXC_LAW_THERMAL is the one for speed_type 3 (thermal speeds): the
@@ -2344,7 +2341,7 @@ constexpr unsigned NXC_SPOT_BLOCK0 = 16;    // Philox draw blocks 16 + 2t, 17 + 
 // three more bisections.  Both are kept out of NXC_LAW_PLAIN, which every other source runs and
 // whose code is that of the kernel before either existed.  No instantiation holds both laws:
 // speed_type 3 with angular_type 2 is refused before the launch (check_node_tables).
-constexpr int NXC_LAW_PLAIN = 0, NXC_LAW_THERMAL = 1, NXC_LAW_NODES = 2;
+// (NXC_LAW_PLAIN, NXC_LAW_THERMAL, NXC_LAW_NODES: nxc_source_limits.hpp)
 
 template <int LAW>
 __global__ void __launch_bounds__(NXC_BLOCK)

@@ -412,16 +412,18 @@ def test_node_law_tables_rebuild_the_angle_axes_of_a_normalised_map(tmp_path):
 
 # ---- the C side's refusals, without a GPU ---------------------------------------------------------------
 def test_descriptor_validation_and_staging_as_a_host_program(tmp_path):
-    """nxc_packets_sample's validation and staging of the per-node tables are host-only code
-    (nxc_source_check.hpp); tests/tools/node_tables_check.cpp feeds them good and bad descriptors
-    up to the first device call.  Built plainly here; the same file is what is built with
+    """Everything nxc_packets_sample does with a descriptor before its first device call -- the
+    refusals, the place of each table in the source buffer, the values the launch derives -- is
+    host-only code (nxc_desc_check.hpp), as are the checks of nxc_set_bounce's spline and
+    nxc_set_stick_map's nodes; tests/tools/desc_check.cpp feeds them one good descriptor per source
+    kind and one bad one per refusal.  Built plainly here; the same file is what is built with
     -fsanitize=address,undefined to check the host code's memory accesses."""
     import subprocess
-    exe = tmp_path / 'node_tables_check'
+    exe = tmp_path / 'desc_check'
     subprocess.check_call(['g++', '-std=c++17', '-O1', '-Wall', '-Werror',
-                           os.path.join(HERE, 'tools', 'node_tables_check.cpp'), '-o', str(exe)])
+                           os.path.join(HERE, 'tools', 'desc_check.cpp'), '-o', str(exe)])
     done = subprocess.run([str(exe)], capture_output=True, text=True)
     assert done.returncode == 0, done.stdout
-    assert '0 unexpected' in done.stdout and done.stdout.count('refused') >= 16
+    assert '0 unexpected' in done.stdout and done.stdout.count('refused') >= 49
     refused = [line for line in done.stdout.splitlines() if ' refused: ' in line]
     assert any(line.startswith('thermal speeds with per-node directions') for line in refused)
