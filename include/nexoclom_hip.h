@@ -466,6 +466,28 @@ int nxc_integrate_const_streamed(nxc_handle *h, int64_t n, const double *soa0, i
  * neither in this driver (Output.py:312-315). */
 int nxc_integrate_var(nxc_handle *h, double resolution, double outeredge, int64_t max_steps,
                       double *final_out, double *hstore_out);
+/* The same launch (same checks, queue order and kernel) with the finals left ON THE DEVICE: [8][n]
+ * fp64 and the stored step in the handle's scratch, where they stay until the next call that
+ * uploads or samples packets, integrates, or takes the scratch (nxc_state, nxc_rk5_step, a
+ * line-of-sight pass, ...).  Only hstore_out (nullable, host [n]) crosses to the host; the counters
+ * come through nxc_counters_get.
+ *   nxc_var_rows_build  the row store of that run, in nxc_rows_build's layout (every *_rows entry
+ *                       point takes it): one row per kept packet, in packet order; the eight state
+ *                       columns are the finals, lossfrac is 0 (this driver never accumulates it,
+ *                       Output.py:328-329) and the index column is the packet's number in the
+ *                       resident set.  compress != 0 keeps a packet iff its fp64 frac > 0 -- save()'s
+ *                       filter on the 64-bit frame (Output.py:523-524), applied before narrowing: a
+ *                       frac that underflows in float32 is kept; NaN, +-0 and negative ones are
+ *                       dropped; compress == 0 keeps every packet.  narrow != 0 stores float32 /
+ *                       int32 (round to nearest even, overflow to inf: numpy's astype), else
+ *                       float64 / int64.  kept_out (nullable, host [n]): 1 where the packet has a
+ *                       row.  A store of no rows is valid.  May be called more than once per run.
+ *                       NXC_ERR_STATE, leaving the handle usable, unless the finals of an
+ *                       nxc_integrate_var_resident over the current resident packets are still in
+ *                       the scratch.  nxc_last_kernel_ms then spans its two passes. */
+int nxc_integrate_var_resident(nxc_handle *h, double resolution, double outeredge,
+                               int64_t max_steps, double *hstore_out);
+int nxc_var_rows_build(nxc_handle *h, int narrow, int compress, nxc_rows **out, uint8_t *kept_out);
 
 /* ---- a-6..a-8: image of p stored samples -------------------------------------------------------
  * Adds to the resident image pair (use nxc_image_clear / nxc_image_download around it). */

@@ -313,9 +313,9 @@ class ModelImage(ModelResult):
         from .distributed import chunk_plan
         inputs = self.inputs
         opt = inputs.options
-        if opt.step_size == 0:
-            raise NotImplementedError('streaming images need constant-step inputs; the '
-                                      'variable-step driver keeps one final row per packet')
+        # step_size = 0: the adaptive driver keeps one final row per packet; a chunk's rows are
+        # built in HBM as save() would store them, binned from there and dropped
+        variable = opt.step_size == 0
         hi = total if hi is None else hi
         ctx = self.context()
         if seed is None and sampler == 'device':
@@ -325,7 +325,8 @@ class ModelImage(ModelResult):
             seed = fresh_key()
         self.seed = seed
         chunk = int(packs_per_it) if packs_per_it else max(1, min(total, 20_000_000))
-        nsteps, n_iter = n_output_steps(opt.endtime.value, float(opt.step_size))
+        nsteps, n_iter = (1, 0) if variable else \
+            n_output_steps(opt.endtime.value, float(opt.step_size))
         first = True
         totals = {}
         src = bounce = bodies = None
@@ -382,9 +383,13 @@ class ModelImage(ModelResult):
                     else:
                         out = host_chunk(k, clen, a - c0, b - c0)
                     bounce, bodies = out._bounce, out._bodies
+                if variable:
+                    assert bounce is None, 'Not set up'                  # Output.py:312-315
                 if first:
                     ctx.set_forces(**out.forces_kwargs())
-                    self._set_image(ctx, out.aplanet, out.vrplanet, downcast)   # clears the image
+                    # (adaptive step: the rows come narrowed from their store, not from the kernel)
+                    self._set_image(ctx, out.aplanet, out.vrplanet,
+                                    downcast and not variable)           # clears the image
                     first = False
                 if sampler != 'device':
                     soa = out.x0_soa()
@@ -393,10 +398,14 @@ class ModelImage(ModelResult):
                 ctx.set_bounce(bounce)
                 ctx.set_bodies(bodies)
                 ctx.set_first_index(a)
-                ctx.integrate_const(float(opt.step_size), n_iter, opt.outeredge, image=True)
-                for key, v in ctx.counters().items():
-                    totals[key] = totals.get(key, 0) + v
-                self.totalsource += n * nsteps                                  # Output.py:434
+                if variable:
+                    self._var_chunk(ctx, opt, downcast, totals)
+                else:
+                    ctx.integrate_const(float(opt.step_size), n_iter, opt.outeredge, image=True)
+                    for key, v in ctx.counters().items():
+                        totals[key] = totals.get(key, 0) + v
+                # Output.py:434; the adaptive driver has no nsteps factor: X0.frac.sum()
+                self.totalsource += n * nsteps
                 self.npackets += n
         finally:
             if pool is not None:
@@ -412,6 +421,27 @@ class ModelImage(ModelResult):
         self.packet_image += counts.astype(float)
         h = Histogram2dResult(image, self.xedges, self.zedges)
         self.xaxis, self.zaxis = h.x, h.y
+
+    @staticmethod
+    def _var_chunk(ctx, opt, downcast, totals):
+        """The resident packets through the adaptive driver and into the image: finals and rows
+        stay in HBM (float32 rows with ``downcast``, like a saved Output's)."""
+        ctx.integrate_var(float(opt.resolution), opt.outeredge, resident=True)
+        ctr = ctx.counters()
+        assert ctr.get('nonfinite', 0) == 0, '\n\tInfinite values of emax or a non-finite impact'
+        assert ctr.get('neg_frac', 0) == 0, 'Found new values of frac that are negative'
+        assert ctr.get('bad_step', 0) == 0, 'Bad step size'
+        assert ctr.get('unfinished', 0) == 0, 'variable-step integration did not finish'
+        store, _ = ctx.var_rows_build(narrow=downcast, compress=True)
+        try:
+            if store.total:
+                ctx.image_accumulate_rows(store)
+                for key, v in ctx.counters().items():
+                    ctr[key] = ctr.get(key, 0) + v
+        finally:
+            store.free()
+        for key, v in ctr.items():
+            totals[key] = totals.get(key, 0) + v
 
     def export(self, filename='image.json'):
         if not filename.endswith('.json'):

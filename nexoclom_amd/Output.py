@@ -26,7 +26,8 @@ loss_info, randgen, compress, inputs, planet) and the same column order of ``X``
 * the trajectory rows of a constant-step run stay in HBM (hip_api.RowStore) in exactly the form
   save() would store them -- frac > 0 rows, float32 / int32 -- and ``X`` is built from them on
   first access; ModelImage and LOSResult read the resident rows directly.  ``Output.integrate_batch``
-  integrates several Outputs of one ``Input.run`` in a single launch.
+  integrates several Outputs of one ``Input.run`` in a single launch.  At ``step_size = 0`` it
+  leaves the finals in HBM the same way: one row per packet with frac > 0.
 """
 import os
 
@@ -43,6 +44,36 @@ STATE_COLS = ['time', 'x', 'y', 'z', 'vx', 'vy', 'vz', 'frac']
 # save()'s 32-bit down-cast and restore()'s way back (Output.py:528-543, 555-570)
 NARROW = {np.int64: np.int32, np.float64: np.float32}
 WIDE = {np.int32: np.int64, np.float32: np.float64}
+
+
+X0_ONLY_COLS = ('longitude', 'latitude', 'local_time')       # what X does not take over from X0
+
+
+def frame_var_rows(rows, index, X0, hs, kept):
+    """``X`` of an adaptive-step Output after save()'s frac > 0 filter, from host arrays: ``rows``
+    (9, k) -- the finals of the k kept packets and lossfrac, float32 (save()'s down-cast) or
+    float64 --, ``index`` (k,) their packet numbers, the launch frame ``X0`` (n rows, or none),
+    ``hs`` (n,) the stored step of every packet and ``kept`` (n,) bool.  Columns, order, dtypes
+    and labels are those of the frame variable_step_size_driver() builds and save() filters
+    (Output.py:221-366, 522-543): X0's columns without longitude / latitude / local_time, the
+    state columns overwritten in place (appended where X0 has none), lossfrac = 0, step_size,
+    Index; the surviving rows keep their packet numbers as labels."""
+    kept = np.asarray(kept, dtype=bool)
+    narrow = rows.dtype == np.float32
+    taken = [c for c in X0.columns if c not in X0_ONLY_COLS]
+    order = taken + ['lossfrac'] + [c for c in STATE_COLS if c not in taken] + ['step_size', 'Index']
+    columns = {name: rows[k] for k, name in enumerate(STATE_COLS)}
+    columns['lossfrac'] = rows[8]
+    columns['step_size'] = np.asarray(hs)[kept].astype(rows.dtype)
+    columns['Index'] = index
+    for name in taken:
+        if name not in columns:
+            values = X0[name].values[kept]
+            target = NARROW.get(values.dtype.type) if narrow else None
+            columns[name] = values.astype(target) if target else values
+    # save() filters only when a row goes (Output.py:523-524): else the labels stay a range
+    labels = pd.RangeIndex(len(kept)) if kept.all() else pd.Index(np.flatnonzero(kept).astype(np.int64))
+    return pd.DataFrame({name: columns[name] for name in order}, index=labels, copy=False)
 
 
 def fresh_key():
@@ -69,6 +100,7 @@ class Output:
     _store = None
     _row0 = _nrows = _packet0 = 0
     _lengths = None
+    _var_hs = None              # adaptive-step Outputs with resident rows: every packet's stored step
 
     def __init__(self, inputs, npackets, compress=True, run_model=True, seed=None, *,
                  device=0, integrate=True, keep_trajectory=True, context=None, save=True,
@@ -447,6 +479,9 @@ class Output:
 
     def _host_rows(self):
         """(rows (9, n), Index (n,)) of this Output as save() stores them, from HBM."""
+        if self._nrows == 0:
+            value, number = (np.float32, np.int32) if self._store.narrow else (np.float64, np.int64)
+            return np.empty((9, 0), dtype=value), np.empty(0, dtype=number)
         rows, idx = self._store.download(self._row0, self._nrows)
         if self._packet0:
             idx -= idx.dtype.type(self._packet0)
@@ -456,6 +491,11 @@ class Output:
         """The reference's X after save()'s frac > 0 filter (Output.py:435-449,523-524): the
         surviving rows keep their original labels packet*nsteps + ct."""
         rows, idx = self._host_rows()
+        if not self.nsteps:
+            # adaptive step: one final row per kept packet (frame_var_rows)
+            kept = np.zeros(self.npackets, dtype=bool)
+            kept[idx] = True
+            return frame_var_rows(rows, idx, self.X0, self._var_hs, kept)
         n, lengths = self.npackets, self._lengths
         starts = np.cumsum(lengths) - lengths
         labels = np.repeat(np.arange(n, dtype=np.int64)*self.nsteps - starts, lengths)
@@ -575,7 +615,10 @@ class Output:
         for out in outputs:
             out._ctx = ctx
             out._narrow_rows = bool(save)
-        if opt.step_size == 0:
+        if opt.step_size == 0 and all(out.compress for out in outputs):
+            print('Running variable step size integrator.')
+            cls._var_rows_pass(ctx, outputs)
+        elif opt.step_size == 0:
             print('Running variable step size integrator.')
             for out in outputs:
                 out.X = out.X0.drop(['longitude', 'latitude', 'local_time'], axis=1, errors='ignore')
@@ -608,6 +651,35 @@ class Output:
         if save:
             for out in outputs:
                 out.save()
+
+    @staticmethod
+    def _var_rows_pass(ctx, outputs):
+        """The adaptive-step driver over the packets of ``outputs``, one Output after the other,
+        with the finals left in HBM: one store of the rows save() keeps (fp64 frac > 0, one per
+        packet at most; float32 / int32 when the Outputs will be saved), a slice per Output.  Only
+        the stored steps come to the host (8 bytes a packet: the scratch they sit in is the next
+        launch's); ``X`` is framed from the rows on first access."""
+        lead = outputs[0]
+        opt = lead.inputs.options
+        for out in outputs:
+            assert out._bounce is None, 'Not set up'         # Output.py:312-315
+        ctx.set_forces(**lead.forces_kwargs())
+        ctx.set_bodies(None)
+        ctx.upload_soa(np.concatenate([out.x0_soa() for out in outputs], axis=1))
+        hs = ctx.integrate_var(float(opt.resolution), opt.outeredge, resident=True)
+        ctr = ctx.counters()
+        store, kept = ctx.var_rows_build(narrow=lead._narrow_rows, compress=True)
+        row0 = packet0 = 0
+        for out in outputs:
+            out._raise_on_counters(ctr)
+            assert ctr.get('unfinished', 0) == 0, 'variable-step integration did not finish'
+            mine = slice(packet0, packet0 + out.npackets)
+            out._var_hs = hs[mine].copy()
+            out._attach_rows(store, row0, kept[mine].astype(np.int64), packet0)
+            out._add_units()
+            row0 += out._nrows
+            packet0 += out.npackets
+        assert row0 == store.total and packet0 == len(hs)
 
     def _add_units(self):
         # Output.py:363-366,452-455: aplanet in au, vrplanet in km/s, GM in R^3/s^2
@@ -668,7 +740,13 @@ class Output:
                 rows = None
         else:
             rows = None
-        if rows is not None:
+        if rows is not None and not self.nsteps:
+            # adaptive step: the file keeps the whole frame (v, altitude, azimuth, step_size)
+            kept = np.zeros(self.npackets, dtype=bool)
+            kept[idx] = True
+            frame = frame_var_rows(rows, idx, self.X0, self._var_hs, kept)
+            data.update({f'X.{c}': frame[c].values for c in frame})
+        elif rows is not None:
             data['X.Index'] = idx
             data.update({f'X.{c}': rows[k] for k, c in enumerate(STATE_COLS)})
             data['X.lossfrac'] = rows[8]

@@ -390,6 +390,9 @@ struct nxc_handle {
     long long rows_total = -1;
     double rows_step = 0, rows_edge = 0;
     int64_t rows_n_iter = 0, rows_n = 0;
+    // adaptive-step rows (nxc_integrate_var_resident -> nxc_var_rows_build): the packets whose finals
+    // [8][n] and stored steps [n] sit in d_scratch, or -1
+    int64_t var_n = -1;
 
     bool have_bodies = false;
     nxc_bodies_desc bodies{};
@@ -541,6 +544,14 @@ int ensure(void **ptr, size_t *cap, size_t bytes)
     }
     *cap = bytes;
     return NXC_OK;
+}
+
+// The handle's generic scratch with room for `bytes`.  Whoever takes it overwrites the finals an
+// adaptive-step run may have left there (nxc_integrate_var_resident -> nxc_var_rows_build).
+int scratch_for(nxc_handle *h, size_t bytes)
+{
+    h->var_n = -1;
+    return ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, bytes);
 }
 
 // NXC_POOL_TRACE=1: every take / give that reaches the driver, with its duration, on stderr
@@ -938,7 +949,7 @@ int count_rows(nxc_handle *h, double step, int64_t n_iter, double outeredge, boo
     const size_t col = (size_t)n * sizeof(double);
     int rc;
     h->rows_total = -1;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, 8 * col))) return rc;
+    if ((rc = scratch_for(h, 8 * col))) return rc;
     if ((rc = ensure(reinterpret_cast<void **>(&h->d_steps), &h->steps_cap,
                      (size_t)n * sizeof(long long))))
         return rc;
@@ -1230,7 +1241,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
                  o_rad = take((size_t)S * 8), o_np = take((size_t)S * 8),
                  o_inc = take(included ? (size_t)n_index : 0),
                  o_used = take(used_pairs ? (size_t)used_cap * 16 : 0), o_nu = take(8);
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, off))) return rc;
+    if ((rc = scratch_for(h, off))) return rc;
     unsigned char *base = reinterpret_cast<unsigned char *>(h->d_scratch);
     // the used pairs go to the host copy (used_pairs) or stay on the device (nxc_los_set_pairs)
     nxc_pairs *const sink = used_pairs ? nullptr : h->los_pairs;
@@ -1762,6 +1773,136 @@ int fit_rows_run(nxc_handle *h, int compress, nxc_rows **out, int64_t *lengths_o
     return NXC_OK;
 }
 
+// The adaptive-step launch over the resident packets (nxc_integrate_var and its resident form):
+// finals [8][n] and stored steps [n] in the scratch, which is sized for `extra_bytes` more
+// (args_ok: what the caller found of its own arguments).
+int var_launch(nxc_handle *h, double resolution, double outeredge, int64_t max_steps,
+               bool args_ok, size_t extra_bytes, double **d_final_out, double **d_hs_out)
+{
+    int rc = need_forces(h);
+    if (rc) return rc;
+    const int64_t n = h->n_packets;
+    if (n < 1) return fail(NXC_ERR_STATE, "no resident packets (nxc_packets_upload)");
+    if (!(resolution > 0) || !args_ok || max_steps < 1) return fail(NXC_ERR_ARG, "bad arguments");
+    if (h->have_bodies)
+        return fail(NXC_ERR_STATE, "nxc_integrate_var: moons need the constant-step driver");
+    if (h->have_bounce)
+        return fail(NXC_ERR_STATE, "nxc_integrate_var: surface re-emission needs the constant-step "
+                                   "driver (nxc_set_bounce(h, NULL) for perfect sticking)");
+    const size_t col = (size_t)n * sizeof(double);
+    if ((rc = scratch_for(h, 9 * col + extra_bytes))) return rc;
+    double *d_final = h->d_scratch, *d_hs = d_final + 8 * n;
+    // the adaptive driver's queue: slow packets with much time left first (nxc_kernels.hpp:
+    // flight_key); once per resident set
+#ifdef NXC_VAR_TRACE      /* experiment: the packets as uploaded are the queue */
+    if (std::getenv("NXC_TEST_VAR_NO_ORDER")) { h->have_order = false; } else
+#endif
+    if (h->order_key != 2 && (rc = order_on_device(h, -1.0, nullptr, 0, true))) return rc;
+    HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
+    int grid = 1;
+    const bool full = h->F.grav && h->F.rad && h->F.loss == LOSS_PHOTO;
+    // Two launch forms of the same arithmetic (nxc_kernels.hpp: k_var), by packets per lane: under
+    // 24 (4.7e6 packets: the launch is mostly tail) with clock-rotated wave priorities and a merged
+    // tail, above it plain (highest throughput).
+    const double per_lane = (double)n / ((double)h->n_cu * BLOCK_PERSIST);
+    bool fair = per_lane < NXC_VAR_FAIR_PACKETS_PER_LANE;
+    if (const char *t = std::getenv("NXC_TEST_VAR_VARIANT"))          // tests: both forms at any size
+        fair = t[0] == 'f';                                           // "fair" / "plain"
+    int block = BLOCK_PERSIST;
+    const size_t lds = ((h->force_bytes + 31) & ~size_t(31)) + (size_t)(block / 64) * NXC_WAVE_LDS_BYTES;
+    auto launch = [&](auto kernel) -> int {
+        int rc2;
+        if ((rc2 = prep_kernel(kernel, lds))) return rc2;
+        if ((rc2 = persistent_grid(h, kernel, &block, lds, n, &grid))) return rc2;
+#ifdef NXC_VAR_ONE_WG_PER_CU          /* experiment: with -DNXC_BLOCK_PERSIST_N=512, two waves per SIMD */
+        if (grid > h->n_cu) grid = h->n_cu;
+#endif
+        if ((rc2 = begin_timed(h))) return rc2;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, h->stream, h->F, h->d_blob,
+                           (int64_t)h->force_bytes, n, h->have_order ? h->d_queue : h->d_packets,
+                           h->have_order ? h->d_order : (const unsigned *)nullptr, resolution, outeredge,
+                           (long long)max_steps, d_final, d_hs, h->d_ctr);
+        return NXC_OK;
+    };
+    if (fair) rc = full ? launch(k_var<true, true>) : launch(k_var<false, true>);
+    else rc = full ? launch(k_var<true, false>) : launch(k_var<false, false>);
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    if ((rc = end_timed(h))) return rc;
+    *d_final_out = d_final;
+    *d_hs_out = d_hs;
+    return NXC_OK;
+}
+
+// Behind the finals and steps in the scratch: what nxc_var_rows_build needs of it
+struct VarAux {
+    int64_t tiles;
+    size_t off_bytes, n_bytes, bytes;        // tile offsets [tiles] i64 | tile counts [tiles] u32 | kept [n] u8
+    explicit VarAux(int64_t n) : tiles((n + NXC_BLOCK - 1) / NXC_BLOCK)
+    {
+        off_bytes = (size_t)tiles * 8;
+        n_bytes = ((size_t)tiles * 4 + 7) & ~size_t(7);
+        bytes = off_bytes + n_bytes + (size_t)n;
+    }
+};
+
+template <typename T, typename I>
+int var_rows_run(nxc_handle *h, int compress, nxc_rows **out, uint8_t *kept_out)
+{
+    const int64_t n = h->var_n;
+    const VarAux aux(n);
+    const int64_t tiles = aux.tiles;
+    const double *fin = h->d_scratch;
+    unsigned char *base = reinterpret_cast<unsigned char *>(h->d_scratch + 9 * n);
+    long long *tile_off = reinterpret_cast<long long *>(base);
+    unsigned *tile_n = reinterpret_cast<unsigned *>(base + aux.off_bytes);
+    unsigned char *d_kept = base + aux.off_bytes + aux.n_bytes;
+    std::vector<unsigned> kept((size_t)tiles);
+    std::vector<long long> offs((size_t)tiles);
+    long long total = 0;
+    int rc;
+    if ((rc = begin_timed(h))) return rc;
+    if (compress) {
+        hipLaunchKernelGGL(k_var_rows_count, dim3((unsigned)tiles), dim3(NXC_BLOCK), 0, h->stream, n,
+                           fin + 7 * n, tile_n);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(kept.data(), tile_n, (size_t)tiles * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(stream_sync(h));
+        for (int64_t t = 0; t < tiles; t++) { offs[t] = total; total += kept[t]; }
+    } else {
+        for (int64_t t = 0; t < tiles; t++) offs[t] = (long long)t * NXC_BLOCK;
+        total = n;
+    }
+    nxc_rows *r = new (std::nothrow) nxc_rows();
+    if (!r) return fail(NXC_ERR_ARG, "out of host memory");
+    r->device = h->device; r->f32 = sizeof(T) == 4; r->total = total;
+    hipError_t e = hipSuccess;
+    if (total > 0) {
+        e = pool_take(h, (size_t)total * 9 * sizeof(T), &r->d_cols, &r->cols_cap);
+        if (e == hipSuccess) e = pool_take(h, (size_t)total * sizeof(I), &r->d_index, &r->index_cap);
+    }
+    // (nothing kept: the pass still runs, for kept_out; it writes no row)
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(tile_off, offs.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL((k_var_rows_write<T, I>), dim3((unsigned)tiles), dim3(NXC_BLOCK), 0, h->stream, n,
+                           compress, fin, tile_off, static_cast<T *>(r->d_cols), (int64_t)total,
+                           static_cast<I *>(r->d_index), d_kept);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
+    if (e == hipSuccess) h->timed = true;
+    if (e == hipSuccess && kept_out)
+        e = hipMemcpyAsync(kept_out, d_kept, (size_t)n, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = stream_sync(h);          // offs must outlive its copy; the store is final
+    if (e != hipSuccess) {
+        nxc_rows_free(h, r);
+        return fail_hip("adaptive-step rows", e);
+    }
+    *out = r;
+    return NXC_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -2241,7 +2382,7 @@ int nxc_state(nxc_handle *h, int64_t n, const double *x, const double *y, const 
     if (h->have_bodies) return fail(NXC_ERR_STATE, "nxc_state: not available with moons set");
     if (n == 0) return NXC_OK;
     const size_t bytes = (size_t)n * sizeof(double);
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, 8 * bytes)))
+    if ((rc = scratch_for(h, 8 * bytes)))
         return rc;
     double *d = h->d_scratch;
     const double *src[4] = {x, y, z, vy};
@@ -2270,7 +2411,7 @@ int nxc_rk5_step(nxc_handle *h, int64_t n, const double *soa_in, const double *h
     if (h->have_bodies) return fail(NXC_ERR_STATE, "nxc_rk5_step: not available with moons set");
     if (n == 0) return NXC_OK;
     const size_t col = (size_t)n * sizeof(double);
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, 25 * col)))
+    if ((rc = scratch_for(h, 25 * col)))
         return rc;
     double *d_in = h->d_scratch, *d_h = d_in + 8 * n, *d_out = d_h + n, *d_delta = d_out + 8 * n;
     HIPCHK(hipMemcpyAsync(d_in, soa_in, 8 * col, hipMemcpyHostToDevice, h->stream));
@@ -2387,6 +2528,7 @@ int nxc_packets_upload(nxc_handle *h, int64_t n, const double *soa0)
     if (rc) return rc;
     if (n) HIPCHK(hipMemcpyAsync(h->d_packets, soa0, bytes, hipMemcpyHostToDevice, h->stream));
     h->n_packets = n;
+    h->var_n = -1;
     h->first_id = 0;
     h->rows_total = -1;
     // Queue order for the persistent kernels (longest-lived first): counting sort of the packet
@@ -2419,6 +2561,7 @@ int nxc_packets_upload_pieces(nxc_handle *h, int32_t n_pieces, const int64_t *co
         at += counts[p];
     }
     h->n_packets = n;
+    h->var_n = -1;
     h->first_id = 0;
     h->rows_total = -1;
     if ((rc = order_on_device(h, -1.0, nullptr, 0))) return rc;
@@ -2506,6 +2649,7 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
                                  "almost everywhere zero?)");
     }
     h->n_packets = total;
+    h->var_n = -1;
     h->rows_total = -1;
     if (offset == 0) h->first_id = d->first_index;
     h->have_order = false;
@@ -2573,6 +2717,7 @@ int nxc_integrate_const_streamed(nxc_handle *h, int64_t n, const double *soa0, i
         if (!h->ev_piece[e]) HIPCHK(hipEventCreateWithFlags(&h->ev_piece[e], hipEventDisableTiming));
     unsigned long long *d_avail = h->d_piece_hist + 32 * per_piece;
     h->n_packets = n;
+    h->var_n = -1;
     h->first_id = 0;
     h->rows_total = -1;
     h->have_order = false;
@@ -2663,7 +2808,7 @@ int nxc_integrate_const(nxc_handle *h, double step, int64_t n_iter, double outer
     long long *d_steps = nullptr;
     if (!traj_out) {
         if (final_out) {
-            if ((rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, 8 * col)))
+            if ((rc = scratch_for(h, 8 * col)))
                 return rc;
             d_final = h->d_scratch;
         }
@@ -3375,62 +3520,50 @@ int nxc_integrate_var(nxc_handle *h, double resolution, double outeredge, int64_
                       double *final_out, double *hstore_out)
 {
     return guarded([&]() -> int {
-    int rc = need_forces(h);
+    double *d_final = nullptr, *d_hs = nullptr;
+    int rc = var_launch(h, resolution, outeredge, max_steps, final_out != nullptr, 0, &d_final, &d_hs);
     if (rc) return rc;
-    const int64_t n = h->n_packets;
-    if (n < 1) return fail(NXC_ERR_STATE, "no resident packets (nxc_packets_upload)");
-    if (!(resolution > 0) || !final_out || max_steps < 1) return fail(NXC_ERR_ARG, "bad arguments");
-    if (h->have_bodies)
-        return fail(NXC_ERR_STATE, "nxc_integrate_var: moons need the constant-step driver");
-    if (h->have_bounce)
-        return fail(NXC_ERR_STATE, "nxc_integrate_var: surface re-emission needs the constant-step "
-                                   "driver (nxc_set_bounce(h, NULL) for perfect sticking)");
-    const size_t col = (size_t)n * sizeof(double);
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, 9 * col)))
-        return rc;
-    double *d_final = h->d_scratch, *d_hs = d_final + 8 * n;
-    // the adaptive driver's queue: slow packets with much time left first (nxc_kernels.hpp:
-    // flight_key); once per resident set
-#ifdef NXC_VAR_TRACE      /* experiment: the packets as uploaded are the queue */
-    if (std::getenv("NXC_TEST_VAR_NO_ORDER")) { h->have_order = false; } else
-#endif
-    if (h->order_key != 2 && (rc = order_on_device(h, -1.0, nullptr, 0, true))) return rc;
-    HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
-    int grid = 1;
-    const bool full = h->F.grav && h->F.rad && h->F.loss == LOSS_PHOTO;
-    // Two launch forms of the same arithmetic (nxc_kernels.hpp: k_var), by packets per lane: under
-    // 24 (4.7e6 packets: the launch is mostly tail) with clock-rotated wave priorities and a merged
-    // tail, above it plain (highest throughput).
-    const double per_lane = (double)n / ((double)h->n_cu * BLOCK_PERSIST);
-    bool fair = per_lane < NXC_VAR_FAIR_PACKETS_PER_LANE;
-    if (const char *t = std::getenv("NXC_TEST_VAR_VARIANT"))          // tests: both forms at any size
-        fair = t[0] == 'f';                                           // "fair" / "plain"
-    int block = BLOCK_PERSIST;
-    const size_t lds = ((h->force_bytes + 31) & ~size_t(31)) + (size_t)(block / 64) * NXC_WAVE_LDS_BYTES;
-    auto launch = [&](auto kernel) -> int {
-        int rc2;
-        if ((rc2 = prep_kernel(kernel, lds))) return rc2;
-        if ((rc2 = persistent_grid(h, kernel, &block, lds, n, &grid))) return rc2;
-#ifdef NXC_VAR_ONE_WG_PER_CU          /* experiment: with -DNXC_BLOCK_PERSIST_N=512, two waves per SIMD */
-        if (grid > h->n_cu) grid = h->n_cu;
-#endif
-        if ((rc2 = begin_timed(h))) return rc2;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, h->stream, h->F, h->d_blob,
-                           (int64_t)h->force_bytes, n, h->have_order ? h->d_queue : h->d_packets,
-                           h->have_order ? h->d_order : (const unsigned *)nullptr, resolution, outeredge,
-                           (long long)max_steps, d_final, d_hs, h->d_ctr);
-        return NXC_OK;
-    };
-    if (fair) rc = full ? launch(k_var<true, true>) : launch(k_var<false, true>);
-    else rc = full ? launch(k_var<true, false>) : launch(k_var<false, false>);
-    if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    if ((rc = end_timed(h))) return rc;
+    const size_t col = (size_t)h->n_packets * sizeof(double);
     HIPCHK(hipMemcpyAsync(final_out, d_final, 8 * col, hipMemcpyDeviceToHost, h->stream));
     if (hstore_out)
         HIPCHK(hipMemcpyAsync(hstore_out, d_hs, col, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(stream_sync(h));
     return NXC_OK;
+    });
+}
+
+int nxc_integrate_var_resident(nxc_handle *h, double resolution, double outeredge, int64_t max_steps,
+                               double *hstore_out)
+{
+    return guarded([&]() -> int {
+    double *d_final = nullptr, *d_hs = nullptr;
+    const size_t extra = h && h->n_packets > 0 ? VarAux(h->n_packets).bytes : 0;
+    int rc = var_launch(h, resolution, outeredge, max_steps, true, extra, &d_final, &d_hs);
+    if (rc) return rc;
+    h->rows_total = -1;                      // a counted constant-step run's finals are gone
+    if (hstore_out)
+        HIPCHK(hipMemcpyAsync(hstore_out, d_hs, (size_t)h->n_packets * sizeof(double),
+                              hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    h->var_n = h->n_packets;
+    return NXC_OK;
+    });
+}
+
+int nxc_var_rows_build(nxc_handle *h, int narrow, int compress, nxc_rows **out, uint8_t *kept_out)
+{
+    return guarded([&]() -> int {
+    if (!out) return fail(NXC_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (!h) return fail(NXC_ERR_ARG, "null handle");
+    if (h->var_n < 1 || h->var_n != h->n_packets)
+        return fail(NXC_ERR_STATE, "nxc_var_rows_build needs a preceding nxc_integrate_var_resident "
+                                   "on the resident packets");
+    if (narrow && h->var_n > (int64_t)INT32_MAX)
+        return fail(NXC_ERR_ARG, "more packets than a 32-bit index column numbers");
+    HIPCHK(hipSetDevice(h->device));
+    if (narrow) return var_rows_run<float, int>(h, compress, out, kept_out);
+    return var_rows_run<double, long long>(h, compress, out, kept_out);
     });
 }
 
@@ -3688,7 +3821,7 @@ int nxc_shader_clock_mhz(nxc_handle *h, double *mhz)
     if (!h || !mhz) return fail(NXC_ERR_ARG, "bad arguments");
     HIPCHK(hipSetDevice(h->device));
     const int blocks = h->n_cu, waves = blocks * (BLOCK_PERSIST / 64);
-    int rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap,
+    int rc = scratch_for(h,
                     (size_t)waves * 3 * sizeof(unsigned long long));
     if (rc) return rc;
     unsigned long long *d = reinterpret_cast<unsigned long long *>(h->d_scratch);
@@ -3722,7 +3855,7 @@ int nxc_pcg64_uniforms(nxc_handle *h, const uint64_t state[2], const uint64_t in
     HIPCHK(hipSetDevice(h->device));
     const std::vector<u128> maps = pcg_tables(((u128)inc[0] << 64) | inc[1], n);
     const size_t map_bytes = maps.size() * sizeof(u128), out_bytes = (size_t)nvec * count * 8;
-    int rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, map_bytes + out_bytes);
+    int rc = scratch_for(h, map_bytes + out_bytes);
     if (rc) return rc;
     unsigned char *base = reinterpret_cast<unsigned char *>(h->d_scratch);
     HIPCHK(hipMemcpyAsync(base, maps.data(), map_bytes, hipMemcpyHostToDevice, h->stream));
@@ -3748,7 +3881,7 @@ int nxc_math_batch(nxc_handle *h, int which, int64_t n, const double *in, const 
     HIPCHK(hipSetDevice(h->device));
     if (n == 0) return NXC_OK;
     const size_t col = (size_t)n * sizeof(double);
-    int rc = ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, 3 * col);
+    int rc = scratch_for(h, 3 * col);
     if (rc) return rc;
     double *d = h->d_scratch;
     HIPCHK(hipMemcpyAsync(d, in, col, hipMemcpyHostToDevice, h->stream));

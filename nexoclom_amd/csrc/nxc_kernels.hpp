@@ -2915,6 +2915,61 @@ k_fit_rows_write(FitK F, const T *__restrict__ cols, int64_t in_stride, const I 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Row store of an adaptive-step run (nxc_var_rows_build): one row per kept packet, in packet
+// order, from the finals [8][n] fp64 that k_var left in the scratch.  A packet is kept when its
+// fp64 frac > 0 (save()'s filter on the 64-bit frame: NaN, +-0 and negative fracs go, a frac that
+// underflows in float32 stays), or always without `compress`.  Two streaming passes over tiles
+// of blockDim.x packets, one packet per lane: every load is a run of consecutive doubles per
+// wave, every store a run of consecutive elements from the wave's first kept row on.
+//
+// pass 1: rows kept per tile, from the waves' ballots (reads the frac column only)
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_var_rows_count(int64_t n, const double *__restrict__ frac, unsigned *__restrict__ tile_kept)
+{
+    __shared__ unsigned wave_kept[NXC_BLOCK / 64];
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool keep = r < n && frac[r] > 0.0;
+    const unsigned long long m = __ballot(keep);
+    if ((threadIdx.x & 63) == 0) wave_kept[threadIdx.x >> 6] = (unsigned)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned kept = 0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); w++) kept += wave_kept[w];
+        tile_kept[blockIdx.x] = kept;
+    }
+}
+
+// pass 2: the kept packets of a tile in their order, from the tile's offset on (offsets: exclusive
+// sums of pass 1's counts, or tile * blockDim.x without compress).  Columns [8][n] fp64 in ->
+// [9][out_stride] out (T: round to nearest even, overflow to inf -- astype(float32)); lossfrac is
+// 0 (the adaptive driver never accumulates it, Output.py:328-329); the index is the packet's
+// number.  kept[r] = 1 where packet r has a row.
+template <typename T, typename I>
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_var_rows_write(int64_t n, int compress, const double *__restrict__ fin,
+                 const long long *__restrict__ tile_off, T *__restrict__ out, int64_t out_stride,
+                 I *__restrict__ out_index, unsigned char *__restrict__ kept)
+{
+    __shared__ unsigned wave_kept[NXC_BLOCK / 64];
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const double f = r < n ? fin[7 * n + r] : 0.0;
+    const bool keep = r < n && (!compress || f > 0.0);
+    const unsigned long long m = __ballot(keep);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_kept[wave] = (unsigned)__popcll(m);
+    if (r < n) kept[r] = keep ? 1 : 0;
+    __syncthreads();
+    if (!keep) return;
+    long long at = tile_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; w++) at += wave_kept[w];
+#pragma unroll
+    for (int c = 0; c < 8; c++)
+        out[c * out_stride + at] = (T)(c == 7 ? f : fin[c * n + r]);
+    out[8 * out_stride + at] = (T)0;
+    out_index[at] = (I)r;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Source maps (data_simulation/make_source_map.py:11-174): per grid point p of an nlon x nlat
 // lon/lat grid, over the X0 packets q in its haversine ball (BallTree.query_radius):
 //   sin(0.5*(phi_p - phi_q))^2 + cos(phi_p)*cos(phi_q)*sin(0.5*(lam_p - lam_q))^2 <= thr_p,

@@ -41,7 +41,8 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_pairs_download', 'nxc_los_set_pairs', 'nxc_fit_set', 'nxc_fit_source_rows',
            'nxc_fit_source', 'nxc_fit_source_f32', 'nxc_fit_packets', 'nxc_fit_radiance',
            'nxc_fit_rows', 'nxc_fit_download', 'nxc_source_map_set', 'nxc_source_map_accumulate',
-           'nxc_source_map_download', 'nxc_set_stick_map')
+           'nxc_source_map_download', 'nxc_set_stick_map', 'nxc_integrate_var_resident',
+           'nxc_var_rows_build')
 ABI_VERSION = 3
 
 
@@ -683,14 +684,36 @@ class Context:
             C.c_int64(n_iter), C.c_double(outeredge), C.c_uint32(NXC_RUN_IMAGE if image else 0)))
         self.n_packets = soa.shape[1]
 
-    def integrate_var(self, resolution, outeredge, max_steps=10**6):
+    def integrate_var(self, resolution, outeredge, max_steps=10**6, resident=False):
+        """Adaptive-step driver over the resident packets: (final (N, 8), stored step (N,)).
+        resident=True leaves the finals in HBM for ``var_rows_build`` and returns the steps only."""
         n = self.n_packets
-        final = np.empty((8, n))
         hs = np.empty(n)
+        if resident:
+            self._check(self.lib.nxc_integrate_var_resident(
+                self._h, C.c_double(resolution), C.c_double(outeredge), C.c_int64(max_steps),
+                _p(hs)))
+            return hs
+        final = np.empty((8, n))
         self._check(self.lib.nxc_integrate_var(self._h, C.c_double(resolution),
                                                C.c_double(outeredge), C.c_int64(max_steps),
                                                _p(final), _p(hs)))
         return np.ascontiguousarray(final.T), hs
+
+    def var_rows_build(self, narrow=False, compress=True):
+        """The row store of the last ``integrate_var(resident=True)``: one row per kept packet
+        (compress: fp64 frac > 0; else all), float32 / int32 when narrow.  Returns (RowStore,
+        kept (N,) bool)."""
+        n = self.n_packets
+        self.make_room(n * 10 * (4 if narrow else 8))
+        handle = C.c_void_p()
+        kept = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.nxc_var_rows_build(
+            self._h, C.c_int(int(bool(narrow))), C.c_int(int(bool(compress))), C.byref(handle),
+            kept.ctypes.data_as(C.POINTER(C.c_uint8))))
+        store = RowStore(self, handle)
+        self._stores.append(weakref.ref(store))
+        return store, kept.view(np.bool_)
 
     # -- stored samples: host columns or a RowStore's rows ----------------------------------
     @staticmethod
