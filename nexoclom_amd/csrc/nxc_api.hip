@@ -20,6 +20,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/nexoclom_hip.h"
@@ -435,7 +436,7 @@ struct nxc_handle {
     size_t fit_pk_cap = 0;
     unsigned char *d_fit_smp = nullptr;  // host columns of the fit on the device
     size_t fit_smp_cap = 0;
-    unsigned char *d_fit_aux = nullptr;  // blob | counters | tile counts and offsets
+    unsigned char *d_fit_aux = nullptr;  // blob | counters, or nxc_fit_rows' tile scratch
     size_t fit_aux_cap = 0;
 
     // source maps (nxc_source_map_*): the grid and tile segments, the resident map and unsmeared
@@ -724,39 +725,6 @@ int prep_kernel(K kernel, size_t lds_bytes)
     return NXC_OK;
 }
 
-// Grid of a persistent kernel: one resident block per CU slot.  When there are fewer packets than
-// lanes (one reference-sized chunk of 80 467 packets against 196 608 lanes), the packets are
-// spread over ALL CUs with fewer waves per block instead of filling a few CUs three waves deep: a
-// packet's steps run one after the other, and a wave that has its SIMD to itself takes them
-// faster.  *block comes back as the number of threads to launch per block (a multiple of 64).
-template <class K>
-int persistent_grid(nxc_handle *h, K kernel, int *block, size_t lds_bytes, int64_t n, int *grid)
-{
-    int per_cu = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, *block, lds_bytes));
-    if (per_cu < 1) per_cu = 1;
-    int64_t g = (int64_t)h->n_cu * per_cu;
-    const int64_t waves = (n + 63) / 64;
-    if (waves < g * (*block / 64)) {
-        int64_t per_block = (waves + g - 1) / g;
-        if (per_block < 1) per_block = 1;
-        *block = (int)per_block * 64;
-        g = (waves + per_block - 1) / per_block;
-    }
-    if (g < 1) g = 1;
-    *grid = (int)g;
-    return NXC_OK;
-}
-
-int flat_grid(nxc_handle *h, int64_t n, int block)
-{
-    int64_t g = (n + block - 1) / block;
-    const int64_t cap = (int64_t)h->n_cu * 8;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 int begin_timed(nxc_handle *h)
 {
     HIPCHK(hipEventRecord(h->ev0, h->stream));
@@ -769,17 +737,47 @@ int end_timed(nxc_handle *h)
     return NXC_OK;
 }
 
+// In front of a persistent kernel's launch: its LDS limit is raised, its grid is formed, and the
+// timing that end_timed() closes after the launch is started.  The grid: one resident block per CU slot.  When there are fewer packets than
+// lanes (one reference-sized chunk of 80 467 packets against 196 608 lanes), the packets are
+// spread over ALL CUs with fewer waves per block instead of filling a few CUs three waves deep: a
+// packet's steps run one after the other, and a wave that has its SIMD to itself takes them
+// faster.  *block comes back as the number of threads to launch per block (a multiple of 64).
+template <class K>
+int prepare_persistent_launch(nxc_handle *h, K kernel, int *block, size_t lds_bytes, int64_t n, int *grid)
+{
+    int per_cu = 0, rc;
+    if ((rc = prep_kernel(kernel, lds_bytes))) return rc;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, *block, lds_bytes));
+    if (per_cu < 1) per_cu = 1;
+    int64_t g = (int64_t)h->n_cu * per_cu;
+    const int64_t waves = (n + 63) / 64;
+    if (waves < g * (*block / 64)) {
+        int64_t per_block = (waves + g - 1) / g;
+        if (per_block < 1) per_block = 1;
+        *block = (int)per_block * 64;
+        g = (waves + per_block - 1) / per_block;
+    }
+    if (g < 1) g = 1;
+    *grid = (int)g;
+    return begin_timed(h);
+}
+
+int flat_grid(nxc_handle *h, int64_t n, int block)
+{
+    int64_t g = (n + block - 1) / block;
+    const int64_t cap = (int64_t)h->n_cu * 8;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
 int need_forces(nxc_handle *h)
 {
     if (!h) return fail(NXC_ERR_ARG, "null handle");
     if (!h->have_forces) return fail(NXC_ERR_STATE, "nxc_set_forces has not been called");
     HIPCHK(hipSetDevice(h->device));
     return NXC_OK;
-}
-
-size_t persist_lds(size_t table_bytes)
-{
-    return ((table_bytes + 31) & ~size_t(31)) + (size_t)(BLOCK_PERSIST / 64) * NXC_WAVE_LDS_BYTES;
 }
 
 // Per-step base phases of the moons, (cos, sin)(phi - omega (t0 - k h)), and the per-stage rotations
@@ -820,16 +818,16 @@ int upload_moon_table(nxc_handle *h, double step, int64_t n_iter)
     return NXC_OK;
 }
 
-// What one launch of the persistent integrator works on: the resident set (default) or a piece of
-// it with its own queue copy, counters (the queue head lives there) and stream.
+// What one launch of the persistent integrator works on besides the handle's resident set: the
+// packets in the order they are taken, and where the per-packet results go.
 struct FusedJob {
     const double *soa = nullptr;
     const unsigned *order = nullptr;
-    int64_t n = 0, first_id = 0;
-    DevCounters *ctr = nullptr;
-    hipStream_t stream = nullptr;
-    bool timed = true;
     const unsigned long long *avail = nullptr;   // streamed upload: positions published so far
+    double *final = nullptr;                     // per-packet outputs: final states [8][n] ...
+    long long *steps = nullptr;                  // ... and steps taken [n]
+    const long long *offsets = nullptr;          // rows pass: every packet's first row [n + 1] ...
+    void *rec = nullptr;                         // ... of the record buffer
 };
 
 FusedJob whole_set(nxc_handle *h)
@@ -837,47 +835,47 @@ FusedJob whole_set(nxc_handle *h)
     FusedJob j;
     j.soa = h->have_order ? h->d_queue : h->d_packets;
     j.order = h->have_order ? h->d_order : nullptr;
-    j.n = h->n_packets; j.first_id = h->first_id; j.ctr = h->d_ctr; j.stream = h->stream;
     return j;
 }
 
-template <int IMAGE, bool BOUNCE, bool FULL = false, bool NBODY = false, bool STREAMED = false>
-int launch_fused(nxc_handle *h, size_t tables, size_t lds, int64_t n_iter, double edge2,
-                 double *d_final, long long *d_steps, const FusedJob &job)
+// Every instantiation of k_const_fused that exists, at its variant's code: the template arguments
+// are decode()'s, what exists is valid()'s (nxc_fused_variant.hpp).
+using FusedKernel = decltype(&k_const_fused<0, false, false>);
+
+template <int CODE>
+constexpr FusedKernel fused_kernel()
 {
-    int grid = 1, block = BLOCK_PERSIST, rc;
-    auto kernel = k_const_fused<IMAGE, BOUNCE, FULL, NBODY, 0, STREAMED>;
-    if ((rc = prep_kernel(kernel, lds))) return rc;
-    if ((rc = persistent_grid(h, kernel, &block, lds, job.n, &grid))) return rc;
-    if (job.timed && (rc = begin_timed(h))) return rc;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, job.stream, h->F, h->d_blob,
-                       (int64_t)tables, job.n, job.soa, job.order, job.first_id, n_iter,
-                       edge2, d_final, d_steps, IMAGE ? h->d_image : (double *)nullptr, job.ctr,
-                       NBODY ? h->d_moonpos : (const double *)nullptr, (const long long *)nullptr,
-                       (void *)nullptr, job.avail);
-    HIPCHK(hipGetLastError());
-    return job.timed ? end_timed(h) : NXC_OK;
+    constexpr FusedVariant v = decode(CODE);
+    if constexpr (valid(v)) return k_const_fused<v.image, v.bounce, v.full, v.nbody, v.rows, v.streamed>;
+    else return nullptr;
 }
 
-// The kernel variant for the handle's force model / re-emission / moons.  Image: 1 = samples
-// binned as they are (64-bit), 2 = binned as the float32 values save() stores (nxc_image_desc.
-// downcast_f32): the frame test comes before the compaction queue, everything else after it.
-int pick_fused(nxc_handle *h, size_t tables, size_t lds, int64_t n_iter, double edge2, bool image,
-               double *d_final, long long *d_steps, const FusedJob &job)
+template <int... CODE>
+FusedKernel fused_kernel(int code, std::integer_sequence<int, CODE...>)
 {
-    const int img = image ? (h->G.downcast_f32 ? 2 : 1) : 0;
-#define NXC_FUSED(...)                                                                              \
-    (img == 2 ? launch_fused<2, __VA_ARGS__>(h, tables, lds, n_iter, edge2, d_final, d_steps, job)  \
-     : img == 1 ? launch_fused<1, __VA_ARGS__>(h, tables, lds, n_iter, edge2, d_final, d_steps, job) \
-                : launch_fused<0, __VA_ARGS__>(h, tables, lds, n_iter, edge2, d_final, d_steps, job))
-    // gravity + radiation pressure + photo-loss: the compile-time specialisation of the force model
-    const bool full = h->F.grav && h->F.rad && h->F.loss == LOSS_PHOTO;
-    if (job.avail)          // streamed upload: the plain force models only (checked by the caller)
-        return full ? NXC_FUSED(false, true, false, true) : NXC_FUSED(false, false, false, true);
-    if (h->have_bodies) return full ? NXC_FUSED(false, true, true) : NXC_FUSED(false, false, true);
-    if (h->have_bounce) return NXC_FUSED(true, false);
-    return full ? NXC_FUSED(false, true) : NXC_FUSED(false, false);
-#undef NXC_FUSED
+    static const FusedKernel table[] = {fused_kernel<CODE>()...};
+    return table[code];
+}
+
+// The one launch of k_const_fused, over `job`: the variant for the handle's force model, moons or
+// re-emission and this call (image: binned; rows: 0 none, 1 wide, 2 narrow records).
+int launch_fused(nxc_handle *h, bool image, int rows, int64_t n_iter, double outeredge, const FusedJob &job)
+{
+    const FusedVariant v = pick_variant(h->F.grav != 0, h->F.rad != 0, h->F.loss == LOSS_PHOTO, h->have_bodies,
+                                        h->have_bounce, image, h->G.downcast_f32 != 0, rows, job.avail != nullptr);
+    const FusedKernel kernel =
+        valid(v) ? fused_kernel(encode(v), std::make_integer_sequence<int, NXC_FUSED_CODES>()) : nullptr;
+    if (!kernel) return fail(NXC_ERR_STATE, "no constant-step kernel for this combination of passes");
+    const size_t tables = v.image ? h->all_bytes : h->force_bytes, lds = persist_lds(tables, v);
+    int grid = 1, block = BLOCK_PERSIST, rc;
+    if ((rc = prepare_persistent_launch(h, kernel, &block, lds, h->n_packets, &grid))) return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, h->stream, h->F, h->d_blob,
+                       (int64_t)tables, h->n_packets, job.soa, job.order, h->first_id, n_iter,
+                       sqrt_threshold(outeredge), job.final, job.steps,
+                       v.image ? h->d_image : (double *)nullptr, h->d_ctr,
+                       v.nbody ? h->d_moonpos : (const double *)nullptr, job.offsets, job.rec, job.avail);
+    HIPCHK(hipGetLastError());
+    return end_timed(h);
 }
 
 // The constant-step kernels want the fastest (longest-lived) packets first: a resident set that the
@@ -888,55 +886,28 @@ int speed_order_for_const(nxc_handle *h)
     return order_on_device(h, -1.0, nullptr, 0);
 }
 
-// Sticking law 2 reads the map at every impact: no launch without one.
-int need_stick_map(nxc_handle *h)
+// In front of a constant-step launch over the resident packets: what cannot run is refused before
+// anything is touched (sticking law 2 reads the map at every impact: no launch without one), then
+// the step weights, the zeroed counters and the moons' phases.
+int const_preamble(nxc_handle *h, double step, int64_t n_iter)
 {
+    if (h->have_bodies && h->have_bounce)
+        return fail(NXC_ERR_STATE, "surface re-emission is not available with moons set");
     if (h->have_bounce && h->header.B.temp_dependent == 2 && !h->have_stick_map)
         return fail(NXC_ERR_STATE, "the bounce description asks for sticking from a surface map "
                                    "(temp_dependent = 2) and no map is set (nxc_set_stick_map)");
-    return NXC_OK;
+    if (int rc = upload_step(h, step)) return rc;
+    HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
+    return h->have_bodies ? upload_moon_table(h, step, n_iter) : NXC_OK;
 }
 
 int launch_const(nxc_handle *h, double step, int64_t n_iter, double outeredge, bool image,
                  double *d_final, long long *d_steps)
 {
-    const size_t tables = image ? h->all_bytes : h->force_bytes;
-    const size_t lds = persist_lds(tables);
-    int rc;
-    if ((rc = upload_step(h, step))) return rc;
-    HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
-    const double edge2 = sqrt_threshold(outeredge);
-    if (h->have_bodies) {
-        if (h->have_bounce)
-            return fail(NXC_ERR_STATE, "surface re-emission is not available with moons set");
-        if ((rc = upload_moon_table(h, step, n_iter))) return rc;
-    }
-    if ((rc = need_stick_map(h))) return rc;
-    return pick_fused(h, tables, lds, n_iter, edge2, image, d_final, d_steps, whole_set(h));
-}
-
-size_t persist_lds_rows(size_t table_bytes)
-{
-    return ((table_bytes + 31) & ~size_t(31)) + (size_t)(BLOCK_PERSIST / 64) * NXC_WAVE_LDS_BYTES_ROWS;
-}
-
-template <bool BOUNCE, bool FULL, bool NBODY, int ROWS>
-int launch_rows(nxc_handle *h, int64_t n_iter, double edge2, void *d_rec)
-{
-    int grid = 1, block = BLOCK_PERSIST, rc;
-    auto kernel = k_const_fused<0, BOUNCE, FULL, NBODY, ROWS>;
-    const size_t tables = h->force_bytes, lds = persist_lds_rows(tables);
-    if ((rc = prep_kernel(kernel, lds))) return rc;
-    if ((rc = persistent_grid(h, kernel, &block, lds, h->n_packets, &grid))) return rc;
-    if ((rc = begin_timed(h))) return rc;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, h->stream, h->F, h->d_blob,
-                       (int64_t)tables, h->n_packets, h->have_order ? h->d_queue : h->d_packets,
-                       h->have_order ? h->d_order : (const unsigned *)nullptr, h->first_id, n_iter,
-                       edge2, (double *)nullptr, (long long *)nullptr, (double *)nullptr, h->d_ctr,
-                       NBODY ? h->d_moonpos : (const double *)nullptr,
-                       (const long long *)h->d_offsets, d_rec, (const unsigned long long *)nullptr);
-    HIPCHK(hipGetLastError());
-    return end_timed(h);
+    if (int rc = const_preamble(h, step, n_iter)) return rc;
+    FusedJob job = whole_set(h);
+    job.final = d_final; job.steps = d_steps;
+    return launch_fused(h, image, 0, n_iter, outeredge, job);
 }
 
 // Pass 1 of every trajectory-producing run: the persistent integrator (optionally binning the
@@ -1011,24 +982,10 @@ int write_records(nxc_handle *h, bool narrow, size_t reserve)
     const size_t roomy = bytes + bytes / 8;
     const bool slack = grow && roomy + reserve <= free_b + back;
     if ((rc = ensure(&h->d_rec, &h->rec_cap, slack ? roomy : bytes))) return rc;
-    if (h->have_bodies) {
-        if (h->have_bounce)
-            return fail(NXC_ERR_STATE, "surface re-emission is not available with moons set");
-        if ((rc = upload_moon_table(h, h->rows_step, h->rows_n_iter))) return rc;
-    }
-    if ((rc = need_stick_map(h))) return rc;
-    if ((rc = upload_step(h, h->rows_step))) return rc;
-    HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
-    const double edge2 = sqrt_threshold(h->rows_edge);
-    const int64_t n_iter = h->rows_n_iter;
-    const bool full = h->F.grav && h->F.rad && h->F.loss == LOSS_PHOTO;
-#define NXC_ROWS_CASE(B, F, N)                                                                  \
-    (narrow ? launch_rows<B, F, N, 2>(h, n_iter, edge2, h->d_rec)                               \
-            : launch_rows<B, F, N, 1>(h, n_iter, edge2, h->d_rec))
-    if (h->have_bodies) return full ? NXC_ROWS_CASE(false, true, true) : NXC_ROWS_CASE(false, false, true);
-    if (h->have_bounce) return NXC_ROWS_CASE(true, false, false);
-    return full ? NXC_ROWS_CASE(false, true, false) : NXC_ROWS_CASE(false, false, false);
-#undef NXC_ROWS_CASE
+    if ((rc = const_preamble(h, h->rows_step, h->rows_n_iter))) return rc;
+    FusedJob job = whole_set(h);
+    job.offsets = h->d_offsets; job.rec = h->d_rec;
+    return launch_fused(h, false, narrow ? 2 : 1, h->rows_n_iter, h->rows_edge, job);
 }
 
 template <typename T, typename I>
@@ -1043,35 +1000,48 @@ int transpose_rows(nxc_handle *h, const void *d_rec, long long total, void *d_co
     return NXC_OK;
 }
 
+// A new store of `total` rows, its two blocks from the pool (a store without rows has none).
+// `what`: the producer, for the report of a failed allocation, which leaves nothing behind.
+int new_rows(nxc_handle *h, long long total, bool f32, nxc_rows **out, const char *what)
+{
+    *out = nullptr;
+    nxc_rows *r = new (std::nothrow) nxc_rows();
+    if (!r) return fail(NXC_ERR_ARG, "out of host memory");
+    r->device = h->device; r->f32 = f32; r->total = total;
+    hipError_t e = hipSuccess;
+    if (total > 0) {
+        const size_t vsz = f32 ? 4 : 8;          // values, and the index column beside them
+        e = pool_take(h, (size_t)total * 9 * vsz, &r->d_cols, &r->cols_cap);
+        if (e == hipSuccess) e = pool_take(h, (size_t)total * vsz, &r->d_index, &r->index_cap);
+    }
+    if (e != hipSuccess) {
+        nxc_rows_free(h, r);
+        return fail_hip(what, e);
+    }
+    *out = r;
+    return NXC_OK;
+}
+
 // Passes 1 -> 2 -> columns: the device-resident row store of the run counted last.
 int rows_build(nxc_handle *h, bool narrow, nxc_rows **out)
 {
     *out = nullptr;
     if (!h) return fail(NXC_ERR_ARG, "null handle");
     const long long total = h->rows_total;
-    const size_t vsz = narrow ? sizeof(float) : sizeof(double), isz = narrow ? sizeof(int) : sizeof(long long);
-    const size_t cols_bytes = (size_t)(total > 0 ? total : 0) * 9 * vsz;
-    const size_t idx_bytes = (size_t)(total > 0 ? total : 0) * isz;
-    int rc = write_records(h, narrow, cols_bytes + idx_bytes);
+    const size_t store_bytes = (size_t)(total > 0 ? total : 0) * 10 * (narrow ? 4 : 8);
+    int rc = write_records(h, narrow, store_bytes);
     if (rc) return rc;
     h->rows_total = -1;
-    nxc_rows *r = new (std::nothrow) nxc_rows();
-    if (!r) return fail(NXC_ERR_ARG, "out of host memory");
-    r->device = h->device; r->f32 = narrow; r->total = total;
-    hipError_t e = hipSuccess;
+    nxc_rows *r = nullptr;
+    if ((rc = new_rows(h, total, narrow, &r, "rows run"))) return rc;
     if (total > 0) {
-        e = pool_take(h, cols_bytes, &r->d_cols, &r->cols_cap);
-        if (e == hipSuccess) e = pool_take(h, idx_bytes, &r->d_index, &r->index_cap);
-        if (e == hipSuccess)
-            rc = narrow ? transpose_rows<float, int>(h, h->d_rec, total, r->d_cols, r->d_index)
-                        : transpose_rows<double, long long>(h, h->d_rec, total, r->d_cols, r->d_index);
-        if (e == hipSuccess && !rc) e = stream_sync(h);
-    }
-    if (e != hipSuccess || rc) {
-        if (r->d_cols) (void)hipFree(r->d_cols);
-        if (r->d_index) (void)hipFree(r->d_index);
-        delete r;
-        return rc ? rc : fail_hip("rows run", e);
+        rc = narrow ? transpose_rows<float, int>(h, h->d_rec, total, r->d_cols, r->d_index)
+                    : transpose_rows<double, long long>(h, h->d_rec, total, r->d_cols, r->d_index);
+        const hipError_t e = rc ? hipSuccess : stream_sync(h);
+        if (rc || e != hipSuccess) {
+            nxc_rows_free(h, r);
+            return rc ? rc : fail_hip("rows run", e);
+        }
     }
     *out = r;
     return NXC_OK;
@@ -1630,18 +1600,14 @@ FitK fit_consts(const nxc_handle *h, const nxc_pairs *p, int64_t n_packets)
     return F;
 }
 
-// device scratch of the fit's small buffers: [blob | 4 counters | tile counts | tile offsets]
-int fit_aux(nxc_handle *h, size_t blob_bytes, int64_t tiles, unsigned char **blob,
-            unsigned long long **ctr, unsigned **tile_n, long long **tile_off)
+// device scratch of the fit's small buffers: [blob | 4 counters]
+int fit_aux(nxc_handle *h, size_t blob_bytes, unsigned char **blob, unsigned long long **ctr)
 {
-    const size_t o_ctr = (blob_bytes + 255) & ~size_t(255), o_n = o_ctr + 256,
-                 o_off = o_n + (((size_t)tiles * 4 + 255) & ~size_t(255));
-    int rc = ensure(reinterpret_cast<void **>(&h->d_fit_aux), &h->fit_aux_cap, o_off + (size_t)tiles * 8 + 8);
+    const size_t o_ctr = (blob_bytes + 255) & ~size_t(255);
+    int rc = ensure(reinterpret_cast<void **>(&h->d_fit_aux), &h->fit_aux_cap, o_ctr + 256);
     if (rc) return rc;
     *blob = h->d_fit_aux;
     *ctr = reinterpret_cast<unsigned long long *>(h->d_fit_aux + o_ctr);
-    if (tile_n) *tile_n = reinterpret_cast<unsigned *>(h->d_fit_aux + o_n);
-    if (tile_off) *tile_off = reinterpret_cast<long long *>(h->d_fit_aux + o_off);
     return NXC_OK;
 }
 
@@ -1716,60 +1682,73 @@ int fit_radiance_run(nxc_handle *h, const nxc_pairs *p, const LosK &K, size_t st
     return NXC_OK;
 }
 
+// Stable compaction of n rows in tiles of NXC_BLOCK: the tiles, and the bytes of its device
+// scratch [tile offsets (i64) | tile counts (u32)]
+int64_t row_tiles(int64_t n) { return (n + NXC_BLOCK - 1) / NXC_BLOCK; }
+size_t tile_scratch_bytes(int64_t n) { return ((size_t)row_tiles(n) * 12 + 7) & ~size_t(7); }
+
+// The kept rows of n, in their order, in a new, finished store (`what`: its producer, for failures).
+// (*count)(tile counts) launches the pass that counts every tile's kept rows; without one all n
+// rows are kept.  The exclusive sums are formed here; write(tile offsets, store) launches the pass
+// that places the rows, and whatever the producer wants behind it on the stream, which is waited for.
+template <class Count, class Write>
+int compact_rows(nxc_handle *h, int64_t n, bool f32, void *d_scratch, const Count *count, Write write,
+                 nxc_rows **out, const char *what)
+{
+    const int64_t tiles = row_tiles(n);
+    long long *tile_off = static_cast<long long *>(d_scratch), total = count ? 0 : n;
+    unsigned *tile_n = reinterpret_cast<unsigned *>(tile_off + tiles);
+    std::vector<long long> offs((size_t)tiles);
+    for (int64_t t = 0; t < tiles; t++) offs[(size_t)t] = (long long)t * NXC_BLOCK;
+    if (count && tiles) {
+        std::vector<unsigned> kept((size_t)tiles);
+        (*count)(tile_n);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(kept.data(), tile_n, (size_t)tiles * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(stream_sync(h));
+        for (int64_t t = 0; t < tiles; t++) { offs[(size_t)t] = total; total += kept[(size_t)t]; }
+    }
+    if (int rc = new_rows(h, total, f32, out, what)) return rc;
+    hipError_t e = hipSuccess;
+    if (tiles) e = hipMemcpyAsync(tile_off, offs.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, h->stream);
+    if (tiles && e == hipSuccess) e = write(tile_off, *out);
+    if (e == hipSuccess) e = stream_sync(h);          // offs must outlive its copy; the store is final
+    if (e != hipSuccess) {
+        nxc_rows_free(h, *out);
+        *out = nullptr;
+        return fail_hip(what, e);
+    }
+    return NXC_OK;
+}
+
 template <typename T, typename I>
 int fit_rows_run(nxc_handle *h, int compress, nxc_rows **out, int64_t *lengths_out)
 {
     const Samples &s = h->fit_src;
-    const int64_t n = s.n, np = h->fit_np, tiles = (n + NXC_BLOCK - 1) / NXC_BLOCK;
+    const int64_t n = s.n, np = h->fit_np;
+    const unsigned tiles = (unsigned)row_tiles(n);
     FitK F = fit_consts(h, nullptr, np);
     F.compress = compress ? 1 : 0;
-    unsigned char *blob;
-    unsigned long long *ctr;
-    unsigned *tile_n;
-    long long *tile_off;
-    int rc = fit_aux(h, 0, tiles, &blob, &ctr, &tile_n, &tile_off);
+    int rc = ensure(reinterpret_cast<void **>(&h->d_fit_aux), &h->fit_aux_cap, tile_scratch_bytes(n));
     if (rc) return rc;
-    const T *frac = s.col<T>(4);
     const I *index = s.idx<I>();
     if (np) HIPCHK(hipMemsetAsync(fit_len(h, np), 0, (size_t)np * 4, h->stream));
-    std::vector<unsigned> kept((size_t)tiles);
-    std::vector<long long> offs((size_t)tiles);
-    long long total = 0;
-    if (tiles) {
-        hipLaunchKernelGGL((k_fit_rows_count<T, I>), dim3((unsigned)tiles), dim3(NXC_BLOCK), 0, h->stream, F,
-                           frac, index, fit_mult(h, np), tile_n, fit_len(h, np));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(kept.data(), tile_n, (size_t)tiles * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(stream_sync(h));
-        for (int64_t t = 0; t < tiles; t++) { offs[t] = total; total += kept[t]; }
-    }
-    nxc_rows *r = new (std::nothrow) nxc_rows();
-    if (!r) return fail(NXC_ERR_ARG, "out of host memory");
-    r->device = h->device; r->f32 = sizeof(T) == 4; r->total = total;
-    hipError_t e = hipSuccess;
-    if (total > 0) {
-        e = pool_take(h, (size_t)total * 9 * sizeof(T), &r->d_cols, &r->cols_cap);
-        if (e == hipSuccess) e = pool_take(h, (size_t)total * sizeof(I), &r->d_index, &r->index_cap);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(tile_off, offs.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL((k_fit_rows_write<T, I>), dim3((unsigned)tiles), dim3(NXC_BLOCK), 0, h->stream, F,
-                               static_cast<const T *>(s.col0), s.stride, index, fit_mult(h, np), tile_off,
-                               static_cast<T *>(r->d_cols), (int64_t)total, static_cast<I *>(r->d_index));
-            e = hipGetLastError();
-        }
-    }
     std::vector<unsigned> len((size_t)np);
-    if (e == hipSuccess && np)
-        e = hipMemcpyAsync(len.data(), fit_len(h, np), (size_t)np * 4, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = stream_sync(h);
-    if (e != hipSuccess) {
-        nxc_rows_free(h, r);
-        return fail_hip("fitted rows", e);
-    }
+    auto count = [&](unsigned *tile_n) {
+        hipLaunchKernelGGL((k_fit_rows_count<T, I>), dim3(tiles), dim3(NXC_BLOCK), 0, h->stream, F,
+                           s.col<T>(4), index, fit_mult(h, np), tile_n, fit_len(h, np));
+    };
+    auto write = [&](const long long *tile_off, nxc_rows *r) {
+        hipLaunchKernelGGL((k_fit_rows_write<T, I>), dim3(tiles), dim3(NXC_BLOCK), 0, h->stream, F,
+                           static_cast<const T *>(s.col0), s.stride, index, fit_mult(h, np), tile_off,
+                           static_cast<T *>(r->d_cols), (int64_t)r->total, static_cast<I *>(r->d_index));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess || !np) return e;
+        return hipMemcpyAsync(len.data(), fit_len(h, np), (size_t)np * 4, hipMemcpyDeviceToHost, h->stream);
+    };
+    if ((rc = compact_rows(h, n, sizeof(T) == 4, h->d_fit_aux, &count, write, out, "fitted rows"))) return rc;
     if (lengths_out)
         for (int64_t i = 0; i < np; i++) lengths_out[i] = len[i];
-    *out = r;
     return NXC_OK;
 }
 
@@ -1799,7 +1778,6 @@ int var_launch(nxc_handle *h, double resolution, double outeredge, int64_t max_s
 #endif
     if (h->order_key != 2 && (rc = order_on_device(h, -1.0, nullptr, 0, true))) return rc;
     HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
-    int grid = 1;
     const bool full = h->F.grav && h->F.rad && h->F.loss == LOSS_PHOTO;
     // Two launch forms of the same arithmetic (nxc_kernels.hpp: k_var), by packets per lane: under
     // 24 (4.7e6 packets: the launch is mostly tail) with clock-rotated wave priorities and a merged
@@ -1808,25 +1786,18 @@ int var_launch(nxc_handle *h, double resolution, double outeredge, int64_t max_s
     bool fair = per_lane < NXC_VAR_FAIR_PACKETS_PER_LANE;
     if (const char *t = std::getenv("NXC_TEST_VAR_VARIANT"))          // tests: both forms at any size
         fair = t[0] == 'f';                                           // "fair" / "plain"
-    int block = BLOCK_PERSIST;
-    const size_t lds = ((h->force_bytes + 31) & ~size_t(31)) + (size_t)(block / 64) * NXC_WAVE_LDS_BYTES;
-    auto launch = [&](auto kernel) -> int {
-        int rc2;
-        if ((rc2 = prep_kernel(kernel, lds))) return rc2;
-        if ((rc2 = persistent_grid(h, kernel, &block, lds, n, &grid))) return rc2;
+    const auto kernel = fair ? (full ? k_var<true, true> : k_var<false, true>)
+                             : (full ? k_var<true, false> : k_var<false, false>);
+    const size_t lds = persist_lds(h->force_bytes);
+    int grid = 1, block = BLOCK_PERSIST;
+    if ((rc = prepare_persistent_launch(h, kernel, &block, lds, n, &grid))) return rc;
 #ifdef NXC_VAR_ONE_WG_PER_CU          /* experiment: with -DNXC_BLOCK_PERSIST_N=512, two waves per SIMD */
-        if (grid > h->n_cu) grid = h->n_cu;
+    if (grid > h->n_cu) grid = h->n_cu;
 #endif
-        if ((rc2 = begin_timed(h))) return rc2;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, h->stream, h->F, h->d_blob,
-                           (int64_t)h->force_bytes, n, h->have_order ? h->d_queue : h->d_packets,
-                           h->have_order ? h->d_order : (const unsigned *)nullptr, resolution, outeredge,
-                           (long long)max_steps, d_final, d_hs, h->d_ctr);
-        return NXC_OK;
-    };
-    if (fair) rc = full ? launch(k_var<true, true>) : launch(k_var<false, true>);
-    else rc = full ? launch(k_var<true, false>) : launch(k_var<false, false>);
-    if (rc) return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, h->stream, h->F, h->d_blob,
+                       (int64_t)h->force_bytes, n, h->have_order ? h->d_queue : h->d_packets,
+                       h->have_order ? h->d_order : (const unsigned *)nullptr, resolution, outeredge,
+                       (long long)max_steps, d_final, d_hs, h->d_ctr);
     HIPCHK(hipGetLastError());
     if ((rc = end_timed(h))) return rc;
     *d_final_out = d_final;
@@ -1834,73 +1805,34 @@ int var_launch(nxc_handle *h, double resolution, double outeredge, int64_t max_s
     return NXC_OK;
 }
 
-// Behind the finals and steps in the scratch: what nxc_var_rows_build needs of it
-struct VarAux {
-    int64_t tiles;
-    size_t off_bytes, n_bytes, bytes;        // tile offsets [tiles] i64 | tile counts [tiles] u32 | kept [n] u8
-    explicit VarAux(int64_t n) : tiles((n + NXC_BLOCK - 1) / NXC_BLOCK)
-    {
-        off_bytes = (size_t)tiles * 8;
-        n_bytes = ((size_t)tiles * 4 + 7) & ~size_t(7);
-        bytes = off_bytes + n_bytes + (size_t)n;
-    }
-};
+// Behind the finals and steps in the scratch, what nxc_var_rows_build needs of it:
+// [tile scratch | kept [n] u8]
+size_t var_rows_scratch(int64_t n) { return tile_scratch_bytes(n) + (size_t)n; }
 
 template <typename T, typename I>
 int var_rows_run(nxc_handle *h, int compress, nxc_rows **out, uint8_t *kept_out)
 {
     const int64_t n = h->var_n;
-    const VarAux aux(n);
-    const int64_t tiles = aux.tiles;
+    const unsigned tiles = (unsigned)row_tiles(n);
     const double *fin = h->d_scratch;
-    unsigned char *base = reinterpret_cast<unsigned char *>(h->d_scratch + 9 * n);
-    long long *tile_off = reinterpret_cast<long long *>(base);
-    unsigned *tile_n = reinterpret_cast<unsigned *>(base + aux.off_bytes);
-    unsigned char *d_kept = base + aux.off_bytes + aux.n_bytes;
-    std::vector<unsigned> kept((size_t)tiles);
-    std::vector<long long> offs((size_t)tiles);
-    long long total = 0;
-    int rc;
-    if ((rc = begin_timed(h))) return rc;
-    if (compress) {
-        hipLaunchKernelGGL(k_var_rows_count, dim3((unsigned)tiles), dim3(NXC_BLOCK), 0, h->stream, n,
-                           fin + 7 * n, tile_n);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(kept.data(), tile_n, (size_t)tiles * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(stream_sync(h));
-        for (int64_t t = 0; t < tiles; t++) { offs[t] = total; total += kept[t]; }
-    } else {
-        for (int64_t t = 0; t < tiles; t++) offs[t] = (long long)t * NXC_BLOCK;
-        total = n;
-    }
-    nxc_rows *r = new (std::nothrow) nxc_rows();
-    if (!r) return fail(NXC_ERR_ARG, "out of host memory");
-    r->device = h->device; r->f32 = sizeof(T) == 4; r->total = total;
-    hipError_t e = hipSuccess;
-    if (total > 0) {
-        e = pool_take(h, (size_t)total * 9 * sizeof(T), &r->d_cols, &r->cols_cap);
-        if (e == hipSuccess) e = pool_take(h, (size_t)total * sizeof(I), &r->d_index, &r->index_cap);
-    }
+    unsigned char *d_tiles = reinterpret_cast<unsigned char *>(h->d_scratch + 9 * n);
+    unsigned char *d_kept = d_tiles + tile_scratch_bytes(n);
+    auto count = [&](unsigned *tile_n) {
+        hipLaunchKernelGGL(k_var_rows_count, dim3(tiles), dim3(NXC_BLOCK), 0, h->stream, n, fin + 7 * n, tile_n);
+    };
     // (nothing kept: the pass still runs, for kept_out; it writes no row)
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(tile_off, offs.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((k_var_rows_write<T, I>), dim3((unsigned)tiles), dim3(NXC_BLOCK), 0, h->stream, n,
-                           compress, fin, tile_off, static_cast<T *>(r->d_cols), (int64_t)total,
+    auto write = [&](const long long *tile_off, nxc_rows *r) {
+        hipLaunchKernelGGL((k_var_rows_write<T, I>), dim3(tiles), dim3(NXC_BLOCK), 0, h->stream, n, compress,
+                           fin, tile_off, static_cast<T *>(r->d_cols), (int64_t)r->total,
                            static_cast<I *>(r->d_index), d_kept);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
-    if (e == hipSuccess) h->timed = true;
-    if (e == hipSuccess && kept_out)
-        e = hipMemcpyAsync(kept_out, d_kept, (size_t)n, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = stream_sync(h);          // offs must outlive its copy; the store is final
-    if (e != hipSuccess) {
-        nxc_rows_free(h, r);
-        return fail_hip("adaptive-step rows", e);
-    }
-    *out = r;
-    return NXC_OK;
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
+        if (e != hipSuccess) return e;
+        h->timed = true;
+        return kept_out ? hipMemcpyAsync(kept_out, d_kept, (size_t)n, hipMemcpyDeviceToHost, h->stream) : e;
+    };
+    if (int rc = begin_timed(h)) return rc;
+    return compact_rows(h, n, sizeof(T) == 4, d_tiles, compress ? &count : nullptr, write, out, "adaptive-step rows");
 }
 
 }  // namespace
@@ -2722,8 +2654,6 @@ int nxc_integrate_const_streamed(nxc_handle *h, int64_t n, const double *soa0, i
     h->rows_total = -1;
     h->have_order = false;
 
-    const size_t tables = image ? h->all_bytes : h->force_bytes;
-    const size_t lds = persist_lds(tables);
     if ((rc = upload_step(h, step))) return rc;
     HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
     HIPCHK(hipMemsetAsync(d_avail, 0, sizeof(unsigned long long), h->stream));
@@ -2732,10 +2662,8 @@ int nxc_integrate_const_streamed(nxc_handle *h, int64_t n, const double *soa0, i
     HIPCHK(hipStreamWaitEvent(h->stream2, h->ev_piece[32], 0));
     HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_piece[32], 0));
     FusedJob job;
-    job.soa = h->d_queue; job.order = h->d_order; job.n = n; job.first_id = 0; job.ctr = h->d_ctr;
-    job.stream = h->stream; job.avail = d_avail;
-    if ((rc = pick_fused(h, tables, lds, n_iter, sqrt_threshold(outeredge), image, nullptr, nullptr, job)))
-        return rc;
+    job.soa = h->d_queue; job.order = h->d_order; job.avail = d_avail;
+    if ((rc = launch_fused(h, image, 0, n_iter, outeredge, job))) return rc;
     // from here on the kernel is waiting for pieces: whatever happens, something must be published
     auto give_up = [&](int code) {
         hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, h->stream2, d_avail, ~0ull);
@@ -3414,7 +3342,7 @@ int nxc_fit_packets(nxc_handle *h, const nxc_pairs *p, int64_t n_packets, double
         return rc;
     unsigned char *blob;
     unsigned long long *ctr;
-    if ((rc = fit_aux(h, 16, 0, &blob, &ctr, nullptr, nullptr))) return rc;
+    if ((rc = fit_aux(h, 16, &blob, &ctr))) return rc;
     double *d_stats = reinterpret_cast<double *>(blob);
     HIPCHK(hipMemsetAsync(h->d_fit_pk, 0, (size_t)n_packets * 28, h->stream));   // num, den, mult, cnt
     HIPCHK(hipMemsetAsync(blob, 0, 256 + 64, h->stream));                         // stats, counters
@@ -3461,7 +3389,7 @@ int nxc_fit_radiance(nxc_handle *h, const nxc_pairs *p, const nxc_los_desc *d)
     if (((blob.size() + 31) & ~size_t(31)) > 160 * 1024) return fail(NXC_ERR_ARG, "g-value tables exceed the LDS");
     unsigned char *d_blob;
     unsigned long long *ctr;
-    if ((rc = fit_aux(h, blob.size(), 0, &d_blob, &ctr, nullptr, nullptr))) return rc;
+    if ((rc = fit_aux(h, blob.size(), &d_blob, &ctr))) return rc;
     HIPCHK(hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(ctr, 0, 16, h->stream));
     if ((rc = begin_timed(h))) return rc;
@@ -3537,7 +3465,7 @@ int nxc_integrate_var_resident(nxc_handle *h, double resolution, double outeredg
 {
     return guarded([&]() -> int {
     double *d_final = nullptr, *d_hs = nullptr;
-    const size_t extra = h && h->n_packets > 0 ? VarAux(h->n_packets).bytes : 0;
+    const size_t extra = h && h->n_packets > 0 ? var_rows_scratch(h->n_packets) : 0;
     int rc = var_launch(h, resolution, outeredge, max_steps, true, extra, &d_final, &d_hs);
     if (rc) return rc;
     h->rows_total = -1;                      // a counted constant-step run's finals are gone

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "nxc_math.hpp"
+#include "nxc_fused_variant.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // Lookup table with np.interp semantics (numpy compiled_base.c arr_interp): the end values outside
@@ -1002,8 +1003,7 @@ NXC_DEV void image_sample(const ImageK &G, const ImageRegs &R, bool has, double 
 // {pixel, radial velocity, masked fraction} in LDS.  push() appends the lanes' samples in lane
 // order (ballot + prefix rank); once 64 are waiting, pop() hands one to every lane.  All calls
 // are wave-uniform; head and tail are wave-uniform counters.
-constexpr int NXC_IMGQ_SLOTS = 128;
-constexpr int NXC_IMGQ_BYTES = NXC_IMGQ_SLOTS * (8 + 8 + 4);
+// (NXC_IMGQ_SLOTS, NXC_IMGQ_BYTES: nxc_fused_variant.hpp, with the LDS size of a launch)
 
 struct ImageQueue {
     int head = 0, tail = 0;

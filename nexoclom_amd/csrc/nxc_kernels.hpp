@@ -17,6 +17,7 @@
 // into LDS from one packed blob.
 #pragma once
 #include "nxc_device.hpp"
+#include "nxc_fused_variant.hpp"
 #include "nxc_source_limits.hpp"
 
 struct DevCounters {
@@ -45,24 +46,7 @@ NXC_DEV unsigned long long nxc_stamp()
 #endif
 
 constexpr int NXC_BLOCK = 256;      // threads per workgroup of the flat kernels (4 waves)
-// The persistent kernels run ONE 12-wave workgroup per CU (3 waves per SIMD, <= 168 VGPRs): the
-// waves of a workgroup share a single LDS copy of the tables (~86 KB for Na with a 512^2 image),
-// which leaves room for the per-wave packet staging blocks and image queues (4.8 KB per wave)
-// inside the CU's 160 KB.
-#ifndef NXC_BLOCK_PERSIST_N          // overridable for occupancy experiments (tools/)
-#define NXC_BLOCK_PERSIST_N 768
-#endif
-#ifndef NXC_CHUNK_N
-#define NXC_CHUNK_N 32
-#endif
-constexpr int NXC_BLOCK_PERSIST = NXC_BLOCK_PERSIST_N;
-constexpr int NXC_CHUNK = NXC_CHUNK_N;   // packets claimed from the global queue per atomic (<= 64: one per lane)
-static_assert(NXC_CHUNK >= 1 && NXC_CHUNK <= 64, "a chunk is loaded by one wave");
-constexpr int NXC_WAVE_STAGE_BYTES = NXC_CHUNK * 9 * 8;   // per-wave LDS staging: 8 columns + packet id
-// per-wave LDS of the persistent kernels: the packet staging block, then the image queue
-constexpr int NXC_WAVE_LDS_BYTES = NXC_WAVE_STAGE_BYTES + NXC_IMGQ_BYTES;
-// the ROWS variant stages two more columns (first row, row count) and has no image queue
-constexpr int NXC_WAVE_LDS_BYTES_ROWS = NXC_CHUNK * 11 * 8;
+// (NXC_BLOCK_PERSIST, NXC_CHUNK, the per-wave LDS of the persistent kernels: nxc_fused_variant.hpp)
 
 // Cooperative copy of the first `bytes` (multiple of 8) of the table blob into LDS, then the
 // derived per-launch constants of the header.
@@ -114,6 +98,24 @@ NXC_DEV void flush_counter(unsigned long long *dst, unsigned long long v)
 {
     v = wave_sum(v);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, v);
+}
+
+// Stable compaction of a tile of blockDim.x rows, one row per lane: the number of kept rows in
+// front of this lane's, and the tile's total, from the waves' ballots.  wave_kept: __shared__, one
+// slot per wave of the block; every thread of the block must call (there is a barrier inside).
+NXC_DEV unsigned tile_rank(bool keep, unsigned *wave_kept, unsigned *tile_total = nullptr)
+{
+    const unsigned long long m = __ballot(keep);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_kept[wave] = (unsigned)__popcll(m);
+    __syncthreads();
+    unsigned rank = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; w++) rank += wave_kept[w];
+    if (tile_total) {
+        *tile_total = 0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); w++) *tile_total += wave_kept[w];
+    }
+    return rank;
 }
 
 // Up to three counters of a whole WORKGROUP: summed in LDS (`lds`: 24 bytes nobody else uses any
@@ -2874,22 +2876,21 @@ k_fit_rows_count(FitK F, const T *__restrict__ frac, const I *__restrict__ index
                  const double *__restrict__ mult, unsigned *__restrict__ tile_kept,
                  unsigned *__restrict__ lengths)
 {
-    __shared__ unsigned kept;
-    if (threadIdx.x == 0) kept = 0;
-    __syncthreads();
+    __shared__ unsigned wave_kept[NXC_BLOCK / 64];
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     double f;
     int64_t pk;
-    if (r < F.n_rows && fit_row(F, frac, index, mult, r, f, pk)) {
-        atomicAdd(&kept, 1u);
-        atomicAdd(&lengths[pk], 1u);
-    }
-    __syncthreads();
+    const bool keep = r < F.n_rows && fit_row(F, frac, index, mult, r, f, pk);
+    if (keep) atomicAdd(&lengths[pk], 1u);
+    unsigned kept;
+    tile_rank(keep, wave_kept, &kept);
     if (threadIdx.x == 0) tile_kept[blockIdx.x] = kept;
 }
 
 // pass 2: the kept rows of a tile in their order, from the tile's offset on (offsets: exclusive
 // sums of pass 1's counts).  Columns [9][n_rows] in (stride in_stride) -> [9][*] out (out_stride).
+// When no row is kept the launch still happens, with null `out` and `out_index` (as for
+// k_var_rows_write): every store must stay behind `keep`.
 template <typename T, typename I>
 __global__ void __launch_bounds__(NXC_BLOCK)
 k_fit_rows_write(FitK F, const T *__restrict__ cols, int64_t in_stride, const I *__restrict__ index,
@@ -2901,13 +2902,9 @@ k_fit_rows_write(FitK F, const T *__restrict__ cols, int64_t in_stride, const I 
     double f = 0.0;
     int64_t pk = -1;
     const bool keep = r < F.n_rows && fit_row(F, cols + 7 * in_stride, index, mult, r, f, pk);
-    const unsigned long long m = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_kept[wave] = (unsigned)__popcll(m);
-    __syncthreads();
+    const unsigned rank = tile_rank(keep, wave_kept);
     if (!keep) return;
-    long long at = tile_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; w++) at += wave_kept[w];
+    const long long at = tile_off[blockIdx.x] + rank;
 #pragma unroll
     for (int c = 0; c < 9; c++)
         out[c * out_stride + at] = c == 7 ? (T)f : cols[c * in_stride + r];
@@ -2922,21 +2919,16 @@ k_fit_rows_write(FitK F, const T *__restrict__ cols, int64_t in_stride, const I 
 // of blockDim.x packets, one packet per lane: every load is a run of consecutive doubles per
 // wave, every store a run of consecutive elements from the wave's first kept row on.
 //
-// pass 1: rows kept per tile, from the waves' ballots (reads the frac column only)
+// pass 1: rows kept per tile (reads the frac column only)
 __global__ void __launch_bounds__(NXC_BLOCK)
 k_var_rows_count(int64_t n, const double *__restrict__ frac, unsigned *__restrict__ tile_kept)
 {
     __shared__ unsigned wave_kept[NXC_BLOCK / 64];
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool keep = r < n && frac[r] > 0.0;
-    const unsigned long long m = __ballot(keep);
-    if ((threadIdx.x & 63) == 0) wave_kept[threadIdx.x >> 6] = (unsigned)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned kept = 0;
-        for (int w = 0; w < (int)(blockDim.x >> 6); w++) kept += wave_kept[w];
-        tile_kept[blockIdx.x] = kept;
-    }
+    unsigned kept;
+    tile_rank(keep, wave_kept, &kept);
+    if (threadIdx.x == 0) tile_kept[blockIdx.x] = kept;
 }
 
 // pass 2: the kept packets of a tile in their order, from the tile's offset on (offsets: exclusive
@@ -2954,14 +2946,10 @@ k_var_rows_write(int64_t n, int compress, const double *__restrict__ fin,
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const double f = r < n ? fin[7 * n + r] : 0.0;
     const bool keep = r < n && (!compress || f > 0.0);
-    const unsigned long long m = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_kept[wave] = (unsigned)__popcll(m);
     if (r < n) kept[r] = keep ? 1 : 0;
-    __syncthreads();
+    const unsigned rank = tile_rank(keep, wave_kept);
     if (!keep) return;
-    long long at = tile_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; w++) at += wave_kept[w];
+    const long long at = tile_off[blockIdx.x] + rank;
 #pragma unroll
     for (int c = 0; c < 8; c++)
         out[c * out_stride + at] = (T)(c == 7 ? f : fin[c * n + r]);
