@@ -589,6 +589,73 @@ int nxc_density_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const f
 int nxc_density_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
 int nxc_density_download(nxc_handle *h, double *sum_frac, double *count);
 
+/* ---- CameraImage: perspective image from a position inside or near the cloud ----------------------
+ * EXTENSION -- the reference images from infinity only (ModelImage.create_image); this is the same
+ * weighting seen by a pinhole (gnomonic) camera at a finite distance.  Samples are x, y, z [R],
+ * vy [R/s], frac in the model frame, as nxc_image_accumulate reads them.  The camera: position o
+ * (|o| >= 1), row-major orthonormal basis C with rows right, boresight, up, and tangent-plane bin
+ * edges uedges[nx + 1], vedges[nz + 1], each np.linspace(-a, a, n + 1) (full field of view
+ * 2 atan(a) < 180 degrees per axis).  Per sample, fp64, one rounding per operation, in this order:
+ *   1. dx = x - o[0], dy = y - o[1], dz = z - o[2];  radvel = vy + vrplanet
+ *      xc = (C[0]*dx + C[1]*dy) + C[2]*dz;  dc = (C[3]*dx + C[4]*dy) + C[5]*dz;
+ *      zc = (C[6]*dx + C[7]*dy) + C[8]*dz
+ *   2. !(dc > 0): behind the camera, not binned
+ *   3. u = xc / dc, v = zc / dc;  ix, iz = the bins of u in uedges and of v in vedges as
+ *      np.histogram2d takes them (searchsorted(edges, ., 'right') - 1, the last edge inclusive);
+ *      outside either range: not binned.  Pixel = ix * nz + iz.  A sample that is not binned (2 or
+ *      3) counts in `nonfinite` iff frac is not finite or radvel is NaN, as outside a ModelImage frame
+ *   4. r2 = (dx*dx + dy*dy) + dz*dz;  b = -((o[0]*dx + o[1]*dy) + o[2]*dz);
+ *      cx = o[1]*z - o[2]*y, cy = o[2]*x - o[0]*z, cz = o[0]*y - o[1]*x;  c2 = (cx*cx + cy*cy) + cz*cz;
+ *      hidden by the unit sphere iff b > 0 && b < r2 && c2 < r2 (the point of the segment camera ->
+ *      sample nearest the centre lies inside it, strictly between its ends; division-free): f =
+ *      frac * 0, else f = frac.  c2 = |o x p|^2 is |o|^2 r2 - b^2 formed without that difference,
+ *      which at a camera distance D cancels two terms of order D^4 to one of order D^2 and has no
+ *      correct digit left from D ~ 1e8.  A hidden sample still counts in the packet image
+ *      (create_image's inview)
+ *   5. quantity 1: f = f * 0 unless (x*x + z*z > 1 + 2^-52) || (y < 0)  (sunlit, as nxc_image_*)
+ *   6. w = f (quantity 0) or (f * sum_l interp(radvel, line_v[l], line_g[l])) / 1e6 (quantity 1;
+ *      the sum starts with line 0 and adds the others in order); w not finite or radvel NaN:
+ *      `nonfinite`, dropped
+ *   7. r = sqrt(r2);  foot = ((dc*dc)*dc) / r  -- r^2 dOmega of a tangent-plane pixel, in R^2 per
+ *      unit du dv;  w = w / (foot * pix_area_cm2), pix_area_cm2 = du dv unit_cm^2 from the host
+ *   8. w not finite: `nonfinite`, dropped; else image[pixel] += w, packets[pixel] += 1
+ * (sqrt and / are IEEE-754 correctly rounded.)  The image is a column density [1/cm^2 per packet
+ * weight] or a radiance along the pixel's line of sight for uniform emitters at the samples.
+ * The camera image is a device buffer of its own: nxc_set_image / nxc_image_* and the calls below
+ * never touch each other's image.  Counters (nxc_counters_get) of an accumulate call: samples,
+ * samples_binned (step 8 reached), nonfinite.  Moons do not occult.
+ *   nxc_camera_set               checks the description (NXC_ERR_ARG: o not finite or inside the
+ *                                planet, C not orthonormal to 1e-12, dims outside 1..8192, edges
+ *                                not finite / increasing / symmetric, n_lines outside
+ *                                0..NXC_MAX_LINES, null tables, pix_area_cm2 not > 0, tables + edges
+ *                                beyond the 160 KiB of LDS), copies the tables to the device and
+ *                                zeroes the resident camera image
+ *   nxc_camera_accumulate[_f32]  adds p samples held on the host (float32 ones are widened exactly)
+ *   nxc_camera_accumulate_rows   adds rows [first, first + count) of a row store
+ *   nxc_camera_download          image[nx * nz], counts[nx * nz] (either nullable) */
+typedef struct nxc_camera_desc {
+    double o[3];          /* camera position, R, model frame                                    */
+    double C[9];          /* row-major: right, boresight, up                                    */
+    double vrplanet;      /* R/s, added to vy for the g-value lookup                            */
+    double pix_area_cm2;  /* du * dv * unit_cm^2                                                */
+    int32_t quantity;     /* 0 = column (w = frac), 1 = radiance                                */
+    int32_t n_lines;      /* g-value tables summed for radiance (<= NXC_MAX_LINES)              */
+    int64_t nx, nz;       /* bins along u (right) and v (up), 1..8192                           */
+    const double *uedges; /* nx + 1 tangent-plane edges, symmetric about 0                      */
+    const double *vedges; /* nz + 1                                                             */
+    int64_t line_n[NXC_MAX_LINES];
+    const double *line_v[NXC_MAX_LINES]; /* R/s ascending                                       */
+    const double *line_g[NXC_MAX_LINES]; /* 1/s                                                 */
+} nxc_camera_desc;
+
+int nxc_camera_set(nxc_handle *h, const nxc_camera_desc *d);
+int nxc_camera_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                          const double *z, const double *vy, const double *frac);
+int nxc_camera_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                              const float *z, const float *vy, const float *frac);
+int nxc_camera_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_camera_download(nxc_handle *h, double *image, uint64_t *counts);
+
 /* ---- Source maps: where the packets of fitted Outputs came from ---------------------------------
  * data_simulation/make_source_map.py:11-174 per Output, summed over the Outputs of a result on the
  * device.  Grid: nlon x nlat points at the bin centres point_lon[nlon], point_lat[nlat]; point p =

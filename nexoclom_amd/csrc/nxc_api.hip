@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/nexoclom_hip.h"
+#include "nxc_camera_check.hpp"
 #include "nxc_desc_check.hpp"
 #include "nxc_kernels.hpp"
 #include "nxc_log_table.hpp"
@@ -421,6 +422,15 @@ struct nxc_handle {
     size_t dens_cell_cap = 0;
     double *d_dens_acc = nullptr;    // interleaved pair [Q][2], as the image's
     size_t dens_acc_cap = 0;
+
+    // CameraImage (nxc_camera_set): the camera, its LDS blob [LdsHeader | g tables | u edges |
+    // v edges] and its own {weight sum, count} image
+    bool have_camera = false;
+    CameraK cam{};
+    unsigned char *d_blob_cam = nullptr;
+    size_t blob_cam_cap = 0, cam_bytes = 0;
+    double *d_cam_image = nullptr;
+    size_t cam_image_cap = 0, cam_npix = 0;
 
     // LOSResultFitted: the pair list the line-of-sight passes fill (nxc_los_set_pairs); the fit's
     // per-spectrum data, its sample source and per-packet sums (nxc_fit_*)
@@ -1575,6 +1585,51 @@ int density_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T
     return rc ? rc : density_run(h, s);
 }
 
+// CameraImage over samples on the device (k_camera)
+template <typename T>
+int camera_run(nxc_handle *h, int64_t p, const T *dx, const T *dy, const T *dz, const T *dvy,
+               const T *dfrac)
+{
+    int per_cu = 0, rc;
+    if ((rc = prep_kernel(k_camera<T>, h->cam_bytes))) return rc;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_camera<T>, NXC_CAMERA_BLOCK,
+                                                        h->cam_bytes));
+    int64_t grid = (int64_t)h->n_cu * (per_cu > 0 ? per_cu : 1);
+    grid = std::max<int64_t>(1, std::min<int64_t>(grid, (p + NXC_CAMERA_BLOCK - 1) / NXC_CAMERA_BLOCK));
+    if ((rc = begin_timed(h))) return rc;
+    hipLaunchKernelGGL(k_camera<T>, dim3((unsigned)grid), dim3(NXC_CAMERA_BLOCK), h->cam_bytes,
+                       h->stream, h->cam, h->d_blob_cam, (int64_t)h->cam_bytes, p, dx, dy, dz, dvy,
+                       dfrac, h->d_cam_image, h->d_ctr);
+    HIPCHK(hipGetLastError());
+    if ((rc = end_timed(h))) return rc;
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+}
+
+// ... over a sample view
+int camera_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) {
+        using T = decltype(t);
+        return camera_run(h, s.n, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3), s.col<T>(4));
+    });
+}
+
+// ... over samples in host memory, 64-bit or as save() keeps them (32-bit)
+template <typename T>
+int camera_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T *z, const T *vy,
+                      const T *frac)
+{
+    if (!h || !h->have_camera) return fail(NXC_ERR_STATE, "nxc_camera_set has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    if (p < 0 || (p && (!x || !y || !z || !vy || !frac))) return fail(NXC_ERR_ARG, "bad arguments");
+    HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
+    if (p == 0) return NXC_OK;
+    const T *cols[5] = {x, y, z, vy, frac};
+    Samples s;
+    int rc = samples_upload(h, &h->d_samples, &h->samples_cap, p, cols, nullptr, &s);
+    return rc ? rc : camera_run(h, s);
+}
 
 // ---- LOSResultFitted -------------------------------------------------------------------------
 int fit_check(nxc_handle *h, const nxc_pairs *p)
@@ -1915,7 +1970,7 @@ int nxc_destroy(nxc_handle *h)
                     h->d_source, h->d_queue, h->d_samples, h->d_tiles, h->d_hist, h->d_rec, h->d_piece_hist,
                     h->d_blob_img, h->d_reduce_n, h->d_losblk, h->d_dens_pts, h->d_dens_cell,
                     h->d_dens_acc, h->d_fit_spec, h->d_fit_pk, h->d_fit_smp, h->d_fit_aux,
-                    h->d_smap_grid, h->d_smap_acc, h->d_smap_pk};
+                    h->d_smap_grid, h->d_smap_acc, h->d_smap_pk, h->d_blob_cam, h->d_cam_image};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     pool_flush(h);
@@ -3002,6 +3057,111 @@ int nxc_density_download(nxc_handle *h, double *sum_frac, double *count)
     for (int64_t j = 0; j < h->dens_q; j++) {
         sum_frac[j] = pair[2 * j];
         count[j] = pair[2 * j + 1];
+    }
+    return NXC_OK;
+    });
+}
+
+// ---- CameraImage ---------------------------------------------------------------------------------
+int nxc_camera_set(nxc_handle *h, const nxc_camera_desc *d)
+{
+    return guarded([&]() -> int {
+    if (!h) return fail(NXC_ERR_ARG, "null handle");
+    const std::string why = check_camera_desc(d);
+    if (!why.empty()) return fail(NXC_ERR_ARG, why);
+    HIPCHK(hipSetDevice(h->device));
+    const int nl = d->quantity == 1 ? d->n_lines : 0;
+    const size_t hb = NXC_HEADER_BYTES;
+    std::vector<unsigned char> blob(hb, 0);
+    LdsHeader hdr = h->header;                 // nxc_log's table; the image's own G is replaced
+    ImageK G{};
+    std::memcpy(G.M, d->C, sizeof G.M);       // the basis, where the image keeps its rotation
+    G.vrplanet = d->vrplanet;
+    G.apix_cm2 = 1.0;                          // the per-sample area divides in camera_sample
+    G.quantity = d->quantity;
+    G.n_lines = nl;
+    G.nx = (int)d->nx;
+    G.nz = (int)d->nz;
+    for (int l = 0; l < nl; l++) {
+        PackedLut lut;
+        int rc = pack_lut(d->line_v[l], d->line_g[l], d->line_n[l], lut, "g-value table");
+        if (rc) return rc;
+        G.line[l] = placed_lut(lut.desc, blob.size());
+        blob.insert(blob.end(), lut.bytes.begin(), lut.bytes.end());
+    }
+    G.xedges_off = (int64_t)blob.size();
+    const unsigned char *ue = reinterpret_cast<const unsigned char *>(d->uedges);
+    blob.insert(blob.end(), ue, ue + (d->nx + 1) * sizeof(double));
+    G.zedges_off = (int64_t)blob.size();
+    const unsigned char *ve = reinterpret_cast<const unsigned char *>(d->vedges);
+    blob.insert(blob.end(), ve, ve + (d->nz + 1) * sizeof(double));
+    G.x_lo = d->uedges[0];
+    G.x_inv_step = (double)d->nx / (d->uedges[d->nx] - d->uedges[0]);
+    G.z_lo = d->vedges[0];
+    G.z_inv_step = (double)d->nz / (d->vedges[d->nz] - d->vedges[0]);
+    if (blob.size() > 160 * 1024)
+        return fail(NXC_ERR_ARG, "nxc_camera_desc: tables and edges exceed the 160 KiB LDS of a gfx950 CU");
+    hdr.G = G;
+    std::memcpy(blob.data(), &hdr, sizeof(LdsHeader));
+
+    CameraK K{};
+    for (int a = 0; a < 3; a++) K.o[a] = d->o[a];
+    K.area = d->pix_area_cm2;
+
+    h->have_camera = false;
+    const size_t npix = (size_t)d->nx * (size_t)d->nz;
+    int rc;
+    if ((rc = ensure(reinterpret_cast<void **>(&h->d_blob_cam), &h->blob_cam_cap, blob.size())) ||
+        (rc = ensure(reinterpret_cast<void **>(&h->d_cam_image), &h->cam_image_cap, 2 * npix * sizeof(double))))
+        return rc;
+    HIPCHK(hipMemcpyAsync(h->d_blob_cam, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_cam_image, 0, 2 * npix * sizeof(double), h->stream));
+    HIPCHK(stream_sync(h));                    // blob is a local
+    h->cam = K;
+    h->cam_bytes = blob.size();
+    h->cam_npix = npix;
+    h->have_camera = true;
+    return NXC_OK;
+    });
+}
+
+int nxc_camera_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                          const double *z, const double *vy, const double *frac)
+{
+    return guarded([&]() -> int { return camera_accumulate(h, p, x, y, z, vy, frac); });
+}
+
+int nxc_camera_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                              const float *z, const float *vy, const float *frac)
+{
+    return guarded([&]() -> int { return camera_accumulate(h, p, x, y, z, vy, frac); });
+}
+
+int nxc_camera_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_camera) return fail(NXC_ERR_STATE, "nxc_camera_set has not been called");
+    Samples s;
+    int rc = samples_from_rows(h, r, first, count, 0, &s);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
+    return count ? camera_run(h, s) : NXC_OK;
+    });
+}
+
+int nxc_camera_download(nxc_handle *h, double *image, uint64_t *counts)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_camera) return fail(NXC_ERR_STATE, "nxc_camera_set has not been called");
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<double> both(2 * h->cam_npix);
+    HIPCHK(hipMemcpyAsync(both.data(), h->d_cam_image, both.size() * sizeof(double),
+                          hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    for (size_t q = 0; q < h->cam_npix; q++) {
+        if (image) image[q] = both[2 * q];
+        if (counts) counts[q] = (uint64_t)both[2 * q + 1];      // integer-valued, < 2^53
     }
     return NXC_OK;
     });

@@ -999,6 +999,76 @@ NXC_DEV void image_sample(const ImageK &G, const ImageRegs &R, bool has, double 
     image_add_pairs(ok, pix, w, acc2);
 }
 
+// ---- CameraImage: the same sample seen by a pinhole camera at a finite distance ------------------
+// (include/nexoclom_hip.h, nxc_camera_desc, holds the definition; the operations below are in its
+// order.)  The camera's position travels as kernel arguments; everything the image has a place
+// for -- the basis C (rows right, boresight, up) as M, g-value tables, the two edge arrays (u as
+// "x", v as "z"), quantity, vrplanet -- sits in the LDS header's ImageK, so image_regs / bin_index /
+// image_weight serve unchanged (and the basis takes no scalar registers: with it the kernel
+// spilled four).  The header's apix_cm2 is 1: image_weight's last division is then exact and the
+// per-sample area divides after.
+struct CameraK {
+    double o[3];
+    double area;           // du dv unit_cm^2
+};
+
+// Pixel (ix*nz + iz) or -1 (behind the camera or outside the field of view, with
+// image_locate_core_xz's bookkeeping for samples outside the frame); radial velocity for the
+// g-value lookup, the masked fraction, and what the footprint is made of.
+NXC_DEV int camera_locate(const CameraK &K, const ImageK &G, const ImageRegs &R, double x, double y,
+                          double z, double vy, double frac, double &radvel_out, double &fw_out,
+                          double &dc_out, double &r2_out, unsigned long long &nonfinite)
+{
+    const double radvel = vy + R.vrplanet;
+    const double dx = x - K.o[0], dy = y - K.o[1], dz = z - K.o[2];
+    const double xc = (G.M[0] * dx + G.M[1] * dy) + G.M[2] * dz;
+    const double dc = (G.M[3] * dx + G.M[4] * dy) + G.M[5] * dz;
+    const double zc = (G.M[6] * dx + G.M[7] * dy) + G.M[8] * dz;
+    int ix = -1, iz = -1;
+    if (dc > 0.0) {
+        const double u = nxc_div(xc, dc), v = nxc_div(zc, dc);
+        ix = bin_index(u, R.xedges, R.nx, R.x_lo, R.x_hi, R.x_inv_step);
+        iz = bin_index(v, R.zedges, R.nz, R.z_lo, R.z_hi, R.z_inv_step);
+    }
+    if (ix < 0 || iz < 0) {
+        if (!(__builtin_fabs(frac) <= 1.7976931348623157e308) || radvel != radvel) nonfinite++;
+        return -1;
+    }
+    const double r2 = (dx * dx + dy * dy) + dz * dz;
+    const double b = -((K.o[0] * dx + K.o[1] * dy) + K.o[2] * dz);
+    // |o x p|^2 = |o|^2 r2 - b^2 without that difference's cancellation (at a camera distance D
+    // both terms are of order D^4, their difference of order D^2)
+    const double cx = K.o[1] * z - K.o[2] * y, cy = K.o[2] * x - K.o[0] * z,
+                 cz = K.o[0] * y - K.o[1] * x;
+    const bool hidden = (b > 0.0) && (b < r2) && ((cx * cx + cy * cy) + cz * cz < r2);
+    frac = hidden ? frac * 0.0 : frac;
+    if (R.quantity != 0) frac = sunlit(x, y, z) ? frac : frac * 0.0;
+    radvel_out = radvel;
+    fw_out = frac;
+    dc_out = dc;
+    r2_out = r2;
+    return ix * R.nz + iz;
+}
+
+// locate + weight + footprint + add of one sample per lane.  Wave-cooperative like image_sample.
+NXC_DEV void camera_sample(const CameraK &K, const ImageK &G, const ImageRegs &R, bool has, double x,
+                           double y, double z, double vy, double frac, double *__restrict__ acc2,
+                           unsigned long long &binned, unsigned long long &nonfinite)
+{
+    int pix = -1;
+    double radvel = 0.0, fw = 0.0, dc = 1.0, r2 = 1.0, w = 0.0;
+    if (has) pix = camera_locate(K, G, R, x, y, z, vy, frac, radvel, fw, dc, r2, nonfinite);
+    bool ok = pix >= 0;
+    if (ok && !image_weight(G, R, radvel, fw, w)) { nonfinite++; ok = false; }
+    if (ok) {
+        const double foot = nxc_div((dc * dc) * dc, nxc_sqrt(r2));
+        w = nxc_div(w, foot * K.area);
+        if (!(__builtin_fabs(w) <= 1.7976931348623157e308)) { nonfinite++; ok = false; }
+    }
+    binned += ok;
+    image_add_pairs(ok, pix, w, acc2);
+}
+
 // Per-wave compaction queue between image_locate and image_weight: a ring of 128 located samples
 // {pixel, radial velocity, masked fraction} in LDS.  push() appends the lanes' samples in lane
 // order (ballot + prefix rank); once 64 are waiting, pop() hands one to every lane.  All calls

@@ -12,6 +12,7 @@
 //                        compact trajectory instead (k_rows_transpose / k_rows_densify shape it).
 //   k_var           a-4  adaptive-step driver, same lane-refill structure
 //   k_image         a-6..a-8  image of stored samples (HBM-bound: 40 B/sample in)
+//   k_camera        the same samples in the perspective image of a camera at a finite distance
 //
 // All lookup tables (radiation acceleration, g-values, bin edges) are staged once per workgroup
 // into LDS from one packed blob.
@@ -2725,6 +2726,37 @@ k_density(DensityK K, int64_t n, const T *__restrict__ x, const T *__restrict__ 
             image_add_pairs(hit, q, w, acc2);
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// CameraImage: stored samples binned into the image of a pinhole camera (camera_sample).  k_image's
+// shape: the blob [header | g tables | u edges | v edges] staged once per workgroup, a grid-stride
+// loop with a wave-uniform trip count, one memory-side atomic request per binned sample.
+// 66 VGPRs: seven waves a SIMD, i.e. three 512-thread groups on a CU where k_image's 1024-thread
+// groups would come to one (asking for eight waves spills to scratch).
+constexpr int NXC_CAMERA_BLOCK = 512;
+template <typename T>
+__global__ void __launch_bounds__(NXC_CAMERA_BLOCK)
+k_camera(CameraK K, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p,
+         const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ z,
+         const T *__restrict__ vy, const T *__restrict__ frac,
+         double *__restrict__ acc2, DevCounters *__restrict__ ctr)
+{
+    stage_tables(blob, stage_bytes);
+    const ImageRegs IR = image_regs(lds_header().G);
+    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p;
+         base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        const bool has = i < p;
+        my_samples += has;
+        double sx = 0, sy = 0, sz = 0, svy = 0, sf = 0;
+        if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
+        camera_sample(K, lds_header().G, IR, has, sx, sy, sz, svy, sf, acc2, my_binned, my_nonfinite);
+    }
+    // (the tables are not read any more: their first bytes carry the workgroup's sums)
+    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
+                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
 }
 
 // ---------------------------------------------------------------------------------------------

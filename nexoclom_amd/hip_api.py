@@ -42,7 +42,8 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_fit_source', 'nxc_fit_source_f32', 'nxc_fit_packets', 'nxc_fit_radiance',
            'nxc_fit_rows', 'nxc_fit_download', 'nxc_source_map_set', 'nxc_source_map_accumulate',
            'nxc_source_map_download', 'nxc_set_stick_map', 'nxc_integrate_var_resident',
-           'nxc_var_rows_build')
+           'nxc_var_rows_build', 'nxc_camera_set', 'nxc_camera_accumulate',
+           'nxc_camera_accumulate_f32', 'nxc_camera_accumulate_rows', 'nxc_camera_download')
 ABI_VERSION = 3
 
 
@@ -87,6 +88,14 @@ class nxc_density_desc(C.Structure):
     _fields_ = [('origin', C.c_double*3), ('h', C.c_double), ('dr', C.c_double),
                 ('dims', C.c_int64*3), ('n_points', C.c_int64), ('points', _dp),
                 ('cell_start', C.POINTER(C.c_int32))]
+
+
+class nxc_camera_desc(C.Structure):
+    _fields_ = [('o', C.c_double*3), ('C', C.c_double*9), ('vrplanet', C.c_double),
+                ('pix_area_cm2', C.c_double), ('quantity', C.c_int32), ('n_lines', C.c_int32),
+                ('nx', C.c_int64), ('nz', C.c_int64), ('uedges', _dp), ('vedges', _dp),
+                ('line_n', C.c_int64*NXC_MAX_LINES), ('line_v', _dp*NXC_MAX_LINES),
+                ('line_g', _dp*NXC_MAX_LINES)]
 
 
 class nxc_source_map_desc(C.Structure):
@@ -864,6 +873,58 @@ class Context:
         total, count = np.zeros(q), np.zeros(q)
         self._check(self.lib.nxc_density_download(self._h, _p(total), _p(count)))
         return total, count
+
+    # -- CameraImage ------------------------------------------------------------------------
+    def camera_set(self, observer, basis, vrplanet, pix_area_cm2, quantity, uedges, vedges,
+                   g_tables=()):
+        """Describe a pinhole camera (nxc_camera_desc) and zero its resident image: position
+        ``observer`` [R], ``basis`` (3, 3) with rows right, boresight, up, tangent-plane bin edges
+        and ``pix_area_cm2`` = du dv unit_cm^2."""
+        d = nxc_camera_desc()
+        d.o = (C.c_double*3)(*np.asarray(observer, dtype=float).reshape(3))
+        d.C = (C.c_double*9)(*np.asarray(basis, dtype=float).reshape(9))
+        d.vrplanet, d.pix_area_cm2 = float(vrplanet), float(pix_area_cm2)
+        if quantity == 'column':
+            d.quantity = 0
+        elif quantity == 'radiance':
+            d.quantity = 1
+        else:
+            raise ValueError(f'{quantity} is invalid.')
+        ue, ve = _f64(uedges), _f64(vedges)
+        d.nx, d.nz = len(ue)-1, len(ve)-1
+        d.uedges, d.vedges = _p(ue), _p(ve)
+        keep = [ue, ve]
+        if d.quantity == 1:
+            if len(g_tables) > NXC_MAX_LINES:
+                raise ValueError('too many emission lines')
+            d.n_lines = len(g_tables)
+            for k, (v, g) in enumerate(g_tables):
+                v, g = _f64(v), _f64(g)
+                keep += [v, g]
+                d.line_n[k], d.line_v[k], d.line_g[k] = len(v), _p(v), _p(g)
+        self._check(self.lib.nxc_camera_set(self._h, C.byref(d)))
+        self.camera_shape = (int(d.nx), int(d.nz))
+
+    def camera_accumulate(self, x=None, y=None, z=None, vy=None, frac=None, rows=None):
+        """Add samples to the camera image: five host columns (float32 ones go over as they are
+        and are widened on the device), or ``rows = (RowStore, first, count)``."""
+        if rows is not None:
+            store, first, count = rows
+            self._check(self.lib.nxc_camera_accumulate_rows(
+                self._h, self._rows_handle(store), C.c_int64(first), C.c_int64(count)))
+            return
+        suffix, ptrs, cols = self._columns((x, y, z, vy, frac))
+        self._check(getattr(self.lib, 'nxc_camera_accumulate' + suffix)(
+            self._h, C.c_int64(len(cols[0])), *ptrs))
+
+    def camera_download(self):
+        """(image (nx, nz) float64, packet counts (nx, nz) uint64) of the camera."""
+        shape = getattr(self, 'camera_shape', None) or (0, 0)
+        image = np.zeros(shape)
+        counts = np.zeros(shape, dtype=np.uint64)
+        self._check(self.lib.nxc_camera_download(
+            self._h, _p(image), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return image, counts
 
     # -- LOSResultFitted ----------------------------------------------------------------------
     def pairs_create(self, capacity):
