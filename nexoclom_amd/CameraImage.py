@@ -31,6 +31,7 @@ degrees), moons as occulters.
 import numpy as np
 
 from .ModelImage import ModelResult
+from .catalogue import sample_spans, shared_context
 from .input_classes import InputError
 from .units import Quantity
 
@@ -145,15 +146,7 @@ class CameraImage(ModelResult):
 
     def context(self):
         if self._ctx is None:
-            # the device the catalogued runs were made on, when there is one: their rows are still
-            # in its HBM; else a fresh one
-            shared = [getattr(run, '_ctx', None) for run in getattr(self.inputs, '_catalogue', ())]
-            shared = [ctx for ctx in shared if ctx is not None and getattr(ctx, '_h', True)]
-            if shared:
-                self._ctx = shared[-1]
-            else:
-                from . import hip_api
-                self._ctx = hip_api.Context(self._device)
+            self._ctx = shared_context(self.inputs, self._device)
         return self._ctx
 
     def _from_catalogue(self):
@@ -168,54 +161,46 @@ class CameraImage(ModelResult):
             return
         ctx = self.context()
         totals = {}
-        state = dict(key=None, span=None)
 
-        def accumulate(**how):
-            ctx.camera_accumulate(**how)
-            for key, v in ctx.counters().items():
-                totals[key] = totals.get(key, 0) + v
+        def announced():
+            for run in runs:
+                print(f'Output filename: {getattr(run, "filename", run)}')
+                self.totalsource += run.totalsource if isinstance(run, Output) else \
+                    float(np.load(run, allow_pickle=False)['totalsource'])
+                yield run
 
-        def flush_span():
-            if state['span'] is not None:
-                if state['span'][2]:
-                    accumulate(rows=state['span'])
-                state['span'] = None
+        def g_values(run):
+            """(aplanet [au], vrplanet [km/s]): what the g-values of a run depend on"""
+            if isinstance(run, Output):
+                return float(run.aplanet), float(run.vrplanet)
+            with np.load(run, allow_pickle=False) as data:
+                return float(data['aplanet']), float(data['vrplanet_kms'])
 
         def collect():
-            flush_span()
-            if state['key'] is not None:
-                image, counts = ctx.camera_download()
-                self.image += image
-                self.packet_image += counts.astype(float)
+            image, counts = ctx.camera_download()
+            self.image += image
+            self.packet_image += counts.astype(float)
 
-        for run in runs:
-            print(f'Output filename: {getattr(run, "filename", run)}')
-            view = run.resident_rows(ctx) if isinstance(run, Output) else None
-            samples = None
-            if view is None:
-                samples, aplanet, vr_kms = Output.image_columns(run)
-            else:
-                aplanet, vr_kms = float(run.aplanet), float(run.vrplanet)
-            if (aplanet, vr_kms) != state['key']:
-                collect()
+        is_set = False
+        for kind, item in sample_spans(announced(), ctx, key=g_values):
+            if kind == 'key':
+                if is_set:
+                    collect()
+                aplanet, vr_kms = item
                 ctx.camera_set(self.observer, self.basis, vr_kms/self.unit_km, self.pix_area_cm2,
                                self.quantity, self.uedges, self.vedges, self.g_tables(aplanet))
-                state['key'] = (aplanet, vr_kms)
-            if view is not None:
-                store, first, count, _ = view
-                span = state['span']
-                if span is not None and span[0] is store and span[1] + span[2] == first:
-                    state['span'] = (store, span[1], span[2] + count)
-                else:
-                    flush_span()
-                    state['span'] = (store, first, count)
+                is_set = True
+                continue
+            if kind == 'rows':
+                ctx.camera_accumulate(rows=item)
             else:
-                flush_span()
-                if samples is not None and len(samples[0]):
-                    x, y, z, vy, frac = samples
-                    accumulate(x=x, y=y, z=z, vy=vy, frac=frac)
-            self.totalsource += run.totalsource if isinstance(run, Output) else \
-                float(np.load(run, allow_pickle=False)['totalsource'])
+                samples = Output.image_columns(item)[0]
+                if samples is None or not len(samples[0]):
+                    continue
+                x, y, z, vy, frac = samples
+                ctx.camera_accumulate(x=x, y=y, z=z, vy=vy, frac=frac)
+            for key, v in ctx.counters().items():
+                totals[key] = totals.get(key, 0) + v
         collect()
         self.counters = totals
         assert totals.get('nonfinite', 0) == 0, 'Non-finite weights'

@@ -23,6 +23,7 @@ import numpy as np
 import pandas as pd
 
 from .ModelImage import ModelResult
+from .catalogue import shared_context
 from .units import Quantity
 
 POSITION = ('x', 'y', 'z')
@@ -144,15 +145,7 @@ class LOSResult(ModelResult):
 
     def context(self):
         if self._ctx is None:
-            # the device the catalogued runs were made on, when there is one: their rows are still
-            # in its HBM (and a new handle costs 0.1 s); else a fresh one
-            shared = [getattr(run, '_ctx', None) for run in getattr(self.inputs, '_catalogue', ())]
-            shared = [ctx for ctx in shared if ctx is not None and getattr(ctx, '_h', True)]
-            if shared:
-                self._ctx = shared[-1]
-            else:
-                from . import hip_api
-                self._ctx = hip_api.Context(self._device)
+            self._ctx = shared_context(self.inputs, self._device)
         return self._ctx
 
     def compute_iteration(self, output, scdata, used_cap=0, pairs=None):

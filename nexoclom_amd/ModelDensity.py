@@ -19,6 +19,7 @@ written.  Bokeh display is out of scope.
 """
 import numpy as np
 
+from .catalogue import sample_spans, shared_context
 from .units import Quantity
 
 MAX_CELLS = 1 << 24           # cells of the point grid (int32 starts; cell coordinates < 2^24)
@@ -132,42 +133,26 @@ class ModelDensity:
 
     def context(self):
         if self._ctx is None:
-            # the device the catalogued runs were made on, when there is one: their rows are still
-            # in its HBM; else a fresh one
-            shared = [getattr(run, '_ctx', None) for run in getattr(self.inputs, '_catalogue', ())]
-            shared = [ctx for ctx in shared if ctx is not None and getattr(ctx, '_h', True)]
-            if shared:
-                self._ctx = shared[-1]
-            else:
-                from . import hip_api
-                self._ctx = hip_api.Context(self._device)
+            self._ctx = shared_context(self.inputs, self._device)
         return self._ctx
 
     def _accumulate(self, index):
         """(frac sums, counts) per indexed point over this process's catalogue
         (ModelDensity.py:62-82).  Rows in HBM are read where they are, one launch per run of
         adjacent slices of a store; other Outputs upload X's x, y, z, frac."""
-        from .Output import Output
         ctx = self.context()
         ctx.density_set(index.points, index.cell_start, index.origin, index.h, index.dr,
                         index.dims)
-        span = None                               # (store, first row, row count)
-        for run in self.inputs._catalogue:
-            print(f'Output filename: {run.filename}')
-            view = run.resident_rows(ctx) if isinstance(run, Output) else None
-            if view is not None:
-                store, first, count, _ = view
-                if span is not None and span[0] is store and span[1] + span[2] == first:
-                    span = (store, span[1], span[2] + count)
-                else:
-                    if span is not None:
-                        ctx.density_accumulate(rows=span)
-                    span = (store, first, count)
-            else:
-                X = run.X
-                if len(X) and 'x' in X:
-                    ctx.density_accumulate(*(X[c].values for c in ('x', 'y', 'z', 'frac')))
-            self.totalsource += run.totalsource
-        if span is not None:
-            ctx.density_accumulate(rows=span)
+
+        def announced():
+            for run in self.inputs._catalogue:
+                print(f'Output filename: {run.filename}')
+                self.totalsource += run.totalsource
+                yield run
+
+        for kind, item in sample_spans(announced(), ctx):
+            if kind == 'rows':
+                ctx.density_accumulate(rows=item)
+            elif len(item.X) and 'x' in item.X:
+                ctx.density_accumulate(*(item.X[c].values for c in ('x', 'y', 'z', 'frac')))
         return ctx.density_download()

@@ -25,6 +25,7 @@ import os
 import numpy as np
 
 from .atomicdata import gValue
+from .catalogue import sample_spans, shared_context
 from .input_classes import InputError
 from .units import Quantity
 
@@ -206,26 +207,18 @@ class ModelImage(ModelResult):
         self._set_image(ctx, aplanet, vrplanet_kms/self.unit_km, downcast=False)    # clears it
         totals = {}
 
-        def accumulate(store, first, count):
-            if count:
-                ctx.image_accumulate_rows(store, first, count)
-                for key, v in ctx.counters().items():
-                    totals[key] = totals.get(key, 0) + v
+        def announced():
+            for run in runs:
+                print(f'Output filename: {run.filename}')
+                self.totalsource += run.totalsource
+                yield run
 
         # the Outputs of a launch group are consecutive slices of one store: one kernel launch per
         # run of adjacent slices instead of one per Output
-        span = None                               # (store, first row, row count)
-        for run, (store, first, count, _) in zip(runs, views):
-            print(f'Output filename: {run.filename}')
-            if span is not None and span[0] is store and span[1] + span[2] == first:
-                span = (store, span[1], span[2] + count)
-            else:
-                if span is not None:
-                    accumulate(*span)
-                span = (store, first, count)
-            self.totalsource += run.totalsource
-        if span is not None:
-            accumulate(*span)
+        for _, span in sample_spans(announced(), ctx):
+            ctx.image_accumulate_rows(*span)
+            for key, v in ctx.counters().items():
+                totals[key] = totals.get(key, 0) + v
         self.counters = totals
         assert totals.get('nonfinite', 0) == 0, 'Non-finite weights'
         image, counts = ctx.image_download()
@@ -246,15 +239,7 @@ class ModelImage(ModelResult):
     # ---- GPU plumbing ---------------------------------------------------------------------
     def context(self):
         if self._ctx is None:
-            # the device the catalogued runs were made on, when there is one (a new handle costs
-            # 0.1 s); else a fresh one
-            shared = [getattr(run, '_ctx', None) for run in getattr(self.inputs, '_catalogue', ())]
-            shared = [ctx for ctx in shared if ctx is not None and getattr(ctx, '_h', True)]
-            if shared:
-                self._ctx = shared[-1]
-            else:
-                from . import hip_api
-                self._ctx = hip_api.Context(self._device)
+            self._ctx = shared_context(self.inputs, self._device)
         return self._ctx
 
     def image_rotation(self):

@@ -18,9 +18,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, 'csrc', 'nxc_api.hip')
-DEPS = [os.path.join(HERE, 'csrc', f) for f in
-        ('nxc_api.hip', 'nxc_kernels.hpp', 'nxc_device.hpp', 'nxc_math.hpp', 'nxc_log_table.hpp',
-         'nxc_desc_check.hpp', 'nxc_camera_check.hpp', 'nxc_source_limits.hpp')]
+# everything under csrc/ is compiled into the library: an edit to any of it rebuilds
+DEPS = sorted(os.path.join(HERE, 'csrc', f) for f in os.listdir(os.path.dirname(SRC)))
 DEPS.append(os.path.join(os.path.dirname(HERE), 'include', 'nexoclom_hip.h'))
 OUT = os.path.join(HERE, 'lib', 'libnexoclom_hip.so')
 # the same library with NumPy's two roundings per tableau term (rk5.py:33-35,41-43) instead of the

@@ -26,6 +26,7 @@
 #include "../../include/nexoclom_hip.h"
 #include "nxc_camera_check.hpp"
 #include "nxc_desc_check.hpp"
+#include "nxc_image_block.hpp"
 #include "nxc_kernels.hpp"
 #include "nxc_log_table.hpp"
 
@@ -235,11 +236,14 @@ int pack_lut(const double *xp, const double *fp, int64_t n, PackedLut &out, cons
     return NXC_OK;
 }
 
-// The descriptor of a packed table that starts at byte `base` of the LDS block.
-LutDesc placed_lut(LutDesc d, size_t base)
+// The g-value tables of an image-shaped descriptor, packed
+int pack_lines(int n_lines, const double *const *v, const double *const *g, const int64_t *n, PackedLut *out)
 {
-    d.rec += (int)base; d.fs += (int)base; d.cell += (int)base;
-    return d;
+    for (int l = 0; l < n_lines; l++) {
+        int rc = pack_lut(v[l], g[l], n[l], out[l], "g-value table");
+        if (rc) return rc;
+    }
+    return NXC_OK;
 }
 
 // Largest double x with sqrt(x) <= e (host sqrt is correctly rounded): r2 > x <=> sqrt(r2) > e,
@@ -335,9 +339,7 @@ struct nxc_handle {
     int force_lut_cells = 0;                     // cells per node force_lut was packed with
     std::vector<unsigned char> image_part;       // lines, then xedges, zedges
     LdsHeader header{};                          // host copy of the blob's first bytes
-    LutDesc line_local[NXC_MAX_LINES]{};         // relative to the table's own start ...
-    size_t line_start[NXC_MAX_LINES]{};          // ... which sits at this offset of image_part
-    int64_t xedges_local = 0, zedges_local = 0;
+    ImageBlock<LutDesc> image_block;             // where image_part's pieces sit
     unsigned char *d_blob = nullptr;
     size_t blob_cap = 0, force_bytes = 0, all_bytes = 0;
     unsigned char *d_blob_img = nullptr;         // [LdsHeader | image part] for the kernels that bin
@@ -683,13 +685,7 @@ int upload_blob(nxc_handle *h)
     int rc = ensure(reinterpret_cast<void **>(&h->d_blob), &h->blob_cap, h->all_bytes);
     if (rc) return rc;
     h->F.tab = placed_lut(h->force_lut.desc, hb);
-    if (h->have_image) {
-        for (int l = 0; l < h->G.n_lines; l++) {
-            h->G.line[l] = placed_lut(h->line_local[l], hb + fb + h->line_start[l]);
-        }
-        h->G.xedges_off = h->xedges_local + (int64_t)(hb + fb);
-        h->G.zedges_off = h->zedges_local + (int64_t)(hb + fb);
-    }
+    if (h->have_image) place_image_block(h->image_block, hb + fb, h->G);
     h->header.G = h->G;
     HIPCHK(hipMemcpyAsync(h->d_blob, &h->header, sizeof(LdsHeader), hipMemcpyHostToDevice,
                           h->stream));
@@ -702,10 +698,7 @@ int upload_blob(nxc_handle *h)
         // the same image tables right behind the header: k_image stages 45 KB instead of 100+, so
         // that several of its workgroups fit a CU (it was one 256-thread group per CU)
         LdsHeader hdr = h->header;
-        for (int l = 0; l < h->G.n_lines; l++)
-            hdr.G.line[l] = placed_lut(h->line_local[l], hb + h->line_start[l]);
-        hdr.G.xedges_off = h->xedges_local + (int64_t)hb;
-        hdr.G.zedges_off = h->zedges_local + (int64_t)hb;
+        place_image_block(h->image_block, hb, hdr.G);
         h->img_bytes = hb + ib;
         rc = ensure(reinterpret_cast<void **>(&h->d_blob_img), &h->blob_img_cap, h->img_bytes);
         if (rc) return rc;
@@ -1469,166 +1462,156 @@ int image_run_tiles(nxc_handle *h, const TilePlan &tp, int64_t p, const T *dx, c
     return NXC_OK;
 }
 
+// An occupancy-sized, grid-stride pass over p stored samples: as many workgroups as the chip holds
+// at once (never more than the samples fill), each striding over the samples; timed and waited for.
+template <class K, class... Args>
+int launch_sample_pass(nxc_handle *h, K kernel, int block, size_t lds_bytes, int64_t p, Args... args)
+{
+    int per_cu = 0, rc;
+    if ((rc = prep_kernel(kernel, lds_bytes))) return rc;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds_bytes));
+    int64_t grid = (int64_t)h->n_cu * (per_cu > 0 ? per_cu : 1);
+    grid = std::max<int64_t>(1, std::min<int64_t>(grid, (p + block - 1) / block));
+    if ((rc = begin_timed(h))) return rc;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), lds_bytes, h->stream, args...);
+    HIPCHK(hipGetLastError());
+    if ((rc = end_timed(h))) return rc;
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+}
+
 // a-6..a-8 over samples on the device
 // below this the two launches do not pay (measured: 2^16 samples 0.027 ms either way, 2^18 0.055
 // against 0.092, 2^23 0.18 against 0.31, 2^26 0.64 against 1.57)
 constexpr int64_t NXC_TILE_MIN_SAMPLES = int64_t(1) << 17;
-template <typename T>
-int image_run(nxc_handle *h, int64_t p, const T *dx, const T *dy, const T *dz, const T *dvy,
-              const T *dfrac)
-{
-    int rc, per_cu = 0;
-    TilePlan tp;
-    const bool fits = tile_plan(h, &tp);
-    if (h->image_mode == 2 && !fits)
-        return fail(NXC_ERR_ARG, "this image does not fit the tiled path (too many pixels)");
-    if (fits && (h->image_mode == 2 || (h->image_mode == 0 && p >= NXC_TILE_MIN_SAMPLES))) {
-        // float32 samples (stored rows, the down-cast image) leave the weight to pass 2 when the
-        // image tables fit a CU's LDS next to a tile
-        const bool f32_values = sizeof(T) == 4 || h->header.G.downcast_f32 != 0;
-        const bool room = ((h->img_bytes + 15) & ~size_t(15)) + (size_t)NXC_TILE_PIXELS * 12 <= 160 * 1024;
-        const bool defer = f32_values && room;
-#define NXC_TILES_CASE(C)                                                                       \
-        case C:                                                                                 \
-            return defer ? image_run_tiles<T, true, C>(h, tp, p, dx, dy, dz, dvy, dfrac)        \
-                         : image_run_tiles<T, false, C>(h, tp, p, dx, dy, dz, dvy, dfrac);
-        switch (tp.cap) {
-            NXC_TILES_CASE(256)
-            NXC_TILES_CASE(128)
-            NXC_TILES_CASE(64)
-        default:
-            return fail(NXC_ERR_STATE, "tile plan with an unknown chunk size");
-        }
-#undef NXC_TILES_CASE
-    }
-    if ((rc = prep_kernel(k_image<T>, h->img_bytes))) return rc;
-    // as many 1024-thread groups as fit a CU (two for Na's 45 KB of tables), each staging the
-    // tables once and striding over the samples
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_image<T>, NXC_IMAGE_BLOCK,
-                                                        h->img_bytes));
-    int64_t grid = (int64_t)h->n_cu * (per_cu > 0 ? per_cu : 1);
-    grid = std::max<int64_t>(1, std::min<int64_t>(grid, (p + NXC_IMAGE_BLOCK - 1) / NXC_IMAGE_BLOCK));
-    if ((rc = begin_timed(h))) return rc;
-    hipLaunchKernelGGL(k_image<T>, dim3((unsigned)grid), dim3(NXC_IMAGE_BLOCK), h->img_bytes,
-                       h->stream, h->d_blob_img, (int64_t)h->img_bytes, p, dx, dy, dz, dvy, dfrac,
-                       h->d_image, h->d_ctr);
-    HIPCHK(hipGetLastError());
-    if ((rc = end_timed(h))) return rc;
-    HIPCHK(stream_sync(h));
-    return NXC_OK;
-}
-
-// ... over a sample view
 int image_run(nxc_handle *h, const Samples &s)
 {
-    return with_sample_types(s, [&](auto t, auto) {
+    return with_sample_types(s, [&](auto t, auto) -> int {
         using T = decltype(t);
-        return image_run(h, s.n, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3), s.col<T>(4));
+        const int64_t p = s.n;
+        const T *dx = s.col<T>(0), *dy = s.col<T>(1), *dz = s.col<T>(2), *dvy = s.col<T>(3),
+                *dfrac = s.col<T>(4);
+        TilePlan tp;
+        const bool fits = tile_plan(h, &tp);
+        if (h->image_mode == 2 && !fits)
+            return fail(NXC_ERR_ARG, "this image does not fit the tiled path (too many pixels)");
+        if (fits && (h->image_mode == 2 || (h->image_mode == 0 && p >= NXC_TILE_MIN_SAMPLES))) {
+            // float32 samples (stored rows, the down-cast image) leave the weight to pass 2 when the
+            // image tables fit a CU's LDS next to a tile
+            const bool f32_values = sizeof(T) == 4 || h->header.G.downcast_f32 != 0;
+            const bool room = ((h->img_bytes + 15) & ~size_t(15)) + (size_t)NXC_TILE_PIXELS * 12 <= 160 * 1024;
+            const bool defer = f32_values && room;
+#define NXC_TILES_CASE(C)                                                                       \
+            case C:                                                                             \
+                return defer ? image_run_tiles<T, true, C>(h, tp, p, dx, dy, dz, dvy, dfrac)    \
+                             : image_run_tiles<T, false, C>(h, tp, p, dx, dy, dz, dvy, dfrac);
+            switch (tp.cap) {
+                NXC_TILES_CASE(256)
+                NXC_TILES_CASE(128)
+                NXC_TILES_CASE(64)
+            default:
+                return fail(NXC_ERR_STATE, "tile plan with an unknown chunk size");
+            }
+#undef NXC_TILES_CASE
+        }
+        // as many 1024-thread groups as fit a CU (two for Na's 45 KB of tables), each staging the
+        // tables once and striding over the samples
+        return launch_sample_pass(h, k_image<T>, NXC_IMAGE_BLOCK, h->img_bytes, p, h->d_blob_img,
+                                  (int64_t)h->img_bytes, p, dx, dy, dz, dvy, dfrac, h->d_image, h->d_ctr);
     });
 }
 
-// ... over samples in host memory, 64-bit or as save() keeps them (32-bit)
-template <typename T>
-int image_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T *z, const T *vy,
-                     const T *frac)
-{
-    if (!h || !h->have_image) return fail(NXC_ERR_STATE, "nxc_set_image has not been called");
-    HIPCHK(hipSetDevice(h->device));
-    if (p < 0 || (p && (!x || !y || !z || !vy || !frac))) return fail(NXC_ERR_ARG, "bad arguments");
-    HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
-    if (p == 0) return NXC_OK;
-    const T *cols[5] = {x, y, z, vy, frac};
-    Samples s;
-    int rc = samples_upload(h, &h->d_samples, &h->samples_cap, p, cols, nullptr, &s);
-    return rc ? rc : image_run(h, s);
-}
-
-// ModelDensity over samples on the device (k_density)
-template <typename T>
-int density_run(nxc_handle *h, int64_t p, const T *dx, const T *dy, const T *dz, const T *dfrac)
-{
-    if (p == 0 || h->dens_q == 0) return NXC_OK;
-    int per_cu = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_density<T>, NXC_BLOCK, 0));
-    int64_t grid = (int64_t)h->n_cu * (per_cu > 0 ? per_cu : 1);
-    grid = std::max<int64_t>(1, std::min<int64_t>(grid, (p + NXC_BLOCK - 1) / NXC_BLOCK));
-    int rc;
-    if ((rc = begin_timed(h))) return rc;
-    hipLaunchKernelGGL(k_density<T>, dim3((unsigned)grid), dim3(NXC_BLOCK), 0, h->stream, h->dens,
-                       p, dx, dy, dz, dfrac, h->d_dens_pts, h->d_dens_cell, h->d_dens_acc);
-    HIPCHK(hipGetLastError());
-    if ((rc = end_timed(h))) return rc;
-    HIPCHK(stream_sync(h));
-    return NXC_OK;
-}
-
-// ... over a sample view (vy is not read)
+// ModelDensity over samples on the device (k_density; vy is not read)
 int density_run(nxc_handle *h, const Samples &s)
 {
-    return with_sample_types(s, [&](auto t, auto) {
+    return with_sample_types(s, [&](auto t, auto) -> int {
         using T = decltype(t);
-        return density_run(h, s.n, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(4));
+        return launch_sample_pass(h, k_density<T>, NXC_BLOCK, 0, s.n, h->dens, s.n, s.col<T>(0),
+                                  s.col<T>(1), s.col<T>(2), s.col<T>(4), h->d_dens_pts,
+                                  h->d_dens_cell, h->d_dens_acc);
     });
-}
-
-// ... over samples in host memory, 64-bit or as save() keeps them (32-bit)
-template <typename T>
-int density_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T *z, const T *frac)
-{
-    if (!h || !h->have_density) return fail(NXC_ERR_STATE, "nxc_density_set has not been called");
-    if (p < 0 || (p && (!x || !y || !z || !frac))) return fail(NXC_ERR_ARG, "bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    if (p == 0 || h->dens_q == 0) return NXC_OK;
-    const T *cols[5] = {x, y, z, nullptr, frac};
-    Samples s;
-    int rc = samples_upload(h, &h->d_samples, &h->samples_cap, p, cols, nullptr, &s);
-    return rc ? rc : density_run(h, s);
 }
 
 // CameraImage over samples on the device (k_camera)
-template <typename T>
-int camera_run(nxc_handle *h, int64_t p, const T *dx, const T *dy, const T *dz, const T *dvy,
-               const T *dfrac)
-{
-    int per_cu = 0, rc;
-    if ((rc = prep_kernel(k_camera<T>, h->cam_bytes))) return rc;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_camera<T>, NXC_CAMERA_BLOCK,
-                                                        h->cam_bytes));
-    int64_t grid = (int64_t)h->n_cu * (per_cu > 0 ? per_cu : 1);
-    grid = std::max<int64_t>(1, std::min<int64_t>(grid, (p + NXC_CAMERA_BLOCK - 1) / NXC_CAMERA_BLOCK));
-    if ((rc = begin_timed(h))) return rc;
-    hipLaunchKernelGGL(k_camera<T>, dim3((unsigned)grid), dim3(NXC_CAMERA_BLOCK), h->cam_bytes,
-                       h->stream, h->cam, h->d_blob_cam, (int64_t)h->cam_bytes, p, dx, dy, dz, dvy,
-                       dfrac, h->d_cam_image, h->d_ctr);
-    HIPCHK(hipGetLastError());
-    if ((rc = end_timed(h))) return rc;
-    HIPCHK(stream_sync(h));
-    return NXC_OK;
-}
-
-// ... over a sample view
 int camera_run(nxc_handle *h, const Samples &s)
 {
-    return with_sample_types(s, [&](auto t, auto) {
+    return with_sample_types(s, [&](auto t, auto) -> int {
         using T = decltype(t);
-        return camera_run(h, s.n, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3), s.col<T>(4));
+        return launch_sample_pass(h, k_camera<T>, NXC_CAMERA_BLOCK, h->cam_bytes, s.n, h->cam,
+                                  h->d_blob_cam, (int64_t)h->cam_bytes, s.n, s.col<T>(0), s.col<T>(1),
+                                  s.col<T>(2), s.col<T>(3), s.col<T>(4), h->d_cam_image, h->d_ctr);
     });
 }
 
-// ... over samples in host memory, 64-bit or as save() keeps them (32-bit)
-template <typename T>
-int camera_accumulate(nxc_handle *h, int64_t p, const T *x, const T *y, const T *z, const T *vy,
-                      const T *frac)
+// What tells one consumer of stored samples from another at its entry points
+struct SampleConsumer {
+    bool nxc_handle::*have;                      // its nxc_*_set has been called ...
+    const char *unset;                           // ... or this is the NXC_ERR_STATE message
+    bool needs_vy, clears_ctr;                   // reads the vy column; zeroes d_ctr per accepted call
+    bool (*idle)(const nxc_handle *);            // nothing to add to, whatever the samples (or null)
+    int (*run)(nxc_handle *, const Samples &);
+};
+const SampleConsumer IMAGE_SAMPLES = {&nxc_handle::have_image, "nxc_set_image has not been called",
+                                      true, true, nullptr, image_run};
+const SampleConsumer DENSITY_SAMPLES = {&nxc_handle::have_density, "nxc_density_set has not been called",
+                                        false, false,
+                                        [](const nxc_handle *h) { return h->dens_q == 0; }, density_run};
+const SampleConsumer CAMERA_SAMPLES = {&nxc_handle::have_camera, "nxc_camera_set has not been called",
+                                       true, true, nullptr, camera_run};
+
+// What every accepted call does, samples or none
+int begin_sample_pass(nxc_handle *h, const SampleConsumer &c)
 {
-    if (!h || !h->have_camera) return fail(NXC_ERR_STATE, "nxc_camera_set has not been called");
     HIPCHK(hipSetDevice(h->device));
-    if (p < 0 || (p && (!x || !y || !z || !vy || !frac))) return fail(NXC_ERR_ARG, "bad arguments");
-    HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
-    if (p == 0) return NXC_OK;
-    const T *cols[5] = {x, y, z, vy, frac};
-    Samples s;
-    int rc = samples_upload(h, &h->d_samples, &h->samples_cap, p, cols, nullptr, &s);
-    return rc ? rc : camera_run(h, s);
+    if (c.clears_ctr) HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
+    return NXC_OK;
+}
+
+// nxc_X_accumulate / nxc_X_accumulate_f32: samples in host memory, 64-bit or as save() keeps them
+// (32-bit), go to the handle's staging buffer first
+template <typename T>
+int accumulate_columns(nxc_handle *h, const SampleConsumer &c, int64_t p, const T *x, const T *y,
+                       const T *z, const T *vy, const T *frac)
+{
+    return guarded([&]() -> int {
+        if (!h || !(h->*c.have)) return fail(NXC_ERR_STATE, c.unset);
+        if (p < 0 || (p && (!x || !y || !z || (c.needs_vy && !vy) || !frac)))
+            return fail(NXC_ERR_ARG, "bad arguments");
+        int rc = begin_sample_pass(h, c);
+        if (rc || p == 0 || (c.idle && c.idle(h))) return rc;
+        const T *cols[5] = {x, y, z, c.needs_vy ? vy : nullptr, frac};
+        Samples s;
+        rc = samples_upload(h, &h->d_samples, &h->samples_cap, p, cols, nullptr, &s);
+        return rc ? rc : c.run(h, s);
+    });
+}
+
+// nxc_X_accumulate_rows: rows [first, first + count) of a store, read where they are
+int accumulate_rows(nxc_handle *h, const SampleConsumer &c, const nxc_rows *r, int64_t first, int64_t count)
+{
+    return guarded([&]() -> int {
+        if (!h || !(h->*c.have)) return fail(NXC_ERR_STATE, c.unset);
+        Samples s;
+        int rc = samples_from_rows(h, r, first, count, 0, &s);
+        if (rc || (rc = begin_sample_pass(h, c)) || count == 0 || (c.idle && c.idle(h))) return rc;
+        return c.run(h, s);
+    });
+}
+
+// n {first, second} fp64 pairs of the device (see image_add_pairs), split into the outputs that
+// are not null
+template <typename T>
+int download_pairs(nxc_handle *h, const double *d_pairs, size_t n, double *first, T *second)
+{
+    std::vector<double> both(2 * n);
+    HIPCHK(hipMemcpyAsync(both.data(), d_pairs, both.size() * sizeof(double), hipMemcpyDeviceToHost,
+                          h->stream));
+    HIPCHK(stream_sync(h));
+    for (size_t q = 0; q < n; q++) {
+        if (first) first[q] = both[2 * q];
+        if (second) second[q] = (T)both[2 * q + 1];         // counts: integer-valued, < 2^53
+    }
+    return NXC_OK;
 }
 
 // ---- LOSResultFitted -------------------------------------------------------------------------
@@ -2106,33 +2089,16 @@ int nxc_set_image(nxc_handle *h, const nxc_image_desc *d)
     G.vrplanet = d->vrplanet;
     G.apix_cm2 = d->apix_cm2;
     G.quantity = d->quantity;
-    G.n_lines = nl;
     G.downcast_f32 = d->downcast_f32 ? 1 : 0;
 #ifdef NXC_EXPERIMENT_KNOBS
     if (const char *dbg = std::getenv("NXC_DEBUG_IMAGE")) G.dbg = std::atoi(dbg);
 #endif
-    G.nx = (int)d->nx;
-    G.nz = (int)d->nz;
     G.x_is_x = (d->M[0] == 1.0 && d->M[1] == 0.0 && d->M[2] == 0.0 && d->M[3] == 0.0 &&
                 d->M[6] == 0.0) ? 1 : 0;
-    for (int l = 0; l < nl; l++) {
-        PackedLut lut;
-        int rc = pack_lut(d->line_v[l], d->line_g[l], d->line_n[l], lut, "g-value table");
-        if (rc) return rc;
-        h->line_local[l] = lut.desc;
-        h->line_start[l] = part.size();
-        part.insert(part.end(), lut.bytes.begin(), lut.bytes.end());
-    }
-    h->xedges_local = (int64_t)part.size();
-    const unsigned char *xe = reinterpret_cast<const unsigned char *>(d->xedges);
-    part.insert(part.end(), xe, xe + (d->nx + 1) * sizeof(double));
-    h->zedges_local = (int64_t)part.size();
-    const unsigned char *ze = reinterpret_cast<const unsigned char *>(d->zedges);
-    part.insert(part.end(), ze, ze + (d->nz + 1) * sizeof(double));
-    G.x_lo = d->xedges[0];
-    G.x_inv_step = (double)d->nx / (d->xedges[d->nx] - d->xedges[0]);
-    G.z_lo = d->zedges[0];
-    G.z_inv_step = (double)d->nz / (d->zedges[d->nz] - d->zedges[0]);
+    PackedLut luts[NXC_MAX_LINES];
+    int rc;
+    if ((rc = pack_lines(nl, d->line_v, d->line_g, d->line_n, luts))) return rc;
+    h->image_block = append_image_block(part, G, d->nx, d->nz, d->xedges, d->zedges, nl, luts);
     h->image_part = std::move(part);
     h->G = G;
     h->have_image = true;
@@ -2144,8 +2110,7 @@ int nxc_set_image(nxc_handle *h, const nxc_image_desc *d)
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&h->d_image), 2 * npix * sizeof(double)));
         h->npix = npix;
     }
-    int rc = upload_blob(h);
-    if (rc) return rc;
+    if ((rc = upload_blob(h))) return rc;
     return nxc_image_clear(h);
     });
 }
@@ -2303,19 +2268,10 @@ int nxc_image_mode(nxc_handle *h, int mode, int tile_pixels, int64_t slab_sample
 
 int nxc_image_download(nxc_handle *h, double *image, uint64_t *counts)
 {
+    return guarded([&]() -> int {
     if (!h || !h->have_image) return fail(NXC_ERR_STATE, "nxc_set_image has not been called");
     HIPCHK(hipSetDevice(h->device));
-    return guarded([&]() -> int {
-    // the device keeps {weight sum, count} interleaved in fp64 (see image_add_pairs); split here
-    std::vector<double> both(2 * h->npix);
-    HIPCHK(hipMemcpyAsync(both.data(), h->d_image, 2 * h->npix * sizeof(double),
-                          hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(stream_sync(h));
-    for (size_t q = 0; q < h->npix; q++) {
-        if (image) image[q] = both[2 * q];
-        if (counts) counts[q] = (uint64_t)both[2 * q + 1];      // integer-valued, < 2^53
-    }
-    return NXC_OK;
+    return download_pairs(h, h->d_image, h->npix, image, counts);
     });
 }
 
@@ -2941,15 +2897,7 @@ int nxc_rows_download(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t c
 
 int nxc_image_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
 {
-    return guarded([&]() -> int {
-    if (!h || !h->have_image) return fail(NXC_ERR_STATE, "nxc_set_image has not been called");
-    Samples s;
-    int rc = samples_from_rows(h, r, first, count, 0, &s);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
-    return count ? image_run(h, s) : NXC_OK;
-    });
+    return accumulate_rows(h, IMAGE_SAMPLES, r, first, count);
 }
 
 int nxc_los_accumulate_rows(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
@@ -3022,25 +2970,18 @@ int nxc_density_set(nxc_handle *h, const nxc_density_desc *d)
 int nxc_density_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
                            const double *z, const double *frac)
 {
-    return guarded([&]() -> int { return density_accumulate(h, p, x, y, z, frac); });
+    return accumulate_columns<double>(h, DENSITY_SAMPLES, p, x, y, z, nullptr, frac);
 }
 
 int nxc_density_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
                                const float *z, const float *frac)
 {
-    return guarded([&]() -> int { return density_accumulate(h, p, x, y, z, frac); });
+    return accumulate_columns<float>(h, DENSITY_SAMPLES, p, x, y, z, nullptr, frac);
 }
 
 int nxc_density_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
 {
-    return guarded([&]() -> int {
-    if (!h || !h->have_density) return fail(NXC_ERR_STATE, "nxc_density_set has not been called");
-    Samples s;
-    int rc = samples_from_rows(h, r, first, count, 0, &s);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    return density_run(h, s);
-    });
+    return accumulate_rows(h, DENSITY_SAMPLES, r, first, count);
 }
 
 int nxc_density_download(nxc_handle *h, double *sum_frac, double *count)
@@ -3050,15 +2991,7 @@ int nxc_density_download(nxc_handle *h, double *sum_frac, double *count)
     if (h->dens_q && (!sum_frac || !count)) return fail(NXC_ERR_ARG, "bad arguments");
     if (h->dens_q == 0) return NXC_OK;
     HIPCHK(hipSetDevice(h->device));
-    std::vector<double> pair((size_t)h->dens_q * 2);
-    HIPCHK(hipMemcpyAsync(pair.data(), h->d_dens_acc, pair.size() * 8, hipMemcpyDeviceToHost,
-                          h->stream));
-    HIPCHK(stream_sync(h));
-    for (int64_t j = 0; j < h->dens_q; j++) {
-        sum_frac[j] = pair[2 * j];
-        count[j] = pair[2 * j + 1];
-    }
-    return NXC_OK;
+    return download_pairs(h, h->d_dens_acc, (size_t)h->dens_q, sum_frac, count);
     });
 }
 
@@ -3071,34 +3004,18 @@ int nxc_camera_set(nxc_handle *h, const nxc_camera_desc *d)
     if (!why.empty()) return fail(NXC_ERR_ARG, why);
     HIPCHK(hipSetDevice(h->device));
     const int nl = d->quantity == 1 ? d->n_lines : 0;
-    const size_t hb = NXC_HEADER_BYTES;
-    std::vector<unsigned char> blob(hb, 0);
+    std::vector<unsigned char> blob((size_t)NXC_HEADER_BYTES, 0);
     LdsHeader hdr = h->header;                 // nxc_log's table; the image's own G is replaced
     ImageK G{};
     std::memcpy(G.M, d->C, sizeof G.M);       // the basis, where the image keeps its rotation
     G.vrplanet = d->vrplanet;
     G.apix_cm2 = 1.0;                          // the per-sample area divides in camera_sample
     G.quantity = d->quantity;
-    G.n_lines = nl;
-    G.nx = (int)d->nx;
-    G.nz = (int)d->nz;
-    for (int l = 0; l < nl; l++) {
-        PackedLut lut;
-        int rc = pack_lut(d->line_v[l], d->line_g[l], d->line_n[l], lut, "g-value table");
-        if (rc) return rc;
-        G.line[l] = placed_lut(lut.desc, blob.size());
-        blob.insert(blob.end(), lut.bytes.begin(), lut.bytes.end());
-    }
-    G.xedges_off = (int64_t)blob.size();
-    const unsigned char *ue = reinterpret_cast<const unsigned char *>(d->uedges);
-    blob.insert(blob.end(), ue, ue + (d->nx + 1) * sizeof(double));
-    G.zedges_off = (int64_t)blob.size();
-    const unsigned char *ve = reinterpret_cast<const unsigned char *>(d->vedges);
-    blob.insert(blob.end(), ve, ve + (d->nz + 1) * sizeof(double));
-    G.x_lo = d->uedges[0];
-    G.x_inv_step = (double)d->nx / (d->uedges[d->nx] - d->uedges[0]);
-    G.z_lo = d->vedges[0];
-    G.z_inv_step = (double)d->nz / (d->vedges[d->nz] - d->vedges[0]);
+    PackedLut luts[NXC_MAX_LINES];
+    int rc;
+    if ((rc = pack_lines(nl, d->line_v, d->line_g, d->line_n, luts))) return rc;
+    place_image_block(append_image_block(blob, G, d->nx, d->nz, d->uedges, d->vedges, nl, luts),
+                      NXC_HEADER_BYTES, G);
     if (blob.size() > 160 * 1024)
         return fail(NXC_ERR_ARG, "nxc_camera_desc: tables and edges exceed the 160 KiB LDS of a gfx950 CU");
     hdr.G = G;
@@ -3110,7 +3027,6 @@ int nxc_camera_set(nxc_handle *h, const nxc_camera_desc *d)
 
     h->have_camera = false;
     const size_t npix = (size_t)d->nx * (size_t)d->nz;
-    int rc;
     if ((rc = ensure(reinterpret_cast<void **>(&h->d_blob_cam), &h->blob_cam_cap, blob.size())) ||
         (rc = ensure(reinterpret_cast<void **>(&h->d_cam_image), &h->cam_image_cap, 2 * npix * sizeof(double))))
         return rc;
@@ -3128,26 +3044,18 @@ int nxc_camera_set(nxc_handle *h, const nxc_camera_desc *d)
 int nxc_camera_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
                           const double *z, const double *vy, const double *frac)
 {
-    return guarded([&]() -> int { return camera_accumulate(h, p, x, y, z, vy, frac); });
+    return accumulate_columns(h, CAMERA_SAMPLES, p, x, y, z, vy, frac);
 }
 
 int nxc_camera_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
                               const float *z, const float *vy, const float *frac)
 {
-    return guarded([&]() -> int { return camera_accumulate(h, p, x, y, z, vy, frac); });
+    return accumulate_columns(h, CAMERA_SAMPLES, p, x, y, z, vy, frac);
 }
 
 int nxc_camera_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
 {
-    return guarded([&]() -> int {
-    if (!h || !h->have_camera) return fail(NXC_ERR_STATE, "nxc_camera_set has not been called");
-    Samples s;
-    int rc = samples_from_rows(h, r, first, count, 0, &s);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), h->stream));
-    return count ? camera_run(h, s) : NXC_OK;
-    });
+    return accumulate_rows(h, CAMERA_SAMPLES, r, first, count);
 }
 
 int nxc_camera_download(nxc_handle *h, double *image, uint64_t *counts)
@@ -3155,15 +3063,7 @@ int nxc_camera_download(nxc_handle *h, double *image, uint64_t *counts)
     return guarded([&]() -> int {
     if (!h || !h->have_camera) return fail(NXC_ERR_STATE, "nxc_camera_set has not been called");
     HIPCHK(hipSetDevice(h->device));
-    std::vector<double> both(2 * h->cam_npix);
-    HIPCHK(hipMemcpyAsync(both.data(), h->d_cam_image, both.size() * sizeof(double),
-                          hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(stream_sync(h));
-    for (size_t q = 0; q < h->cam_npix; q++) {
-        if (image) image[q] = both[2 * q];
-        if (counts) counts[q] = (uint64_t)both[2 * q + 1];      // integer-valued, < 2^53
-    }
-    return NXC_OK;
+    return download_pairs(h, h->d_cam_image, h->cam_npix, image, counts);
     });
 }
 
@@ -3665,13 +3565,13 @@ extern "C" int nxc_debug_var_trace(nxc_handle *h, unsigned long long *out)
 int nxc_image_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
                          const double *z, const double *vy, const double *frac)
 {
-    return guarded([&]() -> int { return image_accumulate(h, p, x, y, z, vy, frac); });
+    return accumulate_columns(h, IMAGE_SAMPLES, p, x, y, z, vy, frac);
 }
 
 int nxc_image_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
                              const float *z, const float *vy, const float *frac)
 {
-    return guarded([&]() -> int { return image_accumulate(h, p, x, y, z, vy, frac); });
+    return accumulate_columns(h, IMAGE_SAMPLES, p, x, y, z, vy, frac);
 }
 
 int nxc_los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,

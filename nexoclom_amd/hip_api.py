@@ -391,25 +391,14 @@ class Context:
         d = nxc_image_desc()
         d.M = (C.c_double*9)(*np.asarray(M, dtype=float).reshape(9))
         d.vrplanet, d.apix_cm2 = float(vrplanet), float(apix_cm2)
-        if quantity in ('column', 'density'):
-            d.quantity = 0
-        elif quantity in ('radiance', 'difrad'):
-            d.quantity = 1
-        else:
-            raise ValueError(f'{quantity} is invalid.')
+        d.quantity = self._quantity(quantity)
         d.downcast_f32 = int(bool(downcast_f32))
         xe, ze = _f64(xedges), _f64(zedges)
         d.nx, d.nz = len(xe)-1, len(ze)-1
         d.xedges, d.zedges = _p(xe), _p(ze)
         keep = [xe, ze]
         if d.quantity == 1:
-            if len(g_tables) > NXC_MAX_LINES:
-                raise ValueError('too many emission lines')
-            d.n_lines = len(g_tables)
-            for k, (v, g) in enumerate(g_tables):
-                v, g = _f64(v), _f64(g)
-                keep += [v, g]
-                d.line_n[k], d.line_v[k], d.line_g[k] = len(v), _p(v), _p(g)
+            self._fill_lines(d, g_tables, keep)
         self._check(self.lib.nxc_set_image(self._h, C.byref(d)))
         self.image_shape = (int(d.nx), int(d.nz))
 
@@ -743,12 +732,42 @@ class Context:
             raise HipError('the row store has been freed')
         return store._r
 
+    def _accumulate(self, entry_name, cols, rows):
+        """One consumer's pass over stored samples: ``rows = (RowStore, first, count)`` through
+        its ``_rows`` entry, else host columns through the entry of their width."""
+        if rows is not None:
+            store, first, count = rows
+            self._check(getattr(self.lib, entry_name + '_rows')(
+                self._h, self._rows_handle(store), C.c_int64(first), C.c_int64(count)))
+            return
+        suffix, ptrs, cols = self._columns(cols)
+        self._check(getattr(self.lib, entry_name + suffix)(self._h, C.c_int64(len(cols[0])), *ptrs))
+
+    QUANTITIES = {'column': 0, 'density': 0, 'radiance': 1, 'difrad': 1}
+
+    @classmethod
+    def _quantity(cls, name, allowed=QUANTITIES):
+        """nxc_image_desc.quantity / nxc_camera_desc.quantity of a quantity's name"""
+        if name not in allowed:
+            raise ValueError(f'{name} is invalid.')
+        return cls.QUANTITIES[name]
+
+    @staticmethod
+    def _fill_lines(desc, g_tables, keep):
+        """The g-value tables [(velocities, g)] into a descriptor's line_n / line_v / line_g;
+        ``keep`` collects the arrays the descriptor then points into."""
+        if len(g_tables) > NXC_MAX_LINES:
+            raise ValueError('too many emission lines')
+        desc.n_lines = len(g_tables)
+        for k, (v, g) in enumerate(g_tables):
+            v, g = _f64(v), _f64(g)
+            keep += [v, g]
+            desc.line_n[k], desc.line_v[k], desc.line_g[k] = len(v), _p(v), _p(g)
+
     # -- a-6..a-8 ---------------------------------------------------------------------------
     def image_accumulate(self, x, y, z, vy, frac):
         """Bin stored samples given as host columns (float32 ones go over as they are)."""
-        suffix, ptrs, cols = self._columns((x, y, z, vy, frac))
-        self._check(getattr(self.lib, 'nxc_image_accumulate' + suffix)(
-            self._h, C.c_int64(len(cols[0])), *ptrs))
+        self._accumulate('nxc_image_accumulate', (x, y, z, vy, frac), None)
 
     IMAGE_MODES = {'auto': 0, 'atomics': 1, 'tiles': 2}
 
@@ -763,8 +782,7 @@ class Context:
     def image_accumulate_rows(self, store, first=0, count=None):
         """Bin rows [first, first + count) of a RowStore: no host round trip."""
         count = store.total - first if count is None else int(count)
-        self._check(self.lib.nxc_image_accumulate_rows(self._h, self._rows_handle(store),
-                                                       C.c_int64(first), C.c_int64(count)))
+        self._accumulate('nxc_image_accumulate', None, (store, first, count))
 
     # -- f-1: spacecraft lines of sight ------------------------------------------------------
     def los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables,
@@ -796,11 +814,7 @@ class Context:
         d.dphi, d.sin_dphi, d.sin_2dphi, d.cos_threshold = dphi, sin_dphi, sin_2dphi, cos_threshold
         d.vrplanet, d.unit_cm = float(vrplanet), float(unit_cm)
         keep = []
-        d.n_lines = len(g_tables)
-        for k, (v, g) in enumerate(g_tables):
-            v, g = _f64(v), _f64(g)
-            keep += [v, g]
-            d.line_n[k], d.line_v[k], d.line_g[k] = len(v), _p(v), _p(g)
+        Context._fill_lines(d, g_tables, keep)
         lad = _f64(ladder)
         keep.append(lad)
         d.n_ladder, d.ladder = len(lad), _p(lad)
@@ -858,14 +872,7 @@ class Context:
     def density_accumulate(self, x=None, y=None, z=None, frac=None, rows=None):
         """Add samples to the per-point sums: four host columns (float32 ones go over as they
         are and are widened on the device), or ``rows = (RowStore, first, count)``."""
-        if rows is not None:
-            store, first, count = rows
-            self._check(self.lib.nxc_density_accumulate_rows(
-                self._h, self._rows_handle(store), C.c_int64(first), C.c_int64(count)))
-            return
-        suffix, ptrs, cols = self._columns((x, y, z, frac))
-        self._check(getattr(self.lib, 'nxc_density_accumulate' + suffix)(
-            self._h, C.c_int64(len(cols[0])), *ptrs))
+        self._accumulate('nxc_density_accumulate', (x, y, z, frac), rows)
 
     def density_download(self):
         """(frac sums, counts) per indexed point, float64, in the index's point order."""
@@ -884,38 +891,20 @@ class Context:
         d.o = (C.c_double*3)(*np.asarray(observer, dtype=float).reshape(3))
         d.C = (C.c_double*9)(*np.asarray(basis, dtype=float).reshape(9))
         d.vrplanet, d.pix_area_cm2 = float(vrplanet), float(pix_area_cm2)
-        if quantity == 'column':
-            d.quantity = 0
-        elif quantity == 'radiance':
-            d.quantity = 1
-        else:
-            raise ValueError(f'{quantity} is invalid.')
+        d.quantity = self._quantity(quantity, ('column', 'radiance'))
         ue, ve = _f64(uedges), _f64(vedges)
         d.nx, d.nz = len(ue)-1, len(ve)-1
         d.uedges, d.vedges = _p(ue), _p(ve)
         keep = [ue, ve]
         if d.quantity == 1:
-            if len(g_tables) > NXC_MAX_LINES:
-                raise ValueError('too many emission lines')
-            d.n_lines = len(g_tables)
-            for k, (v, g) in enumerate(g_tables):
-                v, g = _f64(v), _f64(g)
-                keep += [v, g]
-                d.line_n[k], d.line_v[k], d.line_g[k] = len(v), _p(v), _p(g)
+            self._fill_lines(d, g_tables, keep)
         self._check(self.lib.nxc_camera_set(self._h, C.byref(d)))
         self.camera_shape = (int(d.nx), int(d.nz))
 
     def camera_accumulate(self, x=None, y=None, z=None, vy=None, frac=None, rows=None):
         """Add samples to the camera image: five host columns (float32 ones go over as they are
         and are widened on the device), or ``rows = (RowStore, first, count)``."""
-        if rows is not None:
-            store, first, count = rows
-            self._check(self.lib.nxc_camera_accumulate_rows(
-                self._h, self._rows_handle(store), C.c_int64(first), C.c_int64(count)))
-            return
-        suffix, ptrs, cols = self._columns((x, y, z, vy, frac))
-        self._check(getattr(self.lib, 'nxc_camera_accumulate' + suffix)(
-            self._h, C.c_int64(len(cols[0])), *ptrs))
+        self._accumulate('nxc_camera_accumulate', (x, y, z, vy, frac), rows)
 
     def camera_download(self):
         """(image (nx, nz) float64, packet counts (nx, nz) uint64) of the camera."""

@@ -89,6 +89,20 @@ def test_kernel_matches_kdtree_on_host_columns(ctx, dtype):
     assert np.array_equal(got[1], [0, 0, 0]) and np.array_equal(got[0], [0, 0, 0])
 
 
+def test_second_trip_of_the_grid_stride_loop(ctx):
+    """2^20 + 65 rows: more than the 256 CUs x 8 workgroups x 256 threads that one full grid of
+    k_density holds at most on an MI355X, so the workgroups stride on to a ragged second trip."""
+    rng = np.random.default_rng(3)
+    p, dr = 2**20 + 65, 0.05
+    rows = rng.uniform(-1, 1, (p, 3))
+    frac = rng.uniform(0, 1, p)
+    pts = np.concatenate([rng.uniform(-1, 1, (300, 3)), rows[-3:]])
+    cols = (rows[:, 0], rows[:, 1], rows[:, 2], frac)
+    want = kdtree_sums(pts, dr, *cols)
+    check(device_sums(ctx, pts, dr, columns=cols), want)
+    assert want[1].sum() > 10_000 and want[1][-1] >= 1
+
+
 @pytest.mark.parametrize('narrow', [True, False])
 def test_kernel_matches_kdtree_on_row_stores(ctx, narrow):
     """Rows as Input.run leaves them in HBM (float32, what save() keeps) or 64-bit

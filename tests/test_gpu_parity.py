@@ -198,6 +198,32 @@ def test_image_kernel_matches_numpy_histogram(ctx, coracle):
     np.testing.assert_allclose(image, ref_img, rtol=1e-12, atol=0)
 
 
+def test_image_kernel_second_trip_of_the_grid_stride_loop(ctx):
+    """2^20 + 65 samples through k_image itself (image_mode 'atomics'): more than the 256 CUs x 2
+    workgroups x 1024 threads of one full grid on an MI355X hold, so every workgroup strides on to
+    a second trip, and the last trip is ragged."""
+    f = H.mercury_forces('Na', 1.3)
+    p = 2**20 + 65
+    X = H.random_cloud(p, 23)
+    x, y, z, vy, frac = X[:, 1], X[:, 2], X[:, 3], X[:, 5], X[:, 7]
+    im = H.image_setup(f, 'radiance', dims=(200, 120), width=(8., 6.))
+    ref_img, ref_cnt, _, _ = O.create_image(x, y, z, vy, frac, f.vrplanet, im['M'], 'radiance',
+                                            im['g_tables'], im['dims'], im['xrange'],
+                                            im['zrange'], im['apix'], matmul=False)
+    ctx.set_image(im['M'], f.vrplanet, im['apix'], 'radiance', im['xedges'], im['zedges'],
+                  im['g_tables'])
+    ctx.image_mode('atomics')
+    try:
+        ctx.image_accumulate(x, y, z, vy, frac)
+    finally:
+        ctx.image_mode('auto')
+    image, counts = ctx.image_download()
+    assert ctx.counters()['samples'] == p
+    assert ref_cnt.sum() > 100_000
+    assert np.array_equal(counts, ref_cnt.astype(np.uint64))
+    np.testing.assert_allclose(image, ref_img, rtol=1e-12, atol=0)
+
+
 @pytest.mark.parametrize('quantity', ['radiance', 'column'])
 def test_image_kernel_on_float32_samples_equals_the_restored_path(ctx, quantity):
     """nxc_image_accumulate_f32 (samples as Output.save() stores them) against restore()'s 64-bit

@@ -18,19 +18,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np                                            # noqa: E402
 from nexoclom_amd import CameraImage, Input, ModelImage, hip_api   # noqa: E402
+from nexoclom_amd.catalogue import sample_spans                    # noqa: E402
 
 WARMUP, ROUNDS = 3, 9
 
 
 def spans(inputs, ctx):
-    out = []
-    for run in inputs._catalogue:
-        store, first, count, _ = run.resident_rows(ctx)
-        if out and out[-1][0] is store and out[-1][1] + out[-1][2] == first:
-            out[-1] = (store, out[-1][1], out[-1][2] + count)
-        else:
-            out.append((store, first, count))
-    return out
+    """The row ranges the classes launch over (adjacent slices of a store merged)."""
+    return [span for _, span in sample_spans(inputs._catalogue, ctx)]
 
 
 def main():

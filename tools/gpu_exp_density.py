@@ -18,6 +18,7 @@ sys.path.insert(0, ROOT)
 import numpy as np                                            # noqa: E402
 from nexoclom_amd import Input, ModelDensity, hip_api          # noqa: E402
 from nexoclom_amd.ModelDensity import DensityIndex             # noqa: E402
+from nexoclom_amd.catalogue import sample_spans                # noqa: E402
 
 HBM_BPS = 6.3e12
 ATOMIC_RPS = 2.4e10
@@ -33,15 +34,8 @@ def point_sets():
 
 
 def spans(inputs, ctx):
-    """The row ranges ModelDensity launches over (adjacent slices of a store merged)."""
-    out = []
-    for run in inputs._catalogue:
-        store, first, count, _ = run.resident_rows(ctx)
-        if out and out[-1][0] is store and out[-1][1] + out[-1][2] == first:
-            out[-1] = (store, out[-1][1], out[-1][2] + count)
-        else:
-            out.append((store, first, count))
-    return out
+    """The row ranges the classes launch over (adjacent slices of a store merged)."""
+    return [span for _, span in sample_spans(inputs._catalogue, ctx)]
 
 
 def main():
