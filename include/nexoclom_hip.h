@@ -589,6 +589,37 @@ int nxc_density_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const f
 int nxc_density_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
 int nxc_density_download(nxc_handle *h, double *sum_frac, double *count);
 
+/* Velocity moments at the same points (EXTENSION: the reference stops at the density).  Each sample
+ * that counts for a point (the membership above) also adds, with f = frac and v = (vx, vy, vz)
+ * widened to fp64 as p and frac are, one rounding per operation and no contraction,
+ *     m1_a  = f * v_a             a  = x, y, z
+ *     m2_ab = (f * v_a) * v_b     ab = xx, yy, zz, xy, xz, yz
+ *     ff    = f * f
+ * to ten sums per point, kept in that order: m1x m1y m1z m2xx m2yy m2zz m2xy m2xz m2yz ff.  Nothing is
+ * filtered: a non-finite frac or velocity makes the sums of the points it counts for non-finite, as
+ * a non-finite frac does to sum_frac.  The order of addition is not fixed (device atomics).
+ *   nxc_density_moments_enable          after nxc_density_set: on != 0 allocates and zeroes the
+ *                                       moment sums of the Q points just set, 0 switches them off;
+ *                                       nxc_density_set switches them off again
+ *   nxc_density_moments_accumulate[_f32] adds P host samples to {sum_frac, count} AND the ten sums in
+ *                                       one pass (float32 ones widened as restore() does)
+ *   nxc_density_moments_accumulate_rows the same for rows [first, first + count) of a row store
+ *                                       (columns 1..7: x, y, z, vx, vy, vz, frac)
+ *   nxc_density_moments_download        sums[Q][10], in the index's (sorted) point order
+ * NXC_ERR_STATE names the missing call (nxc_density_set, then the enable); NXC_ERR_ARG for p < 0 or
+ * a null column with p > 0; p = 0 or Q = 0 adds nothing.  nxc_density_accumulate* keep adding to
+ * {sum_frac, count} only, enabled or not, and nxc_density_download keeps returning that pair. */
+int nxc_density_moments_enable(nxc_handle *h, int on);
+int nxc_density_moments_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                                   const double *z, const double *vx, const double *vy,
+                                   const double *vz, const double *frac);
+int nxc_density_moments_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                       const float *z, const float *vx, const float *vy,
+                                       const float *vz, const float *frac);
+int nxc_density_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first,
+                                        int64_t count);
+int nxc_density_moments_download(nxc_handle *h, double *sums);
+
 /* ---- CameraImage: perspective image from a position inside or near the cloud ----------------------
  * EXTENSION -- the reference images from infinity only (ModelImage.create_image); this is the same
  * weighting seen by a pinhole (gnomonic) camera at a finite distance.  Samples are x, y, z [R],

@@ -16,9 +16,16 @@ The membership test is query_ball_point's: with d = q - p in fp64,
 Kept quirk of the reference (ModelDensity.py:56): ``Vpix = 4/3/pi * dr**3`` in cm^3, i.e.
 (4/(3 pi)) dr^3 and not the volume of the ball (4 pi/3) dr^3.  The density is scaled by it as
 written.  Bokeh display is out of scope.
+
+EXTENSION (``moments=True``): the same pass also sums each hit's velocity moments
+(k_density_moments: ``MOMENT_COLUMNS`` per point, the products formed in fp64 as f * v_a,
+(f * v_a) * v_b and f * f), from which the bulk velocity, the velocity covariance, the kinetic
+temperature and the effective number of packets follow per point (``moments_from_sums``).
 """
 import numpy as np
 
+from . import constants as const
+from .atomicdata import atomicmass
 from .catalogue import sample_spans, shared_context
 from .units import Quantity
 
@@ -83,13 +90,47 @@ def vpix_cm3(dr, radius_km):
     return 4/3/np.pi*dr**3 * R_cm**3
 
 
+# the ten sums of ``moment_sums``, per point: f v_a, (f v_a) v_b, f f over the hits (f = frac)
+MOMENT_COLUMNS = ('m1x', 'm1y', 'm1z', 'm2xx', 'm2yy', 'm2zz', 'm2xy', 'm2xz', 'm2yz', 'ff')
+
+
+def moments_from_sums(s0, sums, unit_km, mass_kg):
+    """(velocity (Q, 3) [km/s], velocity_covariance (Q, 3, 3) [km^2/s^2], temperature (Q,) [K],
+    effective_packets (Q,)) from the frac sums ``s0`` (Q,) and the moment sums ``sums`` (Q, 10,
+    ``MOMENT_COLUMNS``, velocities in R/s with R = ``unit_km``):
+
+    u = S1 / S0, C_ab = S2_ab / S0 - u_a u_b, T = m (C_xx + C_yy + C_zz) / (3 k_B) with km^2/s^2
+    taken to m^2/s^2, effective_packets = S0^2 / sum(f^2).  A point whose S0 is not > 0 gets NaN
+    in the first three and 0 in the last."""
+    s0 = np.asarray(s0, dtype=np.float64)
+    sums = np.asarray(sums, dtype=np.float64).reshape(len(s0), 10)
+    ok = s0 > 0
+    with np.errstate(divide='ignore', invalid='ignore'):
+        u = sums[:, 0:3] / s0[:, None] * unit_km
+        second = sums[:, 3:9] / s0[:, None] * (unit_km*unit_km)
+        eff = np.where(ok, s0*s0 / sums[:, 9], 0.)
+    cov = np.empty((len(s0), 3, 3))
+    for col, (a, b) in enumerate(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))):
+        cov[:, a, b] = cov[:, b, a] = second[:, col] - u[:, a]*u[:, b]
+    temperature = mass_kg * (cov[:, 0, 0] + cov[:, 1, 1] + cov[:, 2, 2]) * 1e6 / (3*const.K_B)
+    u[~ok], cov[~ok], temperature[~ok] = np.nan, np.nan, np.nan
+    return u, cov, temperature, eff
+
+
 class ModelDensity:
-    def __init__(self, inputs, xpts, ypts, zpts, dr=0.05, *, cp=None, reduce='rccl',
-                 context=None, device=0):
+    def __init__(self, inputs, xpts, ypts, zpts, dr=0.05, moments=False, *, cp=None,
+                 reduce='rccl', context=None, device=0):
         """Number density at the points (xpts, ypts, zpts) [planet radii] from every catalogued
         Output of ``inputs`` (ModelDensity.py:18-85).  ``cp``: the control plane of a shared run
         (``Input.run(..., cp=cp)``): each rank sums its own Outputs, then the per-point sums and
-        the source totals are summed over the ranks before scaling."""
+        the source totals are summed over the ranks before scaling.
+
+        ``moments=True`` (EXTENSION) also fills, per point and in the planet-centred frame of the
+        rows: ``velocity`` (Q, 3) [km/s], ``velocity_covariance`` (Q, 3, 3) [km^2/s^2],
+        ``temperature`` (Q,) [K] and ``effective_packets`` (Q,) -- ``density /
+        sqrt(effective_packets)`` is the 1-sigma statistical error of ``density`` -- from
+        ``moment_sums`` (Q, 10; ``MOMENT_COLUMNS``), accumulated in the same pass over the rows.
+        A point without weight gets NaN, NaN, NaN and 0."""
         self.type = 'density'
         self.inputs = inputs
         self.origin = inputs.geometry.planet
@@ -106,6 +147,7 @@ class ModelDensity:
         self.packets = np.zeros(Q)
         self.totalsource = 0.
         self._ctx, self._device = context, device
+        self._moments = bool(moments)
         self.counters = {}
 
         self.outid, self.outputfiles, self.npackets, _ = inputs.search()
@@ -113,19 +155,30 @@ class ModelDensity:
         if self.npackets == 0 and not shared:
             raise RuntimeError('No packets found for these Inputs.')
         index = DensityIndex(np.stack(xyz, axis=1), dr)
-        sums, counts = self._accumulate(index)
+        sums, counts, moment_sums = self._accumulate(index, self._moments)
         self.density += index.scatter(sums, Q)
         self.packets += index.scatter(counts, Q)
+        if self._moments:
+            self.moment_sums = np.zeros((Q, 10))
+            self.moment_sums[index.order] = moment_sums
         if shared:
             from .distributed import allreduce_small, guarded
+            parts = [self.density, self.packets, [float(self.totalsource), float(self.npackets)]]
+            if self._moments:
+                parts.append(self.moment_sums.ravel())
             with guarded(cp, self.context()):
-                both = allreduce_small(np.concatenate([
-                    self.density, self.packets, [float(self.totalsource), float(self.npackets)]]),
-                    cp, self.context(), reduce)
+                both = allreduce_small(np.concatenate(parts), cp, self.context(), reduce)
             self.density, self.packets = both[:Q].copy(), both[Q:2*Q].copy()
             self.totalsource, self.npackets = float(both[2*Q]), int(round(both[2*Q + 1]))
+            if self._moments:
+                self.moment_sums = both[2*Q + 2:].reshape(Q, 10).copy()
             if self.npackets == 0:
                 raise RuntimeError('No packets found for these Inputs.')
+        if self._moments:        # quotients of the summed sums; self.density is still the frac sum
+            mass_kg = atomicmass(inputs.options.species).value * const.AMU
+            (self.velocity, self.velocity_covariance, self.temperature,
+             self.effective_packets) = moments_from_sums(self.density, self.moment_sums, unit_km,
+                                                         mass_kg)
         mod_rate = self.totalsource / inputs.options.endtime.value
         self.atoms_per_packet = 1e23 / mod_rate
         self.sourcerate = Quantity(1., '1e23/s')
@@ -136,13 +189,18 @@ class ModelDensity:
             self._ctx = shared_context(self.inputs, self._device)
         return self._ctx
 
-    def _accumulate(self, index):
-        """(frac sums, counts) per indexed point over this process's catalogue
+    def _accumulate(self, index, moments=False):
+        """(frac sums, counts, moment sums | None) per indexed point over this process's catalogue
         (ModelDensity.py:62-82).  Rows in HBM are read where they are, one launch per run of
-        adjacent slices of a store; other Outputs upload X's x, y, z, frac."""
+        adjacent slices of a store; other Outputs upload X's x, y, z, frac (with moments: and
+        vx, vy, vz)."""
         ctx = self.context()
         ctx.density_set(index.points, index.cell_start, index.origin, index.h, index.dr,
                         index.dims)
+        columns, add = ('x', 'y', 'z', 'frac'), ctx.density_accumulate
+        if moments:
+            ctx.density_moments_enable()
+            columns, add = ('x', 'y', 'z', 'vx', 'vy', 'vz', 'frac'), ctx.density_moments_accumulate
 
         def announced():
             for run in self.inputs._catalogue:
@@ -152,7 +210,7 @@ class ModelDensity:
 
         for kind, item in sample_spans(announced(), ctx):
             if kind == 'rows':
-                ctx.density_accumulate(rows=item)
+                add(rows=item)
             elif len(item.X) and 'x' in item.X:
-                ctx.density_accumulate(*(item.X[c].values for c in ('x', 'y', 'z', 'frac')))
-        return ctx.density_download()
+                add(*(item.X[c].values for c in columns))
+        return (*ctx.density_download(), ctx.density_moments_download() if moments else None)

@@ -307,7 +307,7 @@ struct nxc_pairs {
 struct Samples {
     bool f32 = false, index64 = true;
     int64_t n = 0, shift = 0;                // rows, index shift
-    const void *cols[5] = {};                // x, y, z, vy, frac (vy null where nobody reads it)
+    const void *cols[7] = {};                // x, y, z, vy, frac, vx, vz (null where nobody reads it)
     const void *index = nullptr;             // null where the entry allows it
     const nxc_rows *store = nullptr;         // stores: the store, column 0 of row 0 and the
     const void *col0 = nullptr;              // distance between columns (the fit's rows copy
@@ -424,6 +424,9 @@ struct nxc_handle {
     size_t dens_cell_cap = 0;
     double *d_dens_acc = nullptr;    // interleaved pair [Q][2], as the image's
     size_t dens_acc_cap = 0;
+    bool have_dens_mom = false;      // nxc_density_moments_enable since the last nxc_density_set
+    double *d_dens_mom = nullptr;    // the moment sums: [5][Q] 16-byte records (k_density_moments)
+    size_t dens_mom_cap = 0;
 
     // CameraImage (nxc_camera_set): the camera, its LDS blob [LdsHeader | g tables | u edges |
     // v edges] and its own {weight sum, count} image
@@ -1060,7 +1063,8 @@ int rows_check(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
 }
 
 // ---- sample views ------------------------------------------------------------------------------
-constexpr int ROW_SAMPLE_COLS[5] = {1, 2, 3, 5, 7};   // the store columns of x, y, z, vy, frac
+constexpr int N_SAMPLE_COLS = 7;
+constexpr int ROW_SAMPLE_COLS[N_SAMPLE_COLS] = {1, 2, 3, 5, 7, 4, 6};   // the store columns of x, y, z, vy, frac, vx, vz
 
 // rows [first, first + count) of a store (its index is int32 beside float32 rows, else int64)
 int samples_from_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count, int64_t shift,
@@ -1071,7 +1075,7 @@ int samples_from_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t c
     const size_t vsz = r->f32 ? 4 : 8;
     const char *c = static_cast<const char *>(r->d_cols) + (size_t)first * vsz;
     *s = Samples{};
-    for (int k = 0; k < 5; k++) s->cols[k] = c + (size_t)ROW_SAMPLE_COLS[k] * r->total * vsz;
+    for (int k = 0; k < N_SAMPLE_COLS; k++) s->cols[k] = c + (size_t)ROW_SAMPLE_COLS[k] * r->total * vsz;
     s->index = static_cast<const char *>(r->d_index) + (size_t)first * vsz;
     s->f32 = r->f32; s->index64 = !r->f32; s->n = count; s->shift = shift;
     s->store = r; s->col0 = c; s->stride = r->total;
@@ -1081,17 +1085,18 @@ int samples_from_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t c
 // P samples in host memory, 64-bit or as save() keeps them (32-bit), to the device buffer *buf:
 // each column (null ones are skipped) 256-byte aligned, then the int64 index if there is one
 template <typename T>
-int samples_upload(nxc_handle *h, unsigned char **buf, size_t *cap, int64_t P, const T *const cols[5],
+int samples_upload(nxc_handle *h, unsigned char **buf, size_t *cap, int64_t P,
+                   const T *const cols[N_SAMPLE_COLS],
                    const int64_t *index, Samples *s)
 {
     const size_t bytes = (size_t)P * sizeof(T), col = (bytes + 255) & ~size_t(255);
-    const size_t n_cols = 5 - std::count(cols, cols + 5, nullptr);
+    const size_t n_cols = N_SAMPLE_COLS - std::count(cols, cols + N_SAMPLE_COLS, nullptr);
     int rc = ensure(reinterpret_cast<void **>(buf), cap, n_cols * col + (index ? (size_t)P * 8 : 0));
     if (rc) return rc;
     *s = Samples{};
     s->f32 = sizeof(T) == 4; s->n = P;
     unsigned char *d = *buf;
-    for (int c = 0; c < 5; c++) {
+    for (int c = 0; c < N_SAMPLE_COLS; c++) {
         if (!cols[c]) continue;
         if (P) HIPCHK(hipMemcpyAsync(d, cols[c], bytes, hipMemcpyHostToDevice, h->stream));
         s->cols[c] = d;
@@ -1365,7 +1370,7 @@ int los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double
                        n_used);
     if (rc) return rc;
     if (P && (!x || !y || !z || !vy || !frac)) return fail(NXC_ERR_ARG, "bad arguments");
-    const T *cols[5] = {x, y, z, vy, frac};
+    const T *cols[N_SAMPLE_COLS] = {x, y, z, vy, frac, nullptr, nullptr};
     Samples s;
     if ((rc = samples_upload(h, &h->d_samples, &h->samples_cap, P, cols, index, &s))) return rc;
     return los_run(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs, n_used);
@@ -1532,6 +1537,18 @@ int density_run(nxc_handle *h, const Samples &s)
     });
 }
 
+// ModelDensity(moments=True) over samples on the device (k_density_moments)
+int moments_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_density_moments<T>, NXC_BLOCK, 0, s.n, h->dens, s.n, h->dens_q,
+                                  s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(5), s.col<T>(3),
+                                  s.col<T>(6), s.col<T>(4), h->d_dens_pts, h->d_dens_cell,
+                                  h->d_dens_acc, h->d_dens_mom);
+    });
+}
+
 // CameraImage over samples on the device (k_camera)
 int camera_run(nxc_handle *h, const Samples &s)
 {
@@ -1548,16 +1565,28 @@ struct SampleConsumer {
     bool nxc_handle::*have;                      // its nxc_*_set has been called ...
     const char *unset;                           // ... or this is the NXC_ERR_STATE message
     bool needs_vy, clears_ctr;                   // reads the vy column; zeroes d_ctr per accepted call
+    bool needs_vxz;                              // reads the vx and vz columns too
     bool (*idle)(const nxc_handle *);            // nothing to add to, whatever the samples (or null)
     int (*run)(nxc_handle *, const Samples &);
 };
 const SampleConsumer IMAGE_SAMPLES = {&nxc_handle::have_image, "nxc_set_image has not been called",
-                                      true, true, nullptr, image_run};
+                                      true, true, false, nullptr, image_run};
 const SampleConsumer DENSITY_SAMPLES = {&nxc_handle::have_density, "nxc_density_set has not been called",
-                                        false, false,
+                                        false, false, false,
                                         [](const nxc_handle *h) { return h->dens_q == 0; }, density_run};
+// the moments' state is the enable; its entries check nxc_density_set's first (moments_need_set)
+const SampleConsumer MOMENT_SAMPLES = {&nxc_handle::have_dens_mom,
+                                       "nxc_density_moments_enable has not been called",
+                                       true, false, true,
+                                       [](const nxc_handle *h) { return h->dens_q == 0; }, moments_run};
+// the state check that comes in front of MOMENT_SAMPLES': nxc_density_set is the missing call
+int moments_need_set(const nxc_handle *h)
+{
+    if (h && h->have_density) return NXC_OK;
+    return guarded([&]() -> int { return fail(NXC_ERR_STATE, DENSITY_SAMPLES.unset); });
+}
 const SampleConsumer CAMERA_SAMPLES = {&nxc_handle::have_camera, "nxc_camera_set has not been called",
-                                       true, true, nullptr, camera_run};
+                                       true, true, false, nullptr, camera_run};
 
 // What every accepted call does, samples or none
 int begin_sample_pass(nxc_handle *h, const SampleConsumer &c)
@@ -1571,15 +1600,18 @@ int begin_sample_pass(nxc_handle *h, const SampleConsumer &c)
 // (32-bit), go to the handle's staging buffer first
 template <typename T>
 int accumulate_columns(nxc_handle *h, const SampleConsumer &c, int64_t p, const T *x, const T *y,
-                       const T *z, const T *vy, const T *frac)
+                       const T *z, const T *vy, const T *frac, const T *vx = nullptr,
+                       const T *vz = nullptr)
 {
     return guarded([&]() -> int {
         if (!h || !(h->*c.have)) return fail(NXC_ERR_STATE, c.unset);
-        if (p < 0 || (p && (!x || !y || !z || (c.needs_vy && !vy) || !frac)))
+        if (p < 0 || (p && (!x || !y || !z || (c.needs_vy && !vy) || !frac ||
+                            (c.needs_vxz && (!vx || !vz)))))
             return fail(NXC_ERR_ARG, "bad arguments");
         int rc = begin_sample_pass(h, c);
         if (rc || p == 0 || (c.idle && c.idle(h))) return rc;
-        const T *cols[5] = {x, y, z, c.needs_vy ? vy : nullptr, frac};
+        const T *cols[N_SAMPLE_COLS] = {x, y, z, c.needs_vy ? vy : nullptr, frac,
+                                        c.needs_vxz ? vx : nullptr, c.needs_vxz ? vz : nullptr};
         Samples s;
         rc = samples_upload(h, &h->d_samples, &h->samples_cap, p, cols, nullptr, &s);
         return rc ? rc : c.run(h, s);
@@ -1678,7 +1710,7 @@ int fit_source_columns(nxc_handle *h, int64_t P, const T *x, const T *y, const T
     HIPCHK(hipSetDevice(h->device));
     h->have_fit_src = false;
     h->fit_np = -1;
-    const T *cols[5] = {x, y, z, vy, frac};
+    const T *cols[N_SAMPLE_COLS] = {x, y, z, vy, frac, nullptr, nullptr};
     int rc = samples_upload(h, &h->d_fit_smp, &h->fit_smp_cap, P, cols, index, &h->fit_src);
     h->have_fit_src = rc == NXC_OK;
     return rc;
@@ -1952,7 +1984,7 @@ int nxc_destroy(nxc_handle *h)
                     h->d_steps, h->d_reduce, h->d_order, h->d_bounce, h->d_stick_map, h->d_moonpos, h->d_offsets,
                     h->d_source, h->d_queue, h->d_samples, h->d_tiles, h->d_hist, h->d_rec, h->d_piece_hist,
                     h->d_blob_img, h->d_reduce_n, h->d_losblk, h->d_dens_pts, h->d_dens_cell,
-                    h->d_dens_acc, h->d_fit_spec, h->d_fit_pk, h->d_fit_smp, h->d_fit_aux,
+                    h->d_dens_acc, h->d_dens_mom, h->d_fit_spec, h->d_fit_pk, h->d_fit_smp, h->d_fit_aux,
                     h->d_smap_grid, h->d_smap_acc, h->d_smap_pk, h->d_blob_cam, h->d_cam_image};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
@@ -2939,6 +2971,7 @@ int nxc_density_set(nxc_handle *h, const nxc_density_desc *d)
         if (cs[c + 1] < cs[c]) return fail(NXC_ERR_ARG, "cell starts are not sorted");
     HIPCHK(hipSetDevice(h->device));
     h->have_density = false;
+    h->have_dens_mom = false;
     std::vector<double> pts((size_t)Q * 4, 0.0);
     for (int64_t j = 0; j < Q; j++)
         for (int a = 0; a < 3; a++) pts[4 * j + a] = d->points[3 * j + a];
@@ -2992,6 +3025,67 @@ int nxc_density_download(nxc_handle *h, double *sum_frac, double *count)
     if (h->dens_q == 0) return NXC_OK;
     HIPCHK(hipSetDevice(h->device));
     return download_pairs(h, h->d_dens_acc, (size_t)h->dens_q, sum_frac, count);
+    });
+}
+
+int nxc_density_moments_enable(nxc_handle *h, int on)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_density) return fail(NXC_ERR_STATE, DENSITY_SAMPLES.unset);
+    HIPCHK(hipSetDevice(h->device));
+    h->have_dens_mom = false;
+    if (!on) return NXC_OK;
+    const size_t bytes = (size_t)h->dens_q * NXC_MOMENT_PLANES * 16;
+    int rc = ensure(reinterpret_cast<void **>(&h->d_dens_mom), &h->dens_mom_cap, bytes);
+    if (rc) return rc;
+    if (bytes) HIPCHK(hipMemsetAsync(h->d_dens_mom, 0, bytes, h->stream));
+    HIPCHK(stream_sync(h));
+    h->have_dens_mom = true;
+    return NXC_OK;
+    });
+}
+
+int nxc_density_moments_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                                   const double *z, const double *vx, const double *vy,
+                                   const double *vz, const double *frac)
+{
+    if (int rc = moments_need_set(h)) return rc;
+    return accumulate_columns<double>(h, MOMENT_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_density_moments_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                       const float *z, const float *vx, const float *vy,
+                                       const float *vz, const float *frac)
+{
+    if (int rc = moments_need_set(h)) return rc;
+    return accumulate_columns<float>(h, MOMENT_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_density_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    if (int rc = moments_need_set(h)) return rc;
+    return accumulate_rows(h, MOMENT_SAMPLES, r, first, count);
+}
+
+int nxc_density_moments_download(nxc_handle *h, double *sums)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_density) return fail(NXC_ERR_STATE, DENSITY_SAMPLES.unset);
+    if (!h->have_dens_mom) return fail(NXC_ERR_STATE, MOMENT_SAMPLES.unset);
+    const size_t Q = (size_t)h->dens_q;
+    if (Q && !sums) return fail(NXC_ERR_ARG, "bad arguments");
+    if (Q == 0) return NXC_OK;
+    HIPCHK(hipSetDevice(h->device));
+    std::vector<double> planes(Q * NXC_MOMENT_PLANES * 2);
+    HIPCHK(hipMemcpyAsync(planes.data(), h->d_dens_mom, planes.size() * sizeof(double),
+                          hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    for (size_t q = 0; q < Q; q++)
+        for (size_t k = 0; k < NXC_MOMENT_PLANES; k++) {
+            sums[10 * q + 2 * k] = planes[2 * (k * Q + q)];
+            sums[10 * q + 2 * k + 1] = planes[2 * (k * Q + q) + 1];
+        }
+    return NXC_OK;
     });
 }
 

@@ -863,6 +863,36 @@ NXC_DEV void image_add_pairs(bool has, int pix, double w, double *__restrict__ a
     }
 }
 
+// fp64 value held by lane l ^ 32 (two half_swaps: the swap moves 32-bit registers)
+NXC_DEV double half_swap_f64(double v, bool upper)
+{
+    return __hiloint2double(half_swap(__double2hiint(v), upper), half_swap(__double2loint(v), upper));
+}
+
+// image_add_pairs for any {a, b}: `has` lanes add a to rec2[2 * rec] and b to rec2[2 * rec + 1],
+// the two halves of 16-byte record `rec` (0 <= rec < 2^31; the byte offset is formed in 64 bits),
+// again by lanes l and l + 32 of one instruction: one request per record per sample.  Nothing is
+// skipped: a zero is added like any other value and a NaN or infinity reaches the sums.
+// Wave-cooperative: all 64 lanes call it from uniform control flow.
+NXC_DEV void add_record_pairs(bool has, int rec, double a, double b, double *__restrict__ rec2)
+{
+    if (__ballot(has) == 0) return;
+    const bool upper = (threadIdx.x & 32) != 0;
+    const int prec = half_swap(has ? rec : -1, upper);        // partner lane's record, -1 = none
+    const double pb = half_swap_f64(b, upper);                // ... and its second value
+    const bool partner = prec >= 0;
+    {   // samples of lanes 0..31
+        const bool act = upper ? partner : has;
+        if (act)
+            unsafeAtomicAdd(&rec2[2ll * (upper ? prec : rec) + (upper ? 1 : 0)], upper ? pb : a);
+    }
+    {   // samples of lanes 32..63
+        const bool act = upper ? has : partner;
+        if (act)
+            unsafeAtomicAdd(&rec2[2ll * (upper ? rec : prec) + (upper ? 0 : 1)], upper ? a : pb);
+    }
+}
+
 // The image work of one stored sample, in two stages so that the persistent kernel can put a
 // compaction queue between them (about half the samples of the bench workload fall outside the
 // image; the second stage -- g-value lookups, divisions, atomics -- then runs with full waves):

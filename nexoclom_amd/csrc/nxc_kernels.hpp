@@ -2728,6 +2728,80 @@ k_density(DensityK K, int64_t n, const T *__restrict__ x, const T *__restrict__ 
     }
 }
 
+// ModelDensity(moments=True): k_density's pass with the velocity moments of every hit.  The same
+// cull (density_cells), the same candidate walk (copied, so that k_density compiles as before)
+// and the same membership test; p, v and frac are widened to fp64 and a hit adds, with f = frac
+// and one rounding per operation,
+//     {f, 1}                                   to record q of acc2 (k_density's own pair array)
+//     {f vx, f vy}  {f vz, (f vx) vx}  {(f vy) vy, (f vz) vz}  {(f vx) vy, (f vx) vz}
+//     {(f vy) vz, f f}                         to record q of planes 0..4 of mom2, [5][Q] records.
+// The ten products are formed only in a lane that hits; the six pair adds are made from uniform
+// control flow (add_record_pairs), and a trip in which no lane of the wave hits makes none.
+// Nothing is filtered: a non-finite frac or velocity poisons the sums of the points it hits, as
+// a non-finite frac does in k_density.
+constexpr int NXC_MOMENT_PLANES = 5;
+template <typename T>
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_density_moments(DensityK K, int64_t n, int64_t n_points, const T *__restrict__ x,
+                  const T *__restrict__ y, const T *__restrict__ z, const T *__restrict__ vx,
+                  const T *__restrict__ vy, const T *__restrict__ vz, const T *__restrict__ frac,
+                  const double *__restrict__ pts, const int *__restrict__ cell_start,
+                  double *__restrict__ acc2, double *__restrict__ mom2)
+{
+    // wave-uniform trip count (the accumulation is wave-cooperative); the last trip is ragged
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n;
+         base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        double p[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0}, w = 0.0;
+        int lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1};
+        bool live = false;
+        if (i < n) {
+            p[0] = (double)x[i]; p[1] = (double)y[i]; p[2] = (double)z[i];
+            live = density_cells(K, p, lo, hi);
+            if (live) {
+                v[0] = (double)vx[i]; v[1] = (double)vy[i]; v[2] = (double)vz[i];
+                w = (double)frac[i];
+            }
+        }
+        // the candidate points of one (cy, cz) row of cells are one contiguous range [j, e)
+        int cy = lo[1], cz = lo[2], j = 0, e = 0;
+        auto advance = [&]() {
+            while (live && j >= e) {
+                if (cz > hi[2]) { live = false; break; }
+                const int row = (cz * K.n[1] + cy) * K.n[0];
+                j = cell_start[row + lo[0]];
+                e = cell_start[row + hi[0] + 1];
+                if (++cy > hi[1]) { cy = lo[1]; ++cz; }
+            }
+        };
+        advance();
+        while (__ballot(live) != 0) {
+            bool hit = false;
+            int q = 0;
+            if (live) {
+                const double dx = pts[4 * (int64_t)j] - p[0];
+                const double dy = pts[4 * (int64_t)j + 1] - p[1];
+                const double dz = pts[4 * (int64_t)j + 2] - p[2];
+                hit = (dx * dx + dy * dy) + dz * dz <= K.dr2;
+                q = j++;
+                advance();
+            }
+            if (__ballot(hit) == 0) continue;
+            double m[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            if (hit) {
+                m[0] = w * v[0]; m[1] = w * v[1]; m[2] = w * v[2];
+                m[3] = m[0] * v[0]; m[4] = m[1] * v[1]; m[5] = m[2] * v[2];
+                m[6] = m[0] * v[1]; m[7] = m[0] * v[2]; m[8] = m[1] * v[2];
+                m[9] = w * w;
+            }
+            add_record_pairs(hit, q, w, 1.0, acc2);
+#pragma unroll
+            for (int k = 0; k < NXC_MOMENT_PLANES; k++)
+                add_record_pairs(hit, q, m[2 * k], m[2 * k + 1], mom2 + 2 * n_points * k);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // CameraImage: stored samples binned into the image of a pinhole camera (camera_sample).  k_image's
 // shape: the blob [header | g tables | u edges | v edges] staged once per workgroup, a grid-stride

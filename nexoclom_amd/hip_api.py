@@ -43,7 +43,10 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_fit_rows', 'nxc_fit_download', 'nxc_source_map_set', 'nxc_source_map_accumulate',
            'nxc_source_map_download', 'nxc_set_stick_map', 'nxc_integrate_var_resident',
            'nxc_var_rows_build', 'nxc_camera_set', 'nxc_camera_accumulate',
-           'nxc_camera_accumulate_f32', 'nxc_camera_accumulate_rows', 'nxc_camera_download')
+           'nxc_camera_accumulate_f32', 'nxc_camera_accumulate_rows', 'nxc_camera_download',
+           'nxc_density_moments_enable', 'nxc_density_moments_accumulate',
+           'nxc_density_moments_accumulate_f32', 'nxc_density_moments_accumulate_rows',
+           'nxc_density_moments_download')
 ABI_VERSION = 3
 
 
@@ -880,6 +883,24 @@ class Context:
         total, count = np.zeros(q), np.zeros(q)
         self._check(self.lib.nxc_density_download(self._h, _p(total), _p(count)))
         return total, count
+
+    def density_moments_enable(self, on=True):
+        """After ``density_set``: allocate and zero the ten velocity-moment sums per indexed point
+        (``on`` false switches them off; so does the next ``density_set``)."""
+        self._check(self.lib.nxc_density_moments_enable(self._h, C.c_int(int(bool(on)))))
+
+    def density_moments_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
+                                   frac=None, rows=None):
+        """Add samples to the per-point {frac sum, count} and to the moment sums in one pass: seven
+        host columns (float32 ones go over as they are), or ``rows = (RowStore, first, count)``."""
+        self._accumulate('nxc_density_moments_accumulate', (x, y, z, vx, vy, vz, frac), rows)
+
+    def density_moments_download(self):
+        """(Q, 10) float64 in the index's point order: the sums of f v_a (x, y, z), of
+        (f v_a) v_b (xx, yy, zz, xy, xz, yz) and of f f over the samples within dr."""
+        sums = np.zeros((getattr(self, '_density_q', 0), 10))
+        self._check(self.lib.nxc_density_moments_download(self._h, _p(sums)))
+        return sums
 
     # -- CameraImage ------------------------------------------------------------------------
     def camera_set(self, observer, basis, vrplanet, pix_area_cm2, quantity, uedges, vedges,

@@ -5,6 +5,12 @@ two floors of DESIGN.md section 3: reading the rows (16 B per float32 row at 6.3
 hits at 2.4e10 atomic requests/s (profiles/r01_ubench_atomics.txt).
 
     python tools/gpu_exp_density.py [N ...]          (default: 1e6 1e7)
+
+``--moments [--out FILE]``: over the resident rows of Input.run(1e6), k_density and
+k_density_moments alternated in one process on both point sets, 3 warm-up and 9 timed rounds each,
+HIP-event time summed over the launches.  One JSON line per point set (appended to FILE) with the
+moments' two floors: 28 B per float32 row at the box's k_stream_copy rate, and 6 requests per hit
+at 2.4e10 requests/s.
 """
 import contextlib
 import io
@@ -38,7 +44,53 @@ def spans(inputs, ctx):
     return [span for _, span in sample_spans(inputs._catalogue, ctx)]
 
 
+def kernel_ms(ctx, launches, accumulate):
+    ms = 0.0
+    for span in launches:
+        accumulate(rows=span)
+        ms += ctx.last_kernel_ms()
+    return ms
+
+
+def moments_leg(out_path, warm=3, timed=9):
+    ctx = hip_api.Context(0)
+    copy_bps = ctx.stream_copy_gbs() * 1e9
+    inputs = Input(os.path.join(ROOT, 'nexoclom_amd', 'inputfiles', 'Na.mercury.bench.input'))
+    with contextlib.redirect_stdout(io.StringIO()):
+        inputs.run(1e6, seed=7, context=ctx)
+    launches = spans(inputs, ctx)
+    rows = sum(s[2] for s in launches)
+    for name, pts in point_sets().items():
+        index = DensityIndex(pts, DR)
+        ctx.density_set(index.points, index.cell_start, index.origin, index.h, index.dr,
+                        index.dims)
+        ctx.density_moments_enable()
+        plain, moments = [], []
+        for rep in range(warm + timed):
+            a = kernel_ms(ctx, launches, ctx.density_accumulate)
+            b = kernel_ms(ctx, launches, ctx.density_moments_accumulate)
+            if rep >= warm:
+                plain.append(a)
+                moments.append(b)
+        hits = float(ctx.density_download()[1].sum()) / (2*(warm + timed))
+        line = json.dumps(dict(
+            npackets=1e6, points=name, rows=rows, launches=len(launches), hits=hits,
+            k_density_ms=[round(v, 3) for v in plain],
+            k_density_moments_ms=[round(v, 3) for v in moments],
+            stream_copy_gbs=round(copy_bps/1e9, 1),
+            floor_rows_ms=round(rows*28/copy_bps*1e3, 3),
+            floor_atomics_ms=round(6*hits/ATOMIC_RPS*1e3, 3)))
+        print(line, flush=True)
+        if out_path:
+            with open(out_path, 'a') as f:
+                f.write(line + '\n')
+    ctx.close()
+
+
 def main():
+    if '--moments' in sys.argv:
+        out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else None
+        return moments_leg(out)
     sizes = [float(a) for a in sys.argv[1:]] or [1e6, 1e7]
     ctx = hip_api.Context(0)
     for n in sizes:
