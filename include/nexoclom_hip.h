@@ -687,6 +687,65 @@ int nxc_camera_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const fl
 int nxc_camera_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
 int nxc_camera_download(nxc_handle *h, double *image, uint64_t *counts);
 
+/* ---- Pixel moments: Doppler shift, line width and statistical error per pixel ---------------------
+ * EXTENSION -- the reference's images hold a brightness and a packet count per pixel.  A sample runs
+ * through the image steps unchanged (nxc_image_accumulate: rotation, bins, occultation, shadow,
+ * weight; nxc_camera_*: steps 1-8 above).  If it reaches its pixel with a final weight w -- the value
+ * added to image[pixel] -- it also contributes the following, all fp64, one rounding per operation,
+ * no contraction.
+ * Line-of-sight velocity vlos [R/s], planet frame, positive when receding from the observer:
+ *   image:   vlos = (M[3]*vx + M[4]*vy) + M[5]*vz        row 1 of the image rotation (the
+ *            occultation test y_obs < 0 puts the observer at y_obs -> -inf).  With downcast_f32, vx
+ *            and vz take the float32 round trip of the other five values (vy's is the one the image
+ *            itself uses).  The same three products whatever M is, so a non-finite vx always counts
+ *   camera:  vlos = ((dx*vx + dy*vy) + dz*vz) / r         dx, dy, dz of step 1, r = sqrt(r2) of step
+ *            7: the velocity along that sample's own ray, away from the camera
+ * Terms:
+ *   a  = w*vlos
+ *   m1 = a        m2 = a*vlos        m3 = (a*vlos)*vlos        ww = w*w
+ * added to four sums per pixel, kept in the order m1 m2 m3 ww.
+ *   - A sample with w == 0 (hidden, shadowed, frac == 0, g == 0) adds nothing to the four sums; it is
+ *     still counted in the packet image.  vx and vz of such a sample are not read.
+ *   - Nothing else is filtered: a non-finite vx or vz makes that pixel's sums non-finite.
+ *   - The image pair, the counts and the counters (samples, samples_binned, nonfinite) of a moments
+ *     pass are those of the plain pass over the same samples, up to the fp64 addition order of the
+ *     image sum.  The order of addition is not fixed (device atomics).
+ * With S0 = image[pixel] before any scaling: m1/S0 is the mean line-of-sight velocity (Doppler
+ * shift), m2/S0 - (m1/S0)^2 its variance (line width), m3 its third moment, S0^2/ww the effective
+ * number of packets, and S0/sqrt(S0^2/ww) the 1-sigma statistical error of S0.
+ *   nxc_image_moments_enable            after nxc_set_image: on != 0 allocates and zeroes nx*nz*4
+ *                                       doubles (NXC_ERR_NOMEM when they cannot be had), 0 frees
+ *                                       them; nxc_set_image switches the moments off again;
+ *                                       nxc_image_clear zeroes them with the image while they are on
+ *   nxc_image_moments_accumulate[_f32]  adds p host samples to the image pair AND the four sums in one
+ *                                       pass, always one atomic pair per request (at most three
+ *                                       requests per binned sample), never the tiles of
+ *                                       nxc_image_mode
+ *   nxc_image_moments_accumulate_rows   the same for rows [first, first + count) of a row store
+ *   nxc_image_moments_download          sums[nx*nz][4], pixel index ix*nz + iz
+ *   nxc_camera_moments_*                the same five against the camera's own image buffer
+ * NXC_ERR_STATE names the missing call (the set first, then the enable); NXC_ERR_ARG for p < 0 or a
+ * null column with p > 0; p = 0 adds nothing but still zeroes the counters.  nxc_image_accumulate*
+ * and nxc_camera_accumulate* keep adding to the image pair only, moments enabled or not. */
+int nxc_image_moments_enable(nxc_handle *h, int on);
+int nxc_image_moments_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                                 const double *z, const double *vx, const double *vy,
+                                 const double *vz, const double *frac);
+int nxc_image_moments_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                     const float *z, const float *vx, const float *vy,
+                                     const float *vz, const float *frac);
+int nxc_image_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_image_moments_download(nxc_handle *h, double *sums);
+int nxc_camera_moments_enable(nxc_handle *h, int on);
+int nxc_camera_moments_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                                  const double *z, const double *vx, const double *vy,
+                                  const double *vz, const double *frac);
+int nxc_camera_moments_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                      const float *z, const float *vx, const float *vy,
+                                      const float *vz, const float *frac);
+int nxc_camera_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_camera_moments_download(nxc_handle *h, double *sums);
+
 /* ---- Source maps: where the packets of fitted Outputs came from ---------------------------------
  * data_simulation/make_source_map.py:11-174 per Output, summed over the Outputs of a result on the
  * device.  Grid: nlon x nlat points at the bin centres point_lon[nlon], point_lat[nlat]; point p =

@@ -24,13 +24,18 @@ sourcerate, counters.  The sample's weight is spread over the footprint of its p
 sample's distance, so a pixel holds (1 / dOmega) * sum weight / r^2 -- the line-of-sight integral
 of the density through that pixel.
 
+``moments=True`` adds ModelImage's per-pixel velocity moments (moment_sums, velocity,
+velocity_variance, velocity_dispersion, velocity_skewness, effective_packets) in the same pass
+(k_camera_moments), with the line-of-sight velocity taken along each sample's own ray from the
+camera, positive receding.
+
 Not supported, and refused: streaming (``npackets=``), shared runs (``cp=`` / ``shard=``), the
 LDS-tile accumulation, fisheye / all-sky projections (a gnomonic camera sees less than 180
 degrees), moons as occulters.
 """
 import numpy as np
 
-from .ModelImage import ModelResult
+from .ModelImage import PIXEL_MOMENT_COLUMNS, ModelResult, pixel_moments_from_sums, refuse_moments_with
 from .catalogue import sample_spans, shared_context
 from .input_classes import InputError
 from .units import Quantity
@@ -85,7 +90,11 @@ def camera_basis(boresight, up):
 
 
 class CameraImage(ModelResult):
-    def __init__(self, inputs, params, *, context=None, device=0, **unsupported):
+    moments = False           # True: the pass over the rows also fills moment_sums
+
+    def __init__(self, inputs, params, *, context=None, device=0, moments=False, **unsupported):
+        if moments:
+            refuse_moments_with(**{key: unsupported.get(key) for key in ('npackets', 'shard', 'cp')})
         for key in unsupported:
             if key in UNSUPPORTED:
                 raise NotImplementedError(UNSUPPORTED[key])
@@ -97,6 +106,9 @@ class CameraImage(ModelResult):
         self._frame()
         self.image = np.zeros(self.dims)
         self.packet_image = np.zeros(self.dims)
+        self.moments = bool(moments)
+        if self.moments:
+            self.moment_sums = np.zeros(tuple(self.dims) + (len(PIXEL_MOMENT_COLUMNS),))
         self._ctx, self._device = context, device
         self.counters = {}
         self._from_catalogue()
@@ -152,8 +164,9 @@ class CameraImage(ModelResult):
     def _from_catalogue(self):
         """Every catalogued Output through k_camera.  Rows in HBM are read where they are, one
         launch per run of adjacent slices of a store; other Outputs upload their five sample
-        columns.  The image stays on the device while (aplanet, vrplanet) -- the g-values -- stay
-        the same, and is summed on the host across such groups."""
+        columns (seven with ``moments``, through k_camera_moments).  The image stays on the device
+        while (aplanet, vrplanet) -- the g-values -- stay the same, and is summed on the host
+        across such groups."""
         from .Output import Output
         runs = list(self.inputs._catalogue)
         if not runs:
@@ -180,7 +193,10 @@ class CameraImage(ModelResult):
             image, counts = ctx.camera_download()
             self.image += image
             self.packet_image += counts.astype(float)
+            if self.moments:
+                self.moment_sums += ctx.camera_moments_download()
 
+        accumulate = ctx.camera_moments_accumulate if self.moments else ctx.camera_accumulate
         is_set = False
         for kind, item in sample_spans(announced(), ctx, key=g_values):
             if kind == 'key':
@@ -189,16 +205,18 @@ class CameraImage(ModelResult):
                 aplanet, vr_kms = item
                 ctx.camera_set(self.observer, self.basis, vr_kms/self.unit_km, self.pix_area_cm2,
                                self.quantity, self.uedges, self.vedges, self.g_tables(aplanet))
+                if self.moments:
+                    ctx.camera_moments_enable()
                 is_set = True
                 continue
             if kind == 'rows':
-                ctx.camera_accumulate(rows=item)
+                accumulate(rows=item)
             else:
-                samples = Output.image_columns(item)[0]
+                samples = Output.image_columns(item, velocity=self.moments)[0]
                 if samples is None or not len(samples[0]):
                     continue
-                x, y, z, vy, frac = samples
-                ctx.camera_accumulate(x=x, y=y, z=z, vy=vy, frac=frac)
+                names = Output.MOMENT_COLS if self.moments else Output.IMAGE_COLS
+                accumulate(**dict(zip(names, samples)))
             for key, v in ctx.counters().items():
                 totals[key] = totals.get(key, 0) + v
         collect()
@@ -210,4 +228,8 @@ class CameraImage(ModelResult):
         per_second = self.totalsource / self.inputs.options.endtime.value
         self.atoms_per_packet = 1e23 / per_second if per_second > 0 else 0.
         self.sourcerate = Quantity(1., '1e23/s')
+        if self.moments:         # the quotients are of the unscaled sums
+            for name, value in pixel_moments_from_sums(self.image, self.moment_sums,
+                                                       self.unit_km).items():
+                setattr(self, name, value)
         self.image *= self.atoms_per_packet

@@ -344,7 +344,9 @@ class Input:
         every rank bins the Outputs of its own catalogue and the image pairs and source totals
         are summed over the ranks (reduce='rccl': one ncclAllReduce; 'host': over the control
         plane, for tests) -- every rank gets the image of the whole run."""
-        from .ModelImage import ModelImage
+        from .ModelImage import ModelImage, refuse_moments_with
+        if kwargs.get('moments'):
+            refuse_moments_with(cp=cp)
         if cp is None or cp.world == 1:
             return ModelImage(self, format_, overwrite=overwrite, distribute=distribute, **kwargs)
         from .distributed import guarded, merge_catalogue

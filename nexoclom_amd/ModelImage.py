@@ -16,6 +16,12 @@ Two ways to get the packets:
   two-stage pipeline produces.  ``shard=(lo, hi)`` restricts the run to those global packet
   indices (multi-GPU, nexoclom_amd.distributed).
 
+``moments=True`` (catalogued Outputs only; an extension beyond the reference) adds four velocity
+moments per pixel in the same pass: ``moment_sums`` and, from them, ``velocity`` (the line's Doppler
+shift, km/s, positive receding), ``velocity_variance`` / ``velocity_dispersion`` (its width),
+``velocity_skewness`` and ``effective_packets`` (``image / sqrt(effective_packets)`` is the 1-sigma
+statistical error of ``image``).  include/nexoclom_hip.h ("Pixel moments") holds the definition.
+
 Bokeh display / PostgreSQL caching of the reference are out of scope.
 """
 import copy
@@ -34,6 +40,52 @@ QUANTITIES = ('column', 'radiance', 'density', 'difrad')
 EMISSION = ('radiance', 'difrad')
 # resonance lines [Angstrom] summed when params name none (ModelResult.py:124-129)
 DEFAULT_LINES = {'Na': (5891, 5897), 'Ca': (4227,), 'Mg': (2852,)}
+# the four sums per pixel of a moments pass, with w the sample's weight and v its line-of-sight
+# velocity [R/s]: sum w v, sum (w v) v, sum ((w v) v) v, sum w w
+PIXEL_MOMENT_COLUMNS = ('m1', 'm2', 'm3', 'ww')
+MOMENT_ATTRIBUTES = ('velocity', 'velocity_variance', 'velocity_dispersion', 'velocity_skewness',
+                     'effective_packets')
+
+
+def pixel_moments_from_sums(S0, sums, unit_km):
+    """Per-pixel quotients of the moment sums: ``S0`` the unscaled image sum (sum w), ``sums``
+    (..., 4) in PIXEL_MOMENT_COLUMNS order, ``unit_km`` the length unit [km] that turns R/s into
+    km/s.  Returns a dict of
+      velocity             u = m1/S0                                  [km/s]
+      velocity_variance    m2/S0 - u^2, unclamped                     [km^2/s^2]
+      velocity_dispersion  sqrt(max(variance, 0))                     [km/s]
+      velocity_skewness    (m3/S0 - 3 u m2/S0 + 2 u^3)/variance^1.5 where variance > 0, else NaN
+      effective_packets    S0^2/ww
+    A pixel with S0 == 0 gets NaN for the velocity quantities and 0 effective packets."""
+    S0 = np.asarray(S0, dtype=float)
+    sums = np.asarray(sums, dtype=float)
+    m1, m2, m3, ww = (sums[..., k] for k in range(4))
+    filled = S0 != 0
+    with np.errstate(divide='ignore', invalid='ignore'):
+        safe = np.where(filled, S0, np.nan)
+        u, q2, q3 = m1/safe, m2/safe, m3/safe
+        variance = q2 - u*u
+        central3 = q3 - 3*u*q2 + 2*u*u*u
+        skewness = np.where(variance > 0, central3/np.where(variance > 0, variance, np.nan)**1.5,
+                            np.nan)
+        effective = np.where(filled, S0*S0/np.where(filled, ww, 1.0), 0.0)
+    return {'velocity': u*unit_km,
+            'velocity_variance': variance*unit_km**2,
+            'velocity_dispersion': np.sqrt(np.maximum(variance, 0))*unit_km,
+            'velocity_skewness': skewness,
+            'effective_packets': effective}
+
+
+def refuse_moments_with(**given):
+    """NotImplementedError for what a moments pass cannot be combined with."""
+    why = {'npackets': 'moments=True reads catalogued Outputs only: streaming (npackets=) bins inside '
+                       'the fused integrate kernel, which carries no velocity moments',
+           'shard': 'moments=True does not support shard=: the moment sums are not reduced over '
+                    'shards',
+           'cp': 'moments=True does not support cp=: there is no all-reduce of the moment sums yet'}
+    for key, value in given.items():
+        if value is not None:
+            raise NotImplementedError(why[key])
 
 
 def rotation_matrix(theta, axis):
@@ -129,9 +181,13 @@ class ModelResult:
 
 
 class ModelImage(ModelResult):
+    moments = False           # True: the pass over the rows also fills moment_sums
+
     def __init__(self, inputs, params, overwrite=False, distribute=None, *, npackets=None,
                  seed=None, packs_per_it=None, downcast=True, device=0, context=None,
-                 sampler='numpy', shard=None, finalize=True, generator='philox'):
+                 sampler='numpy', shard=None, finalize=True, generator='philox', moments=False):
+        if moments:
+            refuse_moments_with(npackets=npackets, shard=shard)
         super().__init__(inputs, params)
         self.type = 'image'
         self.origin = self.params.get('origin', inputs.geometry.planet)
@@ -141,6 +197,9 @@ class ModelImage(ModelResult):
         self._frame()
         self.image = np.zeros(self.dims)
         self.packet_image = np.zeros(self.dims)
+        self.moments = bool(moments)
+        if self.moments:
+            self.moment_sums = np.zeros(tuple(self.dims) + (len(PIXEL_MOMENT_COLUMNS),))
         self.blimits = None
         self.xaxis = None
         self.zaxis = None
@@ -188,6 +247,8 @@ class ModelImage(ModelResult):
             weighted, counted = self.create_image(run)
             self.image += weighted.histogram
             self.packet_image += counted.histogram
+            if self.moments:
+                self.moment_sums += self._last_moment_sums
             self.totalsource += run.totalsource
             self.xaxis, self.zaxis = weighted.x, weighted.y
 
@@ -216,7 +277,10 @@ class ModelImage(ModelResult):
         # the Outputs of a launch group are consecutive slices of one store: one kernel launch per
         # run of adjacent slices instead of one per Output
         for _, span in sample_spans(announced(), ctx):
-            ctx.image_accumulate_rows(*span)
+            if self.moments:
+                ctx.image_moments_accumulate(rows=span)
+            else:
+                ctx.image_accumulate_rows(*span)
             for key, v in ctx.counters().items():
                 totals[key] = totals.get(key, 0) + v
         self.counters = totals
@@ -224,6 +288,8 @@ class ModelImage(ModelResult):
         image, counts = ctx.image_download()
         self.image += image
         self.packet_image += counts.astype(float)
+        if self.moments:
+            self.moment_sums += ctx.image_moments_download()
         h = Histogram2dResult(image, self.xedges, self.zedges)
         self.xaxis, self.zaxis = h.x, h.y
         return True
@@ -234,6 +300,10 @@ class ModelImage(ModelResult):
         per_second = self.totalsource / self.inputs.options.endtime.value
         self.atoms_per_packet = 1e23 / per_second if per_second > 0 else 0.
         self.sourcerate = Quantity(1., '1e23/s')
+        if self.moments:         # the quotients are of the unscaled sums
+            for name, value in pixel_moments_from_sums(self.image, self.moment_sums,
+                                                       self.unit_km).items():
+                setattr(self, name, value)
         self.image *= self.atoms_per_packet
 
     # ---- GPU plumbing ---------------------------------------------------------------------
@@ -256,6 +326,8 @@ class ModelImage(ModelResult):
     def _set_image(self, ctx, aplanet, vrplanet_Rs, downcast):
         ctx.set_image(self.image_rotation(), vrplanet_Rs, float(self.Apix), self.quantity,
                       self.xedges, self.zedges, self.g_tables(aplanet), downcast_f32=downcast)
+        if self.moments:
+            ctx.image_moments_enable()
 
     def create_image(self, output):
         """ModelImage.py:229-274 for one catalogued Output (or .npz path): the restored sample
@@ -267,18 +339,26 @@ class ModelImage(ModelResult):
             # the rows are still in HBM as save() would have stored them: bin them where they are
             aplanet, vrplanet_kms = float(output.aplanet), float(output.vrplanet)
             self._set_image(ctx, aplanet, vrplanet_kms/self.unit_km, downcast=False)
-            ctx.image_accumulate_rows(view[0], view[1], view[2])
+            if self.moments:
+                ctx.image_moments_accumulate(rows=tuple(view[:3]))
+            else:
+                ctx.image_accumulate_rows(view[0], view[1], view[2])
         else:
-            samples, aplanet, vrplanet_kms = Output.image_columns(output)
+            samples, aplanet, vrplanet_kms = Output.image_columns(output, velocity=self.moments)
             if samples is None or len(samples[0]) == 0:
                 raise ValueError('this Output holds no trajectory (it was run with '
                                  'keep_trajectory=False); use ModelImage(..., npackets=N) instead')
             vr = vrplanet_kms/self.unit_km                 # km/s -> R/s (ModelImage.py:242-243)
             self._set_image(ctx, aplanet, vr, downcast=False)
-            ctx.image_accumulate(*samples)
+            if self.moments:
+                ctx.image_moments_accumulate(*samples)
+            else:
+                ctx.image_accumulate(*samples)
         self.counters = ctx.counters()
         assert self.counters['nonfinite'] == 0, 'Non-finite weights'
         image, counts = ctx.image_download()
+        if self.moments:
+            self._last_moment_sums = ctx.image_moments_download()
         return (Histogram2dResult(image, self.xedges, self.zedges),
                 Histogram2dResult(counts.astype(float), self.xedges, self.zedges))
 

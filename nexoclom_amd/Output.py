@@ -772,6 +772,7 @@ class Output:
         return cls._recast(frame, WIDE)
 
     IMAGE_COLS = ('x', 'y', 'z', 'vy', 'frac')
+    MOMENT_COLS = ('x', 'y', 'z', 'vx', 'vy', 'vz', 'frac')
 
     @staticmethod
     def packet_index(frame):
@@ -780,21 +781,23 @@ class Output:
         return frame['Index'].values if 'Index' in frame.columns else np.arange(len(frame))
 
     @classmethod
-    def image_columns(cls, source):
+    def image_columns(cls, source, velocity=False):
         """What create_image needs of a stored Output, without restoring the rest: the five
         sample columns as stored (32-bit after save(); the device widens them exactly like
         restore()'s up-cast, Output.py:555-570), aplanet [au] and vrplanet [km/s].  ``source``: a
-        catalogued Output or an .npz path."""
+        catalogued Output or an .npz path.  ``velocity``: the seven columns of MOMENT_COLS (vx and
+        vz as well, for the pixel moments) instead of the five of IMAGE_COLS."""
+        names = cls.MOMENT_COLS if velocity else cls.IMAGE_COLS
         if isinstance(source, cls):
             frame = source.X
             if len(frame) == 0 or 'x' not in frame:
                 return None, float(source.aplanet), float(source.vrplanet)
-            columns = [frame[c].values for c in cls.IMAGE_COLS]
+            columns = [frame[c].values for c in names]
             return columns, float(source.aplanet), float(source.vrplanet)
         with np.load(source, allow_pickle=False) as data:
             if 'X.x' not in data.files:
                 return None, float(data['aplanet']), float(data['vrplanet_kms'])
-            columns = [data['X.' + c] for c in cls.IMAGE_COLS]
+            columns = [data['X.' + c] for c in names]
             return columns, float(data['aplanet']), float(data['vrplanet_kms'])
 
     @classmethod

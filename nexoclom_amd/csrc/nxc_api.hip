@@ -347,6 +347,8 @@ struct nxc_handle {
 
     // resident data
     double *d_image = nullptr;       // interleaved {weight sum, packet count} per pixel, fp64
+    bool have_img_mom = false;       // nxc_image_moments_enable since the last nxc_set_image
+    double *d_img_mom = nullptr;     // the pixel moments: [2][npix] 16-byte records (k_image_moments)
     size_t npix = 0;
     double *d_packets = nullptr;
     size_t packets_cap = 0;
@@ -435,6 +437,8 @@ struct nxc_handle {
     unsigned char *d_blob_cam = nullptr;
     size_t blob_cam_cap = 0, cam_bytes = 0;
     double *d_cam_image = nullptr;
+    bool have_cam_mom = false;       // nxc_camera_moments_enable since the last nxc_camera_set
+    double *d_cam_mom = nullptr;     // [2][cam_npix] records (k_camera_moments)
     size_t cam_image_cap = 0, cam_npix = 0;
 
     // LOSResultFitted: the pair list the line-of-sight passes fill (nxc_los_set_pairs); the fit's
@@ -1560,6 +1564,30 @@ int camera_run(nxc_handle *h, const Samples &s)
     });
 }
 
+// ModelImage(moments=True) over samples on the device (k_image_moments: atomics, never the tiles)
+int image_moments_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_image_moments<T>, NXC_IMAGE_MOMENTS_BLOCK, h->img_bytes, s.n,
+                                  h->d_blob_img, (int64_t)h->img_bytes, s.n, (int64_t)h->npix,
+                                  s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(5), s.col<T>(3),
+                                  s.col<T>(6), s.col<T>(4), h->d_image, h->d_img_mom, h->d_ctr);
+    });
+}
+
+// CameraImage(moments=True) over samples on the device (k_camera_moments)
+int camera_moments_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_camera_moments<T>, NXC_CAMERA_BLOCK, h->cam_bytes, s.n, h->cam,
+                                  h->d_blob_cam, (int64_t)h->cam_bytes, s.n, (int64_t)h->cam_npix,
+                                  s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(5), s.col<T>(3),
+                                  s.col<T>(6), s.col<T>(4), h->d_cam_image, h->d_cam_mom, h->d_ctr);
+    });
+}
+
 // What tells one consumer of stored samples from another at its entry points
 struct SampleConsumer {
     bool nxc_handle::*have;                      // its nxc_*_set has been called ...
@@ -1587,6 +1615,63 @@ int moments_need_set(const nxc_handle *h)
 }
 const SampleConsumer CAMERA_SAMPLES = {&nxc_handle::have_camera, "nxc_camera_set has not been called",
                                        true, true, false, nullptr, camera_run};
+// the pixel moments' state is their enable, checked after the set's (pixel_moments_need_set)
+const SampleConsumer IMAGE_MOMENT_SAMPLES = {&nxc_handle::have_img_mom,
+                                             "nxc_image_moments_enable has not been called",
+                                             true, true, true, nullptr, image_moments_run};
+const SampleConsumer CAMERA_MOMENT_SAMPLES = {&nxc_handle::have_cam_mom,
+                                              "nxc_camera_moments_enable has not been called",
+                                              true, true, true, nullptr, camera_moments_run};
+// the state check in front of a moments consumer's own: the set of `base` is the missing call
+int pixel_moments_need_set(const nxc_handle *h, const SampleConsumer &base)
+{
+    if (h && h->*base.have) return NXC_OK;
+    return guarded([&]() -> int { return fail(NXC_ERR_STATE, base.unset); });
+}
+
+// nxc_X_moments_enable: [2][npix] zeroed records beside the image pair of `base`, or none
+int pixel_moments_enable(nxc_handle *h, const SampleConsumer &base, size_t npix, int on,
+                         bool nxc_handle::*have, double *nxc_handle::*d_mom)
+{
+    if (int rc = pixel_moments_need_set(h, base)) return rc;
+    return guarded([&]() -> int {
+        HIPCHK(hipSetDevice(h->device));
+        h->*have = false;
+        if (h->*d_mom) HIPCHK(hipFree(h->*d_mom));
+        h->*d_mom = nullptr;
+        if (!on) return NXC_OK;
+        const size_t bytes = npix * 4 * sizeof(double);
+        size_t cap = 0;
+        int rc = ensure(reinterpret_cast<void **>(&(h->*d_mom)), &cap, bytes);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(h->*d_mom, 0, bytes, h->stream));
+        HIPCHK(stream_sync(h));
+        h->*have = true;
+        return NXC_OK;
+    });
+}
+
+// nxc_X_moments_download: sums[npix][4] = m1 m2 m3 ww from the two planes
+int pixel_moments_download(nxc_handle *h, const SampleConsumer &base, const SampleConsumer &mom,
+                           size_t npix, const double *d_mom, double *sums)
+{
+    if (int rc = pixel_moments_need_set(h, base)) return rc;
+    return guarded([&]() -> int {
+        if (!(h->*mom.have)) return fail(NXC_ERR_STATE, mom.unset);
+        if (!sums) return fail(NXC_ERR_ARG, "bad arguments");
+        HIPCHK(hipSetDevice(h->device));
+        std::vector<double> planes(npix * 4);
+        HIPCHK(hipMemcpyAsync(planes.data(), d_mom, planes.size() * sizeof(double),
+                              hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(stream_sync(h));
+        for (size_t q = 0; q < npix; q++)
+            for (size_t k = 0; k < 2; k++) {
+                sums[4 * q + 2 * k] = planes[2 * (k * npix + q)];
+                sums[4 * q + 2 * k + 1] = planes[2 * (k * npix + q) + 1];
+            }
+        return NXC_OK;
+    });
+}
 
 // What every accepted call does, samples or none
 int begin_sample_pass(nxc_handle *h, const SampleConsumer &c)
@@ -1985,7 +2070,8 @@ int nxc_destroy(nxc_handle *h)
                     h->d_source, h->d_queue, h->d_samples, h->d_tiles, h->d_hist, h->d_rec, h->d_piece_hist,
                     h->d_blob_img, h->d_reduce_n, h->d_losblk, h->d_dens_pts, h->d_dens_cell,
                     h->d_dens_acc, h->d_dens_mom, h->d_fit_spec, h->d_fit_pk, h->d_fit_smp, h->d_fit_aux,
-                    h->d_smap_grid, h->d_smap_acc, h->d_smap_pk, h->d_blob_cam, h->d_cam_image};
+                    h->d_smap_grid, h->d_smap_acc, h->d_smap_pk, h->d_blob_cam, h->d_cam_image,
+                    h->d_img_mom, h->d_cam_mom};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     pool_flush(h);
@@ -2134,6 +2220,7 @@ int nxc_set_image(nxc_handle *h, const nxc_image_desc *d)
     h->image_part = std::move(part);
     h->G = G;
     h->have_image = true;
+    h->have_img_mom = false;
 
     const size_t npix = (size_t)d->nx * (size_t)d->nz;
     if (npix != h->npix) {
@@ -2279,6 +2366,8 @@ int nxc_image_clear(nxc_handle *h)
     if (!h || !h->have_image) return fail(NXC_ERR_STATE, "nxc_set_image has not been called");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemsetAsync(h->d_image, 0, 2 * h->npix * sizeof(double), h->stream));
+    if (h->have_img_mom)
+        HIPCHK(hipMemsetAsync(h->d_img_mom, 0, 4 * h->npix * sizeof(double), h->stream));
     return NXC_OK;
 }
 
@@ -3120,6 +3209,7 @@ int nxc_camera_set(nxc_handle *h, const nxc_camera_desc *d)
     K.area = d->pix_area_cm2;
 
     h->have_camera = false;
+    h->have_cam_mom = false;
     const size_t npix = (size_t)d->nx * (size_t)d->nz;
     if ((rc = ensure(reinterpret_cast<void **>(&h->d_blob_cam), &h->blob_cam_cap, blob.size())) ||
         (rc = ensure(reinterpret_cast<void **>(&h->d_cam_image), &h->cam_image_cap, 2 * npix * sizeof(double))))
@@ -3159,6 +3249,40 @@ int nxc_camera_download(nxc_handle *h, double *image, uint64_t *counts)
     HIPCHK(hipSetDevice(h->device));
     return download_pairs(h, h->d_cam_image, h->cam_npix, image, counts);
     });
+}
+
+int nxc_camera_moments_enable(nxc_handle *h, int on)
+{
+    return pixel_moments_enable(h, CAMERA_SAMPLES, h ? h->cam_npix : 0, on, &nxc_handle::have_cam_mom,
+                                &nxc_handle::d_cam_mom);
+}
+
+int nxc_camera_moments_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                                  const double *z, const double *vx, const double *vy,
+                                  const double *vz, const double *frac)
+{
+    if (int rc = pixel_moments_need_set(h, CAMERA_SAMPLES)) return rc;
+    return accumulate_columns<double>(h, CAMERA_MOMENT_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_camera_moments_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                      const float *z, const float *vx, const float *vy,
+                                      const float *vz, const float *frac)
+{
+    if (int rc = pixel_moments_need_set(h, CAMERA_SAMPLES)) return rc;
+    return accumulate_columns<float>(h, CAMERA_MOMENT_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_camera_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    if (int rc = pixel_moments_need_set(h, CAMERA_SAMPLES)) return rc;
+    return accumulate_rows(h, CAMERA_MOMENT_SAMPLES, r, first, count);
+}
+
+int nxc_camera_moments_download(nxc_handle *h, double *sums)
+{
+    return pixel_moments_download(h, CAMERA_SAMPLES, CAMERA_MOMENT_SAMPLES, h ? h->cam_npix : 0,
+                                  h ? h->d_cam_mom : nullptr, sums);
 }
 
 // ---- source maps ---------------------------------------------------------------------------------
@@ -3666,6 +3790,40 @@ int nxc_image_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const flo
                              const float *z, const float *vy, const float *frac)
 {
     return accumulate_columns(h, IMAGE_SAMPLES, p, x, y, z, vy, frac);
+}
+
+int nxc_image_moments_enable(nxc_handle *h, int on)
+{
+    return pixel_moments_enable(h, IMAGE_SAMPLES, h ? h->npix : 0, on, &nxc_handle::have_img_mom,
+                                &nxc_handle::d_img_mom);
+}
+
+int nxc_image_moments_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                                 const double *z, const double *vx, const double *vy,
+                                 const double *vz, const double *frac)
+{
+    if (int rc = pixel_moments_need_set(h, IMAGE_SAMPLES)) return rc;
+    return accumulate_columns<double>(h, IMAGE_MOMENT_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_image_moments_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                     const float *z, const float *vx, const float *vy,
+                                     const float *vz, const float *frac)
+{
+    if (int rc = pixel_moments_need_set(h, IMAGE_SAMPLES)) return rc;
+    return accumulate_columns<float>(h, IMAGE_MOMENT_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_image_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    if (int rc = pixel_moments_need_set(h, IMAGE_SAMPLES)) return rc;
+    return accumulate_rows(h, IMAGE_MOMENT_SAMPLES, r, first, count);
+}
+
+int nxc_image_moments_download(nxc_handle *h, double *sums)
+{
+    return pixel_moments_download(h, IMAGE_SAMPLES, IMAGE_MOMENT_SAMPLES, h ? h->npix : 0,
+                                  h ? h->d_img_mom : nullptr, sums);
 }
 
 int nxc_los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,

@@ -1099,6 +1099,82 @@ NXC_DEV void camera_sample(const CameraK &K, const ImageK &G, const ImageRegs &R
     image_add_pairs(ok, pix, w, acc2);
 }
 
+// ---- pixel moments: what a sample adds to its pixel besides {w, 1} -------------------------------
+// (include/nexoclom_hip.h, "Pixel moments", holds the definition.)  A sample that reached pixel
+// `pix` with the final weight w != 0 and the line-of-sight velocity vlos adds
+//     {a, a vlos}            to record pix of plane 0 of mom2      a = w vlos
+//     {(a vlos) vlos, w w}   to record pix of plane 1              ([2][n_pix] 16-byte records)
+// one rounding per product.  A sample with w == 0 adds nothing; nothing else is filtered.
+// Wave-cooperative: all 64 lanes call it from uniform control flow; two requests per sample.
+NXC_DEV void pixel_moments_add(bool ok, int pix, double w, double vlos, int64_t n_pix,
+                               double *__restrict__ mom2)
+{
+    const bool has = ok && w != 0.0;
+    const double a = w * vlos, m2 = a * vlos;
+    add_record_pairs(has, pix, a, m2, mom2);
+    add_record_pairs(has, pix, m2 * vlos, w * w, mom2 + 2 * n_pix);
+}
+
+// image_sample with the moments.  vx and vz are read only by a lane whose sample reached a pixel
+// with w != 0; with downcast_f32 they and vy take the float32 round trip image_locate gives the
+// other values.  vlos is row 1 of the rotation applied to the velocity (the observer sits at
+// y_obs -> -inf: positive = receding); the general form also with x_is_x, so that a non-finite vx
+// reaches the sums whatever the rotation.
+template <typename T>
+NXC_DEV void image_moments_sample(const ImageK &G, const ImageRegs &R, bool has, double x, double y,
+                                  double z, double vy, double frac, const T *__restrict__ vx_at,
+                                  const T *__restrict__ vz_at, double *__restrict__ acc2,
+                                  int64_t n_pix, double *__restrict__ mom2,
+                                  unsigned long long &binned, unsigned long long &nonfinite)
+{
+    int pix = -1;
+    double radvel = 0.0, fw = 0.0, w = 0.0, vlos = 0.0;
+    if (has) pix = image_locate(G, R, x, y, z, vy, frac, radvel, fw, nonfinite);
+    bool ok = pix >= 0;
+    if (ok && !image_weight(G, R, radvel, fw, w)) { nonfinite++; ok = false; }
+    binned += ok;
+    image_add_pairs(ok, pix, w, acc2);
+    if (ok && w != 0.0) {
+        double vx = (double)*vx_at, vz = (double)*vz_at;
+        if (R.downcast) {
+            vx = f32_round_trip(vx); vy = f32_round_trip(vy); vz = f32_round_trip(vz);
+        }
+        vlos = (G.M[3] * vx + G.M[4] * vy) + G.M[5] * vz;
+    }
+    pixel_moments_add(ok, pix, w, vlos, n_pix, mom2);
+}
+
+// camera_sample with the moments: vlos is the velocity along the sample's own ray, away from the
+// camera, (d . v) / r with d of step 1 and r of step 7.
+template <typename T>
+NXC_DEV void camera_moments_sample(const CameraK &K, const ImageK &G, const ImageRegs &R, bool has,
+                                   double x, double y, double z, double vy, double frac,
+                                   const T *__restrict__ vx_at, const T *__restrict__ vz_at,
+                                   double *__restrict__ acc2, int64_t n_pix,
+                                   double *__restrict__ mom2, unsigned long long &binned,
+                                   unsigned long long &nonfinite)
+{
+    int pix = -1;
+    double radvel = 0.0, fw = 0.0, dc = 1.0, r2 = 1.0, w = 0.0, r = 1.0, vlos = 0.0;
+    if (has) pix = camera_locate(K, G, R, x, y, z, vy, frac, radvel, fw, dc, r2, nonfinite);
+    bool ok = pix >= 0;
+    if (ok && !image_weight(G, R, radvel, fw, w)) { nonfinite++; ok = false; }
+    if (ok) {
+        r = nxc_sqrt(r2);
+        const double foot = nxc_div((dc * dc) * dc, r);
+        w = nxc_div(w, foot * K.area);
+        if (!(__builtin_fabs(w) <= 1.7976931348623157e308)) { nonfinite++; ok = false; }
+    }
+    binned += ok;
+    image_add_pairs(ok, pix, w, acc2);
+    if (ok && w != 0.0) {
+        const double vx = (double)*vx_at, vz = (double)*vz_at;
+        const double dx = x - K.o[0], dy = y - K.o[1], dz = z - K.o[2];
+        vlos = nxc_div((dx * vx + dy * vy) + dz * vz, r);
+    }
+    pixel_moments_add(ok, pix, w, vlos, n_pix, mom2);
+}
+
 // Per-wave compaction queue between image_locate and image_weight: a ring of 128 located samples
 // {pixel, radial velocity, masked fraction} in LDS.  push() appends the lanes' samples in lane
 // order (ballot + prefix rank); once 64 are waiting, pop() hands one to every lane.  All calls

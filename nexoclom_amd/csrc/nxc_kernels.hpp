@@ -13,6 +13,7 @@
 //   k_var           a-4  adaptive-step driver, same lane-refill structure
 //   k_image         a-6..a-8  image of stored samples (HBM-bound: 40 B/sample in)
 //   k_camera        the same samples in the perspective image of a camera at a finite distance
+//   k_image_moments, k_camera_moments   either pass with four velocity-moment sums per pixel
 //
 // All lookup tables (radiation acceleration, g-values, bin edges) are staged once per workgroup
 // into LDS from one packed blob.
@@ -969,6 +970,37 @@ k_image(const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p,
         image_sample(lds_header().G, IR, has, sx, sy, sz, svy, sf, acc2, my_binned, my_nonfinite);
     }
     // (the tables are not read any more: their first bytes carry the workgroup's sums)
+    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
+                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
+}
+
+// ModelImage(moments=True): k_image's pass over seven columns; a sample that reaches its pixel
+// with w != 0 also adds its four velocity-moment terms to mom2, [2][n_pix] 16-byte records
+// (image_moments_sample): at most three atomic requests per binned sample.  74 VGPRs: six waves a
+// SIMD, which three 512-thread groups fill where one 1024-thread group would leave it at four.
+constexpr int NXC_IMAGE_MOMENTS_BLOCK = 512;
+template <typename T>
+__global__ void __launch_bounds__(NXC_IMAGE_MOMENTS_BLOCK)
+k_image_moments(const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p, int64_t n_pix,
+                const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ z,
+                const T *__restrict__ vx, const T *__restrict__ vy, const T *__restrict__ vz,
+                const T *__restrict__ frac, double *__restrict__ acc2, double *__restrict__ mom2,
+                DevCounters *__restrict__ ctr)
+{
+    stage_tables(blob, stage_bytes);
+    const ImageRegs IR = image_regs(lds_header().G);
+    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
+    // wave-uniform trip count (the accumulation is wave-cooperative); the last trip is ragged
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p;
+         base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        const bool has = i < p;
+        my_samples += has;
+        double sx = 0, sy = 0, sz = 0, svy = 0, sf = 0;
+        if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
+        image_moments_sample(lds_header().G, IR, has, sx, sy, sz, svy, sf, vx + i, vz + i, acc2,
+                             n_pix, mom2, my_binned, my_nonfinite);
+    }
     flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
                       &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
 }
@@ -2829,6 +2861,33 @@ k_camera(CameraK K, const unsigned char *__restrict__ blob, int64_t stage_bytes,
         camera_sample(K, lds_header().G, IR, has, sx, sy, sz, svy, sf, acc2, my_binned, my_nonfinite);
     }
     // (the tables are not read any more: their first bytes carry the workgroup's sums)
+    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
+                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
+}
+
+// CameraImage(moments=True): k_camera's pass over seven columns with the moment terms along each
+// sample's own ray (camera_moments_sample); mom2 as in k_image_moments.
+template <typename T>
+__global__ void __launch_bounds__(NXC_CAMERA_BLOCK)
+k_camera_moments(CameraK K, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p,
+                 int64_t n_pix, const T *__restrict__ x, const T *__restrict__ y,
+                 const T *__restrict__ z, const T *__restrict__ vx, const T *__restrict__ vy,
+                 const T *__restrict__ vz, const T *__restrict__ frac, double *__restrict__ acc2,
+                 double *__restrict__ mom2, DevCounters *__restrict__ ctr)
+{
+    stage_tables(blob, stage_bytes);
+    const ImageRegs IR = image_regs(lds_header().G);
+    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p;
+         base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        const bool has = i < p;
+        my_samples += has;
+        double sx = 0, sy = 0, sz = 0, svy = 0, sf = 0;
+        if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
+        camera_moments_sample(K, lds_header().G, IR, has, sx, sy, sz, svy, sf, vx + i, vz + i, acc2,
+                              n_pix, mom2, my_binned, my_nonfinite);
+    }
     flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
                       &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
 }

@@ -46,7 +46,13 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_camera_accumulate_f32', 'nxc_camera_accumulate_rows', 'nxc_camera_download',
            'nxc_density_moments_enable', 'nxc_density_moments_accumulate',
            'nxc_density_moments_accumulate_f32', 'nxc_density_moments_accumulate_rows',
-           'nxc_density_moments_download')
+           'nxc_density_moments_download',
+           'nxc_image_moments_enable', 'nxc_image_moments_accumulate',
+           'nxc_image_moments_accumulate_f32', 'nxc_image_moments_accumulate_rows',
+           'nxc_image_moments_download',
+           'nxc_camera_moments_enable', 'nxc_camera_moments_accumulate',
+           'nxc_camera_moments_accumulate_f32', 'nxc_camera_moments_accumulate_rows',
+           'nxc_camera_moments_download')
 ABI_VERSION = 3
 
 
@@ -787,6 +793,24 @@ class Context:
         count = store.total - first if count is None else int(count)
         self._accumulate('nxc_image_accumulate', None, (store, first, count))
 
+    def image_moments_enable(self, on=True):
+        """After ``set_image``: allocate and zero the four velocity-moment sums per pixel (``on``
+        false frees them; the next ``set_image`` switches them off)."""
+        self._check(self.lib.nxc_image_moments_enable(self._h, C.c_int(int(bool(on)))))
+
+    def image_moments_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
+                                 frac=None, rows=None):
+        """Add samples to the image pair and to the pixel moments in one pass (always the atomic
+        path): seven host columns (float32 ones go over as they are), or ``rows = (RowStore,
+        first, count)``."""
+        self._accumulate('nxc_image_moments_accumulate', (x, y, z, vx, vy, vz, frac), rows)
+
+    def image_moments_download(self):
+        """(nx, nz, 4) float64: the sums m1 m2 m3 ww of every pixel (PIXEL_MOMENT_COLUMNS)."""
+        sums = np.zeros(tuple(getattr(self, 'image_shape', None) or (0, 0)) + (4,))
+        self._check(self.lib.nxc_image_moments_download(self._h, _p(sums)))
+        return sums
+
     # -- f-1: spacecraft lines of sight ------------------------------------------------------
     def los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables,
                        ladder, sc, x=None, y=None, z=None, vy=None, frac=None, index=None,
@@ -935,6 +959,23 @@ class Context:
         self._check(self.lib.nxc_camera_download(
             self._h, _p(image), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
         return image, counts
+
+    def camera_moments_enable(self, on=True):
+        """After ``camera_set``: allocate and zero the four velocity-moment sums per pixel of the
+        camera image (``on`` false frees them; the next ``camera_set`` switches them off)."""
+        self._check(self.lib.nxc_camera_moments_enable(self._h, C.c_int(int(bool(on)))))
+
+    def camera_moments_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
+                                  frac=None, rows=None):
+        """Add samples to the camera image and to its pixel moments in one pass: seven host
+        columns, or ``rows = (RowStore, first, count)``."""
+        self._accumulate('nxc_camera_moments_accumulate', (x, y, z, vx, vy, vz, frac), rows)
+
+    def camera_moments_download(self):
+        """(nx, nz, 4) float64: the sums m1 m2 m3 ww of every pixel of the camera image."""
+        sums = np.zeros(tuple(getattr(self, 'camera_shape', None) or (0, 0)) + (4,))
+        self._check(self.lib.nxc_camera_moments_download(self._h, _p(sums)))
+        return sums
 
     # -- LOSResultFitted ----------------------------------------------------------------------
     def pairs_create(self, capacity):
