@@ -746,6 +746,64 @@ int nxc_camera_moments_accumulate_f32(nxc_handle *h, int64_t p, const float *x, 
 int nxc_camera_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
 int nxc_camera_moments_download(nxc_handle *h, double *sums);
 
+/* ---- Velocity cube: one image per Doppler bin, a line profile per pixel ---------------------------
+ * EXTENSION -- the pixel moments above stop at a line's shift and width; the cube keeps the profile.
+ * A cube has nv >= 1 bins over [v_lo, v_hi), in the rows' velocity unit (planet radii per second).
+ * The host forms inv_dv = nv / (v_hi - v_lo) once in fp64 and hands it to the device.  A sample
+ * that reaches pixel pix with the final weight w -- exactly what is added to image[pix] -- and
+ * w != 0 has the line-of-sight velocity vlos of "Pixel moments": for the image row 1 of the rotation
+ * (with the float32 round trip under downcast_f32), for the camera (d . v) / r along its own ray.
+ * Then, fp64, one rounding per operation, no contraction:
+ *   t = (vlos - v_lo) * inv_dv
+ *   k = 0                 if t < 0                              (below the range)
+ *   k = 1 + (int)t        if 0 <= t < nv                        (bin (int)t of the range)
+ *   k = nv + 1            otherwise: at or above v_hi, or vlos not a number
+ * and the sample adds {w, w*w} to record pix*(nv + 2) + k.
+ *   - A sample with w == 0 adds nothing to the cube; it is still counted in the packet image.  vx and
+ *     vz of such a sample are not read.
+ *   - Nothing else is filtered: every sample that adds to image[pix] adds the same w to exactly one
+ *     plane of that pixel, so the nv + 2 planes of a pixel sum to image[pix] up to the order of the
+ *     additions.
+ *   - The image pair, the counts and the counters of a cube pass are those of the plain pass.
+ *   - The second half of a record gives w_sum^2 / ww_sum, the effective number of packets of that
+ *     spectral bin: the profile's error bars.
+ *   nxc_image_cube_enable            after nxc_set_image: nv >= 1 allocates and zeroes
+ *                                    nx*nz*(nv + 2) 16-byte records (NXC_ERR_NOMEM when they cannot
+ *                                    be had), nv == 0 frees them; nxc_set_image switches the cube
+ *                                    off again; nxc_image_clear zeroes it with the image while it is
+ *                                    on.  NXC_ERR_ARG, before anything is allocated or freed, for
+ *                                    nv < 0, v_lo or v_hi not finite, v_lo >= v_hi (or a width that
+ *                                    is not finite), nx*nz*(nv + 2) >= 2^31
+ *   nxc_image_cube_accumulate[_f32]  adds p host samples to the image pair AND the cube in one pass,
+ *                                    one atomic pair per request (at most two requests per binned
+ *                                    sample), never the tiles of nxc_image_mode
+ *   nxc_image_cube_accumulate_rows   the same for rows [first, first + count) of a row store
+ *   nxc_image_cube_download          sums[nx*nz][nv + 2][2] = {w sum, w*w sum}, pixel index
+ *                                    ix*nz + iz, plane 0 below, planes 1..nv the bins, nv + 1 above
+ *   nxc_camera_cube_*                the same five against the camera's own image buffer
+ * NXC_ERR_STATE names the missing call (the set first, then the enable), then NXC_ERR_ARG as for the
+ * moments.  The cube and the moments are independent states of a handle: the cube entries add to the
+ * image pair and the cube only, the moments entries to the image pair and the moments only, the
+ * plain entries to the image pair only. */
+int nxc_image_cube_enable(nxc_handle *h, int64_t nv, double v_lo, double v_hi);
+int nxc_image_cube_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                              const double *z, const double *vx, const double *vy,
+                              const double *vz, const double *frac);
+int nxc_image_cube_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                  const float *z, const float *vx, const float *vy,
+                                  const float *vz, const float *frac);
+int nxc_image_cube_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_image_cube_download(nxc_handle *h, double *sums);
+int nxc_camera_cube_enable(nxc_handle *h, int64_t nv, double v_lo, double v_hi);
+int nxc_camera_cube_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                               const double *z, const double *vx, const double *vy,
+                               const double *vz, const double *frac);
+int nxc_camera_cube_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                   const float *z, const float *vx, const float *vy,
+                                   const float *vz, const float *frac);
+int nxc_camera_cube_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_camera_cube_download(nxc_handle *h, double *sums);
+
 /* ---- Source maps: where the packets of fitted Outputs came from ---------------------------------
  * data_simulation/make_source_map.py:11-174 per Output, summed over the Outputs of a result on the
  * device.  Grid: nlon x nlat points at the bin centres point_lon[nlon], point_lat[nlat]; point p =

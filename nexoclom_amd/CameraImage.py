@@ -27,7 +27,9 @@ of the density through that pixel.
 ``moments=True`` adds ModelImage's per-pixel velocity moments (moment_sums, velocity,
 velocity_variance, velocity_dispersion, velocity_skewness, effective_packets) in the same pass
 (k_camera_moments), with the line-of-sight velocity taken along each sample's own ray from the
-camera, positive receding.
+camera, positive receding.  ``cube=(v_lo_kms, v_hi_kms, nbins)`` adds ModelImage's velocity cube
+(cube_sums, cube, cube_below, cube_above, velocity_edges, velocity_axis, cube_effective_packets)
+with the same velocity (k_camera_cube).
 
 Not supported, and refused: streaming (``npackets=``), shared runs (``cp=`` / ``shard=``), the
 LDS-tile accumulation, fisheye / all-sky projections (a gnomonic camera sees less than 180
@@ -35,7 +37,8 @@ degrees), moons as occulters.
 """
 import numpy as np
 
-from .ModelImage import PIXEL_MOMENT_COLUMNS, ModelResult, pixel_moments_from_sums, refuse_moments_with
+from .ModelImage import (PIXEL_MOMENT_COLUMNS, ModelResult, cube_from_sums, new_cube_sums, parse_cube,
+                         pixel_moments_from_sums, refuse_cube_with, refuse_moments_with)
 from .catalogue import sample_spans, shared_context
 from .input_classes import InputError
 from .units import Quantity
@@ -91,8 +94,14 @@ def camera_basis(boresight, up):
 
 class CameraImage(ModelResult):
     moments = False           # True: the pass over the rows also fills moment_sums
+    cube = None               # (v_lo_kms, v_hi_kms, nbins): the pass also fills cube_sums
 
-    def __init__(self, inputs, params, *, context=None, device=0, moments=False, **unsupported):
+    def __init__(self, inputs, params, *, context=None, device=0, moments=False, cube=None,
+                 **unsupported):
+        if cube is not None:
+            refuse_cube_with(moments=moments,
+                             **{key: unsupported.get(key) for key in ('npackets', 'shard', 'cp')})
+            cube = parse_cube(cube)
         if moments:
             refuse_moments_with(**{key: unsupported.get(key) for key in ('npackets', 'shard', 'cp')})
         for key in unsupported:
@@ -109,6 +118,9 @@ class CameraImage(ModelResult):
         self.moments = bool(moments)
         if self.moments:
             self.moment_sums = np.zeros(tuple(self.dims) + (len(PIXEL_MOMENT_COLUMNS),))
+        self.cube = cube
+        if self.cube is not None:
+            self.cube_sums = new_cube_sums(self.dims, self.cube)
         self._ctx, self._device = context, device
         self.counters = {}
         self._from_catalogue()
@@ -164,9 +176,9 @@ class CameraImage(ModelResult):
     def _from_catalogue(self):
         """Every catalogued Output through k_camera.  Rows in HBM are read where they are, one
         launch per run of adjacent slices of a store; other Outputs upload their five sample
-        columns (seven with ``moments``, through k_camera_moments).  The image stays on the device
-        while (aplanet, vrplanet) -- the g-values -- stay the same, and is summed on the host
-        across such groups."""
+        columns (seven with ``moments`` or ``cube``, through k_camera_moments / k_camera_cube).
+        The image stays on the device while (aplanet, vrplanet) -- the g-values -- stay the same,
+        and is summed on the host across such groups."""
         from .Output import Output
         runs = list(self.inputs._catalogue)
         if not runs:
@@ -195,8 +207,12 @@ class CameraImage(ModelResult):
             self.packet_image += counts.astype(float)
             if self.moments:
                 self.moment_sums += ctx.camera_moments_download()
+            if self.cube is not None:
+                self.cube_sums += ctx.camera_cube_download()
 
-        accumulate = ctx.camera_moments_accumulate if self.moments else ctx.camera_accumulate
+        velocity = self.moments or self.cube is not None
+        accumulate = (ctx.camera_cube_accumulate if self.cube is not None else
+                      ctx.camera_moments_accumulate if self.moments else ctx.camera_accumulate)
         is_set = False
         for kind, item in sample_spans(announced(), ctx, key=g_values):
             if kind == 'key':
@@ -207,15 +223,18 @@ class CameraImage(ModelResult):
                                self.quantity, self.uedges, self.vedges, self.g_tables(aplanet))
                 if self.moments:
                     ctx.camera_moments_enable()
+                if self.cube is not None:
+                    v_lo, v_hi, nbins = self.cube
+                    ctx.camera_cube_enable(nbins, v_lo/self.unit_km, v_hi/self.unit_km)
                 is_set = True
                 continue
             if kind == 'rows':
                 accumulate(rows=item)
             else:
-                samples = Output.image_columns(item, velocity=self.moments)[0]
+                samples = Output.image_columns(item, velocity=velocity)[0]
                 if samples is None or not len(samples[0]):
                     continue
-                names = Output.MOMENT_COLS if self.moments else Output.IMAGE_COLS
+                names = Output.MOMENT_COLS if velocity else Output.IMAGE_COLS
                 accumulate(**dict(zip(names, samples)))
             for key, v in ctx.counters().items():
                 totals[key] = totals.get(key, 0) + v
@@ -231,5 +250,9 @@ class CameraImage(ModelResult):
         if self.moments:         # the quotients are of the unscaled sums
             for name, value in pixel_moments_from_sums(self.image, self.moment_sums,
                                                        self.unit_km).items():
+                setattr(self, name, value)
+        if self.cube is not None:
+            for name, value in cube_from_sums(self.cube_sums, self.atoms_per_packet,
+                                              *self.cube[:2]).items():
                 setattr(self, name, value)
         self.image *= self.atoms_per_packet

@@ -344,7 +344,9 @@ class Input:
         every rank bins the Outputs of its own catalogue and the image pairs and source totals
         are summed over the ranks (reduce='rccl': one ncclAllReduce; 'host': over the control
         plane, for tests) -- every rank gets the image of the whole run."""
-        from .ModelImage import ModelImage, refuse_moments_with
+        from .ModelImage import ModelImage, refuse_cube_with, refuse_moments_with
+        if kwargs.get('cube') is not None:
+            refuse_cube_with(cp=cp, moments=kwargs.get('moments'))
         if kwargs.get('moments'):
             refuse_moments_with(cp=cp)
         if cp is None or cp.world == 1:

@@ -22,9 +22,17 @@ shift, km/s, positive receding), ``velocity_variance`` / ``velocity_dispersion``
 ``velocity_skewness`` and ``effective_packets`` (``image / sqrt(effective_packets)`` is the 1-sigma
 statistical error of ``image``).  include/nexoclom_hip.h ("Pixel moments") holds the definition.
 
+``cube=(v_lo_kms, v_hi_kms, nbins)`` (catalogued Outputs only; an extension) adds the line profile of
+every pixel in the same pass: ``cube`` (nx, nz, nbins), the image's quantity per Doppler bin of the
+line-of-sight velocity (planet frame, positive receding), ``cube_below`` / ``cube_above`` for what
+falls outside the range, ``velocity_edges`` / ``velocity_axis`` [km/s], ``cube_effective_packets``
+(the error bars: ``cube / sqrt(cube_effective_packets)``) and the unscaled ``cube_sums``.
+include/nexoclom_hip.h ("Velocity cube") holds the definition.
+
 Bokeh display / PostgreSQL caching of the reference are out of scope.
 """
 import copy
+import operator
 import json
 import os
 
@@ -86,6 +94,68 @@ def refuse_moments_with(**given):
     for key, value in given.items():
         if value is not None:
             raise NotImplementedError(why[key])
+
+
+def parse_cube(cube):
+    """``(v_lo_kms, v_hi_kms, nbins)`` of a ``cube=`` argument as (float, float, int); ValueError
+    for anything but three numbers, a bin count that is no positive integer, or a range that is
+    empty or not finite."""
+    try:
+        v_lo, v_hi, nbins = cube
+        v_lo, v_hi = float(v_lo), float(v_hi)
+    except (TypeError, ValueError):
+        raise ValueError('cube= takes three numbers (v_lo_kms, v_hi_kms, nbins)') from None
+    try:
+        nbins = operator.index(nbins)
+    except TypeError:
+        raise ValueError('cube=: the number of bins must be an integer') from None
+    if nbins < 1:
+        raise ValueError('cube=: the number of bins must be at least 1')
+    if not (np.isfinite(v_lo) and np.isfinite(v_hi) and np.isfinite(v_hi - v_lo)):
+        raise ValueError('cube=: the velocity range must be finite')
+    if not v_lo < v_hi:
+        raise ValueError('cube=: the velocity range is empty (v_lo_kms must be below v_hi_kms)')
+    return v_lo, v_hi, nbins
+
+
+def refuse_cube_with(**given):
+    """NotImplementedError for what a cube pass cannot be combined with."""
+    why = {'npackets': 'cube= reads catalogued Outputs only: streaming (npackets=) bins inside the '
+                       'fused integrate kernel, which carries no velocity cube',
+           'shard': 'cube= does not support shard=: the cube is not reduced over shards',
+           'cp': 'cube= does not support cp=: there is no all-reduce of the cube yet',
+           'moments': 'cube= does not support moments=True: each is a pass of its own that adds to '
+                      'the image, so two passes would add it twice; make two objects'}
+    for key, value in given.items():
+        if value is not None and value is not False:
+            raise NotImplementedError(why[key])
+
+
+def cube_from_sums(cube_sums, atoms_per_packet, v_lo_kms, v_hi_kms):
+    """What a cube pass publishes, from ``cube_sums`` (nx, nz, nbins + 2, 2) = {sum w, sum w w} per
+    pixel and plane (plane 0 below the range, 1..nbins the bins, nbins + 1 at or above it):
+      cube, cube_below, cube_above   sum w times ``atoms_per_packet``, the image's scaling
+      velocity_edges, velocity_axis  v_lo + k (v_hi - v_lo)/nbins and the bins' centres [km/s]
+      cube_effective_packets         (sum w)^2 / sum w w per bin, 0 where a bin is empty"""
+    cube_sums = np.asarray(cube_sums, dtype=float)
+    nbins = cube_sums.shape[-2] - 2
+    S, ww = cube_sums[..., 1:-1, 0], cube_sums[..., 1:-1, 1]
+    filled = ww != 0
+    edges = v_lo_kms + np.arange(nbins + 1)*(v_hi_kms - v_lo_kms)/nbins
+    return {'cube': S*atoms_per_packet,
+            'cube_below': cube_sums[..., 0, 0]*atoms_per_packet,
+            'cube_above': cube_sums[..., -1, 0]*atoms_per_packet,
+            'velocity_edges': edges,
+            'velocity_axis': (edges[:-1] + edges[1:])/2,
+            'cube_effective_packets': np.where(filled, S*S/np.where(filled, ww, 1.0), 0.0)}
+
+
+def new_cube_sums(dims, cube):
+    """Zeroed ``cube_sums`` for an image of ``dims`` pixels; ValueError when the cube has more
+    records than the device addresses (nx nz (nbins + 2) < 2^31)."""
+    if dims[0]*dims[1]*(cube[2] + 2) >= 2**31:
+        raise ValueError('cube=: dims[0]*dims[1]*(nbins + 2) must stay below 2^31')
+    return np.zeros(tuple(dims) + (cube[2] + 2, 2))
 
 
 def rotation_matrix(theta, axis):
@@ -182,10 +252,15 @@ class ModelResult:
 
 class ModelImage(ModelResult):
     moments = False           # True: the pass over the rows also fills moment_sums
+    cube = None               # (v_lo_kms, v_hi_kms, nbins): the pass also fills cube_sums
 
     def __init__(self, inputs, params, overwrite=False, distribute=None, *, npackets=None,
                  seed=None, packs_per_it=None, downcast=True, device=0, context=None,
-                 sampler='numpy', shard=None, finalize=True, generator='philox', moments=False):
+                 sampler='numpy', shard=None, finalize=True, generator='philox', moments=False,
+                 cube=None):
+        if cube is not None:
+            refuse_cube_with(npackets=npackets, shard=shard, moments=moments)
+            cube = parse_cube(cube)
         if moments:
             refuse_moments_with(npackets=npackets, shard=shard)
         super().__init__(inputs, params)
@@ -200,6 +275,9 @@ class ModelImage(ModelResult):
         self.moments = bool(moments)
         if self.moments:
             self.moment_sums = np.zeros(tuple(self.dims) + (len(PIXEL_MOMENT_COLUMNS),))
+        self.cube = cube
+        if self.cube is not None:
+            self.cube_sums = new_cube_sums(self.dims, self.cube)
         self.blimits = None
         self.xaxis = None
         self.zaxis = None
@@ -249,6 +327,8 @@ class ModelImage(ModelResult):
             self.packet_image += counted.histogram
             if self.moments:
                 self.moment_sums += self._last_moment_sums
+            if self.cube is not None:
+                self.cube_sums += self._last_cube_sums
             self.totalsource += run.totalsource
             self.xaxis, self.zaxis = weighted.x, weighted.y
 
@@ -277,10 +357,7 @@ class ModelImage(ModelResult):
         # the Outputs of a launch group are consecutive slices of one store: one kernel launch per
         # run of adjacent slices instead of one per Output
         for _, span in sample_spans(announced(), ctx):
-            if self.moments:
-                ctx.image_moments_accumulate(rows=span)
-            else:
-                ctx.image_accumulate_rows(*span)
+            self._accumulate(ctx, rows=span)
             for key, v in ctx.counters().items():
                 totals[key] = totals.get(key, 0) + v
         self.counters = totals
@@ -290,6 +367,8 @@ class ModelImage(ModelResult):
         self.packet_image += counts.astype(float)
         if self.moments:
             self.moment_sums += ctx.image_moments_download()
+        if self.cube is not None:
+            self.cube_sums += ctx.image_cube_download()
         h = Histogram2dResult(image, self.xedges, self.zedges)
         self.xaxis, self.zaxis = h.x, h.y
         return True
@@ -303,6 +382,10 @@ class ModelImage(ModelResult):
         if self.moments:         # the quotients are of the unscaled sums
             for name, value in pixel_moments_from_sums(self.image, self.moment_sums,
                                                        self.unit_km).items():
+                setattr(self, name, value)
+        if self.cube is not None:
+            for name, value in cube_from_sums(self.cube_sums, self.atoms_per_packet,
+                                              *self.cube[:2]).items():
                 setattr(self, name, value)
         self.image *= self.atoms_per_packet
 
@@ -328,6 +411,21 @@ class ModelImage(ModelResult):
                       self.xedges, self.zedges, self.g_tables(aplanet), downcast_f32=downcast)
         if self.moments:
             ctx.image_moments_enable()
+        if self.cube is not None:
+            v_lo, v_hi, nbins = self.cube
+            ctx.image_cube_enable(nbins, v_lo/self.unit_km, v_hi/self.unit_km)
+
+    def _accumulate(self, ctx, samples=(), rows=None):
+        """One pass over host columns or ``rows = (RowStore, first, count)`` through the entry this
+        image asked for: the cube's, the moments' or the plain one."""
+        if self.cube is not None:
+            ctx.image_cube_accumulate(*samples, rows=rows)
+        elif self.moments:
+            ctx.image_moments_accumulate(*samples, rows=rows)
+        elif rows is not None:
+            ctx.image_accumulate_rows(*rows)
+        else:
+            ctx.image_accumulate(*samples)
 
     def create_image(self, output):
         """ModelImage.py:229-274 for one catalogued Output (or .npz path): the restored sample
@@ -339,26 +437,23 @@ class ModelImage(ModelResult):
             # the rows are still in HBM as save() would have stored them: bin them where they are
             aplanet, vrplanet_kms = float(output.aplanet), float(output.vrplanet)
             self._set_image(ctx, aplanet, vrplanet_kms/self.unit_km, downcast=False)
-            if self.moments:
-                ctx.image_moments_accumulate(rows=tuple(view[:3]))
-            else:
-                ctx.image_accumulate_rows(view[0], view[1], view[2])
+            self._accumulate(ctx, rows=tuple(view[:3]))
         else:
-            samples, aplanet, vrplanet_kms = Output.image_columns(output, velocity=self.moments)
+            samples, aplanet, vrplanet_kms = Output.image_columns(
+                output, velocity=self.moments or self.cube is not None)
             if samples is None or len(samples[0]) == 0:
                 raise ValueError('this Output holds no trajectory (it was run with '
                                  'keep_trajectory=False); use ModelImage(..., npackets=N) instead')
             vr = vrplanet_kms/self.unit_km                 # km/s -> R/s (ModelImage.py:242-243)
             self._set_image(ctx, aplanet, vr, downcast=False)
-            if self.moments:
-                ctx.image_moments_accumulate(*samples)
-            else:
-                ctx.image_accumulate(*samples)
+            self._accumulate(ctx, samples)
         self.counters = ctx.counters()
         assert self.counters['nonfinite'] == 0, 'Non-finite weights'
         image, counts = ctx.image_download()
         if self.moments:
             self._last_moment_sums = ctx.image_moments_download()
+        if self.cube is not None:
+            self._last_cube_sums = ctx.image_cube_download()
         return (Histogram2dResult(image, self.xedges, self.zedges),
                 Histogram2dResult(counts.astype(float), self.xedges, self.zedges))
 

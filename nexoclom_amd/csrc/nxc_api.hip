@@ -25,6 +25,7 @@
 
 #include "../../include/nexoclom_hip.h"
 #include "nxc_camera_check.hpp"
+#include "nxc_cube_check.hpp"
 #include "nxc_desc_check.hpp"
 #include "nxc_image_block.hpp"
 #include "nxc_kernels.hpp"
@@ -349,6 +350,9 @@ struct nxc_handle {
     double *d_image = nullptr;       // interleaved {weight sum, packet count} per pixel, fp64
     bool have_img_mom = false;       // nxc_image_moments_enable since the last nxc_set_image
     double *d_img_mom = nullptr;     // the pixel moments: [2][npix] 16-byte records (k_image_moments)
+    bool have_img_cube = false;      // nxc_image_cube_enable since the last nxc_set_image
+    double *d_img_cube = nullptr;    // the velocity cube: [npix][nv + 2] records (k_image_cube)
+    CubeK img_cube{};
     size_t npix = 0;
     double *d_packets = nullptr;
     size_t packets_cap = 0;
@@ -439,6 +443,9 @@ struct nxc_handle {
     double *d_cam_image = nullptr;
     bool have_cam_mom = false;       // nxc_camera_moments_enable since the last nxc_camera_set
     double *d_cam_mom = nullptr;     // [2][cam_npix] records (k_camera_moments)
+    bool have_cam_cube = false;      // nxc_camera_cube_enable since the last nxc_camera_set
+    double *d_cam_cube = nullptr;    // [cam_npix][nv + 2] records (k_camera_cube)
+    CubeK cam_cube{};
     size_t cam_image_cap = 0, cam_npix = 0;
 
     // LOSResultFitted: the pair list the line-of-sight passes fill (nxc_los_set_pairs); the fit's
@@ -1588,6 +1595,30 @@ int camera_moments_run(nxc_handle *h, const Samples &s)
     });
 }
 
+// ModelImage(cube=...) over samples on the device (k_image_cube: atomics, never the tiles)
+int image_cube_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_image_cube<T>, NXC_IMAGE_MOMENTS_BLOCK, h->img_bytes, s.n,
+                                  h->d_blob_img, (int64_t)h->img_bytes, s.n, h->img_cube,
+                                  s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(5), s.col<T>(3),
+                                  s.col<T>(6), s.col<T>(4), h->d_image, h->d_img_cube, h->d_ctr);
+    });
+}
+
+// CameraImage(cube=...) over samples on the device (k_camera_cube)
+int camera_cube_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_camera_cube<T>, NXC_CAMERA_BLOCK, h->cam_bytes, s.n, h->cam,
+                                  h->d_blob_cam, (int64_t)h->cam_bytes, s.n, h->cam_cube,
+                                  s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(5), s.col<T>(3),
+                                  s.col<T>(6), s.col<T>(4), h->d_cam_image, h->d_cam_cube, h->d_ctr);
+    });
+}
+
 // What tells one consumer of stored samples from another at its entry points
 struct SampleConsumer {
     bool nxc_handle::*have;                      // its nxc_*_set has been called ...
@@ -1669,6 +1700,60 @@ int pixel_moments_download(nxc_handle *h, const SampleConsumer &base, const Samp
                 sums[4 * q + 2 * k] = planes[2 * (k * npix + q)];
                 sums[4 * q + 2 * k + 1] = planes[2 * (k * npix + q) + 1];
             }
+        return NXC_OK;
+    });
+}
+
+// the velocity cube's state is its enable too, checked after the set's (pixel_moments_need_set)
+const SampleConsumer IMAGE_CUBE_SAMPLES = {&nxc_handle::have_img_cube,
+                                           "nxc_image_cube_enable has not been called",
+                                           true, true, true, nullptr, image_cube_run};
+const SampleConsumer CAMERA_CUBE_SAMPLES = {&nxc_handle::have_cam_cube,
+                                            "nxc_camera_cube_enable has not been called",
+                                            true, true, true, nullptr, camera_cube_run};
+
+size_t cube_bytes(size_t npix, const CubeK &Q) { return npix * (size_t)(Q.nv + 2) * 2 * sizeof(double); }
+
+// nxc_X_cube_enable: [npix][nv + 2] zeroed records beside the image pair of `base`, or none; the
+// arguments are checked (check_cube_args) before the cube there is is touched
+int pixel_cube_enable(nxc_handle *h, const SampleConsumer &base, size_t npix, int64_t nv, double v_lo,
+                      double v_hi, bool nxc_handle::*have, double *nxc_handle::*d_cube,
+                      CubeK nxc_handle::*Q)
+{
+    if (int rc = pixel_moments_need_set(h, base)) return rc;
+    return guarded([&]() -> int {
+        if (nv != 0) {
+            const std::string why = check_cube_args((int64_t)npix, nv, v_lo, v_hi);
+            if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
+        }
+        HIPCHK(hipSetDevice(h->device));
+        h->*have = false;
+        if (h->*d_cube) HIPCHK(hipFree(h->*d_cube));
+        h->*d_cube = nullptr;
+        if (nv == 0) return NXC_OK;
+        h->*Q = CubeK{(int)nv, v_lo, cube_inv_dv(nv, v_lo, v_hi)};
+        const size_t bytes = cube_bytes(npix, h->*Q);
+        size_t cap = 0;
+        int rc = ensure(reinterpret_cast<void **>(&(h->*d_cube)), &cap, bytes);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(h->*d_cube, 0, bytes, h->stream));
+        HIPCHK(stream_sync(h));
+        h->*have = true;
+        return NXC_OK;
+    });
+}
+
+// nxc_X_cube_download: sums[npix][nv + 2][2], the device's own order
+int pixel_cube_download(nxc_handle *h, const SampleConsumer &base, const SampleConsumer &cube,
+                        size_t bytes, const double *d_cube, double *sums)
+{
+    if (int rc = pixel_moments_need_set(h, base)) return rc;
+    return guarded([&]() -> int {
+        if (!(h->*cube.have)) return fail(NXC_ERR_STATE, cube.unset);
+        if (!sums) return fail(NXC_ERR_ARG, "bad arguments");
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipMemcpyAsync(sums, d_cube, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(stream_sync(h));
         return NXC_OK;
     });
 }
@@ -2071,7 +2156,7 @@ int nxc_destroy(nxc_handle *h)
                     h->d_blob_img, h->d_reduce_n, h->d_losblk, h->d_dens_pts, h->d_dens_cell,
                     h->d_dens_acc, h->d_dens_mom, h->d_fit_spec, h->d_fit_pk, h->d_fit_smp, h->d_fit_aux,
                     h->d_smap_grid, h->d_smap_acc, h->d_smap_pk, h->d_blob_cam, h->d_cam_image,
-                    h->d_img_mom, h->d_cam_mom};
+                    h->d_img_mom, h->d_cam_mom, h->d_img_cube, h->d_cam_cube};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     pool_flush(h);
@@ -2221,6 +2306,7 @@ int nxc_set_image(nxc_handle *h, const nxc_image_desc *d)
     h->G = G;
     h->have_image = true;
     h->have_img_mom = false;
+    h->have_img_cube = false;
 
     const size_t npix = (size_t)d->nx * (size_t)d->nz;
     if (npix != h->npix) {
@@ -2368,6 +2454,8 @@ int nxc_image_clear(nxc_handle *h)
     HIPCHK(hipMemsetAsync(h->d_image, 0, 2 * h->npix * sizeof(double), h->stream));
     if (h->have_img_mom)
         HIPCHK(hipMemsetAsync(h->d_img_mom, 0, 4 * h->npix * sizeof(double), h->stream));
+    if (h->have_img_cube)
+        HIPCHK(hipMemsetAsync(h->d_img_cube, 0, cube_bytes(h->npix, h->img_cube), h->stream));
     return NXC_OK;
 }
 
@@ -3210,6 +3298,7 @@ int nxc_camera_set(nxc_handle *h, const nxc_camera_desc *d)
 
     h->have_camera = false;
     h->have_cam_mom = false;
+    h->have_cam_cube = false;
     const size_t npix = (size_t)d->nx * (size_t)d->nz;
     if ((rc = ensure(reinterpret_cast<void **>(&h->d_blob_cam), &h->blob_cam_cap, blob.size())) ||
         (rc = ensure(reinterpret_cast<void **>(&h->d_cam_image), &h->cam_image_cap, 2 * npix * sizeof(double))))
@@ -3283,6 +3372,42 @@ int nxc_camera_moments_download(nxc_handle *h, double *sums)
 {
     return pixel_moments_download(h, CAMERA_SAMPLES, CAMERA_MOMENT_SAMPLES, h ? h->cam_npix : 0,
                                   h ? h->d_cam_mom : nullptr, sums);
+}
+
+int nxc_camera_cube_enable(nxc_handle *h, int64_t nv, double v_lo, double v_hi)
+{
+    return pixel_cube_enable(h, CAMERA_SAMPLES, h ? h->cam_npix : 0, nv, v_lo, v_hi,
+                             &nxc_handle::have_cam_cube, &nxc_handle::d_cam_cube,
+                             &nxc_handle::cam_cube);
+}
+
+int nxc_camera_cube_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                               const double *z, const double *vx, const double *vy,
+                               const double *vz, const double *frac)
+{
+    if (int rc = pixel_moments_need_set(h, CAMERA_SAMPLES)) return rc;
+    return accumulate_columns<double>(h, CAMERA_CUBE_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_camera_cube_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                   const float *z, const float *vx, const float *vy,
+                                   const float *vz, const float *frac)
+{
+    if (int rc = pixel_moments_need_set(h, CAMERA_SAMPLES)) return rc;
+    return accumulate_columns<float>(h, CAMERA_CUBE_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_camera_cube_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    if (int rc = pixel_moments_need_set(h, CAMERA_SAMPLES)) return rc;
+    return accumulate_rows(h, CAMERA_CUBE_SAMPLES, r, first, count);
+}
+
+int nxc_camera_cube_download(nxc_handle *h, double *sums)
+{
+    return pixel_cube_download(h, CAMERA_SAMPLES, CAMERA_CUBE_SAMPLES,
+                               h ? cube_bytes(h->cam_npix, h->cam_cube) : 0,
+                               h ? h->d_cam_cube : nullptr, sums);
 }
 
 // ---- source maps ---------------------------------------------------------------------------------
@@ -3824,6 +3949,42 @@ int nxc_image_moments_download(nxc_handle *h, double *sums)
 {
     return pixel_moments_download(h, IMAGE_SAMPLES, IMAGE_MOMENT_SAMPLES, h ? h->npix : 0,
                                   h ? h->d_img_mom : nullptr, sums);
+}
+
+int nxc_image_cube_enable(nxc_handle *h, int64_t nv, double v_lo, double v_hi)
+{
+    return pixel_cube_enable(h, IMAGE_SAMPLES, h ? h->npix : 0, nv, v_lo, v_hi,
+                             &nxc_handle::have_img_cube, &nxc_handle::d_img_cube,
+                             &nxc_handle::img_cube);
+}
+
+int nxc_image_cube_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                              const double *z, const double *vx, const double *vy,
+                              const double *vz, const double *frac)
+{
+    if (int rc = pixel_moments_need_set(h, IMAGE_SAMPLES)) return rc;
+    return accumulate_columns<double>(h, IMAGE_CUBE_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_image_cube_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                  const float *z, const float *vx, const float *vy,
+                                  const float *vz, const float *frac)
+{
+    if (int rc = pixel_moments_need_set(h, IMAGE_SAMPLES)) return rc;
+    return accumulate_columns<float>(h, IMAGE_CUBE_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_image_cube_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    if (int rc = pixel_moments_need_set(h, IMAGE_SAMPLES)) return rc;
+    return accumulate_rows(h, IMAGE_CUBE_SAMPLES, r, first, count);
+}
+
+int nxc_image_cube_download(nxc_handle *h, double *sums)
+{
+    return pixel_cube_download(h, IMAGE_SAMPLES, IMAGE_CUBE_SAMPLES,
+                               h ? cube_bytes(h->npix, h->img_cube) : 0,
+                               h ? h->d_img_cube : nullptr, sums);
 }
 
 int nxc_los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,

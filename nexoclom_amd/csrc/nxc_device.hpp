@@ -1175,6 +1175,85 @@ NXC_DEV void camera_moments_sample(const CameraK &K, const ImageK &G, const Imag
     pixel_moments_add(ok, pix, w, vlos, n_pix, mom2);
 }
 
+// ---- velocity cube: a sample's weight filed under its Doppler bin --------------------------------
+// (include/nexoclom_hip.h, "Velocity cube", holds the definition.)  nv bins over [v_lo, v_hi), inv_dv
+// = nv / (v_hi - v_lo) from the host.  A sample that reached pixel `pix` with the final weight
+// w != 0 and the line-of-sight velocity vlos adds {w, w w} to record pix (nv + 2) + k of cube2,
+//     t = (vlos - v_lo) inv_dv;   k = 0 if t < 0,   1 + (int)t if 0 <= t < nv,   nv + 1 otherwise
+// (otherwise: at or above v_hi, or vlos not a number -- both comparisons are false for a NaN).  The
+// record index stays below 2^31 (check_cube_args).  A sample with w == 0 adds nothing.
+// Wave-cooperative: all 64 lanes call it from uniform control flow; one request per sample.
+struct CubeK {
+    int nv;                 // bins; planes 0 and nv + 1 hold what falls below and above
+    double v_lo, inv_dv;    // [R/s], [s/R]
+};
+
+NXC_DEV void pixel_cube_add(const CubeK &Q, bool ok, int pix, double w, double vlos,
+                            double *__restrict__ cube2)
+{
+    const bool has = ok && w != 0.0;
+    const double t = (vlos - Q.v_lo) * Q.inv_dv;
+    int k = Q.nv + 1;
+    if (t < 0.0) k = 0;
+    else if (t < (double)Q.nv) k = 1 + (int)t;
+    add_record_pairs(has, pix * (Q.nv + 2) + k, w, w * w, cube2);
+}
+
+// image_sample with the cube: image_moments_sample with pixel_cube_add for its tail (the same
+// vlos, read and formed by the same lanes)
+template <typename T>
+NXC_DEV void image_cube_sample(const ImageK &G, const ImageRegs &R, const CubeK &Q, bool has, double x,
+                               double y, double z, double vy, double frac,
+                               const T *__restrict__ vx_at, const T *__restrict__ vz_at,
+                               double *__restrict__ acc2, double *__restrict__ cube2,
+                               unsigned long long &binned, unsigned long long &nonfinite)
+{
+    int pix = -1;
+    double radvel = 0.0, fw = 0.0, w = 0.0, vlos = 0.0;
+    if (has) pix = image_locate(G, R, x, y, z, vy, frac, radvel, fw, nonfinite);
+    bool ok = pix >= 0;
+    if (ok && !image_weight(G, R, radvel, fw, w)) { nonfinite++; ok = false; }
+    binned += ok;
+    image_add_pairs(ok, pix, w, acc2);
+    if (ok && w != 0.0) {
+        double vx = (double)*vx_at, vz = (double)*vz_at;
+        if (R.downcast) {
+            vx = f32_round_trip(vx); vy = f32_round_trip(vy); vz = f32_round_trip(vz);
+        }
+        vlos = (G.M[3] * vx + G.M[4] * vy) + G.M[5] * vz;
+    }
+    pixel_cube_add(Q, ok, pix, w, vlos, cube2);
+}
+
+// camera_sample with the cube: camera_moments_sample with pixel_cube_add for its tail
+template <typename T>
+NXC_DEV void camera_cube_sample(const CameraK &K, const ImageK &G, const ImageRegs &R, const CubeK &Q,
+                                bool has, double x, double y, double z, double vy, double frac,
+                                const T *__restrict__ vx_at, const T *__restrict__ vz_at,
+                                double *__restrict__ acc2, double *__restrict__ cube2,
+                                unsigned long long &binned, unsigned long long &nonfinite)
+{
+    int pix = -1;
+    double radvel = 0.0, fw = 0.0, dc = 1.0, r2 = 1.0, w = 0.0, r = 1.0, vlos = 0.0;
+    if (has) pix = camera_locate(K, G, R, x, y, z, vy, frac, radvel, fw, dc, r2, nonfinite);
+    bool ok = pix >= 0;
+    if (ok && !image_weight(G, R, radvel, fw, w)) { nonfinite++; ok = false; }
+    if (ok) {
+        r = nxc_sqrt(r2);
+        const double foot = nxc_div((dc * dc) * dc, r);
+        w = nxc_div(w, foot * K.area);
+        if (!(__builtin_fabs(w) <= 1.7976931348623157e308)) { nonfinite++; ok = false; }
+    }
+    binned += ok;
+    image_add_pairs(ok, pix, w, acc2);
+    if (ok && w != 0.0) {
+        const double vx = (double)*vx_at, vz = (double)*vz_at;
+        const double dx = x - K.o[0], dy = y - K.o[1], dz = z - K.o[2];
+        vlos = nxc_div((dx * vx + dy * vy) + dz * vz, r);
+    }
+    pixel_cube_add(Q, ok, pix, w, vlos, cube2);
+}
+
 // Per-wave compaction queue between image_locate and image_weight: a ring of 128 located samples
 // {pixel, radial velocity, masked fraction} in LDS.  push() appends the lanes' samples in lane
 // order (ballot + prefix rank); once 64 are waiting, pop() hands one to every lane.  All calls

@@ -14,6 +14,7 @@
 //   k_image         a-6..a-8  image of stored samples (HBM-bound: 40 B/sample in)
 //   k_camera        the same samples in the perspective image of a camera at a finite distance
 //   k_image_moments, k_camera_moments   either pass with four velocity-moment sums per pixel
+//   k_image_cube, k_camera_cube         either pass with the weight filed per pixel and Doppler bin
 //
 // All lookup tables (radiation acceleration, g-values, bin edges) are staged once per workgroup
 // into LDS from one packed blob.
@@ -1000,6 +1001,36 @@ k_image_moments(const unsigned char *__restrict__ blob, int64_t stage_bytes, int
         if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
         image_moments_sample(lds_header().G, IR, has, sx, sy, sz, svy, sf, vx + i, vz + i, acc2,
                              n_pix, mom2, my_binned, my_nonfinite);
+    }
+    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
+                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
+}
+
+// ModelImage(cube=...): k_image_moments' loop; a sample that reaches its pixel with w != 0 adds
+// {w, w w} to the record of its pixel and Doppler bin in cube2, [n_pix][nv + 2] 16-byte records
+// (image_cube_sample): at most two atomic requests per binned sample.  The cube's scalars travel as
+// a kernel argument; ImageK and the LDS blob are k_image's.
+template <typename T>
+__global__ void __launch_bounds__(NXC_IMAGE_MOMENTS_BLOCK)
+k_image_cube(const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p, CubeK Q,
+             const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ z,
+             const T *__restrict__ vx, const T *__restrict__ vy, const T *__restrict__ vz,
+             const T *__restrict__ frac, double *__restrict__ acc2, double *__restrict__ cube2,
+             DevCounters *__restrict__ ctr)
+{
+    stage_tables(blob, stage_bytes);
+    const ImageRegs IR = image_regs(lds_header().G);
+    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
+    // wave-uniform trip count (the accumulation is wave-cooperative); the last trip is ragged
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p;
+         base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        const bool has = i < p;
+        my_samples += has;
+        double sx = 0, sy = 0, sz = 0, svy = 0, sf = 0;
+        if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
+        image_cube_sample(lds_header().G, IR, Q, has, sx, sy, sz, svy, sf, vx + i, vz + i, acc2,
+                          cube2, my_binned, my_nonfinite);
     }
     flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
                       &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
@@ -2887,6 +2918,33 @@ k_camera_moments(CameraK K, const unsigned char *__restrict__ blob, int64_t stag
         if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
         camera_moments_sample(K, lds_header().G, IR, has, sx, sy, sz, svy, sf, vx + i, vz + i, acc2,
                               n_pix, mom2, my_binned, my_nonfinite);
+    }
+    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
+                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
+}
+
+// CameraImage(cube=...): k_camera_moments' loop with the Doppler bin along each sample's own ray
+// (camera_cube_sample); cube2 and Q as in k_image_cube.
+template <typename T>
+__global__ void __launch_bounds__(NXC_CAMERA_BLOCK)
+k_camera_cube(CameraK K, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p,
+              CubeK Q, const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ z,
+              const T *__restrict__ vx, const T *__restrict__ vy, const T *__restrict__ vz,
+              const T *__restrict__ frac, double *__restrict__ acc2, double *__restrict__ cube2,
+              DevCounters *__restrict__ ctr)
+{
+    stage_tables(blob, stage_bytes);
+    const ImageRegs IR = image_regs(lds_header().G);
+    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p;
+         base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        const bool has = i < p;
+        my_samples += has;
+        double sx = 0, sy = 0, sz = 0, svy = 0, sf = 0;
+        if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
+        camera_cube_sample(K, lds_header().G, IR, Q, has, sx, sy, sz, svy, sf, vx + i, vz + i, acc2,
+                           cube2, my_binned, my_nonfinite);
     }
     flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
                       &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);

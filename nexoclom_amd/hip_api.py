@@ -52,7 +52,11 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_image_moments_download',
            'nxc_camera_moments_enable', 'nxc_camera_moments_accumulate',
            'nxc_camera_moments_accumulate_f32', 'nxc_camera_moments_accumulate_rows',
-           'nxc_camera_moments_download')
+           'nxc_camera_moments_download',
+           'nxc_image_cube_enable', 'nxc_image_cube_accumulate', 'nxc_image_cube_accumulate_f32',
+           'nxc_image_cube_accumulate_rows', 'nxc_image_cube_download',
+           'nxc_camera_cube_enable', 'nxc_camera_cube_accumulate', 'nxc_camera_cube_accumulate_f32',
+           'nxc_camera_cube_accumulate_rows', 'nxc_camera_cube_download')
 ABI_VERSION = 3
 
 
@@ -811,6 +815,27 @@ class Context:
         self._check(self.lib.nxc_image_moments_download(self._h, _p(sums)))
         return sums
 
+    def image_cube_enable(self, nv, v_lo=0.0, v_hi=0.0):
+        """After ``set_image``: allocate and zero a velocity cube of ``nv`` bins over [v_lo, v_hi)
+        [R/s] beside the image pair (``nv`` 0 frees it; the next ``set_image`` switches it off)."""
+        self._check(self.lib.nxc_image_cube_enable(self._h, C.c_int64(int(nv)), C.c_double(v_lo),
+                    C.c_double(v_hi)))
+        self._image_cube_nv = int(nv)
+
+    def image_cube_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
+                              frac=None, rows=None):
+        """Add samples to the image pair and to its velocity cube in one pass: seven host columns (float32
+        ones go over as they are), or ``rows = (RowStore, first, count)``."""
+        self._accumulate('nxc_image_cube_accumulate', (x, y, z, vx, vy, vz, frac), rows)
+
+    def image_cube_download(self):
+        """(nx, nz, nv + 2, 2) float64: {sum w, sum w w} per pixel and plane -- plane 0 below the
+        range, 1..nv the bins, nv + 1 at or above it (or not a number)."""
+        nv = getattr(self, '_image_cube_nv', 0)
+        sums = np.zeros(tuple(getattr(self, 'image_shape', None) or (0, 0)) + (nv + 2, 2))
+        self._check(self.lib.nxc_image_cube_download(self._h, _p(sums)))
+        return sums
+
     # -- f-1: spacecraft lines of sight ------------------------------------------------------
     def los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables,
                        ladder, sc, x=None, y=None, z=None, vy=None, frac=None, index=None,
@@ -975,6 +1000,27 @@ class Context:
         """(nx, nz, 4) float64: the sums m1 m2 m3 ww of every pixel of the camera image."""
         sums = np.zeros(tuple(getattr(self, 'camera_shape', None) or (0, 0)) + (4,))
         self._check(self.lib.nxc_camera_moments_download(self._h, _p(sums)))
+        return sums
+
+    def camera_cube_enable(self, nv, v_lo=0.0, v_hi=0.0):
+        """After ``camera_set``: allocate and zero a velocity cube of ``nv`` bins over [v_lo, v_hi)
+        [R/s] beside the camera image (``nv`` 0 frees it; the next ``camera_set`` switches it off)."""
+        self._check(self.lib.nxc_camera_cube_enable(self._h, C.c_int64(int(nv)), C.c_double(v_lo),
+                    C.c_double(v_hi)))
+        self._camera_cube_nv = int(nv)
+
+    def camera_cube_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
+                               frac=None, rows=None):
+        """Add samples to the camera image and to its velocity cube in one pass: seven host columns (float32
+        ones go over as they are), or ``rows = (RowStore, first, count)``."""
+        self._accumulate('nxc_camera_cube_accumulate', (x, y, z, vx, vy, vz, frac), rows)
+
+    def camera_cube_download(self):
+        """(nx, nz, nv + 2, 2) float64: {sum w, sum w w} per pixel and plane -- plane 0 below the
+        range, 1..nv the bins, nv + 1 at or above it (or not a number)."""
+        nv = getattr(self, '_camera_cube_nv', 0)
+        sums = np.zeros(tuple(getattr(self, 'camera_shape', None) or (0, 0)) + (nv + 2, 2))
+        self._check(self.lib.nxc_camera_cube_download(self._h, _p(sums)))
         return sums
 
     # -- LOSResultFitted ----------------------------------------------------------------------
