@@ -620,6 +620,75 @@ int nxc_density_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_
                                         int64_t count);
 int nxc_density_moments_download(nxc_handle *h, double *sums);
 
+/* ---- Density spectrum: speed and flux spectra at the points, seen from a moving spacecraft ---------
+ * EXTENSION -- what a neutral mass spectrometer flown through the cloud counts: the atoms that arrive
+ * within a cone around its boresight, resolved in arrival speed, in the frame of the spacecraft.
+ * Per indexed point q the host hands over a frame record of eight doubles {ux, uy, uz, 0, bx, by, bz,
+ * 0}: u the spacecraft velocity [R/s] in the planet-centred model frame of the rows, b a unit
+ * boresight.  A spectrum has nv >= 1 speed bins over [s_lo, s_hi) [R/s]; the host forms
+ * inv_ds = nv / (s_hi - s_lo) once in fp64; cos_half is the cosine of the cone's half angle; all_sky
+ * (0 or 1) switches the cone off.  For a row that counts for point q (the membership of
+ * nxc_density_set, unchanged), with p, v and f = frac widened to fp64, one rounding per operation and
+ * no contraction:
+ *   1. c = v - u, component by component
+ *   2. s2 = (cx*cx + cy*cy) + cz*cz;   s = sqrt(s2)          (correctly rounded)
+ *   3. a = -((cx*bx + cy*by) + cz*bz)
+ *   4. the row is SEEN iff all_sky != 0 || a >= cos_half * s: the direction the atom arrives from,
+ *      -c/|c|, lies within the half angle of b.  There is no division.  A NaN fails the comparison:
+ *      not seen unless all_sky.
+ *   5. t = (s - s_lo) * inv_ds, and the plane is the velocity cube's rule:
+ *        k = 0            if t < 0
+ *        k = 1 + (int)t   if 0 <= t < nv
+ *        k = nv + 1       otherwise: at or above s_hi, or s not a number
+ *   6. every such row, seen or not, adds {f, 1} to the point's {sum_frac, count} pair, as
+ *      nxc_density_accumulate does
+ *   7. a seen row adds {f, f*f} to record q*(nv + 2) + k of plane 0 and {g, g*g}, g = f*s, to the same
+ *      record of plane 1, which starts 2*Q*(nv + 2) doubles after plane 0 (formed in 64 bits).
+ * Nothing else is filtered: a non-finite value poisons what it reaches, as elsewhere.  Plane 0 is the
+ * density per speed bin of the atoms in view, plane 1 their number flux; the second half of a record
+ * gives sum^2 / sum-of-squares, the effective number of packets of that bin.  The record index is an
+ * int on the device: Q*(nv + 2) must stay below 2^31.  The order of addition is not fixed.
+ *   nxc_density_spectrum_enable          after nxc_density_set: allocates and zeroes 2*Q*(nv + 2)
+ *                                        16-byte records and uploads frames[Q][8], in the index's
+ *                                        (sorted) point order; d == NULL or nv == 0 frees them;
+ *                                        nxc_density_set switches the spectrum off again and frees
+ *                                        them too (they reach gigabytes on a dense grid).
+ *                                        NXC_ERR_ARG, before anything is freed or allocated, unless
+ *                                        nv >= 1, s_lo and s_hi finite with 0 <= s_lo < s_hi and a
+ *                                        finite width, cos_half finite in [-1, 1], every frame value
+ *                                        finite, each |b| within 1e-12 of 1 (not asked with all_sky),
+ *                                        n_frames == Q and Q*(nv + 2) < 2^31
+ *   nxc_density_spectrum_accumulate[_f32] adds p host samples to {sum_frac, count} AND the spectrum in
+ *                                        one pass (float32 ones widened as restore() does)
+ *   nxc_density_spectrum_accumulate_rows the same for rows [first, first + count) of a row store
+ *   nxc_density_spectrum_download        sums[2][Q][nv + 2][2], the device's own order: plane, point
+ *                                        (index order), speed plane (0 below, 1..nv the bins, nv + 1
+ *                                        above), {sum, sum of squares}
+ * NXC_ERR_STATE names the missing call (nxc_density_set, then the enable); NXC_ERR_ARG for p < 0 or a
+ * null column with p > 0; p = 0 or Q = 0 adds nothing.  The spectrum and the moments are independent
+ * states of a handle: the spectrum entries add to {sum_frac, count} and the spectrum only, the moments
+ * entries to {sum_frac, count} and the moments only, the plain entries to {sum_frac, count} only. */
+typedef struct nxc_density_spectrum_desc {
+    int64_t nv;               /* speed bins (0: free the spectrum)                                */
+    double s_lo, s_hi;        /* [R/s]                                                            */
+    double cos_half;          /* cosine of the cone's half angle                                  */
+    int32_t all_sky;          /* != 0: no cone, every row within dr is seen                       */
+    int32_t reserved;
+    int64_t n_frames;         /* records in `frames`: must be Q, the points of nxc_density_set    */
+    const double *frames;     /* host [Q][8]: ux uy uz 0 bx by bz 0, in the index's point order   */
+} nxc_density_spectrum_desc;
+
+int nxc_density_spectrum_enable(nxc_handle *h, const nxc_density_spectrum_desc *d);
+int nxc_density_spectrum_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                                    const double *z, const double *vx, const double *vy,
+                                    const double *vz, const double *frac);
+int nxc_density_spectrum_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                        const float *z, const float *vx, const float *vy,
+                                        const float *vz, const float *frac);
+int nxc_density_spectrum_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first,
+                                         int64_t count);
+int nxc_density_spectrum_download(nxc_handle *h, double *sums);
+
 /* ---- CameraImage: perspective image from a position inside or near the cloud ----------------------
  * EXTENSION -- the reference images from infinity only (ModelImage.create_image); this is the same
  * weighting seen by a pinhole (gnomonic) camera at a finite distance.  Samples are x, y, z [R],

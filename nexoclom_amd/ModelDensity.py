@@ -21,7 +21,15 @@ EXTENSION (``moments=True``): the same pass also sums each hit's velocity moment
 (k_density_moments: ``MOMENT_COLUMNS`` per point, the products formed in fp64 as f * v_a,
 (f * v_a) * v_b and f * f), from which the bulk velocity, the velocity covariance, the kinetic
 temperature and the effective number of packets follow per point (``moments_from_sums``).
+
+EXTENSION (``spectrum=dict(...)``): what an in-situ mass spectrometer counts.  The pass
+(k_density_spectrum) files every hit under its speed in the frame of a spacecraft moving with a
+given velocity at that point, if the direction it arrives from lies within a cone around a
+boresight: per point and speed bin the density of the atoms in view and their number flux
+(``parse_spectrum``, ``spectrum_from_sums``).
 """
+import operator
+
 import numpy as np
 
 from . import constants as const
@@ -117,9 +125,136 @@ def moments_from_sums(s0, sums, unit_km, mass_kg):
     return u, cov, temperature, eff
 
 
+SPECTRUM_KEYS = ('speed', 'velocity', 'boresight', 'half_angle')
+MAX_SPECTRUM_RECORDS = 2**31      # the device's record index is an int
+
+
+def _vectors(value, Q, name):
+    """(Q, 3) float64 from a (3,) or (Q, 3) argument of ``spectrum=``; ValueError otherwise."""
+    try:
+        a = np.asarray(value, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f'spectrum=: {name} must be numbers of shape (3,) or ({Q}, 3)') from None
+    if a.shape == (3,):
+        a = np.broadcast_to(a, (Q, 3))
+    if a.shape != (Q, 3):
+        raise ValueError(f'spectrum=: {name} must have the shape (3,) or ({Q}, 3), not {a.shape}')
+    if not np.isfinite(a).all():
+        raise ValueError(f'spectrum=: {name} must be finite')
+    return np.array(a)
+
+
+def parse_spectrum(spectrum, Q):
+    """A ``spectrum=`` argument for ``Q`` points as a dict: ``speed`` (s_lo_kms, s_hi_kms, nbins),
+    ``velocity`` (Q, 3) [km/s], ``boresight`` (Q, 3) of unit length (zeros without one),
+    ``cos_half`` and ``all_sky``.  ValueError for anything but a dict of ``SPECTRUM_KEYS`` with a
+    ``speed``; a speed range that is not three numbers, not finite, negative or empty; a bin count
+    that is no positive integer; velocities or boresights of another shape than (3,) or (Q, 3),
+    not finite, or a boresight of length 0; ``'ram'`` where the velocity is 0; a ``half_angle``
+    outside (0, 180] degrees; more than 2^31 records."""
+    if not isinstance(spectrum, dict) or 'speed' not in spectrum:
+        raise ValueError("spectrum= takes a dict with 'speed': (s_lo_kms, s_hi_kms, nbins)")
+    unknown = sorted(set(spectrum) - set(SPECTRUM_KEYS))
+    if unknown:
+        raise ValueError(f'spectrum=: unknown keys {unknown}; it takes {SPECTRUM_KEYS}')
+    try:
+        s_lo, s_hi, nbins = spectrum['speed']
+        s_lo, s_hi = float(s_lo), float(s_hi)
+    except (TypeError, ValueError):
+        raise ValueError('spectrum=: speed takes three numbers (s_lo_kms, s_hi_kms, nbins)') from None
+    try:
+        nbins = operator.index(nbins)
+    except TypeError:
+        raise ValueError('spectrum=: the number of bins must be an integer') from None
+    if nbins < 1:
+        raise ValueError('spectrum=: the number of bins must be at least 1')
+    if not (np.isfinite(s_lo) and np.isfinite(s_hi) and np.isfinite(s_hi - s_lo)):
+        raise ValueError('spectrum=: the speed range must be finite')
+    if s_lo < 0:
+        raise ValueError('spectrum=: s_lo_kms must not be negative (it is a speed)')
+    if not s_lo < s_hi:
+        raise ValueError('spectrum=: the speed range is empty (s_lo_kms must be below s_hi_kms)')
+    if Q*(nbins + 2) >= MAX_SPECTRUM_RECORDS:
+        raise ValueError('spectrum=: points * (nbins + 2) must stay below 2^31')
+    velocity = _vectors(spectrum.get('velocity', (0., 0., 0.)), Q, 'velocity')
+    try:
+        half_angle = float(spectrum.get('half_angle', 180.))
+    except (TypeError, ValueError):
+        raise ValueError('spectrum=: half_angle must be a number of degrees') from None
+    if not (np.isfinite(half_angle) and 0 < half_angle <= 180):
+        raise ValueError('spectrum=: half_angle must lie in (0, 180] degrees')
+    boresight = spectrum.get('boresight')
+    if isinstance(boresight, str):
+        if boresight != 'ram':
+            raise ValueError("spectrum=: boresight is (3,), (Q, 3) or the string 'ram'")
+        if not (np.linalg.norm(velocity, axis=1) > 0).all():
+            raise ValueError("spectrum=: boresight 'ram' needs a velocity that is not 0 at every point")
+        boresight = velocity
+    all_sky = boresight is None or half_angle == 180
+    if boresight is None:
+        unit = np.zeros((Q, 3))
+    else:
+        unit = _vectors(boresight, Q, 'boresight')
+        length = np.linalg.norm(unit, axis=1)
+        if not (length > 0).all():
+            raise ValueError('spectrum=: a boresight of length 0 has no direction')
+        unit = unit / length[:, None]
+    return {'speed': (s_lo, s_hi, nbins), 'velocity': velocity, 'boresight': unit,
+            'cos_half': float(np.cos(np.radians(half_angle))), 'all_sky': bool(all_sky)}
+
+
+def refuse_with_spectrum(**given):
+    """NotImplementedError for what a spectrum pass cannot be combined with."""
+    why = {'moments': 'spectrum= does not support moments=True: each is a pass of its own that adds '
+                      'to the density, so two passes would add it twice; make two objects',
+           'cp': 'spectrum= does not support cp=: there is no all-reduce of the spectrum yet'}
+    for key, value in given.items():
+        if value is not None and value is not False:
+            raise NotImplementedError(why[key])
+
+
+def spectrum_frames(parsed, unit_km, order):
+    """(n, 8) frame records ux uy uz 0 bx by bz 0 of the indexed points (``order``: their input
+    positions), the velocity in R/s."""
+    frames = np.zeros((len(order), 8))
+    frames[:, 0:3] = parsed['velocity'][order] / unit_km
+    frames[:, 4:7] = parsed['boresight'][order]
+    return frames
+
+
+def spectrum_from_sums(spectrum_sums, scale, unit_km, s_lo_kms, s_hi_kms, mass_kg):
+    """What a spectrum pass publishes, from ``spectrum_sums`` (2, Q, nbins + 2, 2): plane 0 holds
+    {sum f, sum f f}, plane 1 {sum f s, sum (f s)^2} with s in R/s (R = ``unit_km``), per point and
+    speed plane (0 below the range, 1..nbins the bins, nbins + 1 at or above it), over the rows
+    in view.  ``scale`` = atoms_per_packet / Vpix, the scaling of ``density``.
+      speed_edges, speed_axis    s_lo + k (s_hi - s_lo)/nbins and the bins' centres [km/s]
+      energy_edges               m s^2 / 2 at the edges [eV]
+      density_spectrum (Q, nbins), density_below, density_above (Q,)   sum f * scale [1/cm^3],
+                                 per bin (not per km/s); density_in_view (Q,) their sum
+      flux_spectrum, flux_below, flux_above, flux    sum f s * scale with s in cm/s [1/cm^2/s]
+      spectrum_effective_packets, flux_effective_packets (Q, nbins)   sum^2 / sum of squares,
+                                 0 where a bin is empty"""
+    sums = np.asarray(spectrum_sums, dtype=np.float64)
+    nbins = sums.shape[2] - 2
+    edges = s_lo_kms + np.arange(nbins + 1)*(s_hi_kms - s_lo_kms)/nbins
+    out = {'speed_edges': edges, 'speed_axis': (edges[:-1] + edges[1:])/2,
+           'energy_edges': 0.5*mass_kg*(edges*1e3)**2 / const.EV}
+    for plane, name, factor in ((0, 'density', scale), (1, 'flux', scale*unit_km*1e5)):
+        S, ww = sums[plane, :, :, 0], sums[plane, :, :, 1]
+        out[name + '_spectrum'] = S[:, 1:-1]*factor
+        out[name + '_below'] = S[:, 0]*factor
+        out[name + '_above'] = S[:, -1]*factor
+        total = S.sum(axis=1)*factor
+        out['density_in_view' if plane == 0 else 'flux'] = total
+        filled = ww[:, 1:-1] != 0
+        eff = np.where(filled, S[:, 1:-1]**2/np.where(filled, ww[:, 1:-1], 1.0), 0.0)
+        out[('spectrum' if plane == 0 else 'flux') + '_effective_packets'] = eff
+    return out
+
+
 class ModelDensity:
     def __init__(self, inputs, xpts, ypts, zpts, dr=0.05, moments=False, *, cp=None,
-                 reduce='rccl', context=None, device=0):
+                 reduce='rccl', context=None, device=0, spectrum=None):
         """Number density at the points (xpts, ypts, zpts) [planet radii] from every catalogued
         Output of ``inputs`` (ModelDensity.py:18-85).  ``cp``: the control plane of a shared run
         (``Input.run(..., cp=cp)``): each rank sums its own Outputs, then the per-point sums and
@@ -130,7 +265,19 @@ class ModelDensity:
         ``temperature`` (Q,) [K] and ``effective_packets`` (Q,) -- ``density /
         sqrt(effective_packets)`` is the 1-sigma statistical error of ``density`` -- from
         ``moment_sums`` (Q, 10; ``MOMENT_COLUMNS``), accumulated in the same pass over the rows.
-        A point without weight gets NaN, NaN, NaN and 0."""
+        A point without weight gets NaN, NaN, NaN and 0.
+
+        ``spectrum=dict(speed=(s_lo_kms, s_hi_kms, nbins), velocity=..., boresight=...,
+        half_angle=...)`` (EXTENSION) also fills, per point, the speed spectrum in the frame of a
+        spacecraft that moves with ``velocity`` ((3,) or (Q, 3) [km/s], model frame; default 0)
+        there, of the atoms that arrive within ``half_angle`` degrees (in (0, 180]; default 180) of
+        ``boresight`` ((3,) or (Q, 3), normalised here, or ``'ram'`` for the direction of the
+        velocity).  180 degrees or no boresight is the whole sky: ``density_in_view`` is then
+        ``density`` up to the order of the additions.  Attributes: those of
+        ``spectrum_from_sums`` and the raw ``spectrum_sums`` (2, Q, nbins + 2, 2).  It refuses
+        ``moments=True`` and ``cp=``."""
+        if spectrum is not None:
+            refuse_with_spectrum(moments=moments, cp=cp)
         self.type = 'density'
         self.inputs = inputs
         self.origin = inputs.geometry.planet
@@ -143,6 +290,7 @@ class ModelDensity:
         if not len(xyz[0]) == len(xyz[1]) == len(xyz[2]):
             raise ValueError('xpts, ypts and zpts must have the same length')
         Q = len(xyz[0])
+        self._spectrum = None if spectrum is None else parse_spectrum(spectrum, Q)
         self.density = np.zeros(Q)
         self.packets = np.zeros(Q)
         self.totalsource = 0.
@@ -155,12 +303,17 @@ class ModelDensity:
         if self.npackets == 0 and not shared:
             raise RuntimeError('No packets found for these Inputs.')
         index = DensityIndex(np.stack(xyz, axis=1), dr)
-        sums, counts, moment_sums = self._accumulate(index, self._moments)
+        frames = None if self._spectrum is None else spectrum_frames(self._spectrum, unit_km,
+                                                                      index.order)
+        sums, counts, extra = self._accumulate(index, self._moments, frames)
+        if self._spectrum is not None:
+            self.spectrum_sums = np.zeros((2, Q, self._spectrum['speed'][2] + 2, 2))
+            self.spectrum_sums[:, index.order] = extra
         self.density += index.scatter(sums, Q)
         self.packets += index.scatter(counts, Q)
         if self._moments:
             self.moment_sums = np.zeros((Q, 10))
-            self.moment_sums[index.order] = moment_sums
+            self.moment_sums[index.order] = extra
         if shared:
             from .distributed import allreduce_small, guarded
             parts = [self.density, self.packets, [float(self.totalsource), float(self.npackets)]]
@@ -183,17 +336,24 @@ class ModelDensity:
         self.atoms_per_packet = 1e23 / mod_rate
         self.sourcerate = Quantity(1., '1e23/s')
         self.density = self.density * self.atoms_per_packet/float(self.Vpix)
+        if self._spectrum is not None:
+            s_lo, s_hi, _ = self._spectrum['speed']
+            mass_kg = atomicmass(inputs.options.species).value * const.AMU
+            for name, value in spectrum_from_sums(self.spectrum_sums,
+                                                  self.atoms_per_packet/float(self.Vpix), unit_km,
+                                                  s_lo, s_hi, mass_kg).items():
+                setattr(self, name, value)
 
     def context(self):
         if self._ctx is None:
             self._ctx = shared_context(self.inputs, self._device)
         return self._ctx
 
-    def _accumulate(self, index, moments=False):
-        """(frac sums, counts, moment sums | None) per indexed point over this process's catalogue
-        (ModelDensity.py:62-82).  Rows in HBM are read where they are, one launch per run of
-        adjacent slices of a store; other Outputs upload X's x, y, z, frac (with moments: and
-        vx, vy, vz)."""
+    def _accumulate(self, index, moments=False, frames=None):
+        """(frac sums, counts, moment sums | spectrum sums | None) per indexed point over this
+        process's catalogue (ModelDensity.py:62-82).  Rows in HBM are read where they are, one
+        launch per run of adjacent slices of a store; other Outputs upload X's x, y, z, frac (with
+        moments or a spectrum -- ``frames``, the indexed points' frame records: and vx, vy, vz)."""
         ctx = self.context()
         ctx.density_set(index.points, index.cell_start, index.origin, index.h, index.dr,
                         index.dims)
@@ -201,6 +361,11 @@ class ModelDensity:
         if moments:
             ctx.density_moments_enable()
             columns, add = ('x', 'y', 'z', 'vx', 'vy', 'vz', 'frac'), ctx.density_moments_accumulate
+        if frames is not None:
+            (s_lo, s_hi, nbins), unit_km = self._spectrum['speed'], float(self.origin.radius.value)
+            ctx.density_spectrum_enable(nbins, s_lo/unit_km, s_hi/unit_km, self._spectrum['cos_half'],
+                                        self._spectrum['all_sky'], frames)
+            columns, add = ('x', 'y', 'z', 'vx', 'vy', 'vz', 'frac'), ctx.density_spectrum_accumulate
 
         def announced():
             for run in self.inputs._catalogue:
@@ -213,4 +378,6 @@ class ModelDensity:
                 add(rows=item)
             elif len(item.X) and 'x' in item.X:
                 add(*(item.X[c].values for c in columns))
-        return (*ctx.density_download(), ctx.density_moments_download() if moments else None)
+        extra = ctx.density_spectrum_download() if frames is not None else \
+            ctx.density_moments_download() if moments else None
+        return (*ctx.density_download(), extra)

@@ -30,6 +30,7 @@
 #include "nxc_image_block.hpp"
 #include "nxc_kernels.hpp"
 #include "nxc_log_table.hpp"
+#include "nxc_spectrum_check.hpp"
 
 namespace {
 
@@ -433,6 +434,10 @@ struct nxc_handle {
     bool have_dens_mom = false;      // nxc_density_moments_enable since the last nxc_density_set
     double *d_dens_mom = nullptr;    // the moment sums: [5][Q] 16-byte records (k_density_moments)
     size_t dens_mom_cap = 0;
+    bool have_dens_spec = false;     // nxc_density_spectrum_enable since the last nxc_density_set
+    SpectrumK dens_spec{};
+    double *d_dens_spec = nullptr;   // the spectrum: [2][Q][nv + 2] records (k_density_spectrum)
+    double *d_dens_frames = nullptr; // [Q][8]: ux uy uz 0 bx by bz 0 per indexed point
 
     // CameraImage (nxc_camera_set): the camera, its LDS blob [LdsHeader | g tables | u edges |
     // v edges] and its own {weight sum, count} image
@@ -1560,6 +1565,18 @@ int moments_run(nxc_handle *h, const Samples &s)
     });
 }
 
+// ModelDensity(spectrum=...) over samples on the device (k_density_spectrum)
+int spectrum_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_density_spectrum<T>, NXC_BLOCK, 0, s.n, h->dens, h->dens_spec,
+                                  s.n, h->dens_q, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(5),
+                                  s.col<T>(3), s.col<T>(6), s.col<T>(4), h->d_dens_pts,
+                                  h->d_dens_cell, h->d_dens_frames, h->d_dens_acc, h->d_dens_spec);
+    });
+}
+
 // CameraImage over samples on the device (k_camera)
 int camera_run(nxc_handle *h, const Samples &s)
 {
@@ -1638,11 +1655,30 @@ const SampleConsumer MOMENT_SAMPLES = {&nxc_handle::have_dens_mom,
                                        "nxc_density_moments_enable has not been called",
                                        true, false, true,
                                        [](const nxc_handle *h) { return h->dens_q == 0; }, moments_run};
-// the state check that comes in front of MOMENT_SAMPLES': nxc_density_set is the missing call
+// the state check that comes in front of MOMENT_SAMPLES' and SPECTRUM_SAMPLES': nxc_density_set is
+// the missing call
 int moments_need_set(const nxc_handle *h)
 {
     if (h && h->have_density) return NXC_OK;
     return guarded([&]() -> int { return fail(NXC_ERR_STATE, DENSITY_SAMPLES.unset); });
+}
+// the spectrum's state is its enable too, checked after nxc_density_set's (moments_need_set)
+const SampleConsumer SPECTRUM_SAMPLES = {&nxc_handle::have_dens_spec,
+                                         "nxc_density_spectrum_enable has not been called",
+                                         true, false, true,
+                                         [](const nxc_handle *h) { return h->dens_q == 0; }, spectrum_run};
+// bytes of the two planes of a spectrum over Q points
+size_t spectrum_bytes(size_t Q, const SpectrumK &S) { return 2 * Q * (size_t)(S.nv + 2) * 2 * sizeof(double); }
+
+// the spectrum off, its records and frame records back to the device
+int spectrum_free(nxc_handle *h)
+{
+    h->have_dens_spec = false;
+    if (h->d_dens_spec) HIPCHK(hipFree(h->d_dens_spec));
+    h->d_dens_spec = nullptr;
+    if (h->d_dens_frames) HIPCHK(hipFree(h->d_dens_frames));
+    h->d_dens_frames = nullptr;
+    return NXC_OK;
 }
 const SampleConsumer CAMERA_SAMPLES = {&nxc_handle::have_camera, "nxc_camera_set has not been called",
                                        true, true, false, nullptr, camera_run};
@@ -2156,7 +2192,8 @@ int nxc_destroy(nxc_handle *h)
                     h->d_blob_img, h->d_reduce_n, h->d_losblk, h->d_dens_pts, h->d_dens_cell,
                     h->d_dens_acc, h->d_dens_mom, h->d_fit_spec, h->d_fit_pk, h->d_fit_smp, h->d_fit_aux,
                     h->d_smap_grid, h->d_smap_acc, h->d_smap_pk, h->d_blob_cam, h->d_cam_image,
-                    h->d_img_mom, h->d_cam_mom, h->d_img_cube, h->d_cam_cube};
+                    h->d_img_mom, h->d_cam_mom, h->d_img_cube, h->d_cam_cube, h->d_dens_spec,
+                    h->d_dens_frames};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     pool_flush(h);
@@ -3149,6 +3186,7 @@ int nxc_density_set(nxc_handle *h, const nxc_density_desc *d)
     HIPCHK(hipSetDevice(h->device));
     h->have_density = false;
     h->have_dens_mom = false;
+    if (int rc = spectrum_free(h)) return rc;      // up to gigabytes: not kept for a set that may never enable one
     std::vector<double> pts((size_t)Q * 4, 0.0);
     for (int64_t j = 0; j < Q; j++)
         for (int a = 0; a < 3; a++) pts[4 * j + a] = d->points[3 * j + a];
@@ -3262,6 +3300,76 @@ int nxc_density_moments_download(nxc_handle *h, double *sums)
             sums[10 * q + 2 * k] = planes[2 * (k * Q + q)];
             sums[10 * q + 2 * k + 1] = planes[2 * (k * Q + q) + 1];
         }
+    return NXC_OK;
+    });
+}
+
+int nxc_density_spectrum_enable(nxc_handle *h, const nxc_density_spectrum_desc *d)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_density) return fail(NXC_ERR_STATE, DENSITY_SAMPLES.unset);
+    const size_t Q = (size_t)h->dens_q;
+    const bool on = d && d->nv != 0;
+    if (on) {          // before anything is freed or allocated
+        const std::string why = check_spectrum_args(h->dens_q, d->n_frames, d->nv, d->s_lo, d->s_hi,
+                                                    d->cos_half, d->all_sky, d->frames);
+        if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
+    }
+    HIPCHK(hipSetDevice(h->device));
+    if (int rc = spectrum_free(h)) return rc;
+    if (!on) return NXC_OK;
+    h->dens_spec = SpectrumK{(int)d->nv, d->all_sky != 0 ? 1 : 0, d->s_lo,
+                             spectrum_inv_ds(d->nv, d->s_lo, d->s_hi), d->cos_half};
+    const size_t bytes = spectrum_bytes(Q, h->dens_spec);
+    size_t cap = 0;
+    int rc;
+    if ((rc = ensure(reinterpret_cast<void **>(&h->d_dens_spec), &cap, bytes))) return rc;
+    cap = 0;
+    if ((rc = ensure(reinterpret_cast<void **>(&h->d_dens_frames), &cap, Q * 8 * sizeof(double)))) return rc;
+    if (Q) {
+        HIPCHK(hipMemsetAsync(h->d_dens_spec, 0, bytes, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_dens_frames, d->frames, Q * 8 * sizeof(double), hipMemcpyHostToDevice,
+                              h->stream));
+    }
+    HIPCHK(stream_sync(h));
+    h->have_dens_spec = true;
+    return NXC_OK;
+    });
+}
+
+int nxc_density_spectrum_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                                    const double *z, const double *vx, const double *vy,
+                                    const double *vz, const double *frac)
+{
+    if (int rc = moments_need_set(h)) return rc;
+    return accumulate_columns<double>(h, SPECTRUM_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_density_spectrum_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                        const float *z, const float *vx, const float *vy,
+                                        const float *vz, const float *frac)
+{
+    if (int rc = moments_need_set(h)) return rc;
+    return accumulate_columns<float>(h, SPECTRUM_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_density_spectrum_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    if (int rc = moments_need_set(h)) return rc;
+    return accumulate_rows(h, SPECTRUM_SAMPLES, r, first, count);
+}
+
+int nxc_density_spectrum_download(nxc_handle *h, double *sums)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_density) return fail(NXC_ERR_STATE, DENSITY_SAMPLES.unset);
+    if (!h->have_dens_spec) return fail(NXC_ERR_STATE, SPECTRUM_SAMPLES.unset);
+    if (h->dens_q && !sums) return fail(NXC_ERR_ARG, "bad arguments");
+    if (h->dens_q == 0) return NXC_OK;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(sums, h->d_dens_spec, spectrum_bytes((size_t)h->dens_q, h->dens_spec),
+                          hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
     return NXC_OK;
     });
 }

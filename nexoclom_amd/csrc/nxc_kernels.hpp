@@ -2865,6 +2865,100 @@ k_density_moments(DensityK K, int64_t n, int64_t n_points, const T *__restrict__
     }
 }
 
+// ModelDensity(spectrum=...): k_density's pass with, per point, the speed spectrum seen from a
+// moving spacecraft (include/nexoclom_hip.h, "Density spectrum", holds the definition).  The same
+// cull, candidate walk (copied again, so that k_density and k_density_moments compile as before)
+// and membership test.  Point q has a frame record of eight doubles {ux uy uz 0 bx by bz 0}: the
+// spacecraft velocity u [R/s] and the unit boresight b, read only by a lane that hits.  With
+// f = frac and one rounding per operation, a hit forms
+//     c = v - u;  s = sqrt((cx cx + cy cy) + cz cz);  a = -((cx bx + cy by) + cz bz)
+//     seen = all_sky != 0 || a >= cos_half s                (a NaN is not seen without all_sky)
+//     t = (s - s_lo) inv_ds;  k = 0 if t < 0,  1 + (int)t if 0 <= t < nv,  nv + 1 otherwise
+// and adds
+//     {f, 1}                 to record q of acc2 (k_density's own pair array), seen or not
+//     {f, f f}               to record q (nv + 2) + k of plane 0 of spec2, when seen
+//     {f s, (f s) (f s)}     to the same record of plane 1, 2 Q (nv + 2) doubles further on.
+// The three pair adds are made from uniform control flow (add_record_pairs), and a trip in which
+// no lane of the wave hits makes none.  The record index stays below 2^31
+// (check_spectrum_args).  Nothing else is filtered.
+struct SpectrumK {
+    int nv;                          // bins; planes 0 and nv + 1 hold what falls below and above
+    int all_sky;                     // != 0: every hit is seen
+    double s_lo, inv_ds, cos_half;   // [R/s], [s/R], cosine of the aperture's half angle
+};
+
+template <typename T>
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_density_spectrum(DensityK K, SpectrumK S, int64_t n, int64_t n_points, const T *__restrict__ x,
+                   const T *__restrict__ y, const T *__restrict__ z, const T *__restrict__ vx,
+                   const T *__restrict__ vy, const T *__restrict__ vz, const T *__restrict__ frac,
+                   const double *__restrict__ pts, const int *__restrict__ cell_start,
+                   const double *__restrict__ frames, double *__restrict__ acc2,
+                   double *__restrict__ spec2)
+{
+    double *__restrict__ flux2 = spec2 + 2 * n_points * (int64_t)(S.nv + 2);
+    // wave-uniform trip count (the accumulation is wave-cooperative); the last trip is ragged
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n;
+         base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = base + threadIdx.x;
+        double p[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0}, w = 0.0;
+        int lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1};
+        bool live = false;
+        if (i < n) {
+            p[0] = (double)x[i]; p[1] = (double)y[i]; p[2] = (double)z[i];
+            live = density_cells(K, p, lo, hi);
+            if (live) {
+                v[0] = (double)vx[i]; v[1] = (double)vy[i]; v[2] = (double)vz[i];
+                w = (double)frac[i];
+            }
+        }
+        // the candidate points of one (cy, cz) row of cells are one contiguous range [j, e)
+        int cy = lo[1], cz = lo[2], j = 0, e = 0;
+        auto advance = [&]() {
+            while (live && j >= e) {
+                if (cz > hi[2]) { live = false; break; }
+                const int row = (cz * K.n[1] + cy) * K.n[0];
+                j = cell_start[row + lo[0]];
+                e = cell_start[row + hi[0] + 1];
+                if (++cy > hi[1]) { cy = lo[1]; ++cz; }
+            }
+        };
+        advance();
+        while (__ballot(live) != 0) {
+            bool hit = false;
+            int q = 0;
+            if (live) {
+                const double dx = pts[4 * (int64_t)j] - p[0];
+                const double dy = pts[4 * (int64_t)j + 1] - p[1];
+                const double dz = pts[4 * (int64_t)j + 2] - p[2];
+                hit = (dx * dx + dy * dy) + dz * dz <= K.dr2;
+                q = j++;
+                advance();
+            }
+            if (__ballot(hit) == 0) continue;
+            bool seen = false;
+            int rec = 0;
+            double g = 0.0;
+            if (hit) {
+                const double *__restrict__ fr = frames + 8 * (int64_t)q;
+                const double c[3] = {v[0] - fr[0], v[1] - fr[1], v[2] - fr[2]};
+                const double s = __builtin_sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+                const double a = -((c[0] * fr[4] + c[1] * fr[5]) + c[2] * fr[6]);
+                seen = S.all_sky != 0 || a >= S.cos_half * s;
+                const double t = (s - S.s_lo) * S.inv_ds;
+                int k = S.nv + 1;
+                if (t < 0.0) k = 0;
+                else if (t < (double)S.nv) k = 1 + (int)t;
+                rec = q * (S.nv + 2) + k;
+                g = w * s;
+            }
+            add_record_pairs(hit, q, w, 1.0, acc2);
+            add_record_pairs(hit && seen, rec, w, w * w, spec2);
+            add_record_pairs(hit && seen, rec, g, g * g, flux2);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // CameraImage: stored samples binned into the image of a pinhole camera (camera_sample).  k_image's
 // shape: the blob [header | g tables | u edges | v edges] staged once per workgroup, a grid-stride

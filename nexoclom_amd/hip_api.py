@@ -56,7 +56,10 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_image_cube_enable', 'nxc_image_cube_accumulate', 'nxc_image_cube_accumulate_f32',
            'nxc_image_cube_accumulate_rows', 'nxc_image_cube_download',
            'nxc_camera_cube_enable', 'nxc_camera_cube_accumulate', 'nxc_camera_cube_accumulate_f32',
-           'nxc_camera_cube_accumulate_rows', 'nxc_camera_cube_download')
+           'nxc_camera_cube_accumulate_rows', 'nxc_camera_cube_download',
+           'nxc_density_spectrum_enable', 'nxc_density_spectrum_accumulate',
+           'nxc_density_spectrum_accumulate_f32', 'nxc_density_spectrum_accumulate_rows',
+           'nxc_density_spectrum_download')
 ABI_VERSION = 3
 
 
@@ -101,6 +104,12 @@ class nxc_density_desc(C.Structure):
     _fields_ = [('origin', C.c_double*3), ('h', C.c_double), ('dr', C.c_double),
                 ('dims', C.c_int64*3), ('n_points', C.c_int64), ('points', _dp),
                 ('cell_start', C.POINTER(C.c_int32))]
+
+
+class nxc_density_spectrum_desc(C.Structure):
+    _fields_ = [('nv', C.c_int64), ('s_lo', C.c_double), ('s_hi', C.c_double),
+                ('cos_half', C.c_double), ('all_sky', C.c_int32), ('reserved', C.c_int32),
+                ('n_frames', C.c_int64), ('frames', _dp)]
 
 
 class nxc_camera_desc(C.Structure):
@@ -920,6 +929,7 @@ class Context:
         d.cell_start = starts.ctypes.data_as(C.POINTER(C.c_int32))
         self._check(self.lib.nxc_density_set(self._h, C.byref(d)))
         self._density_q = len(pts)
+        self._density_spectrum_nv = 0            # the set switches the spectrum off
 
     def density_accumulate(self, x=None, y=None, z=None, frac=None, rows=None):
         """Add samples to the per-point sums: four host columns (float32 ones go over as they
@@ -949,6 +959,44 @@ class Context:
         (f v_a) v_b (xx, yy, zz, xy, xz, yz) and of f f over the samples within dr."""
         sums = np.zeros((getattr(self, '_density_q', 0), 10))
         self._check(self.lib.nxc_density_moments_download(self._h, _p(sums)))
+        return sums
+
+    def density_spectrum_enable(self, nv, s_lo=0.0, s_hi=0.0, cos_half=-1.0, all_sky=True,
+                                frames=None):
+        """After ``density_set``: allocate and zero a spectrum of ``nv`` speed bins over
+        [s_lo, s_hi) [R/s] per indexed point, seen through a cone of half angle acos(cos_half)
+        (``all_sky``: no cone), and upload ``frames`` (Q, 8) = ux uy uz 0 bx by bz 0 in the index's
+        point order (``nv = 0`` frees the spectrum; the next ``density_set`` switches it off)."""
+        nv = int(nv)
+        if nv == 0:
+            self._check(self.lib.nxc_density_spectrum_enable(self._h, None))
+            self._density_spectrum_nv = 0
+            return
+        fr = _f64(np.zeros((getattr(self, '_density_q', 0), 8)) if frames is None else frames)
+        if fr.ndim != 2 or fr.shape[1] != 8:
+            raise ValueError('frames must have the shape (Q, 8)')
+        d = nxc_density_spectrum_desc()
+        d.nv, d.s_lo, d.s_hi, d.cos_half = nv, float(s_lo), float(s_hi), float(cos_half)
+        d.all_sky = int(bool(all_sky))
+        # the library compares the number of records with the points of its own index
+        d.n_frames = len(fr)
+        d.frames = _p(fr) if len(fr) else None
+        self._check(self.lib.nxc_density_spectrum_enable(self._h, C.byref(d)))
+        self._density_spectrum_nv = nv
+
+    def density_spectrum_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
+                                    frac=None, rows=None):
+        """Add samples to the per-point {frac sum, count} and to the spectrum in one pass: seven
+        host columns (float32 ones go over as they are), or ``rows = (RowStore, first, count)``."""
+        self._accumulate('nxc_density_spectrum_accumulate', (x, y, z, vx, vy, vz, frac), rows)
+
+    def density_spectrum_download(self):
+        """(2, Q, nv + 2, 2) float64, the device's own order: plane 0 sums f, plane 1 f s, per
+        indexed point and speed plane (0 below, 1..nv the bins, nv + 1 above), {sum, sum of
+        squares} over the seen samples within dr."""
+        nv = getattr(self, '_density_spectrum_nv', 0)
+        sums = np.zeros((2, getattr(self, '_density_q', 0), nv + 2, 2))
+        self._check(self.lib.nxc_density_spectrum_download(self._h, _p(sums)))
         return sums
 
     # -- CameraImage ------------------------------------------------------------------------

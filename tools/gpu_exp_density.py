@@ -11,6 +11,14 @@ k_density_moments alternated in one process on both point sets, 3 warm-up and 9 
 HIP-event time summed over the launches.  One JSON line per point set (appended to FILE) with the
 moments' two floors: 28 B per float32 row at the box's k_stream_copy rate, and 6 requests per hit
 at 2.4e10 requests/s.
+
+``--spectrum [--out FILE]``: the same with k_density, k_density_moments and k_density_spectrum
+alternated: the trajectory seen through a ram cone of 30 degrees (the spacecraft flies along it at
+3 km/s) in 32 bins, the grid with the whole sky in 16 bins (2.1e6 x 18 x 32 B = 1.2 GB of records).
+Median and [min, max] per kernel, and the spectrum's two floors: 28 B per row plus 64 B per hit (the
+frame record) at the k_stream_copy rate, and one request per hit plus two per seen hit at 2.4e10
+requests/s.  The seen hits of the cone are counted by one more pass over the same rows with
+frac = 1 (downloaded and handed back as host columns), where plane 0 of the spectrum holds them.
 """
 import contextlib
 import io
@@ -87,7 +95,90 @@ def moments_leg(out_path, warm=3, timed=9):
     ctx.close()
 
 
+def spread(values):
+    return dict(median=round(float(np.median(values)), 3), min=round(min(values), 3),
+                max=round(max(values), 3))
+
+
+def spectrum_cases(unit_km):
+    """Per point set: (nv, s_lo, s_hi [R/s], cos_half, all_sky, frames in the points' order)."""
+    sets = point_sets()
+    traj = sets['trajectory_1e4']
+    tangent = np.gradient(traj, axis=0)
+    u = 3.0/unit_km * tangent/np.linalg.norm(tangent, axis=1)[:, None]
+    ram = np.zeros((len(traj), 8))
+    ram[:, 0:3] = u
+    ram[:, 4:7] = u/np.linalg.norm(u, axis=1)[:, None]
+    return {'trajectory_1e4': (32, 0.0, 8.0/unit_km, float(np.cos(np.radians(30.))), False, ram),
+            'grid_128^3': (16, 0.0, 8.0/unit_km, -1.0, True, np.zeros((len(sets['grid_128^3']), 8)))}
+
+
+def seen_hits(ctx, launches, chunk=1 << 23):
+    """Rows seen per point and plane, summed: the enabled (zeroed) spectrum after a pass over the
+    rows of ``launches`` with frac = 1, handed over as host columns chunk by chunk."""
+    for store, first, count in launches:
+        for off in range(0, count, chunk):
+            n = min(chunk, count - off)
+            rows, _ = store.download(first + off, n, index=False)
+            ctx.density_spectrum_accumulate(*rows[1:7], np.ones(n, dtype=rows.dtype))
+    return float(ctx.density_spectrum_download()[0, :, :, 0].sum())
+
+
+def spectrum_leg(out_path, warm=3, timed=9):
+    ctx = hip_api.Context(0)
+    copy_bps = ctx.stream_copy_gbs() * 1e9
+    inputs = Input(os.path.join(ROOT, 'nexoclom_amd', 'inputfiles', 'Na.mercury.bench.input'))
+    with contextlib.redirect_stdout(io.StringIO()):
+        inputs.run(1e6, seed=7, context=ctx)
+    launches = spans(inputs, ctx)
+    rows = sum(s[2] for s in launches)
+    cases = spectrum_cases(float(inputs.geometry.planet.radius.value))
+    for name, pts in point_sets().items():
+        index = DensityIndex(pts, DR)
+        nv, s_lo, s_hi, cos_half, all_sky, frames = cases[name]
+        enable = lambda: ctx.density_spectrum_enable(nv, s_lo, s_hi, cos_half, all_sky,  # noqa: E731
+                                                     frames[index.order])
+        ctx.density_set(index.points, index.cell_start, index.origin, index.h, index.dr,
+                        index.dims)
+        ctx.density_moments_enable()
+        enable()
+        times = {'k_density': [], 'k_density_moments': [], 'k_density_spectrum': []}
+        passes = (ctx.density_accumulate, ctx.density_moments_accumulate,
+                  ctx.density_spectrum_accumulate)
+        for rep in range(warm + timed):
+            for key, accumulate in zip(times, passes):
+                ms = kernel_ms(ctx, launches, accumulate)
+                if rep >= warm:
+                    times[key].append(ms)
+        hits = float(ctx.density_download()[1].sum()) / (3*(warm + timed))
+        ctx.density_moments_enable(False)
+        if all_sky:
+            seen = hits
+        else:
+            enable()
+            seen = seen_hits(ctx, launches)
+        record = dict(npackets=1e6, points=name, rows=rows, launches=len(launches), hits=hits,
+                      seen_hits=seen, nv=nv, all_sky=all_sky,
+                      record_bytes=2*len(index.points)*(nv + 2)*16,
+                      stream_copy_gbs=round(copy_bps/1e9, 1),
+                      floor_bytes_ms=round((rows*28 + hits*64)/copy_bps*1e3, 3),
+                      floor_atomics_ms=round((hits + 2*seen)/ATOMIC_RPS*1e3, 3))
+        for key, values in times.items():
+            record[key + '_ms'] = [round(v, 3) for v in values]
+            record[key] = spread(values)
+        line = json.dumps(record)
+        print(line, flush=True)
+        if out_path:
+            with open(out_path, 'a') as f:
+                f.write(line + '\n')
+        ctx.density_spectrum_enable(0)
+    ctx.close()
+
+
 def main():
+    if '--spectrum' in sys.argv:
+        out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else None
+        return spectrum_leg(out)
     if '--moments' in sys.argv:
         out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else None
         return moments_leg(out)
