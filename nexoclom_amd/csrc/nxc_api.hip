@@ -3388,7 +3388,7 @@ int nxc_camera_set(nxc_handle *h, const nxc_camera_desc *d)
     ImageK G{};
     std::memcpy(G.M, d->C, sizeof G.M);       // the basis, where the image keeps its rotation
     G.vrplanet = d->vrplanet;
-    G.apix_cm2 = 1.0;                          // the per-sample area divides in camera_sample
+    G.apix_cm2 = 1.0;                          // the per-sample area divides in camera_located
     G.quantity = d->quantity;
     PackedLut luts[NXC_MAX_LINES];
     int rc;

@@ -1014,19 +1014,58 @@ NXC_DEV bool image_weight(const ImageK &G, const ImageRegs &R, double radvel, do
     return (__builtin_fabs(w) <= 1.7976931348623157e308) && radvel == radvel;   // :170
 }
 
-// locate + weight + add of one sample per lane, for the kernels that need no compaction.
-// Wave-cooperative (all lanes call it; `has`: this lane offers a sample).
-NXC_DEV void image_sample(const ImageK &G, const ImageRegs &R, bool has, double x, double y,
-                          double z, double vy, double frac, double *__restrict__ acc2,
-                          unsigned long long &binned, unsigned long long &nonfinite)
+// One lane's share of a trip of a pixel pass: does it offer a sample, which row, and the row's five
+// values widened to fp64 (zeros without a sample).
+struct PixelSample {
+    bool has;
+    int64_t i;
+    double x, y, z, vy, frac;
+};
+
+// What the front of a pixel pass hands to its tail: did the sample reach a pixel with a finite
+// weight, which, the final weight, and (camera only) the distance r of step 7.
+struct PixelHit {
+    bool ok;
+    int pix;
+    double w, r;
+};
+
+// locate + weight + count + add of one sample per lane, for the kernels that need no compaction:
+// the front of k_image, k_image_moments and k_image_cube.  Wave-cooperative (all lanes call it;
+// s.has: this lane offers a sample).
+NXC_DEV PixelHit image_located(const ImageK &G, const ImageRegs &R, const PixelSample &s,
+                               double *__restrict__ acc2, unsigned long long &binned,
+                               unsigned long long &nonfinite)
 {
-    int pix = -1;
-    double radvel = 0.0, fw = 0.0, w = 0.0;
-    if (has) pix = image_locate(G, R, x, y, z, vy, frac, radvel, fw, nonfinite);
-    bool ok = pix >= 0;
-    if (ok && !image_weight(G, R, radvel, fw, w)) { nonfinite++; ok = false; }
-    binned += ok;
-    image_add_pairs(ok, pix, w, acc2);
+    PixelHit h = {false, -1, 0.0, 1.0};
+    double radvel = 0.0, fw = 0.0;
+    if (s.has) h.pix = image_locate(G, R, s.x, s.y, s.z, s.vy, s.frac, radvel, fw, nonfinite);
+    h.ok = h.pix >= 0;
+    if (h.ok && !image_weight(G, R, radvel, fw, h.w)) { nonfinite++; h.ok = false; }
+    binned += h.ok;
+    image_add_pairs(h.ok, h.pix, h.w, acc2);
+    return h;
+}
+
+// The line-of-sight velocity of a sample image_located placed: row 1 of the rotation applied to
+// the velocity (the observer sits at y_obs -> -inf: positive = receding); the general form also
+// with x_is_x, so that a non-finite vx reaches the sums whatever the rotation.  vx and vz are read
+// only by a lane whose sample reached a pixel with w != 0 (0 otherwise); with downcast_f32 they
+// and vy take the float32 round trip image_locate gives the other values.
+template <typename T>
+NXC_DEV double image_vlos(const ImageK &G, const ImageRegs &R, const PixelHit &h,
+                          const PixelSample &s, const T *__restrict__ vx_col,
+                          const T *__restrict__ vz_col)
+{
+    double vlos = 0.0;
+    if (h.ok && h.w != 0.0) {
+        double vx = (double)vx_col[s.i], vy = s.vy, vz = (double)vz_col[s.i];
+        if (R.downcast) {
+            vx = f32_round_trip(vx); vy = f32_round_trip(vy); vz = f32_round_trip(vz);
+        }
+        vlos = (G.M[3] * vx + G.M[4] * vy) + G.M[5] * vz;
+    }
+    return vlos;
 }
 
 // ---- CameraImage: the same sample seen by a pinhole camera at a finite distance ------------------
@@ -1080,23 +1119,43 @@ NXC_DEV int camera_locate(const CameraK &K, const ImageK &G, const ImageRegs &R,
     return ix * R.nz + iz;
 }
 
-// locate + weight + footprint + add of one sample per lane.  Wave-cooperative like image_sample.
-NXC_DEV void camera_sample(const CameraK &K, const ImageK &G, const ImageRegs &R, bool has, double x,
-                           double y, double z, double vy, double frac, double *__restrict__ acc2,
-                           unsigned long long &binned, unsigned long long &nonfinite)
+// locate + weight + footprint + count + add of one sample per lane: the front of k_camera,
+// k_camera_moments and k_camera_cube.  Wave-cooperative like image_located.
+NXC_DEV PixelHit camera_located(const CameraK &K, const ImageK &G, const ImageRegs &R,
+                                const PixelSample &s, double *__restrict__ acc2,
+                                unsigned long long &binned, unsigned long long &nonfinite)
 {
-    int pix = -1;
-    double radvel = 0.0, fw = 0.0, dc = 1.0, r2 = 1.0, w = 0.0;
-    if (has) pix = camera_locate(K, G, R, x, y, z, vy, frac, radvel, fw, dc, r2, nonfinite);
-    bool ok = pix >= 0;
-    if (ok && !image_weight(G, R, radvel, fw, w)) { nonfinite++; ok = false; }
-    if (ok) {
-        const double foot = nxc_div((dc * dc) * dc, nxc_sqrt(r2));
-        w = nxc_div(w, foot * K.area);
-        if (!(__builtin_fabs(w) <= 1.7976931348623157e308)) { nonfinite++; ok = false; }
+    PixelHit h = {false, -1, 0.0, 1.0};
+    double radvel = 0.0, fw = 0.0, dc = 1.0, r2 = 1.0;
+    if (s.has)
+        h.pix = camera_locate(K, G, R, s.x, s.y, s.z, s.vy, s.frac, radvel, fw, dc, r2, nonfinite);
+    h.ok = h.pix >= 0;
+    if (h.ok && !image_weight(G, R, radvel, fw, h.w)) { nonfinite++; h.ok = false; }
+    if (h.ok) {
+        h.r = nxc_sqrt(r2);
+        const double foot = nxc_div((dc * dc) * dc, h.r);
+        h.w = nxc_div(h.w, foot * K.area);
+        if (!(__builtin_fabs(h.w) <= 1.7976931348623157e308)) { nonfinite++; h.ok = false; }
     }
-    binned += ok;
-    image_add_pairs(ok, pix, w, acc2);
+    binned += h.ok;
+    image_add_pairs(h.ok, h.pix, h.w, acc2);
+    return h;
+}
+
+// The line-of-sight velocity of a sample camera_located placed: the velocity along the sample's
+// own ray, away from the camera, (d . v) / r with d of step 1 and r of step 7.  vx and vz are
+// read only by a lane whose sample reached a pixel with w != 0 (0 otherwise).
+template <typename T>
+NXC_DEV double camera_vlos(const CameraK &K, const PixelHit &h, const PixelSample &s,
+                           const T *__restrict__ vx_col, const T *__restrict__ vz_col)
+{
+    double vlos = 0.0;
+    if (h.ok && h.w != 0.0) {
+        const double vx = (double)vx_col[s.i], vz = (double)vz_col[s.i];
+        const double dx = s.x - K.o[0], dy = s.y - K.o[1], dz = s.z - K.o[2];
+        vlos = nxc_div((dx * vx + dy * s.vy) + dz * vz, h.r);
+    }
+    return vlos;
 }
 
 // ---- pixel moments: what a sample adds to its pixel besides {w, 1} -------------------------------
@@ -1113,66 +1172,6 @@ NXC_DEV void pixel_moments_add(bool ok, int pix, double w, double vlos, int64_t 
     const double a = w * vlos, m2 = a * vlos;
     add_record_pairs(has, pix, a, m2, mom2);
     add_record_pairs(has, pix, m2 * vlos, w * w, mom2 + 2 * n_pix);
-}
-
-// image_sample with the moments.  vx and vz are read only by a lane whose sample reached a pixel
-// with w != 0; with downcast_f32 they and vy take the float32 round trip image_locate gives the
-// other values.  vlos is row 1 of the rotation applied to the velocity (the observer sits at
-// y_obs -> -inf: positive = receding); the general form also with x_is_x, so that a non-finite vx
-// reaches the sums whatever the rotation.
-template <typename T>
-NXC_DEV void image_moments_sample(const ImageK &G, const ImageRegs &R, bool has, double x, double y,
-                                  double z, double vy, double frac, const T *__restrict__ vx_at,
-                                  const T *__restrict__ vz_at, double *__restrict__ acc2,
-                                  int64_t n_pix, double *__restrict__ mom2,
-                                  unsigned long long &binned, unsigned long long &nonfinite)
-{
-    int pix = -1;
-    double radvel = 0.0, fw = 0.0, w = 0.0, vlos = 0.0;
-    if (has) pix = image_locate(G, R, x, y, z, vy, frac, radvel, fw, nonfinite);
-    bool ok = pix >= 0;
-    if (ok && !image_weight(G, R, radvel, fw, w)) { nonfinite++; ok = false; }
-    binned += ok;
-    image_add_pairs(ok, pix, w, acc2);
-    if (ok && w != 0.0) {
-        double vx = (double)*vx_at, vz = (double)*vz_at;
-        if (R.downcast) {
-            vx = f32_round_trip(vx); vy = f32_round_trip(vy); vz = f32_round_trip(vz);
-        }
-        vlos = (G.M[3] * vx + G.M[4] * vy) + G.M[5] * vz;
-    }
-    pixel_moments_add(ok, pix, w, vlos, n_pix, mom2);
-}
-
-// camera_sample with the moments: vlos is the velocity along the sample's own ray, away from the
-// camera, (d . v) / r with d of step 1 and r of step 7.
-template <typename T>
-NXC_DEV void camera_moments_sample(const CameraK &K, const ImageK &G, const ImageRegs &R, bool has,
-                                   double x, double y, double z, double vy, double frac,
-                                   const T *__restrict__ vx_at, const T *__restrict__ vz_at,
-                                   double *__restrict__ acc2, int64_t n_pix,
-                                   double *__restrict__ mom2, unsigned long long &binned,
-                                   unsigned long long &nonfinite)
-{
-    int pix = -1;
-    double radvel = 0.0, fw = 0.0, dc = 1.0, r2 = 1.0, w = 0.0, r = 1.0, vlos = 0.0;
-    if (has) pix = camera_locate(K, G, R, x, y, z, vy, frac, radvel, fw, dc, r2, nonfinite);
-    bool ok = pix >= 0;
-    if (ok && !image_weight(G, R, radvel, fw, w)) { nonfinite++; ok = false; }
-    if (ok) {
-        r = nxc_sqrt(r2);
-        const double foot = nxc_div((dc * dc) * dc, r);
-        w = nxc_div(w, foot * K.area);
-        if (!(__builtin_fabs(w) <= 1.7976931348623157e308)) { nonfinite++; ok = false; }
-    }
-    binned += ok;
-    image_add_pairs(ok, pix, w, acc2);
-    if (ok && w != 0.0) {
-        const double vx = (double)*vx_at, vz = (double)*vz_at;
-        const double dx = x - K.o[0], dy = y - K.o[1], dz = z - K.o[2];
-        vlos = nxc_div((dx * vx + dy * vy) + dz * vz, r);
-    }
-    pixel_moments_add(ok, pix, w, vlos, n_pix, mom2);
 }
 
 // ---- velocity cube: a sample's weight filed under its Doppler bin --------------------------------
@@ -1197,61 +1196,6 @@ NXC_DEV void pixel_cube_add(const CubeK &Q, bool ok, int pix, double w, double v
     if (t < 0.0) k = 0;
     else if (t < (double)Q.nv) k = 1 + (int)t;
     add_record_pairs(has, pix * (Q.nv + 2) + k, w, w * w, cube2);
-}
-
-// image_sample with the cube: image_moments_sample with pixel_cube_add for its tail (the same
-// vlos, read and formed by the same lanes)
-template <typename T>
-NXC_DEV void image_cube_sample(const ImageK &G, const ImageRegs &R, const CubeK &Q, bool has, double x,
-                               double y, double z, double vy, double frac,
-                               const T *__restrict__ vx_at, const T *__restrict__ vz_at,
-                               double *__restrict__ acc2, double *__restrict__ cube2,
-                               unsigned long long &binned, unsigned long long &nonfinite)
-{
-    int pix = -1;
-    double radvel = 0.0, fw = 0.0, w = 0.0, vlos = 0.0;
-    if (has) pix = image_locate(G, R, x, y, z, vy, frac, radvel, fw, nonfinite);
-    bool ok = pix >= 0;
-    if (ok && !image_weight(G, R, radvel, fw, w)) { nonfinite++; ok = false; }
-    binned += ok;
-    image_add_pairs(ok, pix, w, acc2);
-    if (ok && w != 0.0) {
-        double vx = (double)*vx_at, vz = (double)*vz_at;
-        if (R.downcast) {
-            vx = f32_round_trip(vx); vy = f32_round_trip(vy); vz = f32_round_trip(vz);
-        }
-        vlos = (G.M[3] * vx + G.M[4] * vy) + G.M[5] * vz;
-    }
-    pixel_cube_add(Q, ok, pix, w, vlos, cube2);
-}
-
-// camera_sample with the cube: camera_moments_sample with pixel_cube_add for its tail
-template <typename T>
-NXC_DEV void camera_cube_sample(const CameraK &K, const ImageK &G, const ImageRegs &R, const CubeK &Q,
-                                bool has, double x, double y, double z, double vy, double frac,
-                                const T *__restrict__ vx_at, const T *__restrict__ vz_at,
-                                double *__restrict__ acc2, double *__restrict__ cube2,
-                                unsigned long long &binned, unsigned long long &nonfinite)
-{
-    int pix = -1;
-    double radvel = 0.0, fw = 0.0, dc = 1.0, r2 = 1.0, w = 0.0, r = 1.0, vlos = 0.0;
-    if (has) pix = camera_locate(K, G, R, x, y, z, vy, frac, radvel, fw, dc, r2, nonfinite);
-    bool ok = pix >= 0;
-    if (ok && !image_weight(G, R, radvel, fw, w)) { nonfinite++; ok = false; }
-    if (ok) {
-        r = nxc_sqrt(r2);
-        const double foot = nxc_div((dc * dc) * dc, r);
-        w = nxc_div(w, foot * K.area);
-        if (!(__builtin_fabs(w) <= 1.7976931348623157e308)) { nonfinite++; ok = false; }
-    }
-    binned += ok;
-    image_add_pairs(ok, pix, w, acc2);
-    if (ok && w != 0.0) {
-        const double vx = (double)*vx_at, vz = (double)*vz_at;
-        const double dx = x - K.o[0], dy = y - K.o[1], dz = z - K.o[2];
-        vlos = nxc_div((dx * vx + dy * vy) + dz * vz, r);
-    }
-    pixel_cube_add(Q, ok, pix, w, vlos, cube2);
 }
 
 // Per-wave compaction queue between image_locate and image_weight: a ring of 128 located samples

@@ -15,6 +15,10 @@
 //   k_camera        the same samples in the perspective image of a camera at a finite distance
 //   k_image_moments, k_camera_moments   either pass with four velocity-moment sums per pixel
 //   k_image_cube, k_camera_cube         either pass with the weight filed per pixel and Doppler bin
+//                   (all six: pixel_pass -- staging, loop, loads, counters -- with a lambda each)
+//   k_density, k_density_moments, k_density_spectrum   stored samples within dr of query points
+//                   (density_walk -- loop, cull, candidate walk, membership -- with a load and a
+//                   per-trip lambda each; k_density_moments keeps the walk written out)
 //
 // All lookup tables (radiation acceleration, g-values, bin edges) are staged once per workgroup
 // into LDS from one packed blob.
@@ -947,8 +951,42 @@ k_var(ForceK F, const unsigned char *__restrict__ blob, int64_t stage_bytes, int
 }
 
 // ---------------------------------------------------------------------------------------------
+// The pass of the six pixel kernels over stored samples: the tables staged into LDS, a grid-stride
+// loop that hands `sample` one row per lane and trip (wave-cooperative: every lane calls it, with
+// or without a row), and the three counters flushed once per workgroup.  `sample` is the kernel's
+// own: (G, IR, PixelSample, binned, nonfinite) -> what the row adds.
+// first, stride: (int64_t)blockIdx.x * blockDim.x and (int64_t)gridDim.x * blockDim.x, formed in
+// the KERNEL's body.  Formed in here, the block size is read with a vector load behind the staging
+// barrier instead of a scalar load, the stride lives and is multiplied in vector registers, and
+// every instantiation pays 4 VGPRs -- a wave per SIMD for k_image and k_image_cube.
+// Like its callers' other code this addresses LDS from its start (stage_tables): nothing in here
+// may declare static __shared__ data.
 // T = double, or float for samples handed over as the reference stores them (Output.py:528-543);
 // widening a float is exact, so both give the same image.
+template <typename T, typename Sample>
+NXC_DEV void pixel_pass(const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p,
+                        const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ z,
+                        const T *__restrict__ vy, const T *__restrict__ frac,
+                        DevCounters *__restrict__ ctr, int64_t first, int64_t stride, Sample sample)
+{
+    stage_tables(blob, stage_bytes);
+    const ImageRegs IR = image_regs(lds_header().G);
+    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
+    // wave-uniform trip count (the accumulation is wave-cooperative); the last trip is ragged
+    for (int64_t base = first; base < p; base += stride) {
+        PixelSample s = {false, base + threadIdx.x, 0.0, 0.0, 0.0, 0.0, 0.0};
+        s.has = s.i < p;
+        my_samples += s.has;
+        if (s.has) { s.x = x[s.i]; s.y = y[s.i]; s.z = z[s.i]; s.vy = vy[s.i]; s.frac = frac[s.i]; }
+        sample(lds_header().G, IR, s, my_binned, my_nonfinite);
+    }
+    // (the tables are not read any more: their first bytes carry the workgroup's sums)
+    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
+                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
+}
+
+// ModelImage over stored samples: pixel_pass with image_located, one memory-side atomic request
+// per binned sample.
 constexpr int NXC_IMAGE_BLOCK = 1024;
 template <typename T>
 __global__ void __launch_bounds__(NXC_IMAGE_BLOCK)
@@ -957,27 +995,17 @@ k_image(const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p,
         const T *__restrict__ vy, const T *__restrict__ frac,
         double *__restrict__ acc2, DevCounters *__restrict__ ctr)
 {
-    stage_tables(blob, stage_bytes);
-    const ImageRegs IR = image_regs(lds_header().G);
-    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
-    // wave-uniform trip count (the accumulation is wave-cooperative); the last trip is ragged
-    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p;
-         base += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = base + threadIdx.x;
-        const bool has = i < p;
-        my_samples += has;
-        double sx = 0, sy = 0, sz = 0, svy = 0, sf = 0;
-        if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
-        image_sample(lds_header().G, IR, has, sx, sy, sz, svy, sf, acc2, my_binned, my_nonfinite);
-    }
-    // (the tables are not read any more: their first bytes carry the workgroup's sums)
-    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
-                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
+    pixel_pass(blob, stage_bytes, p, x, y, z, vy, frac, ctr, (int64_t)blockIdx.x * blockDim.x,
+               (int64_t)gridDim.x * blockDim.x,
+               [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
+                   unsigned long long &binned, unsigned long long &nonfinite) {
+                   image_located(G, IR, s, acc2, binned, nonfinite);
+               });
 }
 
 // ModelImage(moments=True): k_image's pass over seven columns; a sample that reaches its pixel
 // with w != 0 also adds its four velocity-moment terms to mom2, [2][n_pix] 16-byte records
-// (image_moments_sample): at most three atomic requests per binned sample.  74 VGPRs: six waves a
+// (image_vlos, pixel_moments_add): at most three atomic requests per binned sample.  74 VGPRs: six waves a
 // SIMD, which three 512-thread groups fill where one 1024-thread group would leave it at four.
 constexpr int NXC_IMAGE_MOMENTS_BLOCK = 512;
 template <typename T>
@@ -988,27 +1016,18 @@ k_image_moments(const unsigned char *__restrict__ blob, int64_t stage_bytes, int
                 const T *__restrict__ frac, double *__restrict__ acc2, double *__restrict__ mom2,
                 DevCounters *__restrict__ ctr)
 {
-    stage_tables(blob, stage_bytes);
-    const ImageRegs IR = image_regs(lds_header().G);
-    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
-    // wave-uniform trip count (the accumulation is wave-cooperative); the last trip is ragged
-    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p;
-         base += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = base + threadIdx.x;
-        const bool has = i < p;
-        my_samples += has;
-        double sx = 0, sy = 0, sz = 0, svy = 0, sf = 0;
-        if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
-        image_moments_sample(lds_header().G, IR, has, sx, sy, sz, svy, sf, vx + i, vz + i, acc2,
-                             n_pix, mom2, my_binned, my_nonfinite);
-    }
-    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
-                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
+    pixel_pass(blob, stage_bytes, p, x, y, z, vy, frac, ctr, (int64_t)blockIdx.x * blockDim.x,
+               (int64_t)gridDim.x * blockDim.x,
+               [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
+                   unsigned long long &binned, unsigned long long &nonfinite) {
+                   const PixelHit h = image_located(G, IR, s, acc2, binned, nonfinite);
+                   pixel_moments_add(h.ok, h.pix, h.w, image_vlos(G, IR, h, s, vx, vz), n_pix, mom2);
+               });
 }
 
-// ModelImage(cube=...): k_image_moments' loop; a sample that reaches its pixel with w != 0 adds
-// {w, w w} to the record of its pixel and Doppler bin in cube2, [n_pix][nv + 2] 16-byte records
-// (image_cube_sample): at most two atomic requests per binned sample.  The cube's scalars travel as
+// ModelImage(cube=...): k_image_moments' pass with another tail; a sample that reaches its pixel
+// with w != 0 adds {w, w w} to the record of its pixel and Doppler bin in cube2, [n_pix][nv + 2]
+// 16-byte records (image_vlos, pixel_cube_add): at most two atomic requests per binned sample.  The cube's scalars travel as
 // a kernel argument; ImageK and the LDS blob are k_image's.
 template <typename T>
 __global__ void __launch_bounds__(NXC_IMAGE_MOMENTS_BLOCK)
@@ -1018,22 +1037,13 @@ k_image_cube(const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_
              const T *__restrict__ frac, double *__restrict__ acc2, double *__restrict__ cube2,
              DevCounters *__restrict__ ctr)
 {
-    stage_tables(blob, stage_bytes);
-    const ImageRegs IR = image_regs(lds_header().G);
-    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
-    // wave-uniform trip count (the accumulation is wave-cooperative); the last trip is ragged
-    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p;
-         base += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = base + threadIdx.x;
-        const bool has = i < p;
-        my_samples += has;
-        double sx = 0, sy = 0, sz = 0, svy = 0, sf = 0;
-        if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
-        image_cube_sample(lds_header().G, IR, Q, has, sx, sy, sz, svy, sf, vx + i, vz + i, acc2,
-                          cube2, my_binned, my_nonfinite);
-    }
-    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
-                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
+    pixel_pass(blob, stage_bytes, p, x, y, z, vy, frac, ctr, (int64_t)blockIdx.x * blockDim.x,
+               (int64_t)gridDim.x * blockDim.x,
+               [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
+                   unsigned long long &binned, unsigned long long &nonfinite) {
+                   const PixelHit h = image_located(G, IR, s, acc2, binned, nonfinite);
+                   pixel_cube_add(Q, h.ok, h.pix, h.w, image_vlos(G, IR, h, s, vx, vz), cube2);
+               });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2745,23 +2755,33 @@ NXC_DEV bool density_cells(const DensityK &K, const double p[3], int lo[3], int 
     return true;
 }
 
-template <typename T>
-__global__ void __launch_bounds__(NXC_BLOCK)
-k_density(DensityK K, int64_t n, const T *__restrict__ x, const T *__restrict__ y,
-          const T *__restrict__ z, const T *__restrict__ frac, const double *__restrict__ pts,
-          const int *__restrict__ cell_start, double *__restrict__ acc2)
+// The walk of the three density kernels over stored rows: a grid-stride loop, per row the cull
+// (density_cells), the (cy, cz) range walk over its candidate cells and the membership test.
+//   load(i)       what the consumer needs of row i besides its position.  CULLED = false: of every
+//                 row, issued with the position loads (after the cull it would be one more memory
+//                 round trip per trip of the loop: 3 % of k_density's time where few rows pass);
+//                 CULLED = true: only of a row the cull passed, which spares the other rows'
+//                 bytes.  What it leaves behind is read only by a lane that hits.
+//   each(hit, q)  by all lanes once per trip of the candidate loop, from uniform control flow:
+//                 this lane's candidate q is within dr of its row, or it has none
+// first, stride: formed in the kernel's body, for pixel_pass's reason.
+template <bool CULLED, typename T, typename Load, typename Each>
+NXC_DEV void density_walk(const DensityK &K, int64_t n, const T *__restrict__ x,
+                          const T *__restrict__ y, const T *__restrict__ z,
+                          const double *__restrict__ pts, const int *__restrict__ cell_start,
+                          int64_t first, int64_t stride, Load load, Each each)
 {
     // wave-uniform trip count (the accumulation is wave-cooperative); the last trip is ragged
-    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n;
-         base += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t base = first; base < n; base += stride) {
         const int64_t i = base + threadIdx.x;
-        double p[3] = {0.0, 0.0, 0.0}, w = 0.0;
+        double p[3] = {0.0, 0.0, 0.0};
         int lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1};
         bool live = false;
         if (i < n) {
             p[0] = (double)x[i]; p[1] = (double)y[i]; p[2] = (double)z[i];
-            w = (double)frac[i];
+            if (!CULLED) load(i);
             live = density_cells(K, p, lo, hi);
+            if (CULLED && live) load(i);
         }
         // the candidate points of one (cy, cz) row of cells are one contiguous range [j, e)
         int cy = lo[1], cz = lo[2], j = 0, e = 0;
@@ -2786,15 +2806,30 @@ k_density(DensityK K, int64_t n, const T *__restrict__ x, const T *__restrict__ 
                 q = j++;
                 advance();
             }
-            image_add_pairs(hit, q, w, acc2);
+            each(hit, q);
         }
     }
 }
 
-// ModelDensity(moments=True): k_density's pass with the velocity moments of every hit.  The same
-// cull (density_cells), the same candidate walk (copied, so that k_density compiles as before)
-// and the same membership test; p, v and frac are widened to fp64 and a hit adds, with f = frac
-// and one rounding per operation,
+template <typename T>
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_density(DensityK K, int64_t n, const T *__restrict__ x, const T *__restrict__ y,
+          const T *__restrict__ z, const T *__restrict__ frac, const double *__restrict__ pts,
+          const int *__restrict__ cell_start, double *__restrict__ acc2)
+{
+    double w = 0.0;
+    density_walk<false>(K, n, x, y, z, pts, cell_start, (int64_t)blockIdx.x * blockDim.x,
+                 (int64_t)gridDim.x * blockDim.x, [&](int64_t i) { w = (double)frac[i]; },
+                 [&](bool hit, int q) { image_add_pairs(hit, q, w, acc2); });
+}
+
+
+// ModelDensity(moments=True): k_density's pass with the velocity moments of every hit; v and frac
+// are read only for a row the cull passed.  The loop, cull and candidate walk are density_walk's,
+// written out: through density_walk the kernel either runs five waves a SIMD instead of four and
+// takes 0.2 ms more on the 128^3 grid (45.5 against 45.3 ms), or, with v and w zeroed every trip,
+// 0.03 ms more on the trajectory.  p, v and frac are widened to fp64 and a
+// hit adds, with f = frac and one rounding per operation,
 //     {f, 1}                                   to record q of acc2 (k_density's own pair array)
 //     {f vx, f vy}  {f vz, (f vx) vx}  {(f vy) vy, (f vz) vz}  {(f vx) vy, (f vx) vz}
 //     {(f vy) vz, f f}                         to record q of planes 0..4 of mom2, [5][Q] records.
@@ -2865,10 +2900,10 @@ k_density_moments(DensityK K, int64_t n, int64_t n_points, const T *__restrict__
     }
 }
 
+
 // ModelDensity(spectrum=...): k_density's pass with, per point, the speed spectrum seen from a
-// moving spacecraft (include/nexoclom_hip.h, "Density spectrum", holds the definition).  The same
-// cull, candidate walk (copied again, so that k_density and k_density_moments compile as before)
-// and membership test.  Point q has a frame record of eight doubles {ux uy uz 0 bx by bz 0}: the
+// moving spacecraft (include/nexoclom_hip.h, "Density spectrum", holds the definition).  The walk
+// and the loads are k_density_moments' (density_walk).  Point q has a frame record of eight doubles {ux uy uz 0 bx by bz 0}: the
 // spacecraft velocity u [R/s] and the unit boresight b, read only by a lane that hits.  With
 // f = frac and one rounding per operation, a hit forms
 //     c = v - u;  s = sqrt((cx cx + cy cy) + cz cz);  a = -((cx bx + cy by) + cz bz)
@@ -2897,72 +2932,41 @@ k_density_spectrum(DensityK K, SpectrumK S, int64_t n, int64_t n_points, const T
                    double *__restrict__ spec2)
 {
     double *__restrict__ flux2 = spec2 + 2 * n_points * (int64_t)(S.nv + 2);
-    // wave-uniform trip count (the accumulation is wave-cooperative); the last trip is ragged
-    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < n;
-         base += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = base + threadIdx.x;
-        double p[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0}, w = 0.0;
-        int lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1};
-        bool live = false;
-        if (i < n) {
-            p[0] = (double)x[i]; p[1] = (double)y[i]; p[2] = (double)z[i];
-            live = density_cells(K, p, lo, hi);
-            if (live) {
-                v[0] = (double)vx[i]; v[1] = (double)vy[i]; v[2] = (double)vz[i];
-                w = (double)frac[i];
-            }
-        }
-        // the candidate points of one (cy, cz) row of cells are one contiguous range [j, e)
-        int cy = lo[1], cz = lo[2], j = 0, e = 0;
-        auto advance = [&]() {
-            while (live && j >= e) {
-                if (cz > hi[2]) { live = false; break; }
-                const int row = (cz * K.n[1] + cy) * K.n[0];
-                j = cell_start[row + lo[0]];
-                e = cell_start[row + hi[0] + 1];
-                if (++cy > hi[1]) { cy = lo[1]; ++cz; }
-            }
-        };
-        advance();
-        while (__ballot(live) != 0) {
-            bool hit = false;
-            int q = 0;
-            if (live) {
-                const double dx = pts[4 * (int64_t)j] - p[0];
-                const double dy = pts[4 * (int64_t)j + 1] - p[1];
-                const double dz = pts[4 * (int64_t)j + 2] - p[2];
-                hit = (dx * dx + dy * dy) + dz * dz <= K.dr2;
-                q = j++;
-                advance();
-            }
-            if (__ballot(hit) == 0) continue;
-            bool seen = false;
-            int rec = 0;
-            double g = 0.0;
-            if (hit) {
-                const double *__restrict__ fr = frames + 8 * (int64_t)q;
-                const double c[3] = {v[0] - fr[0], v[1] - fr[1], v[2] - fr[2]};
-                const double s = __builtin_sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
-                const double a = -((c[0] * fr[4] + c[1] * fr[5]) + c[2] * fr[6]);
-                seen = S.all_sky != 0 || a >= S.cos_half * s;
-                const double t = (s - S.s_lo) * S.inv_ds;
-                int k = S.nv + 1;
-                if (t < 0.0) k = 0;
-                else if (t < (double)S.nv) k = 1 + (int)t;
-                rec = q * (S.nv + 2) + k;
-                g = w * s;
-            }
-            add_record_pairs(hit, q, w, 1.0, acc2);
-            add_record_pairs(hit && seen, rec, w, w * w, spec2);
-            add_record_pairs(hit && seen, rec, g, g * g, flux2);
-        }
-    }
+    double v[3] = {0.0, 0.0, 0.0}, w = 0.0;
+    density_walk<true>(K, n, x, y, z, pts, cell_start, (int64_t)blockIdx.x * blockDim.x,
+                 (int64_t)gridDim.x * blockDim.x,
+                 [&](int64_t i) {
+                     v[0] = (double)vx[i]; v[1] = (double)vy[i]; v[2] = (double)vz[i];
+                     w = (double)frac[i];
+                 },
+                 [&](bool hit, int q) {
+                     if (__ballot(hit) == 0) return;
+                     bool seen = false;
+                     int rec = 0;
+                     double g = 0.0;
+                     if (hit) {
+                         const double *__restrict__ fr = frames + 8 * (int64_t)q;
+                         const double c[3] = {v[0] - fr[0], v[1] - fr[1], v[2] - fr[2]};
+                         const double s = __builtin_sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+                         const double a = -((c[0] * fr[4] + c[1] * fr[5]) + c[2] * fr[6]);
+                         seen = S.all_sky != 0 || a >= S.cos_half * s;
+                         const double t = (s - S.s_lo) * S.inv_ds;
+                         int k = S.nv + 1;
+                         if (t < 0.0) k = 0;
+                         else if (t < (double)S.nv) k = 1 + (int)t;
+                         rec = q * (S.nv + 2) + k;
+                         g = w * s;
+                     }
+                     add_record_pairs(hit, q, w, 1.0, acc2);
+                     add_record_pairs(hit && seen, rec, w, w * w, spec2);
+                     add_record_pairs(hit && seen, rec, g, g * g, flux2);
+                 });
 }
 
 // ---------------------------------------------------------------------------------------------
-// CameraImage: stored samples binned into the image of a pinhole camera (camera_sample).  k_image's
-// shape: the blob [header | g tables | u edges | v edges] staged once per workgroup, a grid-stride
-// loop with a wave-uniform trip count, one memory-side atomic request per binned sample.
+// CameraImage: stored samples binned into the image of a pinhole camera (camera_located).
+// k_image's pass (pixel_pass): the blob [header | g tables | u edges | v edges] staged once per
+// workgroup, one memory-side atomic request per binned sample.
 // 66 VGPRs: seven waves a SIMD, i.e. three 512-thread groups on a CU where k_image's 1024-thread
 // groups would come to one (asking for eight waves spills to scratch).
 constexpr int NXC_CAMERA_BLOCK = 512;
@@ -2973,25 +2977,17 @@ k_camera(CameraK K, const unsigned char *__restrict__ blob, int64_t stage_bytes,
          const T *__restrict__ vy, const T *__restrict__ frac,
          double *__restrict__ acc2, DevCounters *__restrict__ ctr)
 {
-    stage_tables(blob, stage_bytes);
-    const ImageRegs IR = image_regs(lds_header().G);
-    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
-    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p;
-         base += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = base + threadIdx.x;
-        const bool has = i < p;
-        my_samples += has;
-        double sx = 0, sy = 0, sz = 0, svy = 0, sf = 0;
-        if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
-        camera_sample(K, lds_header().G, IR, has, sx, sy, sz, svy, sf, acc2, my_binned, my_nonfinite);
-    }
-    // (the tables are not read any more: their first bytes carry the workgroup's sums)
-    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
-                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
+    pixel_pass(blob, stage_bytes, p, x, y, z, vy, frac, ctr, (int64_t)blockIdx.x * blockDim.x,
+               (int64_t)gridDim.x * blockDim.x,
+               [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
+                   unsigned long long &binned, unsigned long long &nonfinite) {
+                   camera_located(K, G, IR, s, acc2, binned, nonfinite);
+               });
 }
 
+
 // CameraImage(moments=True): k_camera's pass over seven columns with the moment terms along each
-// sample's own ray (camera_moments_sample); mom2 as in k_image_moments.
+// sample's own ray (camera_vlos, pixel_moments_add); mom2 as in k_image_moments.
 template <typename T>
 __global__ void __launch_bounds__(NXC_CAMERA_BLOCK)
 k_camera_moments(CameraK K, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p,
@@ -3000,25 +2996,18 @@ k_camera_moments(CameraK K, const unsigned char *__restrict__ blob, int64_t stag
                  const T *__restrict__ vz, const T *__restrict__ frac, double *__restrict__ acc2,
                  double *__restrict__ mom2, DevCounters *__restrict__ ctr)
 {
-    stage_tables(blob, stage_bytes);
-    const ImageRegs IR = image_regs(lds_header().G);
-    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
-    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p;
-         base += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = base + threadIdx.x;
-        const bool has = i < p;
-        my_samples += has;
-        double sx = 0, sy = 0, sz = 0, svy = 0, sf = 0;
-        if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
-        camera_moments_sample(K, lds_header().G, IR, has, sx, sy, sz, svy, sf, vx + i, vz + i, acc2,
-                              n_pix, mom2, my_binned, my_nonfinite);
-    }
-    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
-                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
+    pixel_pass(blob, stage_bytes, p, x, y, z, vy, frac, ctr, (int64_t)blockIdx.x * blockDim.x,
+               (int64_t)gridDim.x * blockDim.x,
+               [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
+                   unsigned long long &binned, unsigned long long &nonfinite) {
+                   const PixelHit h = camera_located(K, G, IR, s, acc2, binned, nonfinite);
+                   pixel_moments_add(h.ok, h.pix, h.w, camera_vlos(K, h, s, vx, vz), n_pix, mom2);
+               });
 }
 
-// CameraImage(cube=...): k_camera_moments' loop with the Doppler bin along each sample's own ray
-// (camera_cube_sample); cube2 and Q as in k_image_cube.
+
+// CameraImage(cube=...): k_camera_moments' pass with the Doppler bin along each sample's own ray
+// (camera_vlos, pixel_cube_add); cube2 and Q as in k_image_cube.
 template <typename T>
 __global__ void __launch_bounds__(NXC_CAMERA_BLOCK)
 k_camera_cube(CameraK K, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p,
@@ -3027,21 +3016,13 @@ k_camera_cube(CameraK K, const unsigned char *__restrict__ blob, int64_t stage_b
               const T *__restrict__ frac, double *__restrict__ acc2, double *__restrict__ cube2,
               DevCounters *__restrict__ ctr)
 {
-    stage_tables(blob, stage_bytes);
-    const ImageRegs IR = image_regs(lds_header().G);
-    unsigned long long my_samples = 0, my_binned = 0, my_nonfinite = 0;
-    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < p;
-         base += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t i = base + threadIdx.x;
-        const bool has = i < p;
-        my_samples += has;
-        double sx = 0, sy = 0, sz = 0, svy = 0, sf = 0;
-        if (has) { sx = x[i]; sy = y[i]; sz = z[i]; svy = vy[i]; sf = frac[i]; }
-        camera_cube_sample(K, lds_header().G, IR, Q, has, sx, sy, sz, svy, sf, vx + i, vz + i, acc2,
-                           cube2, my_binned, my_nonfinite);
-    }
-    flush_counters_wg(reinterpret_cast<unsigned long long *>(nxc_lds), &ctr->samples, my_samples,
-                      &ctr->samples_binned, my_binned, &ctr->nonfinite, my_nonfinite);
+    pixel_pass(blob, stage_bytes, p, x, y, z, vy, frac, ctr, (int64_t)blockIdx.x * blockDim.x,
+               (int64_t)gridDim.x * blockDim.x,
+               [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
+                   unsigned long long &binned, unsigned long long &nonfinite) {
+                   const PixelHit h = camera_located(K, G, IR, s, acc2, binned, nonfinite);
+                   pixel_cube_add(Q, h.ok, h.pix, h.w, camera_vlos(K, h, s, vx, vz), cube2);
+               });
 }
 
 // ---------------------------------------------------------------------------------------------
