@@ -27,6 +27,7 @@
 #include "nxc_camera_check.hpp"
 #include "nxc_cube_check.hpp"
 #include "nxc_desc_check.hpp"
+#include "nxc_devbuf.hpp"
 #include "nxc_image_block.hpp"
 #include "nxc_kernels.hpp"
 #include "nxc_log_table.hpp"
@@ -270,6 +271,22 @@ StepW make_stepw(double h)
     return w;
 }
 
+// What owns a device allocation (nxc_devbuf.hpp) allocates through HIP, reports as HIPCHK does and
+// has the blocks kept from freed row stores given back before an allocation is refused
+void flush_all_pools();
+struct HipAlloc {
+    static inline thread_local hipError_t last = hipSuccess;   // for callers that word a refusal themselves
+    static int alloc(void **ptr, size_t bytes)
+    {
+        if ((last = hipMalloc(ptr, bytes)) == hipSuccess) return NXC_OK;
+        (void)hipGetLastError();
+        return fail_hip("hipMalloc(ptr, bytes ? bytes : 8)", last);
+    }
+    static int free(void *ptr) { HIPCHK(hipFree(ptr)); return NXC_OK; }
+    static int flush() { flush_all_pools(); return NXC_OK; }
+};
+template <typename T> using Dev = DevBuf<T, HipAlloc>;
+
 }  // namespace
 
 // Device-resident compact trajectory rows (nxc_rows_build): nine value columns [9][total] and the
@@ -301,7 +318,19 @@ struct BlockPool {
 struct nxc_pairs {
     int device = 0;
     long long cap = 0, n = 0;        // n: pairs the last pass found (<= cap, or that pass failed)
-    long long *d = nullptr;
+    Dev<long long> d;
+};
+
+// What a pixel grid owns on the device, ModelImage's (nxc_set_image) and CameraImage's
+// (nxc_camera_set) alike.  The moments and the cube are there from their enable to the next set.
+struct PixelSums {
+    Dev<double> image;               // interleaved {weight sum, packet count} per pixel, fp64
+    size_t npix = 0;
+    bool have_mom = false;           // nxc_X_moments_enable since the last set
+    Dev<double> mom;                 // the pixel moments: [2][npix] 16-byte records (k_X_moments)
+    bool have_cube = false;          // nxc_X_cube_enable since the last set
+    Dev<double> cube;                // the velocity cube: [npix][nv + 2] records (k_X_cube)
+    CubeK cubeK{};
 };
 
 // Stored samples on the device, as every consumer (image, line of sight, density, fit) reads them:
@@ -324,13 +353,16 @@ struct nxc_handle {
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;   // row-store downloads, streamed uploads: beside the compute stream
     hipStream_t stream2 = nullptr;       // streamed pass: the pieces' ordering kernels
-    unsigned long long *d_piece_hist = nullptr;   // streamed pass: sort bins (+ max) per piece, then the
-                                                  // word that publishes the queue positions ready
+    Dev<unsigned long long> d_piece_hist;   // streamed pass: sort bins (+ max) per piece, then the
+                                            // word that publishes the queue positions ready
     hipEvent_t ev_piece[33] = {};        // ... piece p uploaded; [32]: start / join
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     char name[256] = {0};
 
+    // Every have_* flag here and below goes false before the first call that can fail touches what
+    // it guards, and true after the last such call: a set or an enable that fails leaves its entries
+    // refusing with NXC_ERR_STATE, never reading half-made state.
     // tables
     bool have_forces = false, have_image = false;
     ForceK F{};
@@ -342,62 +374,42 @@ struct nxc_handle {
     std::vector<unsigned char> image_part;       // lines, then xedges, zedges
     LdsHeader header{};                          // host copy of the blob's first bytes
     ImageBlock<LutDesc> image_block;             // where image_part's pieces sit
-    unsigned char *d_blob = nullptr;
-    size_t blob_cap = 0, force_bytes = 0, all_bytes = 0;
-    unsigned char *d_blob_img = nullptr;         // [LdsHeader | image part] for the kernels that bin
-    size_t blob_img_cap = 0, img_bytes = 0;      // stored samples: no force table in their LDS
+    Dev<unsigned char> d_blob;
+    size_t force_bytes = 0, all_bytes = 0;
+    Dev<unsigned char> d_blob_img;               // [LdsHeader | image part] for the kernels that bin
+    size_t img_bytes = 0;                        // stored samples: no force table in their LDS
 
     // resident data
-    double *d_image = nullptr;       // interleaved {weight sum, packet count} per pixel, fp64
-    bool have_img_mom = false;       // nxc_image_moments_enable since the last nxc_set_image
-    double *d_img_mom = nullptr;     // the pixel moments: [2][npix] 16-byte records (k_image_moments)
-    bool have_img_cube = false;      // nxc_image_cube_enable since the last nxc_set_image
-    double *d_img_cube = nullptr;    // the velocity cube: [npix][nv + 2] records (k_image_cube)
-    CubeK img_cube{};
-    size_t npix = 0;
-    double *d_packets = nullptr;
-    size_t packets_cap = 0;
+    PixelSums img;                   // ModelImage's pair, moments and cube
+    Dev<double> d_packets;
     int64_t n_packets = 0;
-    unsigned *d_order = nullptr;     // packet indices by decreasing launch speed (queue order)
-    double *d_queue = nullptr;       // the packets in that order, one 64-byte record each: [n][8]
-    size_t queue_cap = 0;
-    size_t order_cap = 0;
+    Dev<unsigned> d_order;           // packet indices by decreasing launch speed (queue order)
+    Dev<double> d_queue;             // the packets in that order, one 64-byte record each: [n][8]
     bool have_order = false;
     int order_key = 0;               // what the queue is sorted by: 0 |v|^2, 1 known lifetimes, 2 the adaptive driver's key
     int64_t first_id = 0;            // global index of resident packet 0 (RNG counter space)
     bool have_bounce = false;
-    double *d_bounce = nullptr;      // spline knots + coefficients of the accommodation table
-    size_t bounce_cap = 0;
+    Dev<double> d_bounce;            // spline knots + coefficients of the accommodation table
     bool have_stick_map = false;
-    double *d_stick_map = nullptr;   // sticking map: longitude nodes, latitude nodes, coefficients
-    size_t stick_map_cap = 0;
-    double *d_source = nullptr;      // sampler tables: speed CDF + speeds, surface density map
-    size_t source_cap = 0;
-    DevCounters *d_ctr = nullptr;
-    double *d_scratch = nullptr;     // final states / generic device scratch
-    size_t scratch_cap = 0;
-    unsigned char *d_samples = nullptr;   // host sample columns on their way to k_image / k_los
-    size_t samples_cap = 0;
-    unsigned char *d_tiles = nullptr;     // chunk scratch of the tiled image (k_image_bin -> k_image_tiles)
-    size_t tiles_cap = 0;
-    unsigned char *d_losblk = nullptr;    // block descriptors + spheres (k_los_blocks -> k_los)
-    size_t losblk_cap = 0;
+    Dev<double> d_stick_map;         // sticking map: longitude nodes, latitude nodes, coefficients
+    Dev<double> d_source;            // sampler tables: speed CDF + speeds, surface density map
+    Dev<DevCounters> d_ctr;
+    Dev<double> d_scratch;           // final states / generic device scratch
+    Dev<unsigned char> d_samples;    // host sample columns on their way to k_image / k_los
+    Dev<unsigned char> d_tiles;      // chunk scratch of the tiled image (k_image_bin -> k_image_tiles)
+    Dev<unsigned char> d_losblk;     // block descriptors + spheres (k_los_blocks -> k_los)
     int image_mode = 0;                   // nxc_image_mode: 0 by size, 1 k_image, 2 tiles
     int tile_pixels = NXC_TILE_PIXELS;
     int64_t tile_slab = int64_t(1) << 28; // samples per pass of the tiled image (bounds its scratch)
-    long long *d_steps = nullptr;
-    size_t steps_cap = 0;
-    unsigned long long *d_hist = nullptr;   // counting-sort bins of the queue order
-    size_t hist_cap = 0;
-    void *d_rec = nullptr;           // pass 2's records on their way to columns (grow-only)
-    size_t rec_cap = 0;
+    Dev<long long> d_steps;
+    Dev<unsigned long long> d_hist;  // counting-sort bins of the queue order
+    Dev<void> d_rec;                 // pass 2's records on their way to columns (grow-only)
 
     BlockPool pool;
     LosLutCache los_lut[NXC_MAX_LINES];   // the g-value tables of the last line-of-sight call, packed
 
     // compact-rows protocol (nxc_integrate_const_rows -> nxc_rows_fetch)
-    long long *d_offsets = nullptr;
-    size_t offsets_cap = 0;
+    Dev<long long> d_offsets;
     long long rows_total = -1;
     double rows_step = 0, rows_edge = 0;
     int64_t rows_n_iter = 0, rows_n = 0;
@@ -407,8 +419,7 @@ struct nxc_handle {
 
     bool have_bodies = false;
     nxc_bodies_desc bodies{};
-    double *d_moonpos = nullptr;     // [n_iter][n_moons][cos, sin] of the per-step base phase
-    size_t moonpos_cap = 0;
+    Dev<double> d_moonpos;           // [n_iter][n_moons][cos, sin] of the per-step base phase
 
     ncclComm_t comm = nullptr;
     int rank = 0, nranks = 1;
@@ -417,41 +428,30 @@ struct nxc_handle {
     hipEvent_t ev_pre_coll = nullptr; // recorded in front of the first pending collective
     std::atomic<bool> abort_requested{false};   // nxc_comm_request_abort (any thread)
     double coll_timeout_s = 120.0;   // nxc_comm_set_timeout / NXC_COLLECTIVE_TIMEOUT_S
-    double *d_reduce = nullptr;      // one double for control-plane reductions
-    double *d_reduce_n = nullptr;    // nxc_allreduce_f64's staging (grow-only)
-    size_t reduce_n_cap = 0;
+    Dev<double> d_reduce;            // one double for control-plane reductions
+    Dev<double> d_reduce_n;          // nxc_allreduce_f64's staging (grow-only)
 
     // ModelDensity (nxc_density_set): the point index and the {frac sum, count} pair per point
     bool have_density = false;
     DensityK dens{};
     int64_t dens_q = 0;
-    double *d_dens_pts = nullptr;    // [Q][4]: x, y, z, 0 (two 16-byte loads per candidate)
-    size_t dens_pts_cap = 0;
-    int *d_dens_cell = nullptr;      // cell starts [ncells + 1]
-    size_t dens_cell_cap = 0;
-    double *d_dens_acc = nullptr;    // interleaved pair [Q][2], as the image's
-    size_t dens_acc_cap = 0;
+    Dev<double> d_dens_pts;          // [Q][4]: x, y, z, 0 (two 16-byte loads per candidate)
+    Dev<int> d_dens_cell;            // cell starts [ncells + 1]
+    Dev<double> d_dens_acc;          // interleaved pair [Q][2], as the image's
     bool have_dens_mom = false;      // nxc_density_moments_enable since the last nxc_density_set
-    double *d_dens_mom = nullptr;    // the moment sums: [5][Q] 16-byte records (k_density_moments)
-    size_t dens_mom_cap = 0;
+    Dev<double> d_dens_mom;          // the moment sums: [5][Q] 16-byte records (k_density_moments)
     bool have_dens_spec = false;     // nxc_density_spectrum_enable since the last nxc_density_set
     SpectrumK dens_spec{};
-    double *d_dens_spec = nullptr;   // the spectrum: [2][Q][nv + 2] records (k_density_spectrum)
-    double *d_dens_frames = nullptr; // [Q][8]: ux uy uz 0 bx by bz 0 per indexed point
+    Dev<double> d_dens_spec;         // the spectrum: [2][Q][nv + 2] records (k_density_spectrum)
+    Dev<double> d_dens_frames;       // [Q][8]: ux uy uz 0 bx by bz 0 per indexed point
 
     // CameraImage (nxc_camera_set): the camera, its LDS blob [LdsHeader | g tables | u edges |
     // v edges] and its own {weight sum, count} image
     bool have_camera = false;
     CameraK cam{};
-    unsigned char *d_blob_cam = nullptr;
-    size_t blob_cam_cap = 0, cam_bytes = 0;
-    double *d_cam_image = nullptr;
-    bool have_cam_mom = false;       // nxc_camera_moments_enable since the last nxc_camera_set
-    double *d_cam_mom = nullptr;     // [2][cam_npix] records (k_camera_moments)
-    bool have_cam_cube = false;      // nxc_camera_cube_enable since the last nxc_camera_set
-    double *d_cam_cube = nullptr;    // [cam_npix][nv + 2] records (k_camera_cube)
-    CubeK cam_cube{};
-    size_t cam_image_cap = 0, cam_npix = 0;
+    Dev<unsigned char> d_blob_cam;
+    size_t cam_bytes = 0;
+    PixelSums cam_px;                // the camera's pair, moments and cube
 
     // LOSResultFitted: the pair list the line-of-sight passes fill (nxc_los_set_pairs); the fit's
     // per-spectrum data, its sample source and per-packet sums (nxc_fit_*)
@@ -461,14 +461,10 @@ struct nxc_handle {
     int fit_mode = 0;
     bool have_fit_src = false;
     Samples fit_src;
-    double *d_fit_spec = nullptr;    // position [3][S] | ratio | weight | radiance sums | mask bytes
-    size_t fit_spec_cap = 0;
-    unsigned char *d_fit_pk = nullptr;   // num | den | mult (f64) | cnt | lengths (u32) per packet
-    size_t fit_pk_cap = 0;
-    unsigned char *d_fit_smp = nullptr;  // host columns of the fit on the device
-    size_t fit_smp_cap = 0;
-    unsigned char *d_fit_aux = nullptr;  // blob | counters, or nxc_fit_rows' tile scratch
-    size_t fit_aux_cap = 0;
+    Dev<double> d_fit_spec;          // position [3][S] | ratio | weight | radiance sums | mask bytes
+    Dev<unsigned char> d_fit_pk;     // num | den | mult (f64) | cnt | lengths (u32) per packet
+    Dev<unsigned char> d_fit_smp;    // host columns of the fit on the device
+    Dev<unsigned char> d_fit_aux;    // blob | counters, or nxc_fit_rows' tile scratch
 
     // source maps (nxc_source_map_*): the grid and tile segments, the resident map and unsmeared
     // histogram, and one Output's packets
@@ -476,12 +472,9 @@ struct nxc_handle {
     SmapK smap{};
     int64_t smap_ntiles = 0, smap_ncells = 0;
     std::vector<double> smap_edges;  // alt | az | lon | lat edges (the speed edges come per Output)
-    unsigned char *d_smap_grid = nullptr;  // pt_lon | pt_lat | pt_cos | thr | seg_off | seg
-    size_t smap_grid_cap = 0;
-    double *d_smap_acc = nullptr;    // map [npoints][stride] | hist2d [npoints]
-    size_t smap_acc_cap = 0;
-    unsigned char *d_smap_pk = nullptr;    // columns | geo | bins | cell starts | edges | small
-    size_t smap_pk_cap = 0;
+    Dev<unsigned char> d_smap_grid;  // pt_lon | pt_lat | pt_cos | thr | seg_off | seg
+    Dev<double> d_smap_acc;          // map [npoints][stride] | hist2d [npoints]
+    Dev<unsigned char> d_smap_pk;    // columns | geo | bins | cell starts | edges | small
 };
 
 static int order_on_device(nxc_handle *h, double k2max, const long long *d_lifetimes,
@@ -561,29 +554,12 @@ hipError_t stream_sync(nxc_handle *h)
     return hipErrorNotReady;
 }
 
-void flush_all_pools();
-
-int ensure(void **ptr, size_t *cap, size_t bytes)
-{
-    if (*cap >= bytes && *ptr) return NXC_OK;
-    if (*ptr) HIPCHK(hipFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    if (hipMalloc(ptr, bytes ? bytes : 8) != hipSuccess) {
-        (void)hipGetLastError();
-        flush_all_pools();                 // memory kept from freed row stores goes back first
-        HIPCHK(hipMalloc(ptr, bytes ? bytes : 8));
-    }
-    *cap = bytes;
-    return NXC_OK;
-}
-
 // The handle's generic scratch with room for `bytes`.  Whoever takes it overwrites the finals an
 // adaptive-step run may have left there (nxc_integrate_var_resident -> nxc_var_rows_build).
 int scratch_for(nxc_handle *h, size_t bytes)
 {
     h->var_n = -1;
-    return ensure(reinterpret_cast<void **>(&h->d_scratch), &h->scratch_cap, bytes);
+    return h->d_scratch.ensure(bytes);
 }
 
 // NXC_POOL_TRACE=1: every take / give that reaches the driver, with its duration, on stderr
@@ -660,7 +636,7 @@ void pool_give(nxc_handle *h, void *p, size_t bytes)
     h->pool.bytes += bytes;
 }
 
-// every live handle, for allocations that have no handle at hand (ensure)
+// every live handle, for allocations that have no handle at hand (HipAlloc::flush)
 std::mutex g_handles_lock;
 std::vector<nxc_handle *> g_handles;
 
@@ -677,11 +653,12 @@ size_t pool_bytes(nxc_handle *h)
 }
 
 // Device blob = [LdsHeader | force table | g-value tables | x edges | z edges]; kernels stage
-// the first force_bytes (integrator only) or all_bytes (image) of it into LDS.
-int upload_blob(nxc_handle *h)
+// the first force_bytes (integrator only) or all_bytes (image) of it into LDS.  `with_image`: the
+// handle's image part goes in (have_image, or nxc_set_image on its way to setting it).
+int upload_blob(nxc_handle *h, bool with_image)
 {
     const size_t hb = NXC_HEADER_BYTES;
-    const size_t ib = h->have_image ? h->image_part.size() : 0;
+    const size_t ib = with_image ? h->image_part.size() : 0;
     const size_t limit = 160 * 1024 - 32 - (size_t)(BLOCK_PERSIST / 64) * NXC_WAVE_LDS_BYTES;
     // (the row-writing kernels stage two more words per queued packet and no image tables)
     const size_t limit_rows = 160 * 1024 - 32 - (size_t)(BLOCK_PERSIST / 64) * NXC_WAVE_LDS_BYTES_ROWS;
@@ -701,10 +678,10 @@ int upload_blob(nxc_handle *h)
     h->all_bytes = hb + fb + ib;
     if (h->all_bytes > limit || h->force_bytes > limit_rows)
         return fail(NXC_ERR_ARG, "lookup tables exceed the 160 KiB LDS of a gfx950 CU");
-    int rc = ensure(reinterpret_cast<void **>(&h->d_blob), &h->blob_cap, h->all_bytes);
+    int rc = h->d_blob.ensure(h->all_bytes);
     if (rc) return rc;
     h->F.tab = placed_lut(h->force_lut.desc, hb);
-    if (h->have_image) place_image_block(h->image_block, hb + fb, h->G);
+    if (with_image) place_image_block(h->image_block, hb + fb, h->G);
     h->header.G = h->G;
     HIPCHK(hipMemcpyAsync(h->d_blob, &h->header, sizeof(LdsHeader), hipMemcpyHostToDevice,
                           h->stream));
@@ -713,13 +690,13 @@ int upload_blob(nxc_handle *h)
     if (ib) HIPCHK(hipMemcpyAsync(h->d_blob + hb + fb, h->image_part.data(), ib,
                                   hipMemcpyHostToDevice, h->stream));
     HIPCHK(stream_sync(h));
-    if (h->have_image) {
+    if (with_image) {
         // the same image tables right behind the header: k_image stages 45 KB instead of 100+, so
         // that several of its workgroups fit a CU (it was one 256-thread group per CU)
         LdsHeader hdr = h->header;
         place_image_block(h->image_block, hb, hdr.G);
         h->img_bytes = hb + ib;
-        rc = ensure(reinterpret_cast<void **>(&h->d_blob_img), &h->blob_img_cap, h->img_bytes);
+        rc = h->d_blob_img.ensure(h->img_bytes);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(h->d_blob_img, &hdr, sizeof(LdsHeader), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->d_blob_img + hb, h->image_part.data(), ib, hipMemcpyHostToDevice,
@@ -830,8 +807,7 @@ int upload_moon_table(nxc_handle *h, double step, int64_t n_iter)
             base[((size_t)k * nm + m) * 2 + 1] = sn;
         }
     }
-    int rc = ensure(reinterpret_cast<void **>(&h->d_moonpos), &h->moonpos_cap,
-                    count * sizeof(double));
+    int rc = h->d_moonpos.ensure(count * sizeof(double));
     if (rc) return rc;
     // pageable source: the copy is staged before the call returns
     HIPCHK(hipMemcpyAsync(h->d_moonpos, base.data(), count * sizeof(double), hipMemcpyHostToDevice,
@@ -894,7 +870,7 @@ int launch_fused(nxc_handle *h, bool image, int rows, int64_t n_iter, double out
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, h->stream, h->F, h->d_blob,
                        (int64_t)tables, h->n_packets, job.soa, job.order, h->first_id, n_iter,
                        sqrt_threshold(outeredge), job.final, job.steps,
-                       v.image ? h->d_image : (double *)nullptr, h->d_ctr,
+                       v.image ? h->img.image : (double *)nullptr, h->d_ctr,
                        v.nbody ? h->d_moonpos : (const double *)nullptr, job.offsets, job.rec, job.avail);
     HIPCHK(hipGetLastError());
     return end_timed(h);
@@ -943,8 +919,7 @@ int count_rows(nxc_handle *h, double step, int64_t n_iter, double outeredge, boo
     int rc;
     h->rows_total = -1;
     if ((rc = scratch_for(h, 8 * col))) return rc;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_steps), &h->steps_cap,
-                     (size_t)n * sizeof(long long))))
+    if ((rc = h->d_steps.ensure((size_t)n * sizeof(long long))))
         return rc;
     if ((rc = launch_const(h, step, n_iter, outeredge, image, h->d_scratch, h->d_steps))) return rc;
     std::vector<long long> steps((size_t)n), off((size_t)n + 1);
@@ -961,8 +936,7 @@ int count_rows(nxc_handle *h, double step, int64_t n_iter, double outeredge, boo
         acc += len;
     }
     off[(size_t)n] = acc;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_offsets), &h->offsets_cap,
-                     ((size_t)n + 1) * sizeof(long long))))
+    if ((rc = h->d_offsets.ensure(((size_t)n + 1) * sizeof(long long))))
         return rc;
     HIPCHK(hipMemcpyAsync(h->d_offsets, off.data(), ((size_t)n + 1) * sizeof(long long),
                           hipMemcpyHostToDevice, h->stream));
@@ -994,7 +968,7 @@ int write_records(nxc_handle *h, bool narrow, size_t reserve)
     const size_t bytes = (size_t)total * 10 * (narrow ? sizeof(float) : sizeof(double));
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const size_t grow = bytes > h->rec_cap ? bytes : 0, back = grow ? h->rec_cap : 0;
+    const size_t grow = bytes > h->d_rec.cap ? bytes : 0, back = grow ? h->d_rec.cap : 0;
     if (grow + reserve > free_b + back + pool_bytes(h))
         return fail(NXC_ERR_NOMEM, "trajectory rows do not fit in device memory; run fewer packets "
                                  "per call (the reference chunks too, Input.py:219-222)");
@@ -1003,7 +977,7 @@ int write_records(nxc_handle *h, bool narrow, size_t reserve)
     // later ones a free + malloc of ten-odd GB each
     const size_t roomy = bytes + bytes / 8;
     const bool slack = grow && roomy + reserve <= free_b + back;
-    if ((rc = ensure(&h->d_rec, &h->rec_cap, slack ? roomy : bytes))) return rc;
+    if ((rc = h->d_rec.ensure(slack ? roomy : bytes))) return rc;
     if ((rc = const_preamble(h, h->rows_step, h->rows_n_iter))) return rc;
     FusedJob job = whole_set(h);
     job.offsets = h->d_offsets; job.rec = h->d_rec;
@@ -1101,17 +1075,16 @@ int samples_from_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t c
 // P samples in host memory, 64-bit or as save() keeps them (32-bit), to the device buffer *buf:
 // each column (null ones are skipped) 256-byte aligned, then the int64 index if there is one
 template <typename T>
-int samples_upload(nxc_handle *h, unsigned char **buf, size_t *cap, int64_t P,
-                   const T *const cols[N_SAMPLE_COLS],
-                   const int64_t *index, Samples *s)
+int samples_upload(nxc_handle *h, Dev<unsigned char> &buf, int64_t P,
+                   const T *const cols[N_SAMPLE_COLS], const int64_t *index, Samples *s)
 {
     const size_t bytes = (size_t)P * sizeof(T), col = (bytes + 255) & ~size_t(255);
     const size_t n_cols = N_SAMPLE_COLS - std::count(cols, cols + N_SAMPLE_COLS, nullptr);
-    int rc = ensure(reinterpret_cast<void **>(buf), cap, n_cols * col + (index ? (size_t)P * 8 : 0));
+    int rc = buf.ensure(n_cols * col + (index ? (size_t)P * 8 : 0));
     if (rc) return rc;
     *s = Samples{};
     s->f32 = sizeof(T) == 4; s->n = P;
-    unsigned char *d = *buf;
+    unsigned char *d = buf;
     for (int c = 0; c < N_SAMPLE_COLS; c++) {
         if (!cols[c]) continue;
         if (P) HIPCHK(hipMemcpyAsync(d, cols[c], bytes, hipMemcpyHostToDevice, h->stream));
@@ -1236,7 +1209,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
                  o_inc = take(included ? (size_t)n_index : 0),
                  o_used = take(used_pairs ? (size_t)used_cap * 16 : 0), o_nu = take(8);
     if ((rc = scratch_for(h, off))) return rc;
-    unsigned char *base = reinterpret_cast<unsigned char *>(h->d_scratch);
+    unsigned char *base = reinterpret_cast<unsigned char *>(h->d_scratch.get());
     // the used pairs go to the host copy (used_pairs) or stay on the device (nxc_los_set_pairs)
     nxc_pairs *const sink = used_pairs ? nullptr : h->los_pairs;
     long long *const d_used = used_pairs ? reinterpret_cast<long long *>(base + o_used)
@@ -1270,8 +1243,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
         // it is full k_los decides the pairs itself
         constexpr int pair_chunks = 1 << 15;
         const size_t o_fill = o_n + 256, o_list = o_fill + (size_t)pair_chunks * 4;
-        if ((rc = ensure(reinterpret_cast<void **>(&h->d_losblk), &h->losblk_cap,
-                         o_list + (size_t)pair_chunks * 64 * 8)))
+        if ((rc = h->d_losblk.ensure(o_list + (size_t)pair_chunks * 64 * 8)))
             return rc;
         size_t lds_pairs = ((stage_bytes + 31) & ~size_t(31)) + (size_t)((d->n_ladder + 3) & ~int64_t(3)) * 8;
         if (lds_pairs > 160 * 1024) return fail(NXC_ERR_ARG, "the ladder of ball centres exceeds the LDS");
@@ -1388,7 +1360,7 @@ int los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double
     if (P && (!x || !y || !z || !vy || !frac)) return fail(NXC_ERR_ARG, "bad arguments");
     const T *cols[N_SAMPLE_COLS] = {x, y, z, vy, frac, nullptr, nullptr};
     Samples s;
-    if ((rc = samples_upload(h, &h->d_samples, &h->samples_cap, P, cols, index, &s))) return rc;
+    if ((rc = samples_upload(h, h->d_samples, P, cols, index, &s))) return rc;
     return los_run(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs, n_used);
 }
 
@@ -1453,13 +1425,13 @@ int image_run_tiles(nxc_handle *h, const TilePlan &tp, int64_t p, const T *dx, c
         o_sl = entries * 8;
         o_list = o_sl + entries * 2;
         o_n = (o_list + (size_t)prod * nb * (size_t)mc * 2 + 255) & ~size_t(255);
-        rc = ensure(reinterpret_cast<void **>(&h->d_tiles), &h->tiles_cap, o_n + (size_t)prod * nb * 4);
+        rc = h->d_tiles.ensure(o_n + (size_t)prod * nb * 4);
         if (rc == NXC_OK) break;
         if (slab <= (int64_t(1) << 22)) return rc;        // HBM is full: not even 50 MB
         (void)hipGetLastError();
         slab_max = slab >> 1;                             // a smaller slab needs less scratch
     }
-    double *sw = reinterpret_cast<double *>(h->d_tiles);
+    double *sw = reinterpret_cast<double *>(h->d_tiles.get());
     unsigned short *sl = reinterpret_cast<unsigned short *>(h->d_tiles + o_sl);
     unsigned short *list = reinterpret_cast<unsigned short *>(h->d_tiles + o_list);
     unsigned *nlist = reinterpret_cast<unsigned *>(h->d_tiles + o_n);
@@ -1475,7 +1447,7 @@ int image_run_tiles(nxc_handle *h, const TilePlan &tp, int64_t p, const T *dx, c
         hipLaunchKernelGGL((k_image_tiles<DEFER, CAP>), dim3((unsigned)(nb * ng)), dim3(NXC_IMAGE_BLOCK),
                            lds_tiles, h->stream, h->d_blob_img, (int64_t)h->img_bytes, (int)grid,
                            (int)mc, tp.nb_log2, ng, tp.tile_used, (int)h->header.G.nz, sw, sl, list,
-                           nlist, h->d_image, h->d_ctr);
+                           nlist, h->img.image, h->d_ctr);
         HIPCHK(hipGetLastError());
     }
     if ((rc = end_timed(h))) return rc;
@@ -1485,8 +1457,11 @@ int image_run_tiles(nxc_handle *h, const TilePlan &tp, int64_t p, const T *dx, c
 
 // An occupancy-sized, grid-stride pass over p stored samples: as many workgroups as the chip holds
 // at once (never more than the samples fill), each striding over the samples; timed and waited for.
+// (The arguments come by reference: the handle's buffers turn into pointers at the kernel's own
+// parameters.)
 template <class K, class... Args>
-int launch_sample_pass(nxc_handle *h, K kernel, int block, size_t lds_bytes, int64_t p, Args... args)
+int launch_sample_pass(nxc_handle *h, K kernel, int block, size_t lds_bytes, int64_t p,
+                       const Args &...args)
 {
     int per_cu = 0, rc;
     if ((rc = prep_kernel(kernel, lds_bytes))) return rc;
@@ -1538,7 +1513,7 @@ int image_run(nxc_handle *h, const Samples &s)
         // as many 1024-thread groups as fit a CU (two for Na's 45 KB of tables), each staging the
         // tables once and striding over the samples
         return launch_sample_pass(h, k_image<T>, NXC_IMAGE_BLOCK, h->img_bytes, p, h->d_blob_img,
-                                  (int64_t)h->img_bytes, p, dx, dy, dz, dvy, dfrac, h->d_image, h->d_ctr);
+                                  (int64_t)h->img_bytes, p, dx, dy, dz, dvy, dfrac, h->img.image, h->d_ctr);
     });
 }
 
@@ -1584,7 +1559,7 @@ int camera_run(nxc_handle *h, const Samples &s)
         using T = decltype(t);
         return launch_sample_pass(h, k_camera<T>, NXC_CAMERA_BLOCK, h->cam_bytes, s.n, h->cam,
                                   h->d_blob_cam, (int64_t)h->cam_bytes, s.n, s.col<T>(0), s.col<T>(1),
-                                  s.col<T>(2), s.col<T>(3), s.col<T>(4), h->d_cam_image, h->d_ctr);
+                                  s.col<T>(2), s.col<T>(3), s.col<T>(4), h->cam_px.image, h->d_ctr);
     });
 }
 
@@ -1594,9 +1569,9 @@ int image_moments_run(nxc_handle *h, const Samples &s)
     return with_sample_types(s, [&](auto t, auto) -> int {
         using T = decltype(t);
         return launch_sample_pass(h, k_image_moments<T>, NXC_IMAGE_MOMENTS_BLOCK, h->img_bytes, s.n,
-                                  h->d_blob_img, (int64_t)h->img_bytes, s.n, (int64_t)h->npix,
+                                  h->d_blob_img, (int64_t)h->img_bytes, s.n, (int64_t)h->img.npix,
                                   s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(5), s.col<T>(3),
-                                  s.col<T>(6), s.col<T>(4), h->d_image, h->d_img_mom, h->d_ctr);
+                                  s.col<T>(6), s.col<T>(4), h->img.image, h->img.mom, h->d_ctr);
     });
 }
 
@@ -1606,9 +1581,9 @@ int camera_moments_run(nxc_handle *h, const Samples &s)
     return with_sample_types(s, [&](auto t, auto) -> int {
         using T = decltype(t);
         return launch_sample_pass(h, k_camera_moments<T>, NXC_CAMERA_BLOCK, h->cam_bytes, s.n, h->cam,
-                                  h->d_blob_cam, (int64_t)h->cam_bytes, s.n, (int64_t)h->cam_npix,
+                                  h->d_blob_cam, (int64_t)h->cam_bytes, s.n, (int64_t)h->cam_px.npix,
                                   s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(5), s.col<T>(3),
-                                  s.col<T>(6), s.col<T>(4), h->d_cam_image, h->d_cam_mom, h->d_ctr);
+                                  s.col<T>(6), s.col<T>(4), h->cam_px.image, h->cam_px.mom, h->d_ctr);
     });
 }
 
@@ -1618,9 +1593,9 @@ int image_cube_run(nxc_handle *h, const Samples &s)
     return with_sample_types(s, [&](auto t, auto) -> int {
         using T = decltype(t);
         return launch_sample_pass(h, k_image_cube<T>, NXC_IMAGE_MOMENTS_BLOCK, h->img_bytes, s.n,
-                                  h->d_blob_img, (int64_t)h->img_bytes, s.n, h->img_cube,
+                                  h->d_blob_img, (int64_t)h->img_bytes, s.n, h->img.cubeK,
                                   s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(5), s.col<T>(3),
-                                  s.col<T>(6), s.col<T>(4), h->d_image, h->d_img_cube, h->d_ctr);
+                                  s.col<T>(6), s.col<T>(4), h->img.image, h->img.cube, h->d_ctr);
     });
 }
 
@@ -1630,28 +1605,31 @@ int camera_cube_run(nxc_handle *h, const Samples &s)
     return with_sample_types(s, [&](auto t, auto) -> int {
         using T = decltype(t);
         return launch_sample_pass(h, k_camera_cube<T>, NXC_CAMERA_BLOCK, h->cam_bytes, s.n, h->cam,
-                                  h->d_blob_cam, (int64_t)h->cam_bytes, s.n, h->cam_cube,
+                                  h->d_blob_cam, (int64_t)h->cam_bytes, s.n, h->cam_px.cubeK,
                                   s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(5), s.col<T>(3),
-                                  s.col<T>(6), s.col<T>(4), h->d_cam_image, h->d_cam_cube, h->d_ctr);
+                                  s.col<T>(6), s.col<T>(4), h->cam_px.image, h->cam_px.cube, h->d_ctr);
     });
 }
 
 // What tells one consumer of stored samples from another at its entry points
 struct SampleConsumer {
-    bool nxc_handle::*have;                      // its nxc_*_set has been called ...
+    bool (*have)(const nxc_handle *);            // its nxc_*_set has been called ...
     const char *unset;                           // ... or this is the NXC_ERR_STATE message
     bool needs_vy, clears_ctr;                   // reads the vy column; zeroes d_ctr per accepted call
     bool needs_vxz;                              // reads the vx and vz columns too
     bool (*idle)(const nxc_handle *);            // nothing to add to, whatever the samples (or null)
     int (*run)(nxc_handle *, const Samples &);
+    PixelSums nxc_handle::*px = nullptr;         // the pixel sums its moments and cube sit beside
 };
-const SampleConsumer IMAGE_SAMPLES = {&nxc_handle::have_image, "nxc_set_image has not been called",
-                                      true, true, false, nullptr, image_run};
-const SampleConsumer DENSITY_SAMPLES = {&nxc_handle::have_density, "nxc_density_set has not been called",
+const SampleConsumer IMAGE_SAMPLES = {[](const nxc_handle *h) { return h->have_image; },
+                                      "nxc_set_image has not been called",
+                                      true, true, false, nullptr, image_run, &nxc_handle::img};
+const SampleConsumer DENSITY_SAMPLES = {[](const nxc_handle *h) { return h->have_density; },
+                                        "nxc_density_set has not been called",
                                         false, false, false,
                                         [](const nxc_handle *h) { return h->dens_q == 0; }, density_run};
 // the moments' state is the enable; its entries check nxc_density_set's first (moments_need_set)
-const SampleConsumer MOMENT_SAMPLES = {&nxc_handle::have_dens_mom,
+const SampleConsumer MOMENT_SAMPLES = {[](const nxc_handle *h) { return h->have_dens_mom; },
                                        "nxc_density_moments_enable has not been called",
                                        true, false, true,
                                        [](const nxc_handle *h) { return h->dens_q == 0; }, moments_run};
@@ -1663,7 +1641,7 @@ int moments_need_set(const nxc_handle *h)
     return guarded([&]() -> int { return fail(NXC_ERR_STATE, DENSITY_SAMPLES.unset); });
 }
 // the spectrum's state is its enable too, checked after nxc_density_set's (moments_need_set)
-const SampleConsumer SPECTRUM_SAMPLES = {&nxc_handle::have_dens_spec,
+const SampleConsumer SPECTRUM_SAMPLES = {[](const nxc_handle *h) { return h->have_dens_spec; },
                                          "nxc_density_spectrum_enable has not been called",
                                          true, false, true,
                                          [](const nxc_handle *h) { return h->dens_q == 0; }, spectrum_run};
@@ -1674,61 +1652,57 @@ size_t spectrum_bytes(size_t Q, const SpectrumK &S) { return 2 * Q * (size_t)(S.
 int spectrum_free(nxc_handle *h)
 {
     h->have_dens_spec = false;
-    if (h->d_dens_spec) HIPCHK(hipFree(h->d_dens_spec));
-    h->d_dens_spec = nullptr;
-    if (h->d_dens_frames) HIPCHK(hipFree(h->d_dens_frames));
-    h->d_dens_frames = nullptr;
-    return NXC_OK;
+    const int rc = h->d_dens_spec.release(), rc2 = h->d_dens_frames.release();
+    return rc ? rc : rc2;
 }
-const SampleConsumer CAMERA_SAMPLES = {&nxc_handle::have_camera, "nxc_camera_set has not been called",
-                                       true, true, false, nullptr, camera_run};
+const SampleConsumer CAMERA_SAMPLES = {[](const nxc_handle *h) { return h->have_camera; },
+                                       "nxc_camera_set has not been called",
+                                       true, true, false, nullptr, camera_run, &nxc_handle::cam_px};
 // the pixel moments' state is their enable, checked after the set's (pixel_moments_need_set)
-const SampleConsumer IMAGE_MOMENT_SAMPLES = {&nxc_handle::have_img_mom,
+const SampleConsumer IMAGE_MOMENT_SAMPLES = {[](const nxc_handle *h) { return h->img.have_mom; },
                                              "nxc_image_moments_enable has not been called",
                                              true, true, true, nullptr, image_moments_run};
-const SampleConsumer CAMERA_MOMENT_SAMPLES = {&nxc_handle::have_cam_mom,
+const SampleConsumer CAMERA_MOMENT_SAMPLES = {[](const nxc_handle *h) { return h->cam_px.have_mom; },
                                               "nxc_camera_moments_enable has not been called",
                                               true, true, true, nullptr, camera_moments_run};
 // the state check in front of a moments consumer's own: the set of `base` is the missing call
 int pixel_moments_need_set(const nxc_handle *h, const SampleConsumer &base)
 {
-    if (h && h->*base.have) return NXC_OK;
+    if (h && base.have(h)) return NXC_OK;
     return guarded([&]() -> int { return fail(NXC_ERR_STATE, base.unset); });
 }
 
 // nxc_X_moments_enable: [2][npix] zeroed records beside the image pair of `base`, or none
-int pixel_moments_enable(nxc_handle *h, const SampleConsumer &base, size_t npix, int on,
-                         bool nxc_handle::*have, double *nxc_handle::*d_mom)
+int pixel_moments_enable(nxc_handle *h, const SampleConsumer &base, int on)
 {
     if (int rc = pixel_moments_need_set(h, base)) return rc;
     return guarded([&]() -> int {
+        PixelSums &px = h->*base.px;
         HIPCHK(hipSetDevice(h->device));
-        h->*have = false;
-        if (h->*d_mom) HIPCHK(hipFree(h->*d_mom));
-        h->*d_mom = nullptr;
-        if (!on) return NXC_OK;
-        const size_t bytes = npix * 4 * sizeof(double);
-        size_t cap = 0;
-        int rc = ensure(reinterpret_cast<void **>(&(h->*d_mom)), &cap, bytes);
-        if (rc) return rc;
-        HIPCHK(hipMemsetAsync(h->*d_mom, 0, bytes, h->stream));
+        px.have_mom = false;
+        int rc = px.mom.release();
+        if (rc || !on) return rc;
+        const size_t bytes = px.npix * 4 * sizeof(double);
+        if ((rc = px.mom.ensure(bytes))) return rc;
+        HIPCHK(hipMemsetAsync(px.mom, 0, bytes, h->stream));
         HIPCHK(stream_sync(h));
-        h->*have = true;
+        px.have_mom = true;
         return NXC_OK;
     });
 }
 
 // nxc_X_moments_download: sums[npix][4] = m1 m2 m3 ww from the two planes
 int pixel_moments_download(nxc_handle *h, const SampleConsumer &base, const SampleConsumer &mom,
-                           size_t npix, const double *d_mom, double *sums)
+                           double *sums)
 {
     if (int rc = pixel_moments_need_set(h, base)) return rc;
     return guarded([&]() -> int {
-        if (!(h->*mom.have)) return fail(NXC_ERR_STATE, mom.unset);
+        if (!mom.have(h)) return fail(NXC_ERR_STATE, mom.unset);
         if (!sums) return fail(NXC_ERR_ARG, "bad arguments");
         HIPCHK(hipSetDevice(h->device));
+        const size_t npix = (h->*base.px).npix;
         std::vector<double> planes(npix * 4);
-        HIPCHK(hipMemcpyAsync(planes.data(), d_mom, planes.size() * sizeof(double),
+        HIPCHK(hipMemcpyAsync(planes.data(), (h->*base.px).mom, planes.size() * sizeof(double),
                               hipMemcpyDeviceToHost, h->stream));
         HIPCHK(stream_sync(h));
         for (size_t q = 0; q < npix; q++)
@@ -1741,10 +1715,10 @@ int pixel_moments_download(nxc_handle *h, const SampleConsumer &base, const Samp
 }
 
 // the velocity cube's state is its enable too, checked after the set's (pixel_moments_need_set)
-const SampleConsumer IMAGE_CUBE_SAMPLES = {&nxc_handle::have_img_cube,
+const SampleConsumer IMAGE_CUBE_SAMPLES = {[](const nxc_handle *h) { return h->img.have_cube; },
                                            "nxc_image_cube_enable has not been called",
                                            true, true, true, nullptr, image_cube_run};
-const SampleConsumer CAMERA_CUBE_SAMPLES = {&nxc_handle::have_cam_cube,
+const SampleConsumer CAMERA_CUBE_SAMPLES = {[](const nxc_handle *h) { return h->cam_px.have_cube; },
                                             "nxc_camera_cube_enable has not been called",
                                             true, true, true, nullptr, camera_cube_run};
 
@@ -1752,43 +1726,41 @@ size_t cube_bytes(size_t npix, const CubeK &Q) { return npix * (size_t)(Q.nv + 2
 
 // nxc_X_cube_enable: [npix][nv + 2] zeroed records beside the image pair of `base`, or none; the
 // arguments are checked (check_cube_args) before the cube there is is touched
-int pixel_cube_enable(nxc_handle *h, const SampleConsumer &base, size_t npix, int64_t nv, double v_lo,
-                      double v_hi, bool nxc_handle::*have, double *nxc_handle::*d_cube,
-                      CubeK nxc_handle::*Q)
+int pixel_cube_enable(nxc_handle *h, const SampleConsumer &base, int64_t nv, double v_lo, double v_hi)
 {
     if (int rc = pixel_moments_need_set(h, base)) return rc;
     return guarded([&]() -> int {
+        PixelSums &px = h->*base.px;
         if (nv != 0) {
-            const std::string why = check_cube_args((int64_t)npix, nv, v_lo, v_hi);
+            const std::string why = check_cube_args((int64_t)px.npix, nv, v_lo, v_hi);
             if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
         }
         HIPCHK(hipSetDevice(h->device));
-        h->*have = false;
-        if (h->*d_cube) HIPCHK(hipFree(h->*d_cube));
-        h->*d_cube = nullptr;
-        if (nv == 0) return NXC_OK;
-        h->*Q = CubeK{(int)nv, v_lo, cube_inv_dv(nv, v_lo, v_hi)};
-        const size_t bytes = cube_bytes(npix, h->*Q);
-        size_t cap = 0;
-        int rc = ensure(reinterpret_cast<void **>(&(h->*d_cube)), &cap, bytes);
-        if (rc) return rc;
-        HIPCHK(hipMemsetAsync(h->*d_cube, 0, bytes, h->stream));
+        px.have_cube = false;
+        int rc = px.cube.release();
+        if (rc || nv == 0) return rc;
+        px.cubeK = CubeK{(int)nv, v_lo, cube_inv_dv(nv, v_lo, v_hi)};
+        const size_t bytes = cube_bytes(px.npix, px.cubeK);
+        if ((rc = px.cube.ensure(bytes))) return rc;
+        HIPCHK(hipMemsetAsync(px.cube, 0, bytes, h->stream));
         HIPCHK(stream_sync(h));
-        h->*have = true;
+        px.have_cube = true;
         return NXC_OK;
     });
 }
 
 // nxc_X_cube_download: sums[npix][nv + 2][2], the device's own order
 int pixel_cube_download(nxc_handle *h, const SampleConsumer &base, const SampleConsumer &cube,
-                        size_t bytes, const double *d_cube, double *sums)
+                        double *sums)
 {
     if (int rc = pixel_moments_need_set(h, base)) return rc;
     return guarded([&]() -> int {
-        if (!(h->*cube.have)) return fail(NXC_ERR_STATE, cube.unset);
+        if (!cube.have(h)) return fail(NXC_ERR_STATE, cube.unset);
         if (!sums) return fail(NXC_ERR_ARG, "bad arguments");
         HIPCHK(hipSetDevice(h->device));
-        HIPCHK(hipMemcpyAsync(sums, d_cube, bytes, hipMemcpyDeviceToHost, h->stream));
+        const PixelSums &px = h->*base.px;
+        HIPCHK(hipMemcpyAsync(sums, px.cube, cube_bytes(px.npix, px.cubeK), hipMemcpyDeviceToHost,
+                              h->stream));
         HIPCHK(stream_sync(h));
         return NXC_OK;
     });
@@ -1810,7 +1782,7 @@ int accumulate_columns(nxc_handle *h, const SampleConsumer &c, int64_t p, const 
                        const T *vz = nullptr)
 {
     return guarded([&]() -> int {
-        if (!h || !(h->*c.have)) return fail(NXC_ERR_STATE, c.unset);
+        if (!h || !c.have(h)) return fail(NXC_ERR_STATE, c.unset);
         if (p < 0 || (p && (!x || !y || !z || (c.needs_vy && !vy) || !frac ||
                             (c.needs_vxz && (!vx || !vz)))))
             return fail(NXC_ERR_ARG, "bad arguments");
@@ -1819,7 +1791,7 @@ int accumulate_columns(nxc_handle *h, const SampleConsumer &c, int64_t p, const 
         const T *cols[N_SAMPLE_COLS] = {x, y, z, c.needs_vy ? vy : nullptr, frac,
                                         c.needs_vxz ? vx : nullptr, c.needs_vxz ? vz : nullptr};
         Samples s;
-        rc = samples_upload(h, &h->d_samples, &h->samples_cap, p, cols, nullptr, &s);
+        rc = samples_upload(h, h->d_samples, p, cols, nullptr, &s);
         return rc ? rc : c.run(h, s);
     });
 }
@@ -1828,7 +1800,7 @@ int accumulate_columns(nxc_handle *h, const SampleConsumer &c, int64_t p, const 
 int accumulate_rows(nxc_handle *h, const SampleConsumer &c, const nxc_rows *r, int64_t first, int64_t count)
 {
     return guarded([&]() -> int {
-        if (!h || !(h->*c.have)) return fail(NXC_ERR_STATE, c.unset);
+        if (!h || !c.have(h)) return fail(NXC_ERR_STATE, c.unset);
         Samples s;
         int rc = samples_from_rows(h, r, first, count, 0, &s);
         if (rc || (rc = begin_sample_pass(h, c)) || count == 0 || (c.idle && c.idle(h))) return rc;
@@ -1880,7 +1852,7 @@ FitK fit_consts(const nxc_handle *h, const nxc_pairs *p, int64_t n_packets)
 int fit_aux(nxc_handle *h, size_t blob_bytes, unsigned char **blob, unsigned long long **ctr)
 {
     const size_t o_ctr = (blob_bytes + 255) & ~size_t(255);
-    int rc = ensure(reinterpret_cast<void **>(&h->d_fit_aux), &h->fit_aux_cap, o_ctr + 256);
+    int rc = h->d_fit_aux.ensure(o_ctr + 256);
     if (rc) return rc;
     *blob = h->d_fit_aux;
     *ctr = reinterpret_cast<unsigned long long *>(h->d_fit_aux + o_ctr);
@@ -1894,7 +1866,7 @@ double *fit_rad(nxc_handle *h) { return h->d_fit_spec + 5 * h->fit_S; }
 unsigned char *fit_mask(nxc_handle *h) { return reinterpret_cast<unsigned char *>(h->d_fit_spec + 6 * h->fit_S); }
 
 // per-packet arrays of n packets: num | den | mult (f64) | cnt | lengths (u32)
-double *fit_num(nxc_handle *h, int64_t n) { return reinterpret_cast<double *>(h->d_fit_pk); }
+double *fit_num(nxc_handle *h, int64_t n) { return reinterpret_cast<double *>(h->d_fit_pk.get()); }
 double *fit_den(nxc_handle *h, int64_t n) { return fit_num(h, n) + n; }
 double *fit_mult(nxc_handle *h, int64_t n) { return fit_num(h, n) + 2 * n; }
 unsigned *fit_cnt(nxc_handle *h, int64_t n) { return reinterpret_cast<unsigned *>(fit_num(h, n) + 3 * n); }
@@ -1917,7 +1889,7 @@ int fit_source_columns(nxc_handle *h, int64_t P, const T *x, const T *y, const T
     h->have_fit_src = false;
     h->fit_np = -1;
     const T *cols[N_SAMPLE_COLS] = {x, y, z, vy, frac, nullptr, nullptr};
-    int rc = samples_upload(h, &h->d_fit_smp, &h->fit_smp_cap, P, cols, index, &h->fit_src);
+    int rc = samples_upload(h, h->d_fit_smp, P, cols, index, &h->fit_src);
     h->have_fit_src = rc == NXC_OK;
     return rc;
 }
@@ -2005,7 +1977,7 @@ int fit_rows_run(nxc_handle *h, int compress, nxc_rows **out, int64_t *lengths_o
     const unsigned tiles = (unsigned)row_tiles(n);
     FitK F = fit_consts(h, nullptr, np);
     F.compress = compress ? 1 : 0;
-    int rc = ensure(reinterpret_cast<void **>(&h->d_fit_aux), &h->fit_aux_cap, tile_scratch_bytes(n));
+    int rc = h->d_fit_aux.ensure(tile_scratch_bytes(n));
     if (rc) return rc;
     const I *index = s.idx<I>();
     if (np) HIPCHK(hipMemsetAsync(fit_len(h, np), 0, (size_t)np * 4, h->stream));
@@ -2159,8 +2131,8 @@ int nxc_create(int device, nxc_handle **out)
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&h->ev0);
     if (e == hipSuccess) e = hipEventCreate(&h->ev1);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&h->d_ctr), sizeof(DevCounters));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&h->d_reduce), 64);
+    if (e == hipSuccess && (h->d_ctr.ensure(sizeof(DevCounters)) || h->d_reduce.ensure(64)))
+        e = HipAlloc::last;
     if (e == hipSuccess) e = hipMemset(h->d_ctr, 0, sizeof(DevCounters));
     if (e != hipSuccess) {
         nxc_destroy(h);
@@ -2186,26 +2158,18 @@ int nxc_destroy(nxc_handle *h)
     if (h->stream) (void)stream_sync(h);          // bounded when a collective is still in flight
     g_coll_failure.clear();
     if (h->comm && g_rccl.ok) g_rccl.CommDestroy(h->comm);
-    void *ptrs[] = {h->d_blob, h->d_image, h->d_packets, h->d_ctr, h->d_scratch,
-                    h->d_steps, h->d_reduce, h->d_order, h->d_bounce, h->d_stick_map, h->d_moonpos, h->d_offsets,
-                    h->d_source, h->d_queue, h->d_samples, h->d_tiles, h->d_hist, h->d_rec, h->d_piece_hist,
-                    h->d_blob_img, h->d_reduce_n, h->d_losblk, h->d_dens_pts, h->d_dens_cell,
-                    h->d_dens_acc, h->d_dens_mom, h->d_fit_spec, h->d_fit_pk, h->d_fit_smp, h->d_fit_aux,
-                    h->d_smap_grid, h->d_smap_acc, h->d_smap_pk, h->d_blob_cam, h->d_cam_image,
-                    h->d_img_mom, h->d_cam_mom, h->d_img_cube, h->d_cam_cube, h->d_dens_spec,
-                    h->d_dens_frames};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
     pool_flush(h);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->ev_pre_coll) (void)hipEventDestroy(h->ev_pre_coll);
-    if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
-    if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
-    for (hipEvent_t ev : h->ev_piece)
-        if (ev) (void)hipEventDestroy(ev);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    // the handle's device memory goes with the handle (every buffer frees itself); the streams and
+    // events are destroyed after it, so they are taken out first
+    const hipStream_t stream = h->stream, copy_stream = h->copy_stream, stream2 = h->stream2;
+    hipEvent_t events[3 + 33] = {h->ev0, h->ev1, h->ev_pre_coll};
+    std::copy(h->ev_piece, h->ev_piece + 33, events + 3);
     delete h;
+    if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
+    if (stream2) { (void)hipStreamSynchronize(stream2); (void)hipStreamDestroy(stream2); }
+    for (hipEvent_t ev : events)
+        if (ev) (void)hipEventDestroy(ev);
+    if (stream) (void)hipStreamDestroy(stream);
     return NXC_OK;
 }
 
@@ -2302,7 +2266,7 @@ int nxc_set_forces(nxc_handle *h, const nxc_forces *f)
     h->F.rad = f->radpres ? 1 : 0;
     h->F.loss = f->lifetime > 0 ? LOSS_LIFETIME : (f->has_photo ? LOSS_PHOTO : LOSS_NONE);
     h->have_forces = true;
-    return upload_blob(h);
+    return upload_blob(h, h->have_image);
     });
 }
 
@@ -2338,22 +2302,20 @@ int nxc_set_image(nxc_handle *h, const nxc_image_desc *d)
     PackedLut luts[NXC_MAX_LINES];
     int rc;
     if ((rc = pack_lines(nl, d->line_v, d->line_g, d->line_n, luts))) return rc;
+    h->have_image = false;
+    h->img.have_mom = false;
+    h->img.have_cube = false;
     h->image_block = append_image_block(part, G, d->nx, d->nz, d->xedges, d->zedges, nl, luts);
     h->image_part = std::move(part);
     h->G = G;
-    h->have_image = true;
-    h->have_img_mom = false;
-    h->have_img_cube = false;
 
     const size_t npix = (size_t)d->nx * (size_t)d->nz;
-    if (npix != h->npix) {
-        if (h->d_image) HIPCHK(hipFree(h->d_image));
-        h->d_image = nullptr; h->npix = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&h->d_image), 2 * npix * sizeof(double)));
-        h->npix = npix;
-    }
-    if ((rc = upload_blob(h))) return rc;
-    return nxc_image_clear(h);
+    if ((rc = h->img.image.ensure(2 * npix * sizeof(double)))) return rc;
+    h->img.npix = npix;
+    if ((rc = upload_blob(h, true))) return rc;
+    HIPCHK(hipMemsetAsync(h->img.image, 0, 2 * npix * sizeof(double), h->stream));   // nxc_image_clear
+    h->have_image = true;
+    return NXC_OK;
     });
 }
 
@@ -2377,7 +2339,7 @@ int nxc_set_bounce(nxc_handle *h, const nxc_bounce_desc *d)
     }
     const size_t ncoef = (size_t)(d->nx - 4) * (size_t)(d->ny - 4);
     const size_t total = (size_t)d->nx + (size_t)d->ny + ncoef;
-    int rc = ensure(reinterpret_cast<void **>(&h->d_bounce), &h->bounce_cap, total * sizeof(double));
+    int rc = h->d_bounce.ensure(total * sizeof(double));
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(h->d_bounce, d->tx, (size_t)d->nx * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_bounce + d->nx, d->ty, (size_t)d->ny * 8, hipMemcpyHostToDevice, h->stream));
@@ -2410,7 +2372,7 @@ int nxc_set_stick_map(nxc_handle *h, const nxc_stick_map_desc *d)
         const size_t total = (size_t)(nlon + nlat + ncoef);
         // (a launch that reads the previous map has ended: every launch is followed by a sync or is
         // ordered before these copies on the handle's stream)
-        int rc = ensure(reinterpret_cast<void **>(&h->d_stick_map), &h->stick_map_cap, total * sizeof(double));
+        int rc = h->d_stick_map.ensure(total * sizeof(double));
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(h->d_stick_map, d->lon, (size_t)nlon * 8, hipMemcpyHostToDevice, h->stream));
         if (nlat)
@@ -2488,11 +2450,11 @@ int nxc_image_clear(nxc_handle *h)
 {
     if (!h || !h->have_image) return fail(NXC_ERR_STATE, "nxc_set_image has not been called");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemsetAsync(h->d_image, 0, 2 * h->npix * sizeof(double), h->stream));
-    if (h->have_img_mom)
-        HIPCHK(hipMemsetAsync(h->d_img_mom, 0, 4 * h->npix * sizeof(double), h->stream));
-    if (h->have_img_cube)
-        HIPCHK(hipMemsetAsync(h->d_img_cube, 0, cube_bytes(h->npix, h->img_cube), h->stream));
+    HIPCHK(hipMemsetAsync(h->img.image, 0, 2 * h->img.npix * sizeof(double), h->stream));
+    if (h->img.have_mom)
+        HIPCHK(hipMemsetAsync(h->img.mom, 0, 4 * h->img.npix * sizeof(double), h->stream));
+    if (h->img.have_cube)
+        HIPCHK(hipMemsetAsync(h->img.cube, 0, cube_bytes(h->img.npix, h->img.cubeK), h->stream));
     return NXC_OK;
 }
 
@@ -2517,7 +2479,7 @@ int nxc_image_download(nxc_handle *h, double *image, uint64_t *counts)
     return guarded([&]() -> int {
     if (!h || !h->have_image) return fail(NXC_ERR_STATE, "nxc_set_image has not been called");
     HIPCHK(hipSetDevice(h->device));
-    return download_pairs(h, h->d_image, h->npix, image, counts);
+    return download_pairs(h, h->img.image, h->img.npix, image, counts);
     });
 }
 
@@ -2678,12 +2640,11 @@ static int order_on_device(nxc_handle *h, double k2max, const long long *d_lifet
             (k2max > 0 && !std::isfinite(k2max)))
             return NXC_OK;
     }
-    int rc = ensure(reinterpret_cast<void **>(&h->d_order), &h->order_cap, (size_t)n * sizeof(unsigned));
+    int rc = h->d_order.ensure((size_t)n * sizeof(unsigned));
     if (rc) return rc;
     const size_t hb = (size_t)NXC_ORDER_BINS * sizeof(unsigned long long);
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_hist), &h->hist_cap, hb + 64))) return rc;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_queue), &h->queue_cap,
-                     (size_t)8 * n * sizeof(double))))
+    if ((rc = h->d_hist.ensure(hb + 64))) return rc;
+    if ((rc = h->d_queue.ensure((size_t)8 * n * sizeof(double))))
         return rc;
     unsigned long long *d_max = h->d_hist + NXC_ORDER_BINS;
     double scale = by_steps ? (double)(NXC_ORDER_BINS - 1) / (double)max_steps
@@ -2713,7 +2674,7 @@ int nxc_packets_upload(nxc_handle *h, int64_t n, const double *soa0)
     if (!h || n < 0 || (n && !soa0)) return fail(NXC_ERR_ARG, "bad arguments");
     HIPCHK(hipSetDevice(h->device));
     const size_t bytes = (size_t)8 * n * sizeof(double);
-    int rc = ensure(reinterpret_cast<void **>(&h->d_packets), &h->packets_cap, bytes);
+    int rc = h->d_packets.ensure(bytes);
     if (rc) return rc;
     if (n) HIPCHK(hipMemcpyAsync(h->d_packets, soa0, bytes, hipMemcpyHostToDevice, h->stream));
     h->n_packets = n;
@@ -2738,7 +2699,7 @@ int nxc_packets_upload_pieces(nxc_handle *h, int32_t n_pieces, const int64_t *co
         n += counts[p];
     }
     HIPCHK(hipSetDevice(h->device));
-    int rc = ensure(reinterpret_cast<void **>(&h->d_packets), &h->packets_cap, (size_t)8 * n * sizeof(double));
+    int rc = h->d_packets.ensure((size_t)8 * n * sizeof(double));
     if (rc) return rc;
     // piece p's column c goes behind the same column of the pieces before it: the resident set is
     // the concatenation, without the host ever building it
@@ -2770,12 +2731,12 @@ int nxc_packets_sample(nxc_handle *h, const nxc_source_desc *d, int64_t n, doubl
     HIPCHK(hipSetDevice(h->device));
     const int64_t total = plan.stride, offset = plan.offset;
     const size_t bytes = (size_t)8 * total * sizeof(double);
-    if (offset > 0 && (h->packets_cap < bytes || h->n_packets != total))
+    if (offset > 0 && (h->d_packets.cap < bytes || h->n_packets != total))
         return fail(NXC_ERR_STATE, "nxc_packets_sample: pieces of a set must start with dest_offset 0");
-    int rc = ensure(reinterpret_cast<void **>(&h->d_packets), &h->packets_cap, bytes);
+    int rc = h->d_packets.ensure(bytes);
     if (rc) return rc;
     if (plan.total &&
-        (rc = ensure(reinterpret_cast<void **>(&h->d_source), &h->source_cap, plan.total * sizeof(double))))
+        (rc = h->d_source.ensure(plan.total * sizeof(double))))
         return rc;
     for (const TableCopy &c : plan.copy) {
         if (!c.count) continue;
@@ -2896,12 +2857,10 @@ int nxc_integrate_const_streamed(nxc_handle *h, int64_t n, const double *soa0, i
                                    "surface re-emission upload first (nxc_packets_upload)");
     if ((int64_t)pieces > n) pieces = (int32_t)n;
     const size_t per_piece = NXC_ORDER_BINS + 8;                    // bins, then the largest |v|^2
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_packets), &h->packets_cap, (size_t)8 * n * 8))) return rc;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_queue), &h->queue_cap, (size_t)8 * n * 8))) return rc;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_order), &h->order_cap, (size_t)n * sizeof(unsigned)))) return rc;
-    if (!h->d_piece_hist)
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&h->d_piece_hist),
-                         (32 * per_piece + 8) * sizeof(unsigned long long)));
+    if ((rc = h->d_packets.ensure((size_t)8 * n * 8))) return rc;
+    if ((rc = h->d_queue.ensure((size_t)8 * n * 8))) return rc;
+    if ((rc = h->d_order.ensure((size_t)n * sizeof(unsigned)))) return rc;
+    if ((rc = h->d_piece_hist.ensure((32 * per_piece + 8) * sizeof(unsigned long long)))) return rc;
     for (int e = 0; e <= 32; e++)
         if (!h->ev_piece[e]) HIPCHK(hipEventCreateWithFlags(&h->ev_piece[e], hipEventDisableTiming));
     unsigned long long *d_avail = h->d_piece_hist + 32 * per_piece;
@@ -2998,8 +2957,7 @@ int nxc_integrate_const(nxc_handle *h, double step, int64_t n_iter, double outer
             d_final = h->d_scratch;
         }
         if (steps_out) {
-            if ((rc = ensure(reinterpret_cast<void **>(&h->d_steps), &h->steps_cap,
-                             (size_t)n * sizeof(long long))))
+            if ((rc = h->d_steps.ensure((size_t)n * sizeof(long long))))
                 return rc;
             d_steps = h->d_steps;
         }
@@ -3028,15 +2986,15 @@ int nxc_integrate_const(nxc_handle *h, double step, int64_t n_iter, double outer
         d_steps = h->d_steps;
         if ((rc = write_records(h, false, tbytes))) return rc;
         h->rows_total = -1;
-        const double *d_rec = static_cast<const double *>(h->d_rec);
-        double *d_traj = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_traj), tbytes);
+        const double *d_rec = static_cast<const double *>(h->d_rec.get());
+        Dev<double> d_traj;
+        hipError_t e = d_traj.ensure(tbytes) ? HipAlloc::last : hipSuccess;
         if (e == hipSuccess) {
             const dim3 grid((unsigned)((n + NXC_BLOCK - 1) / NXC_BLOCK),
                             (unsigned)((nrec + NXC_DENSIFY_RECORDS - 1) / NXC_DENSIFY_RECORDS));
             hipLaunchKernelGGL(k_rows_densify, grid, dim3(NXC_BLOCK), 0, h->stream, d_rec,
                                (const long long *)h->d_offsets, (const double *)d_final,
-                               (const long long *)d_steps, n, nrec, d_traj);
+                               (const long long *)d_steps, n, nrec, d_traj.get());
             e = hipGetLastError();
         }
         DevCounters pass2;
@@ -3050,7 +3008,6 @@ int nxc_integrate_const(nxc_handle *h, double step, int64_t n_iter, double outer
             e = hipMemcpyAsync(h->d_ctr, &pass1, sizeof pass1, hipMemcpyHostToDevice, h->stream);
             if (e == hipSuccess) e = stream_sync(h);
         }
-        if (d_traj) (void)hipFree(d_traj);
         if (e != hipSuccess)
             return fail_hip("trajectory run", e);
     }
@@ -3191,10 +3148,9 @@ int nxc_density_set(nxc_handle *h, const nxc_density_desc *d)
     for (int64_t j = 0; j < Q; j++)
         for (int a = 0; a < 3; a++) pts[4 * j + a] = d->points[3 * j + a];
     int rc;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_dens_pts), &h->dens_pts_cap, pts.size() * 8)) ||
-        (rc = ensure(reinterpret_cast<void **>(&h->d_dens_cell), &h->dens_cell_cap,
-                     (size_t)(ncells + 1) * 4)) ||
-        (rc = ensure(reinterpret_cast<void **>(&h->d_dens_acc), &h->dens_acc_cap, (size_t)Q * 16)))
+    if ((rc = h->d_dens_pts.ensure(pts.size() * 8)) ||
+        (rc = h->d_dens_cell.ensure((size_t)(ncells + 1) * 4)) ||
+        (rc = h->d_dens_acc.ensure((size_t)Q * 16)))
         return rc;
     if (Q) HIPCHK(hipMemcpyAsync(h->d_dens_pts, pts.data(), pts.size() * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_dens_cell, cs, (size_t)(ncells + 1) * 4, hipMemcpyHostToDevice, h->stream));
@@ -3251,7 +3207,7 @@ int nxc_density_moments_enable(nxc_handle *h, int on)
     h->have_dens_mom = false;
     if (!on) return NXC_OK;
     const size_t bytes = (size_t)h->dens_q * NXC_MOMENT_PLANES * 16;
-    int rc = ensure(reinterpret_cast<void **>(&h->d_dens_mom), &h->dens_mom_cap, bytes);
+    int rc = h->d_dens_mom.ensure(bytes);
     if (rc) return rc;
     if (bytes) HIPCHK(hipMemsetAsync(h->d_dens_mom, 0, bytes, h->stream));
     HIPCHK(stream_sync(h));
@@ -3321,11 +3277,9 @@ int nxc_density_spectrum_enable(nxc_handle *h, const nxc_density_spectrum_desc *
     h->dens_spec = SpectrumK{(int)d->nv, d->all_sky != 0 ? 1 : 0, d->s_lo,
                              spectrum_inv_ds(d->nv, d->s_lo, d->s_hi), d->cos_half};
     const size_t bytes = spectrum_bytes(Q, h->dens_spec);
-    size_t cap = 0;
     int rc;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_dens_spec), &cap, bytes))) return rc;
-    cap = 0;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_dens_frames), &cap, Q * 8 * sizeof(double)))) return rc;
+    if ((rc = h->d_dens_spec.ensure(bytes)) || (rc = h->d_dens_frames.ensure(Q * 8 * sizeof(double))))
+        return rc;
     if (Q) {
         HIPCHK(hipMemsetAsync(h->d_dens_spec, 0, bytes, h->stream));
         HIPCHK(hipMemcpyAsync(h->d_dens_frames, d->frames, Q * 8 * sizeof(double), hipMemcpyHostToDevice,
@@ -3405,18 +3359,18 @@ int nxc_camera_set(nxc_handle *h, const nxc_camera_desc *d)
     K.area = d->pix_area_cm2;
 
     h->have_camera = false;
-    h->have_cam_mom = false;
-    h->have_cam_cube = false;
+    h->cam_px.have_mom = false;
+    h->cam_px.have_cube = false;
     const size_t npix = (size_t)d->nx * (size_t)d->nz;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_blob_cam), &h->blob_cam_cap, blob.size())) ||
-        (rc = ensure(reinterpret_cast<void **>(&h->d_cam_image), &h->cam_image_cap, 2 * npix * sizeof(double))))
+    if ((rc = h->d_blob_cam.ensure(blob.size())) ||
+        (rc = h->cam_px.image.ensure(2 * npix * sizeof(double))))
         return rc;
     HIPCHK(hipMemcpyAsync(h->d_blob_cam, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->d_cam_image, 0, 2 * npix * sizeof(double), h->stream));
+    HIPCHK(hipMemsetAsync(h->cam_px.image, 0, 2 * npix * sizeof(double), h->stream));
     HIPCHK(stream_sync(h));                    // blob is a local
     h->cam = K;
     h->cam_bytes = blob.size();
-    h->cam_npix = npix;
+    h->cam_px.npix = npix;
     h->have_camera = true;
     return NXC_OK;
     });
@@ -3444,14 +3398,13 @@ int nxc_camera_download(nxc_handle *h, double *image, uint64_t *counts)
     return guarded([&]() -> int {
     if (!h || !h->have_camera) return fail(NXC_ERR_STATE, "nxc_camera_set has not been called");
     HIPCHK(hipSetDevice(h->device));
-    return download_pairs(h, h->d_cam_image, h->cam_npix, image, counts);
+    return download_pairs(h, h->cam_px.image, h->cam_px.npix, image, counts);
     });
 }
 
 int nxc_camera_moments_enable(nxc_handle *h, int on)
 {
-    return pixel_moments_enable(h, CAMERA_SAMPLES, h ? h->cam_npix : 0, on, &nxc_handle::have_cam_mom,
-                                &nxc_handle::d_cam_mom);
+    return pixel_moments_enable(h, CAMERA_SAMPLES, on);
 }
 
 int nxc_camera_moments_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
@@ -3478,15 +3431,12 @@ int nxc_camera_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t
 
 int nxc_camera_moments_download(nxc_handle *h, double *sums)
 {
-    return pixel_moments_download(h, CAMERA_SAMPLES, CAMERA_MOMENT_SAMPLES, h ? h->cam_npix : 0,
-                                  h ? h->d_cam_mom : nullptr, sums);
+    return pixel_moments_download(h, CAMERA_SAMPLES, CAMERA_MOMENT_SAMPLES, sums);
 }
 
 int nxc_camera_cube_enable(nxc_handle *h, int64_t nv, double v_lo, double v_hi)
 {
-    return pixel_cube_enable(h, CAMERA_SAMPLES, h ? h->cam_npix : 0, nv, v_lo, v_hi,
-                             &nxc_handle::have_cam_cube, &nxc_handle::d_cam_cube,
-                             &nxc_handle::cam_cube);
+    return pixel_cube_enable(h, CAMERA_SAMPLES, nv, v_lo, v_hi);
 }
 
 int nxc_camera_cube_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
@@ -3513,9 +3463,7 @@ int nxc_camera_cube_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t fi
 
 int nxc_camera_cube_download(nxc_handle *h, double *sums)
 {
-    return pixel_cube_download(h, CAMERA_SAMPLES, CAMERA_CUBE_SAMPLES,
-                               h ? cube_bytes(h->cam_npix, h->cam_cube) : 0,
-                               h ? h->d_cam_cube : nullptr, sums);
+    return pixel_cube_download(h, CAMERA_SAMPLES, CAMERA_CUBE_SAMPLES, sums);
 }
 
 // ---- source maps ---------------------------------------------------------------------------------
@@ -3600,8 +3548,8 @@ int nxc_source_map_set(nxc_handle *h, const nxc_source_map_desc *d)
         std::copy(d->seg, d->seg + 2 * d->n_seg, reinterpret_cast<int32_t *>(grid.data() + off_seg));
     const size_t acc_bytes = 8 * (size_t)npoints * (size_t)(stride + 1);
     int rc;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_smap_grid), &h->smap_grid_cap, grid_bytes)) ||
-        (rc = ensure(reinterpret_cast<void **>(&h->d_smap_acc), &h->smap_acc_cap, acc_bytes)))
+    if ((rc = h->d_smap_grid.ensure(grid_bytes)) ||
+        (rc = h->d_smap_acc.ensure(acc_bytes)))
         return rc;
     HIPCHK(hipMemcpyAsync(h->d_smap_grid, grid.data(), grid_bytes, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->d_smap_acc, 0, acc_bytes, h->stream));
@@ -3649,8 +3597,7 @@ int nxc_source_map_accumulate(nxc_handle *h, int64_t n, const double *lat, const
     const size_t edges_b = align256(8 * ne);
     const size_t small_b = align256(8 * (size_t)(nh + K.nvel));
     const size_t part_b = 8 * (size_t)h->smap_ntiles * K.nvel;
-    int rc = ensure(reinterpret_cast<void **>(&h->d_smap_pk), &h->smap_pk_cap,
-                    6 * col + geo_b + bins_b + cs_b + edges_b + small_b + part_b);
+    int rc = h->d_smap_pk.ensure(6 * col + geo_b + bins_b + cs_b + edges_b + small_b + part_b);
     if (rc) return rc;
     unsigned char *base = h->d_smap_pk;
     double *dcol = reinterpret_cast<double *>(base);
@@ -3736,8 +3683,7 @@ int nxc_pairs_create(nxc_handle *h, int64_t capacity, nxc_pairs **out)
     if (!p) return fail(NXC_ERR_ARG, "out of host memory");
     p->device = h->device;
     p->cap = capacity;
-    const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p->d), (size_t)capacity * 16);
-    if (e != hipSuccess) {
+    if (p->d.ensure((size_t)capacity * 16)) {
         delete p;
         return fail(NXC_ERR_NOMEM, "pair list of " + std::to_string(capacity) + " pairs");
     }
@@ -3752,7 +3698,6 @@ int nxc_pairs_free(nxc_handle *h, nxc_pairs *p)
     (void)hipSetDevice(p->device);
     if (h && h->stream) (void)stream_sync(h);
     if (h && h->los_pairs == p) h->los_pairs = nullptr;
-    if (p->d) (void)hipFree(p->d);
     delete p;
     return NXC_OK;
 }
@@ -3798,7 +3743,7 @@ int nxc_fit_set(nxc_handle *h, const nxc_fit_desc *d)
     h->have_fit = false;
     h->have_fit_src = false;
     h->fit_np = -1;
-    int rc = ensure(reinterpret_cast<void **>(&h->d_fit_spec), &h->fit_spec_cap, (size_t)S * 6 * 8 + (size_t)S);
+    int rc = h->d_fit_spec.ensure((size_t)S * 6 * 8 + (size_t)S);
     if (rc) return rc;
     h->fit_S = S;
     std::vector<double> w((size_t)S, 1.0);
@@ -3849,7 +3794,7 @@ int nxc_fit_packets(nxc_handle *h, const nxc_pairs *p, int64_t n_packets, double
     if (rc) return rc;
     if (n_packets < 0 || n_packets > INT32_MAX) return fail(NXC_ERR_ARG, "bad packet count");
     h->fit_np = -1;
-    if ((rc = ensure(reinterpret_cast<void **>(&h->d_fit_pk), &h->fit_pk_cap, (size_t)n_packets * 32 + 16)))
+    if ((rc = h->d_fit_pk.ensure((size_t)n_packets * 32 + 16)))
         return rc;
     unsigned char *blob;
     unsigned long long *ctr;
@@ -4027,8 +3972,7 @@ int nxc_image_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const flo
 
 int nxc_image_moments_enable(nxc_handle *h, int on)
 {
-    return pixel_moments_enable(h, IMAGE_SAMPLES, h ? h->npix : 0, on, &nxc_handle::have_img_mom,
-                                &nxc_handle::d_img_mom);
+    return pixel_moments_enable(h, IMAGE_SAMPLES, on);
 }
 
 int nxc_image_moments_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
@@ -4055,15 +3999,12 @@ int nxc_image_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t 
 
 int nxc_image_moments_download(nxc_handle *h, double *sums)
 {
-    return pixel_moments_download(h, IMAGE_SAMPLES, IMAGE_MOMENT_SAMPLES, h ? h->npix : 0,
-                                  h ? h->d_img_mom : nullptr, sums);
+    return pixel_moments_download(h, IMAGE_SAMPLES, IMAGE_MOMENT_SAMPLES, sums);
 }
 
 int nxc_image_cube_enable(nxc_handle *h, int64_t nv, double v_lo, double v_hi)
 {
-    return pixel_cube_enable(h, IMAGE_SAMPLES, h ? h->npix : 0, nv, v_lo, v_hi,
-                             &nxc_handle::have_img_cube, &nxc_handle::d_img_cube,
-                             &nxc_handle::img_cube);
+    return pixel_cube_enable(h, IMAGE_SAMPLES, nv, v_lo, v_hi);
 }
 
 int nxc_image_cube_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
@@ -4090,9 +4031,7 @@ int nxc_image_cube_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t fir
 
 int nxc_image_cube_download(nxc_handle *h, double *sums)
 {
-    return pixel_cube_download(h, IMAGE_SAMPLES, IMAGE_CUBE_SAMPLES,
-                               h ? cube_bytes(h->npix, h->img_cube) : 0,
-                               h ? h->d_img_cube : nullptr, sums);
+    return pixel_cube_download(h, IMAGE_SAMPLES, IMAGE_CUBE_SAMPLES, sums);
 }
 
 int nxc_los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
@@ -4246,7 +4185,7 @@ int nxc_image_allreduce(nxc_handle *h)
     if (int rc = refuse_after_abort_request(h)) return rc;
     // one collective: weights and (integer-valued fp64) counts are interleaved in one array
     if (int rc = mark_collective(h)) return rc;
-    NCCLCHK(g_rccl.AllReduce(h->d_image, h->d_image, 2 * h->npix, ncclFloat64, ncclSum, h->comm,
+    NCCLCHK(g_rccl.AllReduce(h->img.image, h->img.image, 2 * h->img.npix, ncclFloat64, ncclSum, h->comm,
                              h->stream));
     return NXC_OK;
 }
@@ -4260,7 +4199,7 @@ static int allreduce_host(nxc_handle *h, double *values, int64_t n, ncclRedOp_t 
     HIPCHK(hipSetDevice(h->device));
     double *d = h->d_reduce;
     if (n > 1) {
-        int rc = ensure(reinterpret_cast<void **>(&h->d_reduce_n), &h->reduce_n_cap, (size_t)n * 8);
+        int rc = h->d_reduce_n.ensure((size_t)n * 8);
         if (rc) return rc;
         d = h->d_reduce_n;
     }
@@ -4294,8 +4233,8 @@ int nxc_stream_copy_gbs(nxc_handle *h, int64_t bytes, int reps, double *gbs)
     if (!h || !gbs || bytes < (1 << 20) || reps < 1) return fail(NXC_ERR_ARG, "bad arguments");
     HIPCHK(hipSetDevice(h->device));
     const int64_t n16 = bytes / 16;
-    char *buf = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&buf), (size_t)n16 * 32));
+    Dev<char> buf;
+    if (int rc = buf.ensure((size_t)n16 * 32)) return rc;
     hipError_t e = hipMemsetAsync(buf, 1, (size_t)n16 * 32, h->stream);
     float best = 0.f;
     hipEvent_t a = nullptr, b = nullptr;
@@ -4306,7 +4245,7 @@ int nxc_stream_copy_gbs(nxc_handle *h, int64_t bytes, int reps, double *gbs)
         const int64_t per_block = (int64_t)NXC_BLOCK * NXC_COPY_UNROLL;
         hipLaunchKernelGGL(k_stream_copy, dim3((unsigned)((n16 + per_block - 1) / per_block)),
                            dim3(NXC_BLOCK), 0, h->stream,
-                           reinterpret_cast<const nxc_v2d *>(buf),
+                           reinterpret_cast<const nxc_v2d *>(buf.get()),
                            reinterpret_cast<nxc_v2d *>(buf + (size_t)n16 * 16), n16);
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(b, h->stream);
@@ -4317,7 +4256,6 @@ int nxc_stream_copy_gbs(nxc_handle *h, int64_t bytes, int reps, double *gbs)
     }
     if (a) (void)hipEventDestroy(a);
     if (b) (void)hipEventDestroy(b);
-    (void)hipFree(buf);
     if (e != hipSuccess) return fail_hip("stream copy", e);
     *gbs = 2.0 * (double)n16 * 16.0 / ((double)best * 1e-3) / 1e9;      // bytes read + written
     return NXC_OK;
@@ -4333,7 +4271,7 @@ int nxc_shader_clock_mhz(nxc_handle *h, double *mhz)
     int rc = scratch_for(h,
                     (size_t)waves * 3 * sizeof(unsigned long long));
     if (rc) return rc;
-    unsigned long long *d = reinterpret_cast<unsigned long long *>(h->d_scratch);
+    unsigned long long *d = reinterpret_cast<unsigned long long *>(h->d_scratch.get());
     std::vector<unsigned long long> got((size_t)waves * 3);
     for (int round = 0; round < 2; round++) {                    // the first brings the clock up
         hipLaunchKernelGGL(k_clock, dim3(blocks), dim3(BLOCK_PERSIST), 0, h->stream, d,
@@ -4366,7 +4304,7 @@ int nxc_pcg64_uniforms(nxc_handle *h, const uint64_t state[2], const uint64_t in
     const size_t map_bytes = maps.size() * sizeof(u128), out_bytes = (size_t)nvec * count * 8;
     int rc = scratch_for(h, map_bytes + out_bytes);
     if (rc) return rc;
-    unsigned char *base = reinterpret_cast<unsigned char *>(h->d_scratch);
+    unsigned char *base = reinterpret_cast<unsigned char *>(h->d_scratch.get());
     HIPCHK(hipMemcpyAsync(base, maps.data(), map_bytes, hipMemcpyHostToDevice, h->stream));
     PcgK P{};
     P.state = ((u128)state[0] << 64) | state[1];
@@ -4395,7 +4333,7 @@ int nxc_math_batch(nxc_handle *h, int which, int64_t n, const double *in, const 
     double *d = h->d_scratch;
     HIPCHK(hipMemcpyAsync(d, in, col, hipMemcpyHostToDevice, h->stream));
     if (in2) HIPCHK(hipMemcpyAsync(d + n, in2, col, hipMemcpyHostToDevice, h->stream));
-    if (!h->d_blob && (rc = upload_blob(h))) return rc;          // the header with nxc_log's table
+    if (!h->d_blob && (rc = upload_blob(h, h->have_image))) return rc;   // the header with nxc_log's table
     hipLaunchKernelGGL(k_math, dim3(flat_grid(h, n, 256)), dim3(256), NXC_HEADER_BYTES, h->stream,
                        h->d_blob, which, n, d, d + n, d + 2 * n);
     HIPCHK(hipGetLastError());
