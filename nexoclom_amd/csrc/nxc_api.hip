@@ -1364,28 +1364,10 @@ int los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double
     return los_run(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs, n_used);
 }
 
-// Geometry of the tiled image: tile b = image rows ix = b (mod nb), nb a power of two; a tile's
-// pixels (ix / nb, iz) must fit the LDS tile; the chunk shrinks as the tiles multiply
-// (nb x cap = NXC_TILE_STAGE, at most 256).  False when the image has too many pixels for
-// NXC_TILE_MAX tiles (above 1024^2): such images stay with k_image.
-struct TilePlan {
-    int nb_log2 = 0, tile_used = 0, cap = 256;
-    size_t lds_bin = 0;
-};
+// The plan of the tiled image for this handle's image and mode (nxc_tile_plan.hpp).
 bool tile_plan(const nxc_handle *h, TilePlan *out)
 {
-    const int nx = h->header.G.nx, nz = h->header.G.nz;
-    if (nx < 1 || nz < 1 || nz > h->tile_pixels) return false;
-    const int rows = h->tile_pixels / nz;                    // image rows per tile
-    int lg = 0;
-    while (((nx + (1 << lg) - 1) >> lg) > rows) lg++;
-    if ((1 << lg) > NXC_TILE_MAX) return false;
-    out->nb_log2 = lg;
-    out->tile_used = ((nx + (1 << lg) - 1) >> lg) * nz;
-    out->cap = std::min(256, NXC_TILE_STAGE >> lg);
-    out->lds_bin = ((h->img_bytes + 15) & ~size_t(15)) + (size_t)(1 << lg) * out->cap * 10 +
-                   (2 * (size_t)(1 << lg) + 3) * 4;
-    return out->lds_bin <= 160 * 1024;
+    return tile_plan(h->header.G.nx, h->header.G.nz, h->tile_pixels, h->img_bytes, out);
 }
 
 // a-6..a-8 over samples on the device, through LDS-privatised tiles (nxc_kernels.hpp: k_image_bin,
@@ -1397,40 +1379,27 @@ int image_run_tiles(nxc_handle *h, const TilePlan &tp, int64_t p, const T *dx, c
 {
     int rc, per_cu = 0;
     // pass 2 forms the weights (DEFER): the image tables sit in front of its tile
-    const size_t tables = DEFER ? (h->img_bytes + 15) & ~size_t(15) : 0;
+    const size_t tables = DEFER ? nxc_tile_tables(h->img_bytes) : 0;
     const size_t lds_tiles = tables + (size_t)NXC_TILE_PIXELS * 12;
     if ((rc = prep_kernel(k_image_bin<T, DEFER, CAP>, tp.lds_bin))) return rc;
     if ((rc = prep_kernel(k_image_tiles<DEFER, CAP>, lds_tiles))) return rc;
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_image_bin<T, DEFER, CAP>,
                                                         NXC_TILE_BIN_BLOCK, tp.lds_bin));
     const int nb = 1 << tp.nb_log2;
-    const int64_t per_trip = (int64_t)NXC_TILE_BIN_BLOCK * nxc_tile_unroll<T>();
     const int ng = std::max(1, h->n_cu / nb);             // consumer groups per tile
-    int64_t slab_max = std::min<int64_t>(p, h->tile_slab), slab, prod, span, mc;
-    size_t o_sl, o_list, o_n;
+    const int64_t slots = (int64_t)h->n_cu * (per_cu > 0 ? per_cu : 1);
+    int64_t slab_max = h->tile_slab;
+    TileSlabs ts;
     for (;;) {
-        // slabs of equal size: a short last one would run on a fraction of the chip
-        const int64_t n_slabs = (p + slab_max - 1) / slab_max;
-        slab = (p + n_slabs - 1) / n_slabs;
-        prod = (int64_t)h->n_cu * (per_cu > 0 ? per_cu : 1);
-        prod = std::max<int64_t>(1, std::min<int64_t>(prod, (slab + per_trip - 1) / per_trip));
-        span = ((slab + prod - 1) / prod + per_trip - 1) / per_trip * per_trip;
-        if (span > (int64_t(1) << 15) * CAP) {            // a producer's chunk numbers are 16 bits
-            slab_max = (int64_t(1) << 15) * CAP * prod;
-            continue;
-        }
-        mc = span / CAP + nb;
-        // scratch: payloads | pixels-in-tile | chunk lists [producer][tile][mc] | their lengths
-        const size_t entries = (size_t)prod * (size_t)mc * CAP;
-        o_sl = entries * 8;
-        o_list = o_sl + entries * 2;
-        o_n = (o_list + (size_t)prod * nb * (size_t)mc * 2 + 255) & ~size_t(255);
-        rc = h->d_tiles.ensure(o_n + (size_t)prod * nb * 4);
+        ts = tile_slabs(tp, p, slab_max, slots, sizeof(T));
+        rc = h->d_tiles.ensure(ts.bytes);
         if (rc == NXC_OK) break;
-        if (slab <= (int64_t(1) << 22)) return rc;        // HBM is full: not even 50 MB
+        if (ts.slab <= (int64_t(1) << 22)) return rc;     // HBM is full: not even 50 MB
         (void)hipGetLastError();
-        slab_max = slab >> 1;                             // a smaller slab needs less scratch
+        slab_max = ts.slab >> 1;                          // a smaller slab needs less scratch
     }
+    const int64_t slab = ts.slab, span = ts.span, mc = ts.mc;
+    const size_t o_sl = ts.o_sl, o_list = ts.o_list, o_n = ts.o_n;
     double *sw = reinterpret_cast<double *>(h->d_tiles.get());
     unsigned short *sl = reinterpret_cast<unsigned short *>(h->d_tiles + o_sl);
     unsigned short *list = reinterpret_cast<unsigned short *>(h->d_tiles + o_list);
@@ -1477,9 +1446,6 @@ int launch_sample_pass(nxc_handle *h, K kernel, int block, size_t lds_bytes, int
 }
 
 // a-6..a-8 over samples on the device
-// below this the two launches do not pay (measured: 2^16 samples 0.027 ms either way, 2^18 0.055
-// against 0.092, 2^23 0.18 against 0.31, 2^26 0.64 against 1.57)
-constexpr int64_t NXC_TILE_MIN_SAMPLES = int64_t(1) << 17;
 int image_run(nxc_handle *h, const Samples &s)
 {
     return with_sample_types(s, [&](auto t, auto) -> int {
@@ -1495,8 +1461,7 @@ int image_run(nxc_handle *h, const Samples &s)
             // float32 samples (stored rows, the down-cast image) leave the weight to pass 2 when the
             // image tables fit a CU's LDS next to a tile
             const bool f32_values = sizeof(T) == 4 || h->header.G.downcast_f32 != 0;
-            const bool room = ((h->img_bytes + 15) & ~size_t(15)) + (size_t)NXC_TILE_PIXELS * 12 <= 160 * 1024;
-            const bool defer = f32_values && room;
+            const bool defer = f32_values && nxc_tile_room(h->img_bytes);
 #define NXC_TILES_CASE(C)                                                                       \
             case C:                                                                             \
                 return defer ? image_run_tiles<T, true, C>(h, tp, p, dx, dy, dz, dvy, dfrac)    \

@@ -26,6 +26,7 @@
 #include "nxc_device.hpp"
 #include "nxc_fused_variant.hpp"
 #include "nxc_source_limits.hpp"
+#include "nxc_tile_plan.hpp"
 
 struct DevCounters {
     unsigned long long particle_steps, samples, samples_binned, nonfinite, bad_step, neg_frac,
@@ -1067,18 +1068,7 @@ k_image_cube(const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_
 // up to 512^2 pixels (262 144), 64 of 128 up to 524 288, 128 of 64 up to 1024^2 (the reference's
 // default 800 x 800, ModelImage.py:53, takes 128 tiles of 7 image rows).  A chunk of 64 still
 // leaves as 512 + 128 contiguous bytes.  Larger images stay with k_image.
-#ifndef NXC_TILE_STAGE_N          // (overridable: tools/gpu_exp_tile_occupancy.sh)
-#define NXC_TILE_STAGE_N 8192
-#endif
-constexpr int NXC_TILE_STAGE = NXC_TILE_STAGE_N;   // staged entries per workgroup of pass 1 (all tiles)
-constexpr int NXC_TILE_MAX = 128;           // tiles per image at most
-constexpr int NXC_TILE_PIXELS = 8192;       // pixels per tile at most (96 KB of LDS)
-#ifndef NXC_TILE_UNROLL_N
-#define NXC_TILE_UNROLL_N 4
-#endif
-// samples per thread between two workgroup barriers: 4 float32 samples (1.42 / 1.26 / 1.20 / 1.19 ms
-// per 1.34e8 rows for 1 / 2 / 3 / 4), 2 of 64 bits (4 would spill)
-template <typename T> constexpr int nxc_tile_unroll() { return sizeof(T) == 4 ? NXC_TILE_UNROLL_N : 2; }
+// (the constants and the plan: nxc_tile_plan.hpp)
 
 // Workgroup barrier that orders LDS traffic only: the global loads of the next samples stay in
 // flight across it (__syncthreads waits for vmcnt(0) as well).
@@ -1121,10 +1111,6 @@ NXC_DEV void image_add_pairs_n(bool has, int pix, double w, double cnt, double *
 // half of its lanes whose sample fell inside the image; possible whenever the samples are float32
 // values (stored rows, or the down-cast image), since the masked fraction is frac or a zero.
 // Otherwise the payload is the fp64 weight itself.
-#ifndef NXC_TILE_BIN_BLOCK_N
-#define NXC_TILE_BIN_BLOCK_N 1024
-#endif
-constexpr int NXC_TILE_BIN_BLOCK = NXC_TILE_BIN_BLOCK_N;
 template <typename T, bool DEFER, int CAP>
 __global__ void __launch_bounds__(NXC_TILE_BIN_BLOCK)
 k_image_bin(const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p, int64_t span,
@@ -1218,8 +1204,8 @@ k_image_bin(const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t
                 if (ok && !image_weight(lds_header().G, IR, radvel, fw, w[u])) { my_nonfinite++; ok = false; }
                 my_binned += ok;
             }
-            bk[u] = ix & (nb - 1);
-            loc[u] = (ix >> nb_log2) * IR.nz + iz;
+            bk[u] = nxc_tile_of(ix, nb);
+            loc[u] = nxc_tile_loc(ix, iz, nb_log2, IR.nz);
             pend |= ok ? 1u << u : 0u;
         }
         for (;;) {
@@ -1344,7 +1330,7 @@ k_image_tiles(const unsigned char *__restrict__ blob, int64_t stage_bytes, int n
     for (int i0 = 0; i0 < tile_used; i0 += blockDim.x) {           // block-uniform: pairs cooperate
         const int i = i0 + tid;
         const bool has = i < tile_used && tc[i] > 0u;
-        const int lrow = i / nz, iz = i - lrow * nz;
+        const int lrow = i / nz, iz = i - lrow * nz;               // (nxc_tile_pixel, nxc_tile_plan.hpp)
         const int pix = ((lrow << nb_log2) + b) * nz + iz;
         image_add_pairs_n(has, pix, has ? tw[i] : 0.0, has ? (double)tc[i] : 0.0, acc2);
     }
