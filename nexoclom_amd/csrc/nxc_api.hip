@@ -1241,9 +1241,12 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
                      o_n = o_sph + max_slots * 32;
         // the list of (row, spectrum) pairs near a cone: chunks of 64 (k_los -> k_los_pairs); when
         // it is full k_los decides the pairs itself
-        constexpr int pair_chunks = 1 << 15;
-        const size_t o_fill = o_n + 256, o_list = o_fill + (size_t)pair_chunks * 4;
-        if ((rc = h->d_losblk.ensure(o_list + (size_t)pair_chunks * 64 * 8)))
+        constexpr int pair_cap = 1 << 15;
+        int pair_chunks = pair_cap;             // (the scratch is laid out for pair_cap whatever this says)
+        if (const char *t = std::getenv("NXC_TEST_LOS_PAIR_CHUNKS"))     // tests: a full list at small sizes
+            pair_chunks = (int)std::max<long long>(1, std::min<long long>(pair_cap, std::atoll(t)));
+        const size_t o_fill = o_n + 256, o_list = o_fill + (size_t)pair_cap * 4;
+        if ((rc = h->d_losblk.ensure(o_list + (size_t)pair_cap * 64 * 8)))
             return rc;
         size_t lds_pairs = ((stage_bytes + 31) & ~size_t(31)) + (size_t)((d->n_ladder + 3) & ~int64_t(3)) * 8;
         if (lds_pairs > 160 * 1024) return fail(NXC_ERR_ARG, "the ladder of ball centres exceeds the LDS");
@@ -1262,7 +1265,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
             const int64_t n = std::min<int64_t>(slab, P - first);
             const int64_t regions = (n + NXC_LOS_FORM - 1) / NXC_LOS_FORM;
             K.row_base = first;
-            HIPCHK(hipMemsetAsync(n_slots, 0, 256 + (size_t)pair_chunks * 4, st));   // counters + chunk fills
+            HIPCHK(hipMemsetAsync(n_slots, 0, 256 + (size_t)pair_cap * 4, st));   // counters + chunk fills
             hipLaunchKernelGGL((k_los_blocks<T, I>),
                                dim3((unsigned)((regions + NXC_LOS_BLOCKS_THREADS / 64 - 1) /
                                                (NXC_LOS_BLOCKS_THREADS / 64))),
