@@ -873,6 +873,73 @@ int nxc_camera_cube_accumulate_f32(nxc_handle *h, int64_t p, const float *x, con
 int nxc_camera_cube_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
 int nxc_camera_cube_download(nxc_handle *h, double *sums);
 
+/* ---- Line-of-sight profile: radiance per Doppler bin along each line of sight ----------------------
+ * EXTENSION -- nxc_los_accumulate gives one radiance per spectrum; the profile keeps the line: per
+ * spectrum nv >= 1 bins over [v_lo, v_hi), in the rows' velocity unit (planet radii per second), and
+ * the four moment sums of "Pixel moments".  A (sample, spectrum) pair is decided exactly as in
+ * nxc_los_accumulate.  If it reaches the point where its wtemp = weight/Apix (times 0 when the
+ * foot point is in shadow) is added to radiance[spectrum], and wtemp != 0, it also contributes the
+ * following, all fp64, one rounding per operation, no contraction:
+ *   vlos = (vx*bx + vy*by) + vz*bz       bx, by, bz: the spectrum's boresight as given in sc; the
+ *                                        velocity of the sample along it [R/s], planet frame,
+ *                                        positive when receding from the spacecraft.  float32
+ *                                        columns are widened exactly, as the other columns are
+ *   t = (vlos - v_lo) * inv_dv           inv_dv = nv / (v_hi - v_lo), formed once on the host
+ *   k = 0                 if t < 0
+ *   k = 1 + (int)t        if 0 <= t < nv
+ *   k = nv + 1            otherwise: at or above v_hi, or vlos not a number
+ * and the pair adds {wtemp, wtemp*wtemp} to record spectrum*(nv + 2) + k (the cube's rule), and
+ *   a  = wtemp*vlos
+ *   m1 = a        m2 = a*vlos        m3 = (a*vlos)*vlos        ww = wtemp*wtemp
+ * to four sums per spectrum, kept in the order m1 m2 m3 ww.
+ *   - A pair with wtemp == 0 (foot point in shadow, frac == 0, g == 0) adds nothing to either; it is
+ *     still counted in npackets and `included`.  vx and vz of a pair that is not decided, or that has
+ *     wtemp == 0, are not read.
+ *   - Nothing else is filtered: the nv + 2 records of a spectrum sum to its radiance up to the order
+ *     of the additions; a non-finite vx or vz makes that spectrum's moment sums non-finite and
+ *     files the pair under nv + 1.
+ *   - The spacecraft's own velocity is NOT subtracted: vlos is the planet-frame velocity along the
+ *     boresight.  A moving spacecraft shifts every bin of its spectrum by its own velocity along
+ *     its boresight; the caller subtracts that.
+ *   - radiance, npackets, `included`, the used pairs and the counters of a profile pass are those of
+ *     the plain pass over the same samples, up to the fp64 addition order of radiance.
+ * With S0 = radiance[spectrum] of the same passes the quotients are those of "Pixel moments".
+ *   nxc_los_profile_enable          nv >= 1 allocates and zeroes S*(nv + 2) 16-byte records and S*4
+ *                                   doubles (NXC_ERR_NOMEM when they cannot be had), nv == 0 frees
+ *                                   them; a second enable replaces and zeroes.  NXC_ERR_ARG, before
+ *                                   anything is allocated or freed, for S < 1, nv < 0, v_lo or v_hi
+ *                                   not finite, v_lo >= v_hi (or a width that is not finite),
+ *                                   S*(nv + 2) >= 2^31
+ *   nxc_los_profile_accumulate[_f32], _rows
+ *                                   nxc_los_accumulate[_f32], _rows with the vx and vz columns
+ *                                   (a row store carries them): everything the plain entry returns,
+ *                                   and the pairs' contributions added to the profile.  Sums
+ *                                   accumulate over calls.  NXC_ERR_STATE without an enabled
+ *                                   profile; NXC_ERR_ARG when S is not the enabled one, or vx or vz is
+ *                                   null with P > 0; P == 0 adds nothing
+ *   nxc_los_profile_download        sums[S][nv + 2][2] = {wtemp sum, wtemp*wtemp sum}, record 0 below
+ *                                   the range, 1..nv the bins, nv + 1 above; moments[S][4]
+ * nxc_los_accumulate* never touch the profile, enabled or not. */
+int nxc_los_profile_enable(nxc_handle *h, int64_t S, int64_t nv, double v_lo, double v_hi);
+int nxc_los_profile_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                               int64_t P, const double *x, const double *y, const double *z,
+                               const double *vx, const double *vy, const double *vz,
+                               const double *frac, const int64_t *index, int64_t n_index,
+                               double *radiance, int64_t *npackets, uint8_t *included,
+                               int64_t used_cap, int64_t *used_pairs, int64_t *n_used);
+int nxc_los_profile_accumulate_f32(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                                   int64_t P, const float *x, const float *y, const float *z,
+                                   const float *vx, const float *vy, const float *vz,
+                                   const float *frac, const int64_t *index, int64_t n_index,
+                                   double *radiance, int64_t *npackets, uint8_t *included,
+                                   int64_t used_cap, int64_t *used_pairs, int64_t *n_used);
+int nxc_los_profile_accumulate_rows(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                                    const nxc_rows *r, int64_t first, int64_t count,
+                                    int64_t index_shift, int64_t n_index, double *radiance,
+                                    int64_t *npackets, uint8_t *included, int64_t used_cap,
+                                    int64_t *used_pairs, int64_t *n_used);
+int nxc_los_profile_download(nxc_handle *h, double *sums, double *moments);
+
 /* ---- Source maps: where the packets of fitted Outputs came from ---------------------------------
  * data_simulation/make_source_map.py:11-174 per Output, summed over the Outputs of a result on the
  * device.  Grid: nlon x nlat points at the bin centres point_lon[nlon], point_lat[nlat]; point p =

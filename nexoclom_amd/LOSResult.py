@@ -18,11 +18,17 @@ fit is NOT called by ``simulate_data_from_inputs`` here (the reference calls it 
 explicitly before handing the result to ``LOSResultFitted`` (LOSResultFitted.py).
 ``make_source_map`` restates LOSResult.py:310-458 with make_source_map.py on the GPU (sourcemap.py).
 The PostgreSQL caching of iterations is out of scope.
+
+``profile=(v_lo_kms, v_hi_kms, nbins)`` (an extension; include/nexoclom_hip.h, "Line-of-sight
+profile") adds the line profile of every spectrum -- its radiance per bin of the packets' velocity
+along the boresight -- and the line's shift, width, skewness and effective packet number, from the
+same pass over the samples.  Velocities are in the planet frame: the spacecraft's own velocity is not
+subtracted.
 """
 import numpy as np
 import pandas as pd
 
-from .ModelImage import ModelResult
+from .ModelImage import (ModelResult, cube_from_sums, parse_cube, pixel_moments_from_sums)
 from .catalogue import shared_context
 from .units import Quantity
 
@@ -119,10 +125,24 @@ def los_geometry(data, outeredge, dphi):
     return dist_from_plan, lengths, ladder[:lengths.max()]
 
 
+def parse_profile(profile, n_spectra):
+    """``(v_lo_kms, v_hi_kms, nbins)`` of a ``profile=`` argument, by parse_cube's rules;
+    ValueError also when ``n_spectra`` spectra would have more records than the device addresses
+    (S (nbins + 2) < 2^31)."""
+    try:
+        v_lo, v_hi, nbins = parse_cube(profile)
+    except ValueError as err:
+        raise ValueError(str(err).replace('cube=', 'profile=')) from None
+    if n_spectra*(nbins + 2) >= 2**31:
+        raise ValueError('profile=: len(scdata)*(nbins + 2) must stay below 2^31')
+    return v_lo, v_hi, nbins
+
+
 class LOSResult(ModelResult):
     def __init__(self, scdata, inputs, params=None, dphi=np.radians(1.), *, device=0,
-                 context=None, **kwargs):
+                 context=None, profile=None, **kwargs):
         scdata.set_frame('Model')
+        self._profile = None if profile is None else parse_profile(profile, len(scdata.data))
         super().__init__(inputs, {'quantity': 'radiance'} if params is None else params)
         if self.quantity != 'radiance':
             assert False, 'Other quantities not set up.'      # compute_iteration.py:213
@@ -148,9 +168,10 @@ class LOSResult(ModelResult):
             self._ctx = shared_context(self.inputs, self._device)
         return self._ctx
 
-    def compute_iteration(self, output, scdata, used_cap=0, pairs=None):
+    def compute_iteration(self, output, scdata, used_cap=0, pairs=None, profile=False):
         """One catalogued Output against all spectra (compute_iteration.py:90-240).  ``pairs``: a
-        device pair list (hip_api.PairList) that receives the pairs with weight > 0."""
+        device pair list (hip_api.PairList) that receives the pairs with weight > 0.  ``profile``:
+        the pass also adds to the context's enabled line-of-sight profile."""
         from .Output import Output
         if not isinstance(output, Output):       # a file; a catalogued Output is used as stored:
             output = Output.restore(output)      # the binding widens just the columns it sends
@@ -166,6 +187,10 @@ class LOSResult(ModelResult):
                  float(output.vrplanet)/self.unit_km, self.unit_km*1e5,
                  self.g_tables(float(output.aplanet)), ladder, sc)
         extra = {} if pairs is None else {'pairs': pairs}
+        velocity = ()
+        if profile:                            # the profile's entries, which read vx and vz too
+            extra['profile'] = True
+            velocity = ('vx', 'vz')
         view = output.resident_rows(self.context())
         if view is not None:
             # the Output's rows are still in HBM: no host round trip
@@ -179,7 +204,8 @@ class LOSResult(ModelResult):
             n_index = int(len(output.X0)) if len(output.X0) else int(index.max()) + 1
             res = self.context().los_accumulate(
                 *setup, *(samples[c].values for c in ('x', 'y', 'z', 'vy', 'frac')),
-                index=index, n_index=n_index, used_cap=used_cap, **extra)
+                index=index, n_index=n_index, used_cap=used_cap,
+                **{c: samples[c].values for c in velocity}, **extra)
         assert self.context().counters()['nonfinite'] == 0, 'Non-finite weights'
         res['totalsource'] = output.totalsource
         for key in ('radiance', 'npackets'):
@@ -195,12 +221,24 @@ class LOSResult(ModelResult):
         all-reduce.  ``iterations`` (with their `included` flags) stay those of the local Outputs."""
         if distribute in (True, 'delay', 'delayed'):
             assert False, "Don't do this"
+        if self._profile is not None and cp is not None:
+            raise NotImplementedError('profile= does not support cp=: there is no all-reduce of the '
+                                      'profile yet')
         self.outid, self.outputfiles, self.npackets, self.totalsource = self.inputs.search()
         print(f'LOSResult: {len(self.outid)} output files found.')
         shared = cp is not None and cp.world > 1
         if self.npackets == 0 and not shared:
             raise RuntimeError('No packets found for these Inputs.')
-        self.iterations = [self.compute_iteration(run, scdata) for run in self.inputs._catalogue]
+        if self._profile is not None:
+            # one profile for the whole run: every Output's pass adds to it on the device
+            v_lo, v_hi, nbins = self._profile
+            self.context().los_profile_enable(len(scdata.data), nbins, v_lo/self.unit_km,
+                                              v_hi/self.unit_km)
+        self.iterations = [self.compute_iteration(run, scdata, profile=self._profile is not None)
+                           for run in self.inputs._catalogue]
+        if self._profile is not None:
+            self.profile_sums, self.moment_sums = self.context().los_profile_download()
+            self.context().los_profile_enable(len(scdata.data), 0)
         for it in self.iterations:
             assert len(it['radiance']) == len(scdata.data)
             self.radiance += it['radiance']
@@ -219,7 +257,24 @@ class LOSResult(ModelResult):
                 raise RuntimeError('No packets found for these Inputs.')
         per_second = self.totalsource / self.inputs.options.endtime.value
         self.atoms_per_packet = 1e23 / per_second
+        if self._profile is not None:
+            self._publish_profile(scdata.data.index)
         self.radiance *= self.atoms_per_packet/1e3      # kR
+
+    def _publish_profile(self, rows):
+        """The profile's attributes from ``profile_sums`` and ``moment_sums``: the quotients are
+        those of the pixel moments with S0 the unscaled radiance, the bins get the radiance's
+        scaling; indexed like ``radiance``."""
+        got = dict(pixel_moments_from_sums(np.asarray(self.radiance, dtype=float), self.moment_sums,
+                                           self.unit_km))
+        for name, value in cube_from_sums(self.profile_sums, self.atoms_per_packet/1e3,
+                                          *self._profile[:2]).items():
+            got[name.replace('cube', 'profile')] = value
+        for name, value in got.items():
+            if name not in ('velocity_edges', 'velocity_axis'):
+                value = (pd.Series(value, index=rows) if value.ndim == 1
+                         else pd.DataFrame(value, index=rows))
+            setattr(self, name, value)
 
     def make_mask(self, data):
         """(mask, sigma limit) of the ``masking`` keyword (LOSResult.py:171-200): ';'-separated

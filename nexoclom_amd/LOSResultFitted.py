@@ -58,6 +58,9 @@ def fitted_inputs(inputs):
 
 class LOSResultFitted(LOSResult):
     def __init__(self, scdata, label_for_fitted, params=None, dphi=np.radians(1.), **kwargs):
+        if kwargs.get('profile') is not None:
+            raise NotImplementedError('profile= is not supported by LOSResultFitted: the profile '
+                                      'carries no fitted weights')
         unfit = scdata.model_result[label_for_fitted]
         inputs = fitted_inputs(unfit.inputs)
         if 'context' not in kwargs and getattr(unfit, '_ctx', None) is not None:

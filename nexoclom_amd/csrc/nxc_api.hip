@@ -26,6 +26,7 @@
 #include "../../include/nexoclom_hip.h"
 #include "nxc_camera_check.hpp"
 #include "nxc_cube_check.hpp"
+#include "nxc_los_profile_check.hpp"
 #include "nxc_desc_check.hpp"
 #include "nxc_devbuf.hpp"
 #include "nxc_image_block.hpp"
@@ -456,6 +457,11 @@ struct nxc_handle {
     // LOSResultFitted: the pair list the line-of-sight passes fill (nxc_los_set_pairs); the fit's
     // per-spectrum data, its sample source and per-packet sums (nxc_fit_*)
     nxc_pairs *los_pairs = nullptr;
+    // the line-of-sight profile (nxc_los_profile_enable): there from its enable to the next one
+    bool have_los_prof = false;
+    int64_t los_prof_S = 0;          // spectra it was enabled for
+    CubeK los_profK{};
+    Dev<double> d_los_prof;          // [S][nv + 2] records {w, w w} | [S][4] sums m1 m2 m3 ww
     bool have_fit = false;
     int64_t fit_S = 0, fit_np = -1;  // fit_np: packets whose multipliers are ready (nxc_fit_packets)
     int fit_mode = 0;
@@ -1127,6 +1133,9 @@ int rows_fetch(nxc_handle *h, void *rows_out, bool narrow)
     return NXC_OK;
 }
 
+// records of the handle's line-of-sight profile
+size_t los_profile_records(const nxc_handle *h) { return (size_t)h->los_prof_S * (size_t)(h->los_profK.nv + 2); }
+
 // The pass constants and the LDS blob [header space | g-value tables] of a line-of-sight
 // descriptor (los_run, fit_radiance)
 int los_tables(nxc_handle *h, const nxc_los_desc *d, LosK &K, std::vector<unsigned char> &blob)
@@ -1168,9 +1177,12 @@ int los_tables(nxc_handle *h, const nxc_los_desc *d, LosK &K, std::vector<unsign
 }
 
 // f-1 over stored samples that are already on the device (64-bit, or 32-bit as save() keeps them)
-template <typename T, typename I>
+// PROFILE: the pass of nxc_los_profile_accumulate*, which also adds to the handle's line-of-sight
+// profile (dvx, dvz: the two columns only it reads); the plain pass launches what it always did
+template <bool PROFILE, typename T, typename I>
 int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, int64_t P,
-            const T *dx, const T *dy, const T *dz, const T *dvy, const T *dfrac, const I *d_index,
+            const T *dx, const T *dy, const T *dz, const T *dvy, const T *dfrac, const T *dvx,
+            const T *dvz, const I *d_index,
             int64_t index_shift, int64_t n_index, double *radiance, int64_t *npackets, uint8_t *included,
             int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
 {
@@ -1226,7 +1238,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
     HIPCHK(hipMemsetAsync(base + o_nu, 0, 8, st));
     HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), st));
     if (P > 0) {
-        if ((rc = prep_kernel(k_los<T, I>, lds))) return rc;
+        if ((rc = prep_kernel(k_los<T, I, PROFILE>, lds))) return rc;
         const int tiles = (int)((S + K.tile_cap - 1) / K.tile_cap);
         constexpr int WPG = NXC_LOS_THREADS / 64;                  // waves per workgroup of k_los
         // the samples go through in slabs: the block scratch is sized for the worst case of one
@@ -1251,9 +1263,17 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
         size_t lds_pairs = ((stage_bytes + 31) & ~size_t(31)) + (size_t)((d->n_ladder + 3) & ~int64_t(3)) * 8;
         if (lds_pairs > 160 * 1024) return fail(NXC_ERR_ARG, "the ladder of ball centres exceeds the LDS");
         // the per-spectrum sums of a workgroup in LDS when they leave room for two workgroups per CU
-        const int lds_sums = lds_pairs + (size_t)S * 16 <= 80 * 1024 ? 1 : 0;
-        if (lds_sums) lds_pairs += (size_t)S * 16;
-        if ((rc = prep_kernel(k_los_pairs<T, I>, lds_pairs))) return rc;
+        // (a profile pass: radiance, count and the four moment sums)
+        const size_t sums_bytes = (size_t)S * (PROFILE ? 48 : 16);
+        const int lds_sums = lds_pairs + sums_bytes <= 80 * 1024 ? 1 : 0;
+        if (lds_sums) lds_pairs += sums_bytes;
+        if ((rc = prep_kernel(k_los_pairs<T, I, PROFILE>, lds_pairs))) return rc;
+        LosProf<T, PROFILE> prof{};
+        if constexpr (PROFILE) {
+            prof.bins = h->los_profK;
+            prof.rec = h->d_los_prof;
+            prof.mom = h->d_los_prof + los_profile_records(h) * 2;
+        }
         unsigned *pair_used = reinterpret_cast<unsigned *>(h->d_losblk + o_n + 8);
         unsigned *pair_fill = reinterpret_cast<unsigned *>(h->d_losblk + o_fill);
         unsigned long long *pair_list = reinterpret_cast<unsigned long long *>(h->d_losblk + o_list);
@@ -1265,6 +1285,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
             const int64_t n = std::min<int64_t>(slab, P - first);
             const int64_t regions = (n + NXC_LOS_FORM - 1) / NXC_LOS_FORM;
             K.row_base = first;
+            if constexpr (PROFILE) { prof.vx = dvx + first; prof.vz = dvz + first; }
             HIPCHK(hipMemsetAsync(n_slots, 0, 256 + (size_t)pair_cap * 4, st));   // counters + chunk fills
             hipLaunchKernelGGL((k_los_blocks<T, I>),
                                dim3((unsigned)((regions + NXC_LOS_BLOCKS_THREADS / 64 - 1) /
@@ -1274,7 +1295,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
             HIPCHK(hipGetLastError());
             // persistent waves, one workgroup per CU (its LDS holds all the spectra of a tile)
             const int64_t groups = std::max<int64_t>(1, std::min<int64_t>(h->n_cu, (n / 8 / 64 + WPG) / WPG));
-            hipLaunchKernelGGL((k_los<T, I>), dim3((unsigned)groups, tiles),
+            hipLaunchKernelGGL((k_los<T, I, PROFILE>), dim3((unsigned)groups, tiles),
                                dim3(NXC_LOS_THREADS), lds, st, K, base + o_blob,
                                (int64_t)stage_bytes, S, reinterpret_cast<const double *>(base + o_sc),
                                n_slots, bdesc, bsph, pair_list, pair_fill, pair_used, pair_chunks,
@@ -1284,9 +1305,9 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
                                reinterpret_cast<double *>(base + o_rad),
                                reinterpret_cast<unsigned long long *>(base + o_np),
                                included ? base + o_inc : nullptr, cap_used, d_used,
-                               reinterpret_cast<unsigned long long *>(base + o_nu), h->d_ctr);
+                               reinterpret_cast<unsigned long long *>(base + o_nu), h->d_ctr, prof);
             HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL((k_los_pairs<T, I>), dim3((unsigned)(h->n_cu * 2)), dim3(NXC_BLOCK),
+            hipLaunchKernelGGL((k_los_pairs<T, I, PROFILE>), dim3((unsigned)(h->n_cu * 2)), dim3(NXC_BLOCK),
                                lds_pairs, st, K, base + o_blob, (int64_t)stage_bytes, S,
                                reinterpret_cast<const double *>(base + o_sc), pair_list, pair_fill,
                                pair_used, pair_chunks, lds_sums, dx + first, dy + first, dz + first,
@@ -1295,7 +1316,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
                                reinterpret_cast<double *>(base + o_rad),
                                reinterpret_cast<unsigned long long *>(base + o_np),
                                included ? base + o_inc : nullptr, cap_used, d_used,
-                               reinterpret_cast<unsigned long long *>(base + o_nu), h->d_ctr);
+                               reinterpret_cast<unsigned long long *>(base + o_nu), h->d_ctr, prof);
             HIPCHK(hipGetLastError());
         }
         if ((rc = end_timed(h))) return rc;
@@ -1338,33 +1359,88 @@ int los_check(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
 }
 
 // ... over a sample view
+template <bool PROFILE>
 int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, const Samples &s,
             int64_t n_index, double *radiance, int64_t *npackets, uint8_t *included, int64_t used_cap,
             int64_t *used_pairs, int64_t *n_used)
 {
     return with_sample_types(s, [&](auto t, auto i) {
         using T = decltype(t);
-        return los_run(h, d, S, sc, s.n, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3), s.col<T>(4),
-                       s.idx<decltype(i)>(), s.shift, n_index, radiance, npackets, included, used_cap,
-                       used_pairs, n_used);
+        return los_run<PROFILE>(h, d, S, sc, s.n, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3),
+                                s.col<T>(4), s.col<T>(5), s.col<T>(6), s.idx<decltype(i)>(), s.shift,
+                                n_index, radiance, npackets, included, used_cap, used_pairs, n_used);
     });
 }
 
-// ... over samples in host memory: five columns (+ the index column) go to the device first
-template <typename T>
-int los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, int64_t P,
-                   const T *x, const T *y, const T *z, const T *vy, const T *frac,
-                   const int64_t *index, int64_t n_index, double *radiance, int64_t *npackets,
-                   uint8_t *included, int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
+// What a profile entry checks in front of the plain entry's own checks
+int los_profile_check(const nxc_handle *h, int64_t S)
 {
-    int rc = los_check(h, d, S, sc, P, radiance, npackets, included, n_index, used_cap, used_pairs,
-                       n_used);
+    if (!h) return fail(NXC_ERR_ARG, "bad arguments");
+    if (!h->have_los_prof) return fail(NXC_ERR_STATE, "nxc_los_profile_enable has not been called");
+    if (S != h->los_prof_S)
+        return fail(NXC_ERR_ARG, "the profile was enabled for " + std::to_string(h->los_prof_S) +
+                                     " spectra, this call has " + std::to_string(S));
+    return NXC_OK;
+}
+
+// ... over samples in host memory: five columns, seven for a profile pass (+ the index column) go
+// to the device first
+template <bool PROFILE, typename T>
+int los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, int64_t P,
+                   const T *x, const T *y, const T *z, const T *vx, const T *vy, const T *vz,
+                   const T *frac, const int64_t *index, int64_t n_index, double *radiance,
+                   int64_t *npackets, uint8_t *included, int64_t used_cap, int64_t *used_pairs,
+                   int64_t *n_used)
+{
+    int rc = PROFILE ? los_profile_check(h, S) : NXC_OK;
+    if (rc) return rc;
+    rc = los_check(h, d, S, sc, P, radiance, npackets, included, n_index, used_cap, used_pairs, n_used);
     if (rc) return rc;
     if (P && (!x || !y || !z || !vy || !frac)) return fail(NXC_ERR_ARG, "bad arguments");
-    const T *cols[N_SAMPLE_COLS] = {x, y, z, vy, frac, nullptr, nullptr};
+    if (PROFILE && P && (!vx || !vz)) return fail(NXC_ERR_ARG, "bad arguments");
+    const T *cols[N_SAMPLE_COLS] = {x, y, z, vy, frac, vx, vz};
     Samples s;
     if ((rc = samples_upload(h, h->d_samples, P, cols, index, &s))) return rc;
-    return los_run(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs, n_used);
+    return los_run<PROFILE>(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs,
+                            n_used);
+}
+
+// nxc_los_profile_enable: S (nv + 2) zeroed records and S x 4 moment sums in one block, or none; the
+// arguments are checked (check_los_profile_args) before the profile there is is touched
+int los_profile_enable(nxc_handle *h, int64_t S, int64_t nv, double v_lo, double v_hi)
+{
+    if (!h) return fail(NXC_ERR_ARG, "bad arguments");
+    if (nv != 0) {
+        const std::string why = check_los_profile_args(S, nv, v_lo, v_hi);
+        if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
+    }
+    HIPCHK(hipSetDevice(h->device));
+    h->have_los_prof = false;
+    int rc = h->d_los_prof.release();
+    if (rc || nv == 0) return rc;
+    h->los_prof_S = S;
+    h->los_profK = CubeK{(int)nv, v_lo, cube_inv_dv(nv, v_lo, v_hi)};
+    const size_t bytes = (los_profile_records(h) * 2 + (size_t)S * 4) * sizeof(double);
+    if ((rc = h->d_los_prof.ensure(bytes))) return rc;
+    HIPCHK(hipMemsetAsync(h->d_los_prof, 0, bytes, h->stream));
+    HIPCHK(stream_sync(h));
+    h->have_los_prof = true;
+    return NXC_OK;
+}
+
+// nxc_los_profile_download: sums[S][nv + 2][2] and moments[S][4], the device's own order
+int los_profile_download(nxc_handle *h, double *sums, double *moments)
+{
+    if (!h) return fail(NXC_ERR_ARG, "bad arguments");
+    if (!h->have_los_prof) return fail(NXC_ERR_STATE, "nxc_los_profile_enable has not been called");
+    if (!sums || !moments) return fail(NXC_ERR_ARG, "bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t n_rec = los_profile_records(h) * 2;
+    HIPCHK(hipMemcpyAsync(sums, h->d_los_prof, n_rec * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(moments, h->d_los_prof + n_rec, (size_t)h->los_prof_S * 4 * sizeof(double),
+                          hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
 }
 
 // The plan of the tiled image for this handle's image and mode (nxc_tile_plan.hpp).
@@ -3083,7 +3159,27 @@ int nxc_los_accumulate_rows(nxc_handle *h, const nxc_los_desc *d, int64_t S, con
     if (rc) return rc;
     Samples s;
     if ((rc = samples_from_rows(h, r, first, count, index_shift, &s))) return rc;
-    return los_run(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs, n_used);
+    return los_run<false>(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs,
+                          n_used);
+    });
+}
+
+int nxc_los_profile_accumulate_rows(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                                    const nxc_rows *r, int64_t first, int64_t count,
+                                    int64_t index_shift, int64_t n_index, double *radiance,
+                                    int64_t *npackets, uint8_t *included, int64_t used_cap,
+                                    int64_t *used_pairs, int64_t *n_used)
+{
+    return guarded([&]() -> int {
+    int rc = los_profile_check(h, S);
+    if (rc) return rc;
+    rc = los_check(h, d, S, sc, count, radiance, npackets, included, n_index, used_cap, used_pairs,
+                   n_used);
+    if (rc) return rc;
+    Samples s;
+    if ((rc = samples_from_rows(h, r, first, count, index_shift, &s))) return rc;
+    return los_run<true>(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs,
+                         n_used);
     });
 }
 
@@ -4009,8 +4105,9 @@ int nxc_los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const do
                        int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
 {
     return guarded([&]() -> int {
-        return los_accumulate(h, d, S, sc, P, x, y, z, vy, frac, index, n_index, radiance, npackets,
-                              included, used_cap, used_pairs, n_used);
+        return los_accumulate<false>(h, d, S, sc, P, x, y, z, decltype(x)(nullptr), vy,
+                                     decltype(x)(nullptr), frac, index, n_index, radiance, npackets,
+                                     included, used_cap, used_pairs, n_used);
     });
 }
 
@@ -4021,9 +4118,46 @@ int nxc_los_accumulate_f32(nxc_handle *h, const nxc_los_desc *d, int64_t S, cons
                            int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
 {
     return guarded([&]() -> int {
-        return los_accumulate(h, d, S, sc, P, x, y, z, vy, frac, index, n_index, radiance, npackets,
-                              included, used_cap, used_pairs, n_used);
+        return los_accumulate<false>(h, d, S, sc, P, x, y, z, decltype(x)(nullptr), vy,
+                                     decltype(x)(nullptr), frac, index, n_index, radiance, npackets,
+                                     included, used_cap, used_pairs, n_used);
     });
+}
+
+int nxc_los_profile_enable(nxc_handle *h, int64_t S, int64_t nv, double v_lo, double v_hi)
+{
+    return guarded([&]() -> int { return los_profile_enable(h, S, nv, v_lo, v_hi); });
+}
+
+int nxc_los_profile_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                               int64_t P, const double *x, const double *y, const double *z,
+                               const double *vx, const double *vy, const double *vz,
+                               const double *frac, const int64_t *index, int64_t n_index,
+                               double *radiance, int64_t *npackets, uint8_t *included,
+                               int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
+{
+    return guarded([&]() -> int {
+        return los_accumulate<true>(h, d, S, sc, P, x, y, z, vx, vy, vz, frac, index, n_index, radiance,
+                                    npackets, included, used_cap, used_pairs, n_used);
+    });
+}
+
+int nxc_los_profile_accumulate_f32(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                                   int64_t P, const float *x, const float *y, const float *z,
+                                   const float *vx, const float *vy, const float *vz,
+                                   const float *frac, const int64_t *index, int64_t n_index,
+                                   double *radiance, int64_t *npackets, uint8_t *included,
+                                   int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
+{
+    return guarded([&]() -> int {
+        return los_accumulate<true>(h, d, S, sc, P, x, y, z, vx, vy, vz, frac, index, n_index, radiance,
+                                    npackets, included, used_cap, used_pairs, n_used);
+    });
+}
+
+int nxc_los_profile_download(nxc_handle *h, double *sums, double *moments)
+{
+    return guarded([&]() -> int { return los_profile_download(h, sums, moments); });
 }
 
 // ---- RCCL -------------------------------------------------------------------------------------

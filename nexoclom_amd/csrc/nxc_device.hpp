@@ -1198,6 +1198,18 @@ NXC_DEV void pixel_cube_add(const CubeK &Q, bool ok, int pix, double w, double v
     add_record_pairs(has, pix * (Q.nv + 2) + k, w, w * w, cube2);
 }
 
+// The same rule on its own, for the line-of-sight profile (k_los_pairs, k_los), which files a pair
+// under spectrum (nv + 2) + k with per-lane atomics.  (pixel_cube_add keeps its own copy: taken
+// from here its kernels compile to another instruction order.)
+NXC_DEV int cube_plane(const CubeK &Q, double vlos)
+{
+    const double t = (vlos - Q.v_lo) * Q.inv_dv;
+    int k = Q.nv + 1;
+    if (t < 0.0) k = 0;
+    else if (t < (double)Q.nv) k = 1 + (int)t;
+    return k;
+}
+
 // Per-wave compaction queue between image_locate and image_weight: a ring of 128 located samples
 // {pixel, radial velocity, masked fraction} in LDS.  push() appends the lanes' samples in lane
 // order (ballot + prefix rank); once 64 are waiting, pop() hands one to every lane.  All calls

@@ -59,7 +59,9 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_camera_cube_accumulate_rows', 'nxc_camera_cube_download',
            'nxc_density_spectrum_enable', 'nxc_density_spectrum_accumulate',
            'nxc_density_spectrum_accumulate_f32', 'nxc_density_spectrum_accumulate_rows',
-           'nxc_density_spectrum_download')
+           'nxc_density_spectrum_download',
+           'nxc_los_profile_enable', 'nxc_los_profile_accumulate', 'nxc_los_profile_accumulate_f32',
+           'nxc_los_profile_accumulate_rows', 'nxc_los_profile_download')
 ABI_VERSION = 3
 
 
@@ -848,25 +850,48 @@ class Context:
     # -- f-1: spacecraft lines of sight ------------------------------------------------------
     def los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables,
                        ladder, sc, x=None, y=None, z=None, vy=None, frac=None, index=None,
-                       n_index=0, used_cap=0, rows=None, pairs=None):
+                       n_index=0, used_cap=0, rows=None, pairs=None, vx=None, vz=None,
+                       profile=False):
         """sc: (8, S) array x,y,z,xbore,ybore,zbore,dist_from_plan,ladder_len.  Samples: five host
         columns (+ index), or ``rows = (RowStore, first, count, index_shift)`` for rows that are
         already in HBM.  Returns dict(radiance, npackets, included|None, used (2, m)|None,
         n_used).  ``pairs``: a PairList that receives the used pairs on the device instead of
-        ``used`` (HipError with code NXC_ERR_OVERFLOW when they do not fit)."""
+        ``used`` (HipError with code NXC_ERR_OVERFLOW when they do not fit).  ``profile``: the
+        pass also adds to the profile of ``los_profile_enable``; host columns then come with
+        ``vx`` and ``vz`` (a row store carries them)."""
+        if profile and rows is None and (vx is None or vz is None):
+            raise ValueError('profile=True over host columns needs vx and vz')
+        velocity = (vx, vz) if profile else None
         if pairs is None:
             return self._los_accumulate(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet,
                                         unit_cm, g_tables, ladder, sc, x, y, z, vy, frac, index,
-                                        n_index, used_cap, rows)
+                                        n_index, used_cap, rows, velocity)
         if used_cap:
             raise ValueError('used_cap and pairs exclude each other')
         self._check(self.lib.nxc_los_set_pairs(self._h, pairs._p))
         try:
             return self._los_accumulate(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet,
                                         unit_cm, g_tables, ladder, sc, x, y, z, vy, frac, index,
-                                        n_index, 0, rows)
+                                        n_index, 0, rows, velocity)
         finally:
             self.lib.nxc_los_set_pairs(self._h, None)
+
+    def los_profile_enable(self, S, nv, v_lo=0.0, v_hi=0.0):
+        """Allocate and zero the line-of-sight profile of ``S`` spectra: ``nv`` bins over
+        [v_lo, v_hi) [R/s] and four moment sums per spectrum (``nv`` 0 frees it; a second enable
+        replaces and zeroes it)."""
+        self._check(self.lib.nxc_los_profile_enable(self._h, C.c_int64(int(S)), C.c_int64(int(nv)),
+                                                    C.c_double(v_lo), C.c_double(v_hi)))
+        self._los_profile_shape = (int(S), int(nv)) if int(nv) else None
+
+    def los_profile_download(self):
+        """(sums (S, nv + 2, 2), moments (S, 4)) float64: {sum w, sum w w} per spectrum and
+        record -- record 0 below the range, 1..nv the bins, nv + 1 at or above it (or not a
+        number) -- and the sums m1 m2 m3 ww (PIXEL_MOMENT_COLUMNS) of every spectrum."""
+        S, nv = getattr(self, '_los_profile_shape', None) or (0, 0)
+        sums, moments = np.zeros((S, nv + 2, 2)), np.zeros((S, 4))
+        self._check(self.lib.nxc_los_profile_download(self._h, _p(sums), _p(moments)))
+        return sums, moments
 
     @staticmethod
     def _los_desc(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables, ladder):
@@ -882,7 +907,10 @@ class Context:
         return d, keep
 
     def _los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm,
-                        g_tables, ladder, sc, x, y, z, vy, frac, index, n_index, used_cap, rows):
+                        g_tables, ladder, sc, x, y, z, vy, frac, index, n_index, used_cap, rows,
+                        velocity=None):
+        """``velocity``: None for the plain entries, (vx, vz) for the profile's."""
+        name = 'nxc_los_accumulate' if velocity is None else 'nxc_los_profile_accumulate'
         d, keep = self._los_desc(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm,
                                  g_tables, ladder)
         sc = _f64(sc)
@@ -890,12 +918,13 @@ class Context:
         i64p = C.POINTER(C.c_int64)
         if rows is not None:
             store, first, count, shift = rows
-            entry = self.lib.nxc_los_accumulate_rows
+            entry = getattr(self.lib, name + '_rows')
             samples = (self._rows_handle(store), C.c_int64(first), C.c_int64(count), C.c_int64(shift))
         else:
-            suffix, ptrs, cols = self._columns((x, y, z, vy, frac))
+            suffix, ptrs, cols = self._columns((x, y, z, vy, frac) if velocity is None else
+                                               (x, y, z, velocity[0], vy, velocity[1], frac))
             idx = None if index is None else np.ascontiguousarray(index, dtype=np.int64)
-            entry = getattr(self.lib, 'nxc_los_accumulate' + suffix)
+            entry = getattr(self.lib, name + suffix)
             samples = (C.c_int64(len(cols[0])), *ptrs,
                        idx.ctypes.data_as(i64p) if idx is not None else None)
         radiance = np.zeros(S)
