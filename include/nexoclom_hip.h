@@ -873,6 +873,77 @@ int nxc_camera_cube_accumulate_f32(nxc_handle *h, int64_t p, const float *x, con
 int nxc_camera_cube_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
 int nxc_camera_cube_download(nxc_handle *h, double *sums);
 
+/* ---- ShellMap: density on spherical shells and zenith column per local time ------------------------
+ * EXTENSION -- the reference has nothing like it.  Every stored sample is binned into cells of
+ * solar-fixed longitude x sin(latitude) x altitude around the planet's centre.  Samples are x, y, z
+ * [R], vy [R/s], frac in the model frame, as nxc_image_accumulate reads them.  The grid: nlon
+ * longitude bins with lon_edges[nlon + 1] = np.linspace(0, 2 pi, nlon + 1), nlat latitude bands with
+ * mu_edges[nlat + 1] = np.linspace(-1, 1, nlat + 1) (uniform in sin(latitude): every cell has the
+ * solid angle dlon dmu), and nalt >= 1 altitude bins over [r_lo, r_hi) in planet radii from the
+ * centre; the host forms inv_dr = nalt / (r_hi - r_lo) once in fp64.  Per sample, fp64, one rounding
+ * per operation, no contraction, in this order:
+ *   1. radvel = vy + vrplanet;  r2 = (x*x + y*y) + z*z;  r = sqrt(r2);  mu = z / r
+ *   2. lon = atan2(x, -y);  if lon < 0: lon = lon + 2 pi (the double nearest 2 pi, lon_edges[nlon]).
+ *      The package's solar-fixed longitude: 0 at the sub-solar point, pi/2 at dusk
+ *   3. ix, iz = the bins of lon in lon_edges and of mu in mu_edges as np.histogram2d takes them
+ *      (searchsorted(edges, ., 'right') - 1, the last edge inclusive, NaN outside);  cell =
+ *      ix * nlat + iz.  A sample outside either axis (r = 0 makes mu a NaN) is not binned; it counts
+ *      in `nonfinite` iff frac is not finite or radvel is NaN, as outside a ModelImage frame
+ *   4. f = frac;  quantity 1: f = f * 0 unless (x*x + z*z > 1 + 2^-52) || (y < 0)  (sunlit, as
+ *      nxc_image_*).  Nothing occults: there is no observer
+ *   5. w = f (quantity 0) or (f * sum_l interp(radvel, line_v[l], line_g[l])) / 1e6 (quantity 1; the
+ *      sum starts with line 0 and adds the others in order); w not finite or radvel NaN:
+ *      `nonfinite`, dropped
+ *   6. c = w / r2;  c not finite: `nonfinite`, dropped
+ *   7. column[cell] += c, packets[cell] += 1
+ *   8. if w != 0:  t = (r - r_lo) * inv_dr;  k = 0 if t < 0,  1 + (int)t if 0 <= t < nalt,  nalt + 1
+ *      otherwise (the velocity cube's rule with r in the velocity's place);  {w, w*w} is added to
+ *      record cell * (nalt + 2) + k of plane A and {c, c*c} to the same record of plane B
+ * (sqrt and / are IEEE-754 correctly rounded.)  lon is the only transcendental value: it decides a
+ * bin and enters no sum, so only its bin is part of the definition, for samples whose lon is not
+ * within rounding of an edge.  Three atomic requests per binned sample at most; the order of addition
+ * is not fixed.  Plane A over a shell's volume is the number density, plane B and column over the
+ * cell's solid angle the zenith column: sum_k B[cell][k] = column[cell] up to the order of addition.
+ * The shell map owns its device buffers: nxc_set_image / nxc_camera_set and their entries never touch
+ * them, nor the calls below theirs.  Counters (nxc_counters_get) of an accumulate call: samples,
+ * samples_binned (step 7 reached), nonfinite.
+ *   nxc_shell_set               checks the description (NXC_ERR_ARG: nlon or nlat outside 1..8192,
+ *                               nalt < 1, r_lo or r_hi not finite, r_lo < 1, r_lo >= r_hi,
+ *                               nlon*nlat*(nalt + 2) >= 2^31 records, edges null / not finite / not
+ *                               increasing / not spanning [0, 2 pi] and [-1, 1], vrplanet not finite,
+ *                               quantity not 0 or 1, n_lines outside 0..NXC_MAX_LINES, null tables,
+ *                               tables + edges beyond the 160 KiB of LDS), copies the tables to the
+ *                               device and zeroes the resident sums (NXC_ERR_NOMEM when they cannot be
+ *                               had)
+ *   nxc_shell_accumulate[_f32]  adds p samples held on the host (float32 ones are widened exactly)
+ *   nxc_shell_accumulate_rows   adds rows [first, first + count) of a row store
+ *   nxc_shell_download          column[nlon*nlat], counts[nlon*nlat], sums[2][nlon*nlat][nalt + 2][2]
+ *                               = plane A, plane B, record 0 below r_lo, 1..nalt the bins, nalt + 1 at
+ *                               or above r_hi (each nullable)
+ * NXC_ERR_STATE before nxc_shell_set; NXC_ERR_ARG for p < 0 or a null column with p > 0; p = 0 adds
+ * nothing but still zeroes the counters. */
+typedef struct nxc_shell_desc {
+    double vrplanet;        /* R/s, added to vy for the g-value lookup                          */
+    double r_lo, r_hi;      /* altitude range in R from the centre, 1 <= r_lo < r_hi            */
+    int32_t quantity;       /* 0 = column (w = frac), 1 = radiance                              */
+    int32_t n_lines;        /* g-value tables summed for radiance (<= NXC_MAX_LINES)            */
+    int64_t nlon, nlat;     /* bins in longitude and in sin(latitude), 1..8192                  */
+    int64_t nalt;           /* altitude bins, >= 1                                              */
+    const double *lon_edges; /* nlon + 1: np.linspace(0, 2 pi, nlon + 1)                        */
+    const double *mu_edges;  /* nlat + 1: np.linspace(-1, 1, nlat + 1)                          */
+    int64_t line_n[NXC_MAX_LINES];
+    const double *line_v[NXC_MAX_LINES]; /* R/s ascending                                       */
+    const double *line_g[NXC_MAX_LINES]; /* 1/s                                                 */
+} nxc_shell_desc;
+
+int nxc_shell_set(nxc_handle *h, const nxc_shell_desc *d);
+int nxc_shell_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                         const double *z, const double *vy, const double *frac);
+int nxc_shell_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                             const float *z, const float *vy, const float *frac);
+int nxc_shell_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_shell_download(nxc_handle *h, double *column, uint64_t *counts, double *sums);
+
 /* ---- Line-of-sight profile: radiance per Doppler bin along each line of sight ----------------------
  * EXTENSION -- nxc_los_accumulate gives one radiance per spectrum; the profile keeps the line: per
  * spectrum nv >= 1 bins over [v_lo, v_hi), in the rows' velocity unit (planet radii per second), and

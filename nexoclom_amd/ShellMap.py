@@ -1,0 +1,232 @@
+"""ShellMap: the cloud in planet-facing coordinates -- density on spherical shells and the zenith
+column per local time and latitude, accumulated on the GPU.
+
+An extension beyond the reference, whose products all look at the cloud from outside.
+``ShellMap(inputs, params)`` bins every stored sample of the catalogued Outputs into cells of
+solar-fixed longitude (local time) x sin(latitude) x altitude around the planet's centre, in one
+pass over the rows.  The longitude is the package's: 0 at the sub-solar point (noon), pi/2 at dusk,
+the convention of the source maps and the sticking maps.  Latitude bands are uniform in
+sin(latitude), so every cell has the same solid angle.  include/nexoclom_hip.h ("ShellMap") holds
+the definition operation by operation; the HIP kernel is k_shell.
+
+``params`` (a dict or a ``key = value`` file, like ModelImage's):
+
+    quantity     'column' or 'radiance'
+    dims         'nlon,nlat'      default '72,36'
+    altitude     'lo,hi,nbins'    planet radii above the surface, 0 <= lo < hi (required)
+    g / wavelength                as ModelResult
+
+Attributes: longitude, local_time (hours; 12 at longitude 0, 18 at pi/2), latitude (asin of the
+band centres, rad), lon_edges, mu_edges, altitude_edges, altitude_axis (planet radii above the
+surface; altitude_edges_km, altitude_axis_km), solid_angle (sr per cell), column (nlon, nlat: the zenith column
+atoms_per_packet sum w/r^2 / (solid_angle R_cm^2) -- atoms/cm^2, or the zenith radiance in
+ModelImage's units), packets, density (nlon, nlat, nalt: atoms_per_packet sum w / V_k with V_k =
+solid_angle (r_{k+1}^3 - r_k^3)/3 R_cm^3 -- atoms/cm^3, or the radiance per cm of path),
+column_profile (the zenith column per shell) with column_below and column_above
+(column_profile.sum(-1) + column_below + column_above is column), density_effective_packets and
+column_effective_packets ((sum a)^2 / sum a^2 per cell and shell, 0 where a shell is empty),
+shell_sums (the unscaled download), totalsource, atoms_per_packet, sourcerate, counters.
+
+Not supported, and refused: streaming (``npackets=``), shared runs (``cp=`` / ``shard=``).
+"""
+import numpy as np
+
+from .ModelImage import ModelResult
+from .catalogue import sample_spans, shared_context
+from .input_classes import InputError
+from .units import Quantity
+
+MAX_DIM = 8192
+UNSUPPORTED = {
+    'npackets': 'streaming (npackets=) is not supported: run the inputs first (Input.run)',
+    'cp': 'shared runs (cp=) are not supported by ShellMap',
+    'shard': 'shards are not supported by ShellMap',
+    'reduce': 'shared runs (cp=) are not supported by ShellMap',
+}
+
+
+def parse_dims(text):
+    """``'nlon,nlat'`` as two ints in 1..8192."""
+    try:
+        dims = [int(v) for v in str(text).split(',')]
+    except ValueError:
+        dims = []
+    if len(dims) != 2:
+        raise InputError('ShellMap.__init__', "dims must be two integers 'nlon,nlat'")
+    if not all(1 <= d <= MAX_DIM for d in dims):
+        raise InputError('ShellMap.__init__', f'dims must be 1..{MAX_DIM}')
+    return dims
+
+
+def parse_altitude(text):
+    """``'lo,hi,nbins'`` [planet radii above the surface] as (float, float, int)."""
+    parts = str(text).split(',')
+    try:
+        lo, hi = float(parts[0]), float(parts[1])
+        nbins = int(parts[2])
+    except (ValueError, IndexError):
+        parts = []
+    if len(parts) != 3:
+        raise InputError('ShellMap.__init__',
+                         "altitude must be 'lo,hi,nbins' (two numbers and an integer)")
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise InputError('ShellMap.__init__', 'altitude: lo and hi must be finite')
+    if not 0.0 <= lo < hi:
+        raise InputError('ShellMap.__init__', 'altitude: 0 <= lo < hi is required')
+    if nbins < 1:
+        raise InputError('ShellMap.__init__', 'altitude: nbins must be at least 1')
+    return lo, hi, nbins
+
+
+def shell_axes(nlon, nlat, alt_lo, alt_hi, nalt):
+    """The grid of a shell map: a dict of lon_edges, mu_edges, r_edges [R from the centre] and what
+    follows from them (longitude, local_time, latitude, solid_angle, shell volumes in R^3)."""
+    lon_edges = np.linspace(0, 2*np.pi, nlon + 1)
+    mu_edges = np.linspace(-1, 1, nlat + 1)
+    r_lo, r_hi = 1.0 + alt_lo, 1.0 + alt_hi
+    r_edges = r_lo + np.arange(nalt + 1)*(r_hi - r_lo)/nalt
+    r_edges[-1] = r_hi
+    longitude = 0.5*(lon_edges[:-1] + lon_edges[1:])
+    solid_angle = (2*np.pi/nlon)*(2.0/nlat)
+    return {'lon_edges': lon_edges, 'mu_edges': mu_edges, 'r_edges': r_edges,
+            'longitude': longitude,
+            'local_time': (12.0 + longitude*12.0/np.pi) % 24.0,
+            'latitude': np.arcsin(0.5*(mu_edges[:-1] + mu_edges[1:])),
+            'solid_angle': solid_angle,
+            'volume': solid_angle*(r_edges[1:]**3 - r_edges[:-1]**3)/3}
+
+
+def _effective(S, ww):
+    filled = ww != 0
+    return np.where(filled, S*S/np.where(filled, ww, 1.0), 0.0)
+
+
+def shell_from_sums(column_sum, shell_sums, atoms_per_packet, solid_angle, volume, R_cm):
+    """What a shell map publishes, from ``column_sum`` (nlon, nlat) = sum w/r^2 and ``shell_sums``
+    (2, nlon, nlat, nalt + 2, 2) = {sum w, sum w w} and {sum c, sum c c}, c = w/r^2, per cell and
+    altitude record (record 0 below the range, 1..nalt the bins, nalt + 1 at or above it);
+    ``volume`` (nalt) in R^3, ``R_cm`` the planet's radius."""
+    shell_sums = np.asarray(shell_sums, dtype=float)
+    A, B = shell_sums[0], shell_sums[1]
+    per_area = atoms_per_packet/(solid_angle*R_cm**2)
+    return {'column': np.asarray(column_sum, dtype=float)*per_area,
+            'density': A[..., 1:-1, 0]*atoms_per_packet/(np.asarray(volume)*R_cm**3),
+            'column_profile': B[..., 1:-1, 0]*per_area,
+            'column_below': B[..., 0, 0]*per_area,
+            'column_above': B[..., -1, 0]*per_area,
+            'density_effective_packets': _effective(A[..., 1:-1, 0], A[..., 1:-1, 1]),
+            'column_effective_packets': _effective(B[..., 1:-1, 0], B[..., 1:-1, 1])}
+
+
+class ShellMap(ModelResult):
+    def __init__(self, inputs, params, *, context=None, device=0, **unsupported):
+        for key in unsupported:
+            if key in UNSUPPORTED:
+                raise NotImplementedError(UNSUPPORTED[key])
+            raise TypeError(f'ShellMap() got an unexpected keyword argument {key!r}')
+        super().__init__(inputs, params)
+        self.type = 'shell map'
+        if self.quantity not in ('column', 'radiance'):
+            raise InputError('ShellMap.__init__', "quantity must be 'column' or 'radiance'")
+        self._frame()
+        self._column_sum = np.zeros(self.dims)
+        self.packets = np.zeros(self.dims)
+        self.shell_sums = np.zeros((2,) + tuple(self.dims) + (self.altitude[2] + 2, 2))
+        self._ctx, self._device = context, device
+        self.counters = {}
+        self._from_catalogue()
+        self.finalize()
+
+    def _frame(self):
+        get = self.params.get
+        if get('origin', None) not in (None, self.inputs.geometry.planet):
+            raise NotImplementedError('moon-centred shells are out of scope')
+        self.dims = parse_dims(get('dims', '72,36'))
+        if 'altitude' not in self.params:
+            raise InputError('ShellMap.__init__',
+                             "params need altitude = 'lo,hi,nbins' [planet radii above the surface]")
+        self.altitude = parse_altitude(get('altitude'))
+        if self.dims[0]*self.dims[1]*(self.altitude[2] + 2) >= 2**31:
+            raise InputError('ShellMap.__init__',
+                             'nlon*nlat*(nbins + 2) must stay below 2^31 records')
+        axes = shell_axes(*self.dims, *self.altitude)
+        for name in ('lon_edges', 'mu_edges', 'longitude', 'local_time', 'latitude', 'solid_angle'):
+            setattr(self, name, axes[name])
+        self.r_edges = axes['r_edges']
+        self._volume = axes['volume']
+        self.altitude_edges = self.r_edges - 1.0                      # [self.unit]
+        self.altitude_axis = 0.5*(self.r_edges[:-1] + self.r_edges[1:]) - 1.0
+        self.altitude_edges_km = self.altitude_edges*self.unit_km
+        self.altitude_axis_km = self.altitude_axis*self.unit_km
+
+    def context(self):
+        if self._ctx is None:
+            self._ctx = shared_context(self.inputs, self._device)
+        return self._ctx
+
+    def _from_catalogue(self):
+        """Every catalogued Output through k_shell.  Rows in HBM are read where they are, one
+        launch per run of adjacent slices of a store; other Outputs upload their five sample
+        columns.  The sums stay on the device while (aplanet, vrplanet) -- the g-values -- stay the
+        same, and are summed on the host across such groups."""
+        from .Output import Output
+        runs = list(self.inputs._catalogue)
+        if not runs:
+            print('No model outputs found for these inputs.')
+            return
+        ctx = self.context()
+        totals = {}
+
+        def announced():
+            for run in runs:
+                print(f'Output filename: {getattr(run, "filename", run)}')
+                self.totalsource += run.totalsource if isinstance(run, Output) else \
+                    float(np.load(run, allow_pickle=False)['totalsource'])
+                yield run
+
+        def g_values(run):
+            """(aplanet [au], vrplanet [km/s]): what the g-values of a run depend on"""
+            if isinstance(run, Output):
+                return float(run.aplanet), float(run.vrplanet)
+            with np.load(run, allow_pickle=False) as data:
+                return float(data['aplanet']), float(data['vrplanet_kms'])
+
+        def collect():
+            column, counts, sums = ctx.shell_download()
+            self._column_sum += column
+            self.packets += counts.astype(float)
+            self.shell_sums += sums
+
+        is_set = False
+        for kind, item in sample_spans(announced(), ctx, key=g_values):
+            if kind == 'key':
+                if is_set:
+                    collect()
+                aplanet, vr_kms = item
+                ctx.shell_set(vr_kms/self.unit_km, self.quantity, self.lon_edges, self.mu_edges,
+                              self.r_edges[0], self.r_edges[-1], self.altitude[2],
+                              self.g_tables(aplanet))
+                is_set = True
+                continue
+            if kind == 'rows':
+                ctx.shell_accumulate(rows=item)
+            else:
+                samples = Output.image_columns(item)[0]
+                if samples is None or not len(samples[0]):
+                    continue
+                ctx.shell_accumulate(**dict(zip(Output.IMAGE_COLS, samples)))
+            for key, v in ctx.counters().items():
+                totals[key] = totals.get(key, 0) + v
+        collect()
+        self.counters = totals
+        assert totals.get('nonfinite', 0) == 0, 'Non-finite weights'
+
+    def finalize(self):
+        """Scale to a source rate of 1e23 atoms/s, as ModelImage.finalize does."""
+        per_second = self.totalsource / self.inputs.options.endtime.value
+        self.atoms_per_packet = 1e23 / per_second if per_second > 0 else 0.
+        self.sourcerate = Quantity(1., '1e23/s')
+        products = shell_from_sums(self._column_sum, self.shell_sums, self.atoms_per_packet,
+                                   self.solid_angle, self._volume, self.unit_km*1e5)
+        for name, value in products.items():
+            setattr(self, name, value)

@@ -2,7 +2,8 @@
 
 Same front door as the reference package (nexoclom/__init__.py:9-14): Input, Output, ModelImage,
 SSObject, ModelDensity (data_simulation/ModelDensity.py), LOSResult and LOSResultFitted
-(data_simulation/LOSResult*.py), plus CameraImage (perspective images, an extension).  Importing this package touches
+(data_simulation/LOSResult*.py), plus CameraImage (perspective images) and ShellMap (density and
+zenith column per local time, latitude and altitude), both extensions.  Importing this package touches
 neither a database nor the GPU; the HIP library is loaded on first use and there is no CPU
 fallback for the integrator or the image kernels.
 """
@@ -14,6 +15,7 @@ from .ModelImage import ModelImage, ModelResult   # noqa: F401
 from .LOSResult import LOSResult, SpacecraftData   # noqa: F401
 from .ModelDensity import ModelDensity        # noqa: F401
 from .CameraImage import CameraImage          # noqa: F401
+from .ShellMap import ShellMap                # noqa: F401
 from .LOSResultFitted import LOSResultFitted  # noqa: F401
 from .sourcemap import SourceMap              # noqa: F401
 from .solarsystem import SSObject, planet_dist    # noqa: F401

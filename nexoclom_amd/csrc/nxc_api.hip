@@ -25,6 +25,7 @@
 
 #include "../../include/nexoclom_hip.h"
 #include "nxc_camera_check.hpp"
+#include "nxc_shell_check.hpp"
 #include "nxc_cube_check.hpp"
 #include "nxc_los_profile_check.hpp"
 #include "nxc_desc_check.hpp"
@@ -453,6 +454,16 @@ struct nxc_handle {
     Dev<unsigned char> d_blob_cam;
     size_t cam_bytes = 0;
     PixelSums cam_px;                // the camera's pair, moments and cube
+
+    // ShellMap (nxc_shell_set): the altitude axis, its LDS blob [LdsHeader | g tables | lon edges |
+    // mu edges], its own {c sum, count} pair per cell and the two planes of records
+    bool have_shell = false;
+    ShellK shell{};
+    Dev<unsigned char> d_blob_shell;
+    size_t shell_bytes = 0;
+    PixelSums shell_px;              // shell.replicas copies of the pair per cell, summed by the
+                                     // download (its moments and cube stay off)
+    Dev<double> d_shell_planes;      // [2][cells][nalt + 2] records: {w, w w} | {c, c c} (k_shell)
 
     // LOSResultFitted: the pair list the line-of-sight passes fill (nxc_los_set_pairs); the fit's
     // per-spectrum data, its sample source and per-packet sums (nxc_fit_*)
@@ -1607,6 +1618,18 @@ int camera_run(nxc_handle *h, const Samples &s)
     });
 }
 
+// ShellMap over samples on the device (k_shell)
+int shell_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_shell<T>, NXC_SHELL_BLOCK, h->shell_bytes, s.n, h->shell,
+                                  h->d_blob_shell, (int64_t)h->shell_bytes, s.n, s.col<T>(0),
+                                  s.col<T>(1), s.col<T>(2), s.col<T>(3), s.col<T>(4),
+                                  h->shell_px.image, h->d_shell_planes, h->d_ctr);
+    });
+}
+
 // ModelImage(moments=True) over samples on the device (k_image_moments: atomics, never the tiles)
 int image_moments_run(nxc_handle *h, const Samples &s)
 {
@@ -1702,6 +1725,9 @@ int spectrum_free(nxc_handle *h)
 const SampleConsumer CAMERA_SAMPLES = {[](const nxc_handle *h) { return h->have_camera; },
                                        "nxc_camera_set has not been called",
                                        true, true, false, nullptr, camera_run, &nxc_handle::cam_px};
+const SampleConsumer SHELL_SAMPLES = {[](const nxc_handle *h) { return h->have_shell; },
+                                      "nxc_shell_set has not been called",
+                                      true, true, false, nullptr, shell_run, &nxc_handle::shell_px};
 // the pixel moments' state is their enable, checked after the set's (pixel_moments_need_set)
 const SampleConsumer IMAGE_MOMENT_SAMPLES = {[](const nxc_handle *h) { return h->img.have_mom; },
                                              "nxc_image_moments_enable has not been called",
@@ -3528,6 +3554,106 @@ int nxc_camera_cube_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t fi
 int nxc_camera_cube_download(nxc_handle *h, double *sums)
 {
     return pixel_cube_download(h, CAMERA_SAMPLES, CAMERA_CUBE_SAMPLES, sums);
+}
+
+// ---- ShellMap --------------------------------------------------------------------------------------
+int nxc_shell_set(nxc_handle *h, const nxc_shell_desc *d)
+{
+    return guarded([&]() -> int {
+    if (!h) return fail(NXC_ERR_ARG, "null handle");
+    std::string why = check_shell_desc(d);
+    if (!why.empty()) return fail(NXC_ERR_ARG, why);
+    HIPCHK(hipSetDevice(h->device));
+    const int nl = d->quantity == 1 ? d->n_lines : 0;
+    std::vector<unsigned char> blob((size_t)NXC_HEADER_BYTES, 0);
+    LdsHeader hdr = h->header;                 // nxc_log's table; the image's own G is replaced
+    ImageK G{};
+    G.vrplanet = d->vrplanet;
+    G.apix_cm2 = 1.0;                          // image_weight's last division is exact
+    G.quantity = d->quantity;
+    PackedLut luts[NXC_MAX_LINES];
+    int rc;
+    if ((rc = pack_lines(nl, d->line_v, d->line_g, d->line_n, luts))) return rc;
+    place_image_block(append_image_block(blob, G, d->nlon, d->nlat, d->lon_edges, d->mu_edges, nl, luts),
+                      NXC_HEADER_BYTES, G);
+    why = check_shell_blob(blob.size());
+    if (!why.empty()) return fail(NXC_ERR_ARG, why);
+    hdr.G = G;
+    std::memcpy(blob.data(), &hdr, sizeof(LdsHeader));
+
+    ShellK K{};
+    K.nalt = (int)d->nalt;
+    K.r_lo = d->r_lo;
+    K.inv_dr = shell_inv_dr(d->nalt, d->r_lo, d->r_hi);
+    K.plane = (int64_t)shell_plane_doubles(d->nlon, d->nlat, d->nalt);
+    K.replicas = (int)shell_replicas(d->nlon * d->nlat);
+    K.pairs = 2 * d->nlon * d->nlat;
+
+    h->have_shell = false;
+    const size_t cells = (size_t)d->nlon * (size_t)d->nlat;
+    const size_t pair_bytes = (size_t)K.replicas * 2 * cells * sizeof(double);
+    const size_t plane_bytes = 2 * (size_t)K.plane * sizeof(double);
+    if ((rc = h->d_blob_shell.ensure(blob.size())) ||
+        (rc = h->shell_px.image.ensure(pair_bytes)) ||
+        (rc = h->d_shell_planes.ensure(plane_bytes)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(h->d_blob_shell, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->shell_px.image, 0, pair_bytes, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_shell_planes, 0, plane_bytes, h->stream));
+    HIPCHK(stream_sync(h));                    // blob is a local
+    h->shell = K;
+    h->shell_bytes = blob.size();
+    h->shell_px.npix = cells;
+    h->have_shell = true;
+    return NXC_OK;
+    });
+}
+
+int nxc_shell_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                         const double *z, const double *vy, const double *frac)
+{
+    return accumulate_columns(h, SHELL_SAMPLES, p, x, y, z, vy, frac);
+}
+
+int nxc_shell_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                             const float *z, const float *vy, const float *frac)
+{
+    return accumulate_columns(h, SHELL_SAMPLES, p, x, y, z, vy, frac);
+}
+
+int nxc_shell_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    return accumulate_rows(h, SHELL_SAMPLES, r, first, count);
+}
+
+int nxc_shell_download(nxc_handle *h, double *column, uint64_t *counts, double *sums)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_shell) return fail(NXC_ERR_STATE, SHELL_SAMPLES.unset);
+    HIPCHK(hipSetDevice(h->device));
+    if (sums) {
+        HIPCHK(hipMemcpyAsync(sums, h->d_shell_planes, 2 * (size_t)h->shell.plane * sizeof(double),
+                              hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(stream_sync(h));
+    }
+    if (!column && !counts) return NXC_OK;
+    // the copies of the pair array, summed in their order (the counts are integers below 2^53)
+    const size_t cells = h->shell_px.npix, copies = (size_t)h->shell.replicas;
+    std::vector<double> all(copies * 2 * cells);
+    HIPCHK(hipMemcpyAsync(all.data(), h->shell_px.image, all.size() * sizeof(double),
+                          hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    for (size_t q = 0; q < cells; q++) {
+        double c = 0.0, n = 0.0;
+        for (size_t r = 0; r < copies; r++) {
+            c += all[2 * (r * cells + q)];
+            n += all[2 * (r * cells + q) + 1];
+        }
+        if (column) column[q] = c;
+        if (counts) counts[q] = (uint64_t)n;
+    }
+    return NXC_OK;
+    });
 }
 
 // ---- source maps ---------------------------------------------------------------------------------

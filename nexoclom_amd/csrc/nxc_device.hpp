@@ -1210,6 +1210,65 @@ NXC_DEV int cube_plane(const CubeK &Q, double vlos)
     return k;
 }
 
+// ---- ShellMap: the same sample filed by local time, latitude and altitude --------------------------
+// (include/nexoclom_hip.h, "ShellMap", holds the definition; the operations below are in its
+// order.)  Everything the image has a place for -- g-value tables, the two edge arrays (longitude as
+// "x", sin(latitude) as "z"), quantity, vrplanet -- sits in the LDS header's ImageK, so image_regs /
+// bin_index / image_weight serve unchanged; the header's apix_cm2 is 1 (the camera's reason).  The
+// altitude axis and the distance between the two planes travel as a kernel argument.
+struct ShellK {
+    int nalt;               // bins; records 0 and nalt + 1 hold what falls below and above
+    double r_lo, inv_dr;    // [R], [1/R]
+    int64_t plane;          // doubles from plane A to plane B: cells (nalt + 2) 2
+    int replicas;           // copies of the pair per cell; workgroup b adds to copy b % replicas
+    int64_t pairs;          // doubles from one copy to the next: cells 2
+};
+
+// locate + weight + count + add of one sample per lane, and its two records: k_shell's sample.
+// Wave-cooperative like image_located.  The atan2 is the only value here that is not correctly
+// rounded; it reaches nothing but bin_index.
+NXC_DEV void shell_located(const ShellK &S, const ImageK &G, const ImageRegs &R, const PixelSample &s,
+                           double *__restrict__ acc2, double *__restrict__ planes2,
+                           unsigned long long &binned, unsigned long long &nonfinite)
+{
+    bool ok = false;
+    int cell = -1;
+    double w = 0.0, c = 0.0, r = 1.0;
+    if (s.has) {
+        const double radvel = s.vy + R.vrplanet;
+        const double r2 = (s.x * s.x + s.y * s.y) + s.z * s.z;
+        r = nxc_sqrt(r2);
+        const double mu = nxc_div(s.z, r);
+        double lon = atan2(s.x, -s.y);
+        if (lon < 0.0) lon = lon + 0x1.921fb54442d18p+2;
+        const int ix = bin_index(lon, R.xedges, R.nx, R.x_lo, R.x_hi, R.x_inv_step);
+        const int iz = bin_index(mu, R.zedges, R.nz, R.z_lo, R.z_hi, R.z_inv_step);
+        if (ix < 0 || iz < 0) {
+            if (!(__builtin_fabs(s.frac) <= 1.7976931348623157e308) || radvel != radvel) nonfinite++;
+        } else {
+            cell = ix * R.nz + iz;
+            double f = s.frac;
+            if (R.quantity != 0) f = sunlit(s.x, s.y, s.z) ? f : f * 0.0;
+            ok = image_weight(G, R, radvel, f, w);
+            if (ok) {
+                c = nxc_div(w, r2);
+                ok = __builtin_fabs(c) <= 1.7976931348623157e308;
+            }
+            if (!ok) nonfinite++;
+        }
+    }
+    binned += ok;
+    image_add_pairs(ok, cell, c, acc2);
+    const bool has = ok && w != 0.0;
+    const double t = (r - S.r_lo) * S.inv_dr;
+    int k = S.nalt + 1;
+    if (t < 0.0) k = 0;
+    else if (t < (double)S.nalt) k = 1 + (int)t;
+    const int rec = cell * (S.nalt + 2) + k;
+    add_record_pairs(has, rec, w, w * w, planes2);
+    add_record_pairs(has, rec, c, c * c, planes2 + S.plane);
+}
+
 // Per-wave compaction queue between image_locate and image_weight: a ring of 128 located samples
 // {pixel, radial velocity, masked fraction} in LDS.  push() appends the lanes' samples in lane
 // order (ballot + prefix rank); once 64 are waiting, pop() hands one to every lane.  All calls

@@ -15,7 +15,8 @@
 //   k_camera        the same samples in the perspective image of a camera at a finite distance
 //   k_image_moments, k_camera_moments   either pass with four velocity-moment sums per pixel
 //   k_image_cube, k_camera_cube         either pass with the weight filed per pixel and Doppler bin
-//                   (all six: pixel_pass -- staging, loop, loads, counters -- with a lambda each)
+//   k_shell         the same samples by solar-fixed longitude, sin(latitude) and altitude (ShellMap)
+//                   (all seven: pixel_pass -- staging, loop, loads, counters -- with a lambda each)
 //   k_density, k_density_moments, k_density_spectrum   stored samples within dr of query points
 //                   (density_walk -- loop, cull, candidate walk, membership -- with a load and a
 //                   per-trip lambda each; k_density_moments keeps the walk written out)
@@ -952,7 +953,7 @@ k_var(ForceK F, const unsigned char *__restrict__ blob, int64_t stage_bytes, int
 }
 
 // ---------------------------------------------------------------------------------------------
-// The pass of the six pixel kernels over stored samples: the tables staged into LDS, a grid-stride
+// The pass of the seven pixel kernels over stored samples: the tables staged into LDS, a grid-stride
 // loop that hands `sample` one row per lane and trip (wave-cooperative: every lane calls it, with
 // or without a row), and the three counters flushed once per workgroup.  `sample` is the kernel's
 // own: (G, IR, PixelSample, binned, nonfinite) -> what the row adds.
@@ -3056,6 +3057,34 @@ k_camera_cube(CameraK K, const unsigned char *__restrict__ blob, int64_t stage_b
                    unsigned long long &binned, unsigned long long &nonfinite) {
                    const PixelHit h = camera_located(K, G, IR, s, acc2, binned, nonfinite);
                    pixel_cube_add(Q, h.ok, h.pix, h.w, camera_vlos(K, h, s, vx, vz), cube2);
+               });
+}
+
+// ---------------------------------------------------------------------------------------------
+// ShellMap: stored samples binned by solar-fixed longitude, sin(latitude) and altitude
+// (shell_located).  k_image's pass (pixel_pass) over five columns: the blob [header | g tables |
+// lon edges | mu edges] staged once per workgroup; a binned sample adds its pair to acc2 and, with
+// w != 0, {w, w w} and {c, c c} to its record of the two planes of planes2, [2][cells][nalt + 2]
+// 16-byte records: at most three atomic requests per binned sample, as k_image_moments.  The shell
+// scalars travel as a kernel argument, like CubeK.  Every sample adds to the pair array, which has
+// few records: workgroup b adds to copy b % replicas of it (shell_replicas; the download sums them).
+// 76 VGPRs (the atan2 costs two over k_image_moments' 74), no scratch: six waves a SIMD, which three
+// 512-thread groups fill (two waves a SIMD each; Na's 45 KB of tables three times fit the 160 KiB
+// of LDS) where one 1024-thread group would leave it at four.
+constexpr int NXC_SHELL_BLOCK = 512;
+template <typename T>
+__global__ void __launch_bounds__(NXC_SHELL_BLOCK)
+k_shell(ShellK S, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p,
+        const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ z,
+        const T *__restrict__ vy, const T *__restrict__ frac, double *__restrict__ acc2,
+        double *__restrict__ planes2, DevCounters *__restrict__ ctr)
+{
+    double *__restrict__ own2 = acc2 + (int64_t)(blockIdx.x % (unsigned)S.replicas) * S.pairs;
+    pixel_pass(blob, stage_bytes, p, x, y, z, vy, frac, ctr, (int64_t)blockIdx.x * blockDim.x,
+               (int64_t)gridDim.x * blockDim.x,
+               [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
+                   unsigned long long &binned, unsigned long long &nonfinite) {
+                   shell_located(S, G, IR, s, own2, planes2, binned, nonfinite);
                });
 }
 

@@ -61,7 +61,9 @@ EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_
            'nxc_density_spectrum_accumulate_f32', 'nxc_density_spectrum_accumulate_rows',
            'nxc_density_spectrum_download',
            'nxc_los_profile_enable', 'nxc_los_profile_accumulate', 'nxc_los_profile_accumulate_f32',
-           'nxc_los_profile_accumulate_rows', 'nxc_los_profile_download')
+           'nxc_los_profile_accumulate_rows', 'nxc_los_profile_download',
+           'nxc_shell_set', 'nxc_shell_accumulate', 'nxc_shell_accumulate_f32',
+           'nxc_shell_accumulate_rows', 'nxc_shell_download')
 ABI_VERSION = 3
 
 
@@ -118,6 +120,14 @@ class nxc_camera_desc(C.Structure):
     _fields_ = [('o', C.c_double*3), ('C', C.c_double*9), ('vrplanet', C.c_double),
                 ('pix_area_cm2', C.c_double), ('quantity', C.c_int32), ('n_lines', C.c_int32),
                 ('nx', C.c_int64), ('nz', C.c_int64), ('uedges', _dp), ('vedges', _dp),
+                ('line_n', C.c_int64*NXC_MAX_LINES), ('line_v', _dp*NXC_MAX_LINES),
+                ('line_g', _dp*NXC_MAX_LINES)]
+
+
+class nxc_shell_desc(C.Structure):
+    _fields_ = [('vrplanet', C.c_double), ('r_lo', C.c_double), ('r_hi', C.c_double),
+                ('quantity', C.c_int32), ('n_lines', C.c_int32), ('nlon', C.c_int64),
+                ('nlat', C.c_int64), ('nalt', C.c_int64), ('lon_edges', _dp), ('mu_edges', _dp),
                 ('line_n', C.c_int64*NXC_MAX_LINES), ('line_v', _dp*NXC_MAX_LINES),
                 ('line_g', _dp*NXC_MAX_LINES)]
 
@@ -1099,6 +1109,40 @@ class Context:
         sums = np.zeros(tuple(getattr(self, 'camera_shape', None) or (0, 0)) + (nv + 2, 2))
         self._check(self.lib.nxc_camera_cube_download(self._h, _p(sums)))
         return sums
+
+    # -- ShellMap ---------------------------------------------------------------------------
+    def shell_set(self, vrplanet, quantity, lon_edges, mu_edges, r_lo, r_hi, nalt, g_tables=()):
+        """Describe a shell map (nxc_shell_desc) and zero its resident sums: longitude edges
+        np.linspace(0, 2 pi, nlon + 1), sin(latitude) edges np.linspace(-1, 1, nlat + 1) and
+        ``nalt`` altitude bins over [r_lo, r_hi) [R from the centre]."""
+        d = nxc_shell_desc()
+        d.vrplanet, d.r_lo, d.r_hi = float(vrplanet), float(r_lo), float(r_hi)
+        d.quantity = self._quantity(quantity, ('column', 'radiance'))
+        le, me = _f64(lon_edges), _f64(mu_edges)
+        d.nlon, d.nlat, d.nalt = len(le)-1, len(me)-1, int(nalt)
+        d.lon_edges, d.mu_edges = _p(le), _p(me)
+        keep = [le, me]
+        if d.quantity == 1:
+            self._fill_lines(d, g_tables, keep)
+        self._check(self.lib.nxc_shell_set(self._h, C.byref(d)))
+        self.shell_shape = (int(d.nlon), int(d.nlat), int(d.nalt))
+
+    def shell_accumulate(self, x=None, y=None, z=None, vy=None, frac=None, rows=None):
+        """Add samples to the shell map: five host columns (float32 ones go over as they are and
+        are widened on the device), or ``rows = (RowStore, first, count)``."""
+        self._accumulate('nxc_shell_accumulate', (x, y, z, vy, frac), rows)
+
+    def shell_download(self):
+        """(column (nlon, nlat) float64, packet counts (nlon, nlat) uint64, sums (2, nlon, nlat,
+        nalt + 2, 2) float64: {sum w, sum w w} and {sum c, sum c c}, c = w / r^2, per cell and
+        altitude record -- record 0 below r_lo, 1..nalt the bins, nalt + 1 at or above r_hi)."""
+        nlon, nlat, nalt = getattr(self, 'shell_shape', None) or (0, 0, 0)
+        column = np.zeros((nlon, nlat))
+        counts = np.zeros((nlon, nlat), dtype=np.uint64)
+        sums = np.zeros((2, nlon, nlat, nalt + 2, 2))
+        self._check(self.lib.nxc_shell_download(
+            self._h, _p(column), counts.ctypes.data_as(C.POINTER(C.c_uint64)), _p(sums)))
+        return column, counts, sums
 
     # -- LOSResultFitted ----------------------------------------------------------------------
     def pairs_create(self, capacity):
