@@ -12,6 +12,8 @@ import numpy as np
 import pandas as pd
 import pytest
 
+from tests.density_walk_cases import candidate_cells
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INPUT = os.path.join(ROOT, 'nexoclom_amd', 'inputfiles', 'Na.mercury.bench.input')
 
@@ -26,24 +28,6 @@ def brute_force(points, dr, x, y, z, frac):
         hit = (dx*dx + dy*dy) + dz*dz <= dr*dr
         sums[j], counts[j] = frac[hit].sum(), hit.sum()
     return sums, counts
-
-
-def candidate_cells(index, p):
-    """The cells k_density visits for a row at p (restated from nxc_kernels.hpp density_cells):
-    per axis the row's cell and the neighbour on each side it is within dr/h (+ 1e-6) of."""
-    r_cell = index.dr / index.h + 1e-6
-    ranges = []
-    for a in range(3):
-        t = (p[a] - index.origin[a]) * (1.0 / index.h)
-        if not (-1.0 <= t < index.dims[a] + 1.0):
-            return []
-        c = np.floor(t)
-        f = t - c
-        lo = int(c) - 1 if f <= r_cell else int(c)
-        hi = int(c) + 1 if f >= 1.0 - r_cell else int(c)
-        ranges.append(range(max(lo, 0), min(hi, index.dims[a] - 1) + 1))
-    nx, ny, _ = index.dims
-    return [(cz*ny + cy)*nx + cx for cz in ranges[2] for cy in ranges[1] for cx in ranges[0]]
 
 
 def _check_cover(points, rows, dr):
