@@ -37,11 +37,10 @@ degrees), moons as occulters.
 """
 import numpy as np
 
-from .ModelImage import (PIXEL_MOMENT_COLUMNS, ModelResult, cube_from_sums, new_cube_sums, parse_cube,
-                         pixel_moments_from_sums, refuse_cube_with, refuse_moments_with)
-from .catalogue import sample_spans, shared_context
+from .ModelImage import ModelImage, ModelResult, parse_cube, refuse_cube_with, refuse_moments_with
+from .Output import Output
+from .catalogue import sample_pass
 from .input_classes import InputError
-from .units import Quantity
 
 MAX_DIM = 8192
 UNSUPPORTED = {
@@ -93,9 +92,6 @@ def camera_basis(boresight, up):
 
 
 class CameraImage(ModelResult):
-    moments = False           # True: the pass over the rows also fills moment_sums
-    cube = None               # (v_lo_kms, v_hi_kms, nbins): the pass also fills cube_sums
-
     def __init__(self, inputs, params, *, context=None, device=0, moments=False, cube=None,
                  **unsupported):
         if cube is not None:
@@ -113,14 +109,7 @@ class CameraImage(ModelResult):
         if self.quantity not in ('column', 'radiance'):
             raise InputError('CameraImage.__init__', "quantity must be 'column' or 'radiance'")
         self._frame()
-        self.image = np.zeros(self.dims)
-        self.packet_image = np.zeros(self.dims)
-        self.moments = bool(moments)
-        if self.moments:
-            self.moment_sums = np.zeros(tuple(self.dims) + (len(PIXEL_MOMENT_COLUMNS),))
-        self.cube = cube
-        if self.cube is not None:
-            self.cube_sums = new_cube_sums(self.dims, self.cube)
+        self._new_pixel_sums(moments, cube)
         self._ctx, self._device = context, device
         self.counters = {}
         self._from_catalogue()
@@ -168,91 +157,27 @@ class CameraImage(ModelResult):
         d = u[:, None, None]*right + bore + v[None, :, None]*up
         return d/np.linalg.norm(d, axis=2, keepdims=True)
 
-    def context(self):
-        if self._ctx is None:
-            self._ctx = shared_context(self.inputs, self._device)
-        return self._ctx
-
     def _from_catalogue(self):
         """Every catalogued Output through k_camera.  Rows in HBM are read where they are, one
         launch per run of adjacent slices of a store; other Outputs upload their five sample
         columns (seven with ``moments`` or ``cube``, through k_camera_moments / k_camera_cube).
         The image stays on the device while (aplanet, vrplanet) -- the g-values -- stay the same,
         and is summed on the host across such groups."""
-        from .Output import Output
-        runs = list(self.inputs._catalogue)
-        if not runs:
-            print('No model outputs found for these inputs.')
-            return
-        ctx = self.context()
-        totals = {}
-
-        def announced():
-            for run in runs:
-                print(f'Output filename: {getattr(run, "filename", run)}')
-                self.totalsource += run.totalsource if isinstance(run, Output) else \
-                    float(np.load(run, allow_pickle=False)['totalsource'])
-                yield run
-
-        def g_values(run):
-            """(aplanet [au], vrplanet [km/s]): what the g-values of a run depend on"""
-            if isinstance(run, Output):
-                return float(run.aplanet), float(run.vrplanet)
-            with np.load(run, allow_pickle=False) as data:
-                return float(data['aplanet']), float(data['vrplanet_kms'])
-
-        def collect():
-            image, counts = ctx.camera_download()
-            self.image += image
-            self.packet_image += counts.astype(float)
-            if self.moments:
-                self.moment_sums += ctx.camera_moments_download()
-            if self.cube is not None:
-                self.cube_sums += ctx.camera_cube_download()
-
         velocity = self.moments or self.cube is not None
-        accumulate = (ctx.camera_cube_accumulate if self.cube is not None else
-                      ctx.camera_moments_accumulate if self.moments else ctx.camera_accumulate)
-        is_set = False
-        for kind, item in sample_spans(announced(), ctx, key=g_values):
-            if kind == 'key':
-                if is_set:
-                    collect()
-                aplanet, vr_kms = item
-                ctx.camera_set(self.observer, self.basis, vr_kms/self.unit_km, self.pix_area_cm2,
-                               self.quantity, self.uedges, self.vedges, self.g_tables(aplanet))
-                if self.moments:
-                    ctx.camera_moments_enable()
-                if self.cube is not None:
-                    v_lo, v_hi, nbins = self.cube
-                    ctx.camera_cube_enable(nbins, v_lo/self.unit_km, v_hi/self.unit_km)
-                is_set = True
-                continue
-            if kind == 'rows':
-                accumulate(rows=item)
-            else:
-                samples = Output.image_columns(item, velocity=velocity)[0]
-                if samples is None or not len(samples[0]):
-                    continue
-                names = Output.MOMENT_COLS if velocity else Output.IMAGE_COLS
-                accumulate(**dict(zip(names, samples)))
-            for key, v in ctx.counters().items():
-                totals[key] = totals.get(key, 0) + v
-        collect()
-        self.counters = totals
-        assert totals.get('nonfinite', 0) == 0, 'Non-finite weights'
+
+        def set_up(ctx, aplanet, vr_kms):
+            ctx.camera_set(self.observer, self.basis, vr_kms/self.unit_km, self.pix_area_cm2,
+                           self.quantity, self.uedges, self.vedges, self.g_tables(aplanet))
+            self._enable_velocity(ctx, 'camera')
+
+        def accumulate(ctx, **samples):
+            (ctx.camera_cube_accumulate if self.cube is not None else
+             ctx.camera_moments_accumulate if self.moments else ctx.camera_accumulate)(**samples)
+
+        sample_pass(self, list(self.inputs._catalogue), accumulate,
+                    Output.MOMENT_COLS if velocity else Output.IMAGE_COLS, set_up,
+                    lambda ctx: self._collect_pixels(ctx, 'camera'))
 
     def finalize(self):
         """Scale to a source rate of 1e23 atoms/s, as ModelImage.finalize does."""
-        per_second = self.totalsource / self.inputs.options.endtime.value
-        self.atoms_per_packet = 1e23 / per_second if per_second > 0 else 0.
-        self.sourcerate = Quantity(1., '1e23/s')
-        if self.moments:         # the quotients are of the unscaled sums
-            for name, value in pixel_moments_from_sums(self.image, self.moment_sums,
-                                                       self.unit_km).items():
-                setattr(self, name, value)
-        if self.cube is not None:
-            for name, value in cube_from_sums(self.cube_sums, self.atoms_per_packet,
-                                              *self.cube[:2]).items():
-                setattr(self, name, value)
-        self.image *= self.atoms_per_packet
+        ModelImage.finalize(self)

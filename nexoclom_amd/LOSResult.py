@@ -29,7 +29,6 @@ import numpy as np
 import pandas as pd
 
 from .ModelImage import (ModelResult, cube_from_sums, parse_cube, pixel_moments_from_sums)
-from .catalogue import shared_context
 from .units import Quantity
 
 POSITION = ('x', 'y', 'z')
@@ -162,11 +161,6 @@ class LOSResult(ModelResult):
         self._ctx, self._device = context, device
         self.iterations = []
         self._geometry = None
-
-    def context(self):
-        if self._ctx is None:
-            self._ctx = shared_context(self.inputs, self._device)
-        return self._ctx
 
     def compute_iteration(self, output, scdata, used_cap=0, pairs=None, profile=False):
         """One catalogued Output against all spectra (compute_iteration.py:90-240).  ``pairs``: a

@@ -33,8 +33,9 @@ import operator
 import numpy as np
 
 from . import constants as const
+from .ModelImage import ModelResult
 from .atomicdata import atomicmass
-from .catalogue import sample_spans, shared_context
+from .catalogue import sample_pass
 from .units import Quantity
 
 MAX_CELLS = 1 << 24           # cells of the point grid (int32 starts; cell coordinates < 2^24)
@@ -344,10 +345,7 @@ class ModelDensity:
                                                   s_lo, s_hi, mass_kg).items():
                 setattr(self, name, value)
 
-    def context(self):
-        if self._ctx is None:
-            self._ctx = shared_context(self.inputs, self._device)
-        return self._ctx
+    context = ModelResult.context         # the catalogue's shared context, found once and kept
 
     def _accumulate(self, index, moments=False, frames=None):
         """(frac sums, counts, moment sums | spectrum sums | None) per indexed point over this
@@ -367,17 +365,10 @@ class ModelDensity:
                                         self._spectrum['all_sky'], frames)
             columns, add = ('x', 'y', 'z', 'vx', 'vy', 'vz', 'frac'), ctx.density_spectrum_accumulate
 
-        def announced():
-            for run in self.inputs._catalogue:
-                print(f'Output filename: {run.filename}')
-                self.totalsource += run.totalsource
-                yield run
-
-        for kind, item in sample_spans(announced(), ctx):
-            if kind == 'rows':
-                add(rows=item)
-            elif len(item.X) and 'x' in item.X:
-                add(*(item.X[c].values for c in columns))
+        runs = list(self.inputs._catalogue)
+        if runs:        # (without runs __init__ has raised, or a shared run leaves this rank none)
+            # k_density* leave the context's counters alone: nothing to total
+            sample_pass(self, runs, lambda ctx, **samples: add(**samples), columns, counters=False)
         extra = ctx.density_spectrum_download() if frames is not None else \
             ctx.density_moments_download() if moments else None
         return (*ctx.density_download(), extra)

@@ -39,7 +39,7 @@ import os
 import numpy as np
 
 from .atomicdata import gValue
-from .catalogue import sample_spans, shared_context
+from .catalogue import run_g_values, sample_pass, shared_context
 from .input_classes import InputError
 from .units import Quantity
 
@@ -249,11 +249,51 @@ class ModelResult:
         lines = (gValue(species, w, aplanet) for w in self.wavelength)
         return [(line.velocity/self.unit_km, line.g) for line in lines]
 
+    def context(self):
+        if self._ctx is None:
+            self._ctx = shared_context(self.inputs, self._device)
+        return self._ctx
 
-class ModelImage(ModelResult):
+    def _scale(self):
+        """atoms_per_packet for a source rate of 1e23 atoms/s (ModelImage.py:102-105)."""
+        per_second = self.totalsource / self.inputs.options.endtime.value
+        self.atoms_per_packet = 1e23 / per_second if per_second > 0 else 0.
+        self.sourcerate = Quantity(1., '1e23/s')
+
+    # ---- the pixels of ModelImage and CameraImage; ``prefix``: the context's 'image' or 'camera'
     moments = False           # True: the pass over the rows also fills moment_sums
     cube = None               # (v_lo_kms, v_hi_kms, nbins): the pass also fills cube_sums
 
+    def _new_pixel_sums(self, moments, cube):
+        self.image = np.zeros(self.dims)
+        self.packet_image = np.zeros(self.dims)
+        self.moments = bool(moments)
+        if self.moments:
+            self.moment_sums = np.zeros(tuple(self.dims) + (len(PIXEL_MOMENT_COLUMNS),))
+        self.cube = cube
+        if self.cube is not None:
+            self.cube_sums = new_cube_sums(self.dims, self.cube)
+
+    def _enable_velocity(self, ctx, prefix):
+        if self.moments:
+            getattr(ctx, prefix + '_moments_enable')()
+        if self.cube is not None:
+            v_lo, v_hi, nbins = self.cube
+            getattr(ctx, prefix + '_cube_enable')(nbins, v_lo/self.unit_km, v_hi/self.unit_km)
+
+    def _collect_pixels(self, ctx, prefix):
+        """Add the context's resident sums to the host's; the downloaded image."""
+        image, counts = getattr(ctx, prefix + '_download')()
+        self.image += image
+        self.packet_image += counts.astype(float)
+        if self.moments:
+            self.moment_sums += getattr(ctx, prefix + '_moments_download')()
+        if self.cube is not None:
+            self.cube_sums += getattr(ctx, prefix + '_cube_download')()
+        return image
+
+
+class ModelImage(ModelResult):
     def __init__(self, inputs, params, overwrite=False, distribute=None, *, npackets=None,
                  seed=None, packs_per_it=None, downcast=True, device=0, context=None,
                  sampler='numpy', shard=None, finalize=True, generator='philox', moments=False,
@@ -270,14 +310,7 @@ class ModelImage(ModelResult):
             raise NotImplementedError('images centred on another object '
                                       '(ModelResult.transform_reference_frame) are out of scope')
         self._frame()
-        self.image = np.zeros(self.dims)
-        self.packet_image = np.zeros(self.dims)
-        self.moments = bool(moments)
-        if self.moments:
-            self.moment_sums = np.zeros(tuple(self.dims) + (len(PIXEL_MOMENT_COLUMNS),))
-        self.cube = cube
-        if self.cube is not None:
-            self.cube_sums = new_cube_sums(self.dims, self.cube)
+        self._new_pixel_sums(moments, cube)
         self.blimits = None
         self.xaxis = None
         self.zaxis = None
@@ -340,35 +373,17 @@ class ModelImage(ModelResult):
         if not runs or not all(isinstance(run, Output) for run in runs):
             return False
         ctx = self.context()
-        views = [run.resident_rows(ctx) for run in runs]
-        same = {(float(run.aplanet), float(run.vrplanet)) for run in runs}
-        if any(v is None for v in views) or len(same) != 1:
+        if any(run.resident_rows(ctx) is None for run in runs) or \
+                len({run_g_values(run) for run in runs}) != 1:
             return False
-        (aplanet, vrplanet_kms), = same
-        self._set_image(ctx, aplanet, vrplanet_kms/self.unit_km, downcast=False)    # clears it
-        totals = {}
 
-        def announced():
-            for run in runs:
-                print(f'Output filename: {run.filename}')
-                self.totalsource += run.totalsource
-                yield run
+        def set_up(ctx, aplanet, vr_kms):
+            self._set_image(ctx, aplanet, vr_kms/self.unit_km, downcast=False)      # clears it
 
         # the Outputs of a launch group are consecutive slices of one store: one kernel launch per
         # run of adjacent slices instead of one per Output
-        for _, span in sample_spans(announced(), ctx):
-            self._accumulate(ctx, rows=span)
-            for key, v in ctx.counters().items():
-                totals[key] = totals.get(key, 0) + v
-        self.counters = totals
-        assert totals.get('nonfinite', 0) == 0, 'Non-finite weights'
-        image, counts = ctx.image_download()
-        self.image += image
-        self.packet_image += counts.astype(float)
-        if self.moments:
-            self.moment_sums += ctx.image_moments_download()
-        if self.cube is not None:
-            self.cube_sums += ctx.image_cube_download()
+        sample_pass(self, runs, lambda ctx, rows: self._accumulate(ctx, rows=rows), (), set_up)
+        image = self._collect_pixels(ctx, 'image')
         h = Histogram2dResult(image, self.xedges, self.zedges)
         self.xaxis, self.zaxis = h.x, h.y
         return True
@@ -376,25 +391,14 @@ class ModelImage(ModelResult):
     def finalize(self):
         """Scale to a source rate of 1e23 atoms/s (ModelImage.py:102-105); deferred by the
         multi-GPU path until the shards are summed."""
-        per_second = self.totalsource / self.inputs.options.endtime.value
-        self.atoms_per_packet = 1e23 / per_second if per_second > 0 else 0.
-        self.sourcerate = Quantity(1., '1e23/s')
+        self._scale()
         if self.moments:         # the quotients are of the unscaled sums
-            for name, value in pixel_moments_from_sums(self.image, self.moment_sums,
-                                                       self.unit_km).items():
-                setattr(self, name, value)
+            vars(self).update(pixel_moments_from_sums(self.image, self.moment_sums, self.unit_km))
         if self.cube is not None:
-            for name, value in cube_from_sums(self.cube_sums, self.atoms_per_packet,
-                                              *self.cube[:2]).items():
-                setattr(self, name, value)
+            vars(self).update(cube_from_sums(self.cube_sums, self.atoms_per_packet, *self.cube[:2]))
         self.image *= self.atoms_per_packet
 
     # ---- GPU plumbing ---------------------------------------------------------------------
-    def context(self):
-        if self._ctx is None:
-            self._ctx = shared_context(self.inputs, self._device)
-        return self._ctx
-
     def image_rotation(self):
         """Sun frame -> observer frame (ModelImage.py:367-384): the rotation that carries the
         sub-solar direction (0,-1,0) onto the sub-observer direction."""
@@ -409,11 +413,7 @@ class ModelImage(ModelResult):
     def _set_image(self, ctx, aplanet, vrplanet_Rs, downcast):
         ctx.set_image(self.image_rotation(), vrplanet_Rs, float(self.Apix), self.quantity,
                       self.xedges, self.zedges, self.g_tables(aplanet), downcast_f32=downcast)
-        if self.moments:
-            ctx.image_moments_enable()
-        if self.cube is not None:
-            v_lo, v_hi, nbins = self.cube
-            ctx.image_cube_enable(nbins, v_lo/self.unit_km, v_hi/self.unit_km)
+        self._enable_velocity(ctx, 'image')
 
     def _accumulate(self, ctx, samples=(), rows=None):
         """One pass over host columns or ``rows = (RowStore, first, count)`` through the entry this

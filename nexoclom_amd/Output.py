@@ -773,6 +773,7 @@ class Output:
 
     IMAGE_COLS = ('x', 'y', 'z', 'vy', 'frac')
     MOMENT_COLS = ('x', 'y', 'z', 'vx', 'vy', 'vz', 'frac')
+    PATH = (str, os.PathLike)        # a stored run (.npz) where a catalogued Output may stand
 
     @staticmethod
     def packet_index(frame):
@@ -781,23 +782,25 @@ class Output:
         return frame['Index'].values if 'Index' in frame.columns else np.arange(len(frame))
 
     @classmethod
-    def image_columns(cls, source, velocity=False):
-        """What create_image needs of a stored Output, without restoring the rest: the five
-        sample columns as stored (32-bit after save(); the device widens them exactly like
-        restore()'s up-cast, Output.py:555-570), aplanet [au] and vrplanet [km/s].  ``source``: a
-        catalogued Output or an .npz path.  ``velocity``: the seven columns of MOMENT_COLS (vx and
-        vz as well, for the pixel moments) instead of the five of IMAGE_COLS."""
-        names = cls.MOMENT_COLS if velocity else cls.IMAGE_COLS
-        if isinstance(source, cls):
+    def sample_columns(cls, source, names):
+        """The columns ``names`` of a stored run's X, without restoring the rest: as stored (32-bit
+        after save(); the device widens them exactly like restore()'s up-cast, Output.py:555-570).
+        ``source``: a catalogued Output or an .npz path.  None: it holds no trajectory."""
+        if not isinstance(source, cls.PATH):
             frame = source.X
-            if len(frame) == 0 or 'x' not in frame:
-                return None, float(source.aplanet), float(source.vrplanet)
-            columns = [frame[c].values for c in names]
+            return [frame[c].values for c in names] if len(frame) and 'x' in frame else None
+        with np.load(source, allow_pickle=False) as data:
+            return [data['X.' + c] for c in names] if 'X.x' in data.files else None
+
+    @classmethod
+    def image_columns(cls, source, velocity=False):
+        """What create_image needs of a stored Output: its five sample columns (``sample_columns``
+        of IMAGE_COLS; ``velocity``: the seven of MOMENT_COLS, vx and vz as well, for the pixel
+        moments), aplanet [au] and vrplanet [km/s]."""
+        columns = cls.sample_columns(source, cls.MOMENT_COLS if velocity else cls.IMAGE_COLS)
+        if not isinstance(source, cls.PATH):
             return columns, float(source.aplanet), float(source.vrplanet)
         with np.load(source, allow_pickle=False) as data:
-            if 'X.x' not in data.files:
-                return None, float(data['aplanet']), float(data['vrplanet_kms'])
-            columns = [data['X.' + c] for c in names]
             return columns, float(data['aplanet']), float(data['vrplanet_kms'])
 
     @classmethod

@@ -32,9 +32,9 @@ Not supported, and refused: streaming (``npackets=``), shared runs (``cp=`` / ``
 import numpy as np
 
 from .ModelImage import ModelResult
-from .catalogue import sample_spans, shared_context
+from .Output import Output
+from .catalogue import sample_pass
 from .input_classes import InputError
-from .units import Quantity
 
 MAX_DIM = 8192
 UNSUPPORTED = {
@@ -159,73 +159,29 @@ class ShellMap(ModelResult):
         self.altitude_edges_km = self.altitude_edges*self.unit_km
         self.altitude_axis_km = self.altitude_axis*self.unit_km
 
-    def context(self):
-        if self._ctx is None:
-            self._ctx = shared_context(self.inputs, self._device)
-        return self._ctx
-
     def _from_catalogue(self):
         """Every catalogued Output through k_shell.  Rows in HBM are read where they are, one
         launch per run of adjacent slices of a store; other Outputs upload their five sample
         columns.  The sums stay on the device while (aplanet, vrplanet) -- the g-values -- stay the
         same, and are summed on the host across such groups."""
-        from .Output import Output
-        runs = list(self.inputs._catalogue)
-        if not runs:
-            print('No model outputs found for these inputs.')
-            return
-        ctx = self.context()
-        totals = {}
+        def set_up(ctx, aplanet, vr_kms):
+            ctx.shell_set(vr_kms/self.unit_km, self.quantity, self.lon_edges, self.mu_edges,
+                          self.r_edges[0], self.r_edges[-1], self.altitude[2],
+                          self.g_tables(aplanet))
 
-        def announced():
-            for run in runs:
-                print(f'Output filename: {getattr(run, "filename", run)}')
-                self.totalsource += run.totalsource if isinstance(run, Output) else \
-                    float(np.load(run, allow_pickle=False)['totalsource'])
-                yield run
-
-        def g_values(run):
-            """(aplanet [au], vrplanet [km/s]): what the g-values of a run depend on"""
-            if isinstance(run, Output):
-                return float(run.aplanet), float(run.vrplanet)
-            with np.load(run, allow_pickle=False) as data:
-                return float(data['aplanet']), float(data['vrplanet_kms'])
-
-        def collect():
+        def collect(ctx):
             column, counts, sums = ctx.shell_download()
             self._column_sum += column
             self.packets += counts.astype(float)
             self.shell_sums += sums
 
-        is_set = False
-        for kind, item in sample_spans(announced(), ctx, key=g_values):
-            if kind == 'key':
-                if is_set:
-                    collect()
-                aplanet, vr_kms = item
-                ctx.shell_set(vr_kms/self.unit_km, self.quantity, self.lon_edges, self.mu_edges,
-                              self.r_edges[0], self.r_edges[-1], self.altitude[2],
-                              self.g_tables(aplanet))
-                is_set = True
-                continue
-            if kind == 'rows':
-                ctx.shell_accumulate(rows=item)
-            else:
-                samples = Output.image_columns(item)[0]
-                if samples is None or not len(samples[0]):
-                    continue
-                ctx.shell_accumulate(**dict(zip(Output.IMAGE_COLS, samples)))
-            for key, v in ctx.counters().items():
-                totals[key] = totals.get(key, 0) + v
-        collect()
-        self.counters = totals
-        assert totals.get('nonfinite', 0) == 0, 'Non-finite weights'
+        sample_pass(self, list(self.inputs._catalogue),
+                    lambda ctx, **samples: ctx.shell_accumulate(**samples), Output.IMAGE_COLS,
+                    set_up, collect)
 
     def finalize(self):
         """Scale to a source rate of 1e23 atoms/s, as ModelImage.finalize does."""
-        per_second = self.totalsource / self.inputs.options.endtime.value
-        self.atoms_per_packet = 1e23 / per_second if per_second > 0 else 0.
-        self.sourcerate = Quantity(1., '1e23/s')
+        self._scale()
         products = shell_from_sums(self._column_sum, self.shell_sums, self.atoms_per_packet,
                                    self.solid_angle, self._volume, self.unit_km*1e5)
         for name, value in products.items():

@@ -1,6 +1,10 @@
 """What every consumer of a catalogue's stored samples (ModelImage, ModelDensity, CameraImage,
-LOSResult) does before its own kernel runs: find the device the runs were made on, and walk the
-catalogue so that rows still in HBM are read where they are, in as few launches as they allow."""
+ShellMap, LOSResult) does around its own kernel: find the device the runs were made on, and walk
+the catalogue so that rows still in HBM are read where they are, in as few launches as they allow
+(``sample_pass``: the whole pass of the four that sum over a catalogue)."""
+import numpy as np
+
+from .Output import Output
 
 
 def shared_context(inputs, device):
@@ -55,3 +59,70 @@ def sample_spans(runs, ctx, key=None):
             yield from flush()
             span = (store, first, count)
     yield from flush()
+
+
+def run_totalsource(run):
+    """totalsource of a catalogued Output or an .npz path"""
+    if not isinstance(run, Output.PATH):
+        return run.totalsource
+    with np.load(run, allow_pickle=False) as data:
+        return float(data['totalsource'])
+
+
+def run_g_values(run):
+    """(aplanet [au], vrplanet [km/s]) of a catalogued Output or an .npz path: what the g-values
+    of a run depend on"""
+    if not isinstance(run, Output.PATH):
+        return float(run.aplanet), float(run.vrplanet)
+    with np.load(run, allow_pickle=False) as data:
+        return float(data['aplanet']), float(data['vrplanet_kms'])
+
+
+def sample_pass(product, runs, accumulate, columns, set_up=None, collect=None, counters=True):
+    """Every stored sample of the catalogue ``runs`` through one consumer, on
+    ``product.context()``.
+
+    Each run is announced and its totalsource added to ``product.totalsource``, in catalogue
+    order.  Rows in HBM go to ``accumulate(ctx, rows=(store, first, count))``, one launch per
+    stretch of adjacent slices of a store; any other run that holds a trajectory uploads its
+    host ``columns``: ``accumulate(ctx, x=..., ...)``.
+    ``set_up(ctx, aplanet, vr_kms)`` runs in front of every stretch of runs of equal (aplanet
+    [au], vrplanet [km/s]) -- the sums stay on the device over such a stretch -- and
+    ``collect(ctx)`` at the end of each.
+    ``counters``: the consumer's kernels clear the context's counters, so they are read after
+    every launch, totalled into ``product.counters`` and must show no non-finite weight."""
+    if not runs:
+        print('No model outputs found for these inputs.')
+        return
+    ctx = product.context()
+    totals = {}
+
+    def announced():
+        for run in runs:
+            print(f'Output filename: {getattr(run, "filename", run)}')
+            product.totalsource += run_totalsource(run)
+            yield run
+
+    is_set = False
+    for kind, item in sample_spans(announced(), ctx, key=run_g_values if set_up else None):
+        if kind == 'key':
+            if is_set and collect:
+                collect(ctx)
+            set_up(ctx, *item)
+            is_set = True
+            continue
+        if kind == 'rows':
+            accumulate(ctx, rows=item)
+        else:
+            samples = Output.sample_columns(item, columns)
+            if samples is None or not len(samples[0]):
+                continue
+            accumulate(ctx, **dict(zip(columns, samples)))
+        if counters:
+            for key, v in ctx.counters().items():
+                totals[key] = totals.get(key, 0) + v
+    if collect:
+        collect(ctx)
+    if counters:
+        product.counters = totals
+        assert totals.get('nonfinite', 0) == 0, 'Non-finite weights'

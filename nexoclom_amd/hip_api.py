@@ -777,6 +777,21 @@ class Context:
         suffix, ptrs, cols = self._columns(cols)
         self._check(getattr(self.lib, entry_name + suffix)(self._h, C.c_int64(len(cols[0])), *ptrs))
 
+    # a pixel image's velocity products; ``prefix``: 'image' or 'camera', as in nxc_<prefix>_...
+    def _moments_enable(self, prefix, on):
+        self._check(getattr(self.lib, f'nxc_{prefix}_moments_enable')(self._h, C.c_int(int(bool(on)))))
+
+    def _cube_enable(self, prefix, nv, v_lo, v_hi):
+        self._check(getattr(self.lib, f'nxc_{prefix}_cube_enable')(
+            self._h, C.c_int64(int(nv)), C.c_double(v_lo), C.c_double(v_hi)))
+        setattr(self, f'_{prefix}_cube_nv', int(nv))
+
+    def _pixel_sums_download(self, prefix, what):
+        per_pixel = (4,) if what == 'moments' else (getattr(self, f'_{prefix}_cube_nv', 0) + 2, 2)
+        sums = np.zeros(tuple(getattr(self, prefix + '_shape', None) or (0, 0)) + per_pixel)
+        self._check(getattr(self.lib, f'nxc_{prefix}_{what}_download')(self._h, _p(sums)))
+        return sums
+
     QUANTITIES = {'column': 0, 'density': 0, 'radiance': 1, 'difrad': 1}
 
     @classmethod
@@ -821,7 +836,7 @@ class Context:
     def image_moments_enable(self, on=True):
         """After ``set_image``: allocate and zero the four velocity-moment sums per pixel (``on``
         false frees them; the next ``set_image`` switches them off)."""
-        self._check(self.lib.nxc_image_moments_enable(self._h, C.c_int(int(bool(on)))))
+        self._moments_enable('image', on)
 
     def image_moments_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
                                  frac=None, rows=None):
@@ -832,16 +847,12 @@ class Context:
 
     def image_moments_download(self):
         """(nx, nz, 4) float64: the sums m1 m2 m3 ww of every pixel (PIXEL_MOMENT_COLUMNS)."""
-        sums = np.zeros(tuple(getattr(self, 'image_shape', None) or (0, 0)) + (4,))
-        self._check(self.lib.nxc_image_moments_download(self._h, _p(sums)))
-        return sums
+        return self._pixel_sums_download('image', 'moments')
 
     def image_cube_enable(self, nv, v_lo=0.0, v_hi=0.0):
         """After ``set_image``: allocate and zero a velocity cube of ``nv`` bins over [v_lo, v_hi)
         [R/s] beside the image pair (``nv`` 0 frees it; the next ``set_image`` switches it off)."""
-        self._check(self.lib.nxc_image_cube_enable(self._h, C.c_int64(int(nv)), C.c_double(v_lo),
-                    C.c_double(v_hi)))
-        self._image_cube_nv = int(nv)
+        self._cube_enable('image', nv, v_lo, v_hi)
 
     def image_cube_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
                               frac=None, rows=None):
@@ -852,10 +863,7 @@ class Context:
     def image_cube_download(self):
         """(nx, nz, nv + 2, 2) float64: {sum w, sum w w} per pixel and plane -- plane 0 below the
         range, 1..nv the bins, nv + 1 at or above it (or not a number)."""
-        nv = getattr(self, '_image_cube_nv', 0)
-        sums = np.zeros(tuple(getattr(self, 'image_shape', None) or (0, 0)) + (nv + 2, 2))
-        self._check(self.lib.nxc_image_cube_download(self._h, _p(sums)))
-        return sums
+        return self._pixel_sums_download('image', 'cube')
 
     # -- f-1: spacecraft lines of sight ------------------------------------------------------
     def los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables,
@@ -1075,7 +1083,7 @@ class Context:
     def camera_moments_enable(self, on=True):
         """After ``camera_set``: allocate and zero the four velocity-moment sums per pixel of the
         camera image (``on`` false frees them; the next ``camera_set`` switches them off)."""
-        self._check(self.lib.nxc_camera_moments_enable(self._h, C.c_int(int(bool(on)))))
+        self._moments_enable('camera', on)
 
     def camera_moments_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
                                   frac=None, rows=None):
@@ -1085,16 +1093,12 @@ class Context:
 
     def camera_moments_download(self):
         """(nx, nz, 4) float64: the sums m1 m2 m3 ww of every pixel of the camera image."""
-        sums = np.zeros(tuple(getattr(self, 'camera_shape', None) or (0, 0)) + (4,))
-        self._check(self.lib.nxc_camera_moments_download(self._h, _p(sums)))
-        return sums
+        return self._pixel_sums_download('camera', 'moments')
 
     def camera_cube_enable(self, nv, v_lo=0.0, v_hi=0.0):
         """After ``camera_set``: allocate and zero a velocity cube of ``nv`` bins over [v_lo, v_hi)
         [R/s] beside the camera image (``nv`` 0 frees it; the next ``camera_set`` switches it off)."""
-        self._check(self.lib.nxc_camera_cube_enable(self._h, C.c_int64(int(nv)), C.c_double(v_lo),
-                    C.c_double(v_hi)))
-        self._camera_cube_nv = int(nv)
+        self._cube_enable('camera', nv, v_lo, v_hi)
 
     def camera_cube_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
                                frac=None, rows=None):
@@ -1105,10 +1109,7 @@ class Context:
     def camera_cube_download(self):
         """(nx, nz, nv + 2, 2) float64: {sum w, sum w w} per pixel and plane -- plane 0 below the
         range, 1..nv the bins, nv + 1 at or above it (or not a number)."""
-        nv = getattr(self, '_camera_cube_nv', 0)
-        sums = np.zeros(tuple(getattr(self, 'camera_shape', None) or (0, 0)) + (nv + 2, 2))
-        self._check(self.lib.nxc_camera_cube_download(self._h, _p(sums)))
-        return sums
+        return self._pixel_sums_download('camera', 'cube')
 
     # -- ShellMap ---------------------------------------------------------------------------
     def shell_set(self, vrplanet, quantity, lon_edges, mu_edges, r_lo, r_hi, nalt, g_tables=()):
