@@ -16,6 +16,9 @@ import os
 import time
 
 from . import input_classes as spec
+from .Output import Output
+from .distributed import pass_plan, shard_range
+from .draws import DrawAhead, Draws
 
 HOST_SAMPLER_THREADS = 8        # Outputs drawn side by side, ahead of the device (16: no faster)
 
@@ -115,14 +118,12 @@ class Input:
         """Integrate until the catalogue holds ``npackets`` packets (Input.py:175-268).
 
         Every pass plans ``ceil(todo / size)`` Outputs of ``size = min(todo, chunk_size)``
-        packets -- the reference's arithmetic, so the last Output of a pass may overshoot.  With a
-        ``seed`` the k-th Output of this call is drawn from ``seed + k``: Output 0 is the
-        reference's stream; the reference itself passes the same seed to every Output
-        (Input.py:246), which repeats identical packets.  ``sampler='device'`` draws the initial
-        states on the GPU instead (counter-based: the k-th Output continues the index space of
-        the ones before it under the one ``seed``; with ``generator='pcg64'`` the device follows
-        the host sampler's seeded streams instead -- Output k from ``seed + k``, the same packets
-        as sampler='numpy' to libm rounding, without the host drawing or uploading them).
+        packets -- the reference's arithmetic, so the last Output of a pass may overshoot
+        (distributed.pass_plan).  With a ``seed`` the k-th Output of this call is drawn from
+        ``seed + k``: Output 0 is the reference's stream; the reference itself passes the same
+        seed to every Output (Input.py:246), which repeats identical packets.  ``sampler='device'``
+        draws the initial states on the GPU instead, counter-based under the one ``seed`` or, with
+        ``generator='pcg64'``, following the host's streams (the rule of each kind: draws.py).
 
         The Outputs of a pass are independent, so they are INTEGRATED TOGETHER (``batch``): one
         upload, one launch of each kernel over all their packets (Output.integrate_batch), each
@@ -138,13 +139,9 @@ class Input:
         packet count that ends the run is summed over the ranks.  ``produce_image(..., cp=cp)`` and
         ``LOSResult.simulate_data_from_inputs(..., cp=cp)`` then sum over the ranks what the
         reference sums over the files (ModelImage.py:96-98, LOSResult.py:264-266)."""
-        from .Output import Output
         started = time.time()
         rank, world = (cp.rank, cp.world) if cp is not None else (0, 1)
-        if world > 1 and seed is None and sampler != 'device':
-            # the host sampler seeds Output k with seed + k: without a seed the ranks would not
-            # make the Outputs of one run
-            seed = int.from_bytes(cp.bcast_bytes(os.urandom(4), 4), 'little')
+        rule = Draws(sampler, generator, seed, cp)   # (an unseeded shared run agrees on a seed)
 
         def report():
             local = self._report()
@@ -155,157 +152,93 @@ class Input:
             self.delete_files()
         have = report()
         want = int(npackets)
-        made = 0
-        drawn = have                             # device sampler: next free global packet index
         # re-emission draws are keyed by (the Output's seed, the packet's number): Outputs that
         # each have their own seed (host-sampled, or following the host streams with 'pcg64')
         # cannot share a launch when packets are re-emitted
         spec = self.surfaceinteraction
         sticks = spec.sticktype == 'constant' and spec.stickcoef == 1.
-        one_key = sampler == 'device' and generator != 'pcg64'
         together = bool(batch) and keep_trajectory and (compress or self.options.step_size == 0) \
-            and (sticks or one_key)
+            and (sticks or rule.one_key)
         if together and context is None:
             from . import hip_api
             context = hip_api.Context(device)
-        if seed is None and sampler == 'device':
-            from .Output import fresh_key
-            seed = fresh_key()                   # one key for the whole (unseeded) run
-            if world > 1:
-                seed = int.from_bytes(cp.bcast_bytes(seed.to_bytes(8, 'little'), 8), 'little')
+
+        def make(entry):
+            # a planned Output: it draws for itself or, together, the device's launch group does
+            return Output(self, entry.size, compress=compress, device=device, context=context,
+                          keep_trajectory=keep_trajectory, integrate=not together,
+                          save=not together, **rule.output_keywords(entry, presampled=together))
+
+        made, drawn = 0, have                    # Outputs of this call; next free packet index
         while have < want:
-            todo = want - have
-            size = min(todo, self.chunk_size(packs_per_it))
-            passes = -(-todo // size)
+            todo, passes, size, made, drawn = pass_plan(
+                have, want, self.chunk_size(packs_per_it), made, drawn, rank, world)
             print('Running Model')
             print(f'Will complete {passes} iterations of {size} packets.')
-            number = 0
-            stop = passes
             if world > 1:
-                # this rank's Outputs of the pass; the counters move as if the others were made here
-                from .distributed import shard_range
-                number, stop = shard_range(passes, rank, world)
-                made += number
-                drawn += size*number
-                print(f'Rank {rank} of {world}: iterations {number + 1} to {stop}.')
-            pipeline = None                      # host-drawn Outputs on their way, in order
-            pool = None
-            launched = False
-            submitted = number                   # next Output of the pass to hand to the drawers
-
-            def draw_one(k):
-                # Output k of the pass: an independent draw from seed + (its number in the run)
-                s_ = None if seed is None else seed + made + (k - number)
-                def job():
-                    out = Output(self, size, compress=compress, device=device,
-                                 keep_trajectory=keep_trajectory, context=context,
-                                 integrate=False, save=False, seed=s_)
-                    return out.prepare_for_launch()
-                return pool.submit(job)
-
+                lo, hi = shard_range(passes, rank, world)
+                print(f'Rank {rank} of {world}: iterations {lo + 1} to {hi}.')
+            ahead, at = None, 0     # host-drawn Outputs on their way; next of ``todo`` to launch
             try:
-                while number < stop:
+                while at < len(todo):
                     tick = time.time()
                     # as many Outputs per launch as HBM takes (rows: nsteps records per packet at
                     # most, far fewer in practice; the row store spills its oldest runs to the host)
                     limit = self._group_limit(size, context) if together else 1
-                    group = min(stop - number, limit)
                     outs = []
-                    if together and sampler == 'numpy' and (group > 1 or pipeline):
+                    if together and rule.on_host and (min(len(todo) - at, limit) > 1 or ahead):
                         # The Outputs are drawn on a few threads (NumPy releases the GIL in its
                         # loops) a window ahead of the device, and a launch takes what is drawn by
                         # the time the device is free: the first launch starts after the first
                         # draws instead of after a whole group's, later ones find Outputs waiting.
-                        if pool is None:
-                            from collections import deque
-                            from concurrent.futures import ThreadPoolExecutor
-                            pool = ThreadPoolExecutor(max_workers=HOST_SAMPLER_THREADS)
-                            pipeline = deque()
-                        window = max(2*HOST_SAMPLER_THREADS, 2*limit)
-                        while submitted < stop and len(pipeline) < window:
-                            pipeline.append(draw_one(submitted))
-                            submitted += 1
                         # A launch has a fixed cost of several milliseconds (two passes, row
                         # offsets, a store): the first takes a handful of Outputs so that the
                         # device starts early, the later ones wait for a third of what HBM takes
                         # (or the rest of the pass) and then add whatever else is drawn by then.
-                        floor = max(1, min(limit, HOST_SAMPLER_THREADS)) if not launched else \
+                        floor = max(1, min(limit, HOST_SAMPLER_THREADS)) if ahead is None else \
                             max(1, min(limit//3, HOST_SAMPLER_THREADS*2))
-                        launched = True
-                        outs = []
-                        while pipeline and len(outs) < floor:
-                            outs.append(pipeline.popleft().result())
-                            while submitted < stop and len(pipeline) < window:
-                                pipeline.append(draw_one(submitted))
-                                submitted += 1
-                        while pipeline and pipeline[0].done() and len(outs) < limit:
-                            outs.append(pipeline.popleft().result())
-                        number += len(outs)
-                        drawn += size*len(outs)
-                        made += len(outs)
-                        group = 0
-                    for g in range(group):
-                        number += 1
-                        print(f'Starting iteration #{number} of {passes}')
-                        if sampler == 'device' and generator == 'pcg64':
-                            draw = dict(seed=seed + made, sampler='device', generator='pcg64',
-                                        first_index=drawn, presampled=together,
-                                        materialize_x0=not together)
-                        elif sampler == 'device':
-                            draw = dict(seed=seed, sampler='device', first_index=drawn,
-                                        presampled=together, materialize_x0=not together)
-                        else:
-                            draw = dict(seed=None if seed is None else seed + made)
-                        out = Output(self, size, compress=compress, device=device,
-                                     keep_trajectory=keep_trajectory, context=context,
-                                     integrate=not together, save=not together, **draw)
-                        context = out.context()      # every Output of the run shares one device
-                        outs.append(out)
-                        drawn += size
-                        made += 1
-                    if together and outs:
-                        first = None if seed is None else seed + made - len(outs)
-                        self._launch_group(outs, context, sampler, generator, seed, size,
-                                           first_seed=first)
-                    print(f'Completed iteration #{number} in {time.time() - tick} seconds.')
+                        if ahead is None:
+                            ahead = DrawAhead(lambda entry: make(entry).prepare_for_launch(),
+                                              todo[at:], HOST_SAMPLER_THREADS)
+                        window = max(2*HOST_SAMPLER_THREADS, 2*limit)
+                        ahead.fill(window)
+                        while ahead and len(outs) < floor:
+                            outs.append(ahead.popleft().result())
+                            ahead.fill(window)
+                        while ahead and ahead[0].done() and len(outs) < limit:
+                            outs.append(ahead.popleft().result())
+                    else:
+                        for entry in todo[at:at + limit]:
+                            print(f'Starting iteration #{entry.number + 1} of {passes}')
+                            outs.append(make(entry))
+                            context = outs[-1].context()     # every Output shares one device
+                    at += len(outs)
+                    if together:
+                        self._launch_group(outs, context, rule)
+                    print(f'Completed iteration #{todo[at - 1].number + 1} in '
+                          f'{time.time() - tick} seconds.')
             finally:
-                if pool is not None:
-                    pool.shutdown(cancel_futures=True)
-            made += passes - stop                # the Outputs of the ranks after this one
-            drawn += size*(passes - stop)
+                if ahead is not None:
+                    ahead.pool.shutdown(cancel_futures=True)
             have = report()
         self.wait()                              # files of this run are on disk when it returns
         print(f'Model run completed in {time.time() - started:.2f} sec.')
 
-    def _launch_group(self, outs, context, sampler, generator, seed, size, first_seed):
+    def _launch_group(self, outs, context, rule):
         """Draw (device samplers) and integrate the Outputs ``outs`` in one launch.  If their rows
         turn out not to fit in HBM beside what is resident -- the estimate of _group_limit assumes
         typical lifetimes -- the group is split in halves and tried again."""
         from . import hip_api
-        from .Output import Output
         try:
-            if sampler == 'device' and generator == 'pcg64':
-                # every Output follows its own seeded stream: one piece of the resident set each
-                src, whole = outs[0].source_desc(), size*len(outs)
-                for g, out in enumerate(outs):
-                    out._adopt_x0(context.sample_packets(
-                        size, first_seed + g, outs[0]._first_index, download=True,
-                        pcg64=(size, 0), piece=(g*size, whole), **src))
-            elif sampler == 'device':
-                lead = outs[0]
-                soa = context.sample_packets(size*len(outs), seed, lead._first_index,
-                                             download=True, **lead.source_desc())
-                for g, out in enumerate(outs):
-                    out._adopt_x0(soa[:, g*size:(g + 1)*size])
+            rule.fill_group(context, outs)
             Output.integrate_batch(outs, context)
         except hip_api.HipError as exc:
             if exc.code != hip_api.NXC_ERR_NOMEM or len(outs) < 2:
                 raise
             half = len(outs)//2
             print(f'{len(outs)} Outputs in one launch need more HBM than is free: two launches')
-            self._launch_group(outs[:half], context, sampler, generator, seed, size, first_seed)
-            self._launch_group(outs[half:], context, sampler, generator, seed, size,
-                               None if first_seed is None else first_seed + half)
+            self._launch_group(outs[:half], context, rule)
+            self._launch_group(outs[half:], context, rule)
 
     def _group_limit(self, size, context):
         """How many Outputs of ``size`` packets one launch may take: the packets' states and a

@@ -466,11 +466,10 @@ class ModelImage(ModelResult):
         sampler is drawn from the generator seeded ``seed + k``, so the packets with global index
         in [lo, hi) are the same packets whether this process handles the whole run or one shard
         of it.  The device sampler is counter-based on the global index
-        (generator='philox'), or follows the host sampler's own seeded streams, chunk k from
-        ``seed + k`` (generator='pcg64': the same packets as sampler='numpy' to libm rounding,
-        drawn where they are integrated)."""
+        (generator='philox') or follows the host's streams (generator='pcg64'): draws.py."""
         from .Output import Output, n_output_steps
         from .distributed import chunk_plan
+        from .draws import DrawAhead, Draws
         inputs = self.inputs
         opt = inputs.options
         # step_size = 0: the adaptive driver keeps one final row per packet; a chunk's rows are
@@ -478,85 +477,36 @@ class ModelImage(ModelResult):
         variable = opt.step_size == 0
         hi = total if hi is None else hi
         ctx = self.context()
-        if seed is None and sampler == 'device':
-            # an unseeded run: one fresh key for all its chunks (recorded; default_rng(None) of
-            # the host sampler is entropy-seeded too), not the same key 0 for every run
-            from .Output import fresh_key
-            seed = fresh_key()
-        self.seed = seed
+        rule = Draws(sampler, generator, seed)          # (an unseeded device run: one fresh key)
+        self.seed = seed = rule.seed
         chunk = int(packs_per_it) if packs_per_it else max(1, min(total, 20_000_000))
         nsteps, n_iter = (1, 0) if variable else \
             n_output_steps(opt.endtime.value, float(opt.step_size))
-        first = True
         totals = {}
-        src = bounce = bodies = None
         plan = list(chunk_plan(total, chunk, lo, hi))
-
-        from .source_distribution import WindowGenerator
-        windowed = seed is not None and WindowGenerator.windowable(inputs)
-
-        def host_chunk(k, clen, lo_row, hi_row):
-            # a rank that owns only rows [lo_row, hi_row) of the chunk draws only those (the
-            # seeded stream is jumped into with PCG64.advance: bit-identical to slicing the whole
-            # draw); sources whose draws cannot be windowed draw the chunk and slice
-            if windowed and (lo_row, hi_row) != (0, clen):
-                return Output(inputs, clen, seed=seed + k, window=(clen, lo_row, hi_row),
-                              integrate=False, save=False, context=ctx)
-            return Output(inputs, clen, seed=None if seed is None else seed + k,
-                          integrate=False, save=False, context=ctx)
-
         # host-sampled chunks are independent generators (seed + k): the next ones are drawn by
         # worker threads (NumPy releases the GIL) while the device integrates the current one
-        ahead, pool = {}, None
-        if sampler != 'device' and len(plan) > 1:
-            from concurrent.futures import ThreadPoolExecutor
-            pool = ThreadPoolExecutor(max_workers=min(len(plan), HOST_SAMPLER_THREADS))
+        ahead = None if sampler == 'device' or len(plan) < 2 else DrawAhead(
+            lambda piece: rule.chunk_output(inputs, ctx, piece), plan,
+            min(len(plan), HOST_SAMPLER_THREADS))
         try:
-            for position, (k, c0, clen, a, b) in enumerate(plan):
-                n = b - a
-                if sampler == 'device' and generator == 'pcg64':
-                    if seed is None:
-                        raise ValueError("generator='pcg64' needs a seed")
-                    if first:
-                        out = Output(inputs, clen, seed=seed + k, integrate=False, save=False,
-                                     context=ctx, sampler='device', generator='pcg64',
-                                     window=(clen, a - c0, b - c0), first_index=a,
-                                     materialize_x0=False)
-                        src, bounce, bodies = out.source_desc(), out._bounce, out._bodies
-                    else:
-                        ctx.sample_packets(n, seed + k, a, pcg64=(clen, a - c0), **src)
-                elif sampler == 'device' and not first:
-                    # same inputs, next slice of the counter space: no need to rebuild the tables
-                    ctx.sample_packets(n, 0 if seed is None else seed, a, **src)
-                elif sampler == 'device':     # one counter space: packet i is draw block i
-                    out = Output(inputs, n, seed=seed, integrate=False, save=False, context=ctx,
-                                 sampler='device', first_index=a, materialize_x0=False)
-                    src, bounce, bodies = out.source_desc(), out._bounce, out._bodies
+            for piece in plan:
+                a, n = piece[3], piece[4] - piece[3]
+                if ahead is not None:
+                    ahead.fill(HOST_SAMPLER_THREADS)
+                    out = ahead.popleft().result()
                 else:
-                    if pool is not None:
-                        for later in plan[position:position + HOST_SAMPLER_THREADS]:
-                            if later[0] not in ahead:
-                                ahead[later[0]] = pool.submit(host_chunk, later[0], later[2],
-                                                              later[3] - later[1],
-                                                              later[4] - later[1])
-                        out = ahead.pop(k).result()
-                    else:
-                        out = host_chunk(k, clen, a - c0, b - c0)
-                    bounce, bodies = out._bounce, out._bodies
+                    out = rule.chunk_output(inputs, ctx, piece)
                 if variable:
-                    assert bounce is None, 'Not set up'                  # Output.py:312-315
-                if first:
+                    assert out._bounce is None, 'Not set up'             # Output.py:312-315
+                if piece is plan[0]:
                     ctx.set_forces(**out.forces_kwargs())
                     # (adaptive step: the rows come narrowed from their store, not from the kernel)
                     self._set_image(ctx, out.aplanet, out.vrplanet,
                                     downcast and not variable)           # clears the image
-                    first = False
-                if sampler != 'device':
-                    soa = out.x0_soa()
-                    ctx.upload_soa(soa if soa.shape[1] == n
-                                   else np.ascontiguousarray(soa[:, a-c0:b-c0]))
-                ctx.set_bounce(bounce)
-                ctx.set_bodies(bodies)
+                rule.upload_chunk(ctx, out, piece)       # (device draws are resident)
+                ctx.set_bounce(out._bounce)
+                ctx.set_bodies(out._bodies)
                 ctx.set_first_index(a)
                 if variable:
                     self._var_chunk(ctx, opt, downcast, totals)
@@ -568,11 +518,11 @@ class ModelImage(ModelResult):
                 self.totalsource += n * nsteps
                 self.npackets += n
         finally:
-            if pool is not None:
-                pool.shutdown(cancel_futures=True)
+            if ahead is not None:
+                ahead.pool.shutdown(cancel_futures=True)
         self.counters = totals
         assert totals.get('nonfinite', 0) == 0, 'Non-finite weights'
-        if first:       # an empty shard still owns a resident (zero) image for the reduce
+        if not plan:    # an empty shard still owns a resident (zero) image for the reduce
             out = Output(inputs, 0, seed=seed, integrate=False, save=False, context=ctx)
             ctx.set_forces(**out.forces_kwargs())
             self._set_image(ctx, out.aplanet, out.vrplanet, downcast)

@@ -29,6 +29,7 @@ import select
 import tempfile
 import threading
 import time
+from collections import namedtuple
 
 import numpy as np
 
@@ -61,6 +62,24 @@ def chunk_plan(total, chunk, lo=0, hi=None):
         if b > a:
             yield k, c0, clen, a, b
         k += 1
+
+
+PlannedOutput = namedtuple('PlannedOutput', 'number call_number size first_index')
+PassPlan = namedtuple('PassPlan', 'outputs passes size made drawn')
+
+
+def pass_plan(have, want, chunk, made, drawn, rank=0, world=1):
+    """One pass of Input.run (Input.py:243-246) as a value, ``made`` Outputs into this call of
+    run and ``drawn`` the next free global packet index: ``passes = ceil(todo / size)`` Outputs of
+    ``size = min(todo, chunk)`` packets (the last may overshoot); Output j is number ``made + j``
+    of the call, its packets ``drawn + size*j`` onwards, whoever makes it.  ``outputs``: those of
+    ``rank``; ``made`` and ``drawn`` of the result: after the whole pass, for the next one."""
+    todo = int(want) - int(have)
+    size = min(todo, int(chunk))
+    passes = -(-todo // size)
+    lo, hi = shard_range(passes, rank, world)
+    mine = [PlannedOutput(j, made + j, size, drawn + size*j) for j in range(lo, hi)]
+    return PassPlan(mine, passes, size, made + passes, drawn + size*passes)
 
 
 # ---- control plane ---------------------------------------------------------------------------
