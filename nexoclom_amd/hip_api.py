@@ -13,57 +13,13 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # NEXOCLOM_HIP_LIB: load another build of the same library (installation elsewhere, experiments)
 LIB_PATH = os.environ.get('NEXOCLOM_HIP_LIB') or os.path.join(_HERE, 'lib', 'libnexoclom_hip.so')
-_dp = C.POINTER(C.c_double)
+_dp, _fp, _cp = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_char)
+_i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+_u8p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
 NXC_MAX_LINES = 4
 NXC_RUN_IMAGE = 1
 NXC_UNIQUE_ID_BYTES = 128
 
-# every symbol include/nexoclom_hip.h declares
-EXPORTS = ('nxc_abi_version', 'nxc_device_count', 'nxc_last_error_string', 'nxc_create',
-           'nxc_destroy', 'nxc_device_name', 'nxc_synchronize', 'nxc_set_forces',
-           'nxc_set_image', 'nxc_state', 'nxc_rk5_step', 'nxc_packets_upload', 'nxc_image_clear',
-           'nxc_image_download', 'nxc_counters_get', 'nxc_last_kernel_ms', 'nxc_integrate_const',
-           'nxc_integrate_const_async', 'nxc_integrate_var', 'nxc_image_accumulate',
-           'nxc_image_accumulate_f32',
-           'nxc_comm_unique_id', 'nxc_comm_init', 'nxc_comm_destroy', 'nxc_image_allreduce',
-           'nxc_allreduce_max_f64', 'nxc_barrier', 'nxc_math_batch', 'nxc_los_accumulate',
-           'nxc_los_accumulate_f32', 'nxc_packets_sample',
-           'nxc_set_bounce', 'nxc_set_first_index', 'nxc_set_bodies',
-           'nxc_integrate_const_rows', 'nxc_rows_fetch', 'nxc_rows_fetch_f32', 'nxc_device_bus_id',
-           'nxc_allreduce_sum_f64', 'nxc_rows_build', 'nxc_rows_info', 'nxc_rows_download',
-           'nxc_rows_free', 'nxc_image_accumulate_rows', 'nxc_los_accumulate_rows', 'nxc_mem_info',
-           'nxc_stream_copy_gbs', 'nxc_shader_clock_mhz', 'nxc_pcg64_uniforms',
-           'nxc_integrate_const_streamed', 'nxc_image_mode', 'nxc_allreduce_f64',
-           'nxc_comm_set_timeout', 'nxc_comm_abort', 'nxc_comm_request_abort',
-           'nxc_comm_test_stall', 'nxc_packets_upload_pieces', 'nxc_density_set',
-           'nxc_density_accumulate', 'nxc_density_accumulate_f32', 'nxc_density_accumulate_rows',
-           'nxc_density_download', 'nxc_pairs_create', 'nxc_pairs_free', 'nxc_pairs_count',
-           'nxc_pairs_download', 'nxc_los_set_pairs', 'nxc_fit_set', 'nxc_fit_source_rows',
-           'nxc_fit_source', 'nxc_fit_source_f32', 'nxc_fit_packets', 'nxc_fit_radiance',
-           'nxc_fit_rows', 'nxc_fit_download', 'nxc_source_map_set', 'nxc_source_map_accumulate',
-           'nxc_source_map_download', 'nxc_set_stick_map', 'nxc_integrate_var_resident',
-           'nxc_var_rows_build', 'nxc_camera_set', 'nxc_camera_accumulate',
-           'nxc_camera_accumulate_f32', 'nxc_camera_accumulate_rows', 'nxc_camera_download',
-           'nxc_density_moments_enable', 'nxc_density_moments_accumulate',
-           'nxc_density_moments_accumulate_f32', 'nxc_density_moments_accumulate_rows',
-           'nxc_density_moments_download',
-           'nxc_image_moments_enable', 'nxc_image_moments_accumulate',
-           'nxc_image_moments_accumulate_f32', 'nxc_image_moments_accumulate_rows',
-           'nxc_image_moments_download',
-           'nxc_camera_moments_enable', 'nxc_camera_moments_accumulate',
-           'nxc_camera_moments_accumulate_f32', 'nxc_camera_moments_accumulate_rows',
-           'nxc_camera_moments_download',
-           'nxc_image_cube_enable', 'nxc_image_cube_accumulate', 'nxc_image_cube_accumulate_f32',
-           'nxc_image_cube_accumulate_rows', 'nxc_image_cube_download',
-           'nxc_camera_cube_enable', 'nxc_camera_cube_accumulate', 'nxc_camera_cube_accumulate_f32',
-           'nxc_camera_cube_accumulate_rows', 'nxc_camera_cube_download',
-           'nxc_density_spectrum_enable', 'nxc_density_spectrum_accumulate',
-           'nxc_density_spectrum_accumulate_f32', 'nxc_density_spectrum_accumulate_rows',
-           'nxc_density_spectrum_download',
-           'nxc_los_profile_enable', 'nxc_los_profile_accumulate', 'nxc_los_profile_accumulate_f32',
-           'nxc_los_profile_accumulate_rows', 'nxc_los_profile_download',
-           'nxc_shell_set', 'nxc_shell_accumulate', 'nxc_shell_accumulate_f32',
-           'nxc_shell_accumulate_rows', 'nxc_shell_download')
 ABI_VERSION = 3
 
 
@@ -107,7 +63,7 @@ class nxc_los_desc(C.Structure):
 class nxc_density_desc(C.Structure):
     _fields_ = [('origin', C.c_double*3), ('h', C.c_double), ('dr', C.c_double),
                 ('dims', C.c_int64*3), ('n_points', C.c_int64), ('points', _dp),
-                ('cell_start', C.POINTER(C.c_int32))]
+                ('cell_start', _i32p)]
 
 
 class nxc_density_spectrum_desc(C.Structure):
@@ -137,14 +93,14 @@ class nxc_source_map_desc(C.Structure):
                 ('nalt', C.c_int64), ('naz', C.c_int64), ('tile', C.c_int64), ('r_km', C.c_double),
                 ('alt_edges', _dp), ('az_edges', _dp), ('lon_edges', _dp), ('lat_edges', _dp),
                 ('point_lon', _dp), ('point_lat', _dp), ('point_cos', _dp), ('threshold', _dp),
-                ('n_seg', C.c_int64), ('seg', C.POINTER(C.c_int32)),
-                ('seg_off', C.POINTER(C.c_int32))]
+                ('n_seg', C.c_int64), ('seg', _i32p),
+                ('seg_off', _i32p)]
 
 
 class nxc_fit_desc(C.Structure):
     _fields_ = [('n_spectra', C.c_int64), ('weight_mode', C.c_int32), ('reserved', C.c_int32),
                 ('position', _dp), ('ratio', _dp), ('weight', _dp),
-                ('mask', C.POINTER(C.c_uint8))]
+                ('mask', _u8p)]
 
 
 class nxc_source_desc(C.Structure):
@@ -191,6 +147,136 @@ class nxc_counters(C.Structure):
                  'neg_frac', 'unfinished', 'wave_trips')]
 
 
+# The argument types of every function include/nexoclom_hip.h declares, in the header's order of
+# sections.  load_library() hands them to ctypes, which then converts and checks each call;
+# tests/test_abi.py holds them against the prototypes of the header itself.
+_int, _i32, _i64, _u32, _dbl = C.c_int, C.c_int32, C.c_int64, C.c_uint32, C.c_double
+_h = C.c_void_p                          # nxc_handle *, nxc_rows *, nxc_pairs *, void *
+_out = C.POINTER(C.c_void_p)             # nxc_rows **, nxc_pairs **, nxc_handle **
+_los_results = (_i64, _dp, _i64p, _u8p, _i64, _i64p, _i64p)   # n_index .. n_used
+
+
+def _sample_entries(name, ncols, head=(), index=False, tail=()):
+    """The three entries that read stored samples: ``name`` (P rows of ``ncols`` double columns),
+    ``name``_f32 (float columns) and ``name``_rows (a row store, first, count).  ``head`` and
+    ``tail`` are the arguments around the samples; ``index``: the samples come with their packet
+    index (host columns: an int64 column; rows: the shift of the store's own)."""
+    host = {name + suffix: (_h, *head, _i64, *[col]*ncols, *[_i64p]*index, *tail)
+            for suffix, col in (('', _dp), ('_f32', _fp))}
+    return {**host, name + '_rows': (_h, *head, _h, _i64, _i64, *[_i64]*index, *tail)}
+
+
+def _desc(struct):
+    return (_h, C.POINTER(struct))
+
+
+SIGNATURES = {
+    'nxc_abi_version': (),
+    'nxc_device_count': (C.POINTER(_int),),
+    'nxc_last_error_string': (),
+    'nxc_create': (_int, _out),
+    'nxc_destroy': (_h,),
+    'nxc_device_name': (_h, _cp, _int),
+    'nxc_device_bus_id': (_h, _cp, _int),
+    'nxc_synchronize': (_h,),
+    'nxc_mem_info': (_h, _u64p, _u64p),
+    'nxc_set_forces': _desc(nxc_forces),
+    'nxc_set_image': _desc(nxc_image_desc),
+    'nxc_set_bounce': _desc(nxc_bounce_desc),
+    'nxc_set_first_index': (_h, _i64),
+    'nxc_set_stick_map': _desc(nxc_stick_map_desc),
+    'nxc_set_bodies': _desc(nxc_bodies_desc),
+    'nxc_state': (_h, _i64, *[_dp]*8),
+    'nxc_rk5_step': (_h, _i64, _dp, _dp, _dp, _dp),
+    'nxc_packets_upload': (_h, _i64, _dp),
+    'nxc_packets_upload_pieces': (_h, _i32, _i64p, C.POINTER(_dp)),
+    'nxc_image_clear': (_h,),
+    'nxc_image_download': (_h, _dp, _u64p),
+    'nxc_counters_get': _desc(nxc_counters),
+    'nxc_last_kernel_ms': (_h, _fp),
+    'nxc_packets_sample': (*_desc(nxc_source_desc), _i64, _dp),
+    'nxc_integrate_const': (_h, _dbl, _i64, _dbl, _u32, _dp, _i64, _dp, _i64p),
+    'nxc_integrate_const_rows': (_h, _dbl, _i64, _dbl, _i64p, _i64p),
+    'nxc_rows_fetch': (_h, _dp),
+    'nxc_rows_fetch_f32': (_h, _fp),
+    'nxc_rows_build': (_h, _int, _out),
+    'nxc_rows_info': (_h, _i64p, _i32p),
+    'nxc_rows_download': (_h, _h, _i64, _i64, _h, _h),
+    'nxc_rows_free': (_h, _h),
+    'nxc_integrate_const_async': (_h, _dbl, _i64, _dbl, _u32),
+    'nxc_integrate_const_streamed': (_h, _i64, _dp, _i32, _dbl, _i64, _dbl, _u32),
+    'nxc_integrate_var': (_h, _dbl, _dbl, _i64, _dp, _dp),
+    'nxc_integrate_var_resident': (_h, _dbl, _dbl, _i64, _dp),
+    'nxc_var_rows_build': (_h, _int, _int, _out, _u8p),
+    **_sample_entries('nxc_image_accumulate', 5),
+    'nxc_image_mode': (_h, _int, _int, _i64),
+    **_sample_entries('nxc_los_accumulate', 5, (C.POINTER(nxc_los_desc), _i64, _dp), True,
+                      _los_results),
+    'nxc_density_set': _desc(nxc_density_desc),
+    **_sample_entries('nxc_density_accumulate', 4),
+    'nxc_density_download': (_h, _dp, _dp),
+    'nxc_density_moments_enable': (_h, _int),
+    **_sample_entries('nxc_density_moments_accumulate', 7),
+    'nxc_density_moments_download': (_h, _dp),
+    'nxc_density_spectrum_enable': _desc(nxc_density_spectrum_desc),
+    **_sample_entries('nxc_density_spectrum_accumulate', 7),
+    'nxc_density_spectrum_download': (_h, _dp),
+    'nxc_camera_set': _desc(nxc_camera_desc),
+    **_sample_entries('nxc_camera_accumulate', 5),
+    'nxc_camera_download': (_h, _dp, _u64p),
+    'nxc_image_moments_enable': (_h, _int),
+    **_sample_entries('nxc_image_moments_accumulate', 7),
+    'nxc_image_moments_download': (_h, _dp),
+    'nxc_camera_moments_enable': (_h, _int),
+    **_sample_entries('nxc_camera_moments_accumulate', 7),
+    'nxc_camera_moments_download': (_h, _dp),
+    'nxc_image_cube_enable': (_h, _i64, _dbl, _dbl),
+    **_sample_entries('nxc_image_cube_accumulate', 7),
+    'nxc_image_cube_download': (_h, _dp),
+    'nxc_camera_cube_enable': (_h, _i64, _dbl, _dbl),
+    **_sample_entries('nxc_camera_cube_accumulate', 7),
+    'nxc_camera_cube_download': (_h, _dp),
+    'nxc_shell_set': _desc(nxc_shell_desc),
+    **_sample_entries('nxc_shell_accumulate', 5),
+    'nxc_shell_download': (_h, _dp, _u64p, _dp),
+    'nxc_los_profile_enable': (_h, _i64, _i64, _dbl, _dbl),
+    **_sample_entries('nxc_los_profile_accumulate', 7, (C.POINTER(nxc_los_desc), _i64, _dp), True,
+                      _los_results),
+    'nxc_los_profile_download': (_h, _dp, _dp),
+    'nxc_source_map_set': _desc(nxc_source_map_desc),
+    'nxc_source_map_accumulate': (_h, _i64, *[_dp]*6, _i32p, _dp, _i32, _dbl, _dp),
+    'nxc_source_map_download': (_h, _dp, _dp),
+    'nxc_pairs_create': (_h, _i64, _out),
+    'nxc_pairs_free': (_h, _h),
+    'nxc_pairs_count': (_h, _i64p),
+    'nxc_pairs_download': (_h, _h, _i64p, _i64p),
+    'nxc_los_set_pairs': (_h, _h),
+    'nxc_fit_set': _desc(nxc_fit_desc),
+    **_sample_entries('nxc_fit_source', 5, index=True),
+    'nxc_fit_packets': (_h, _h, _i64, _dp, _dp, _i32p, _dp, _dp),
+    'nxc_fit_radiance': (_h, _h, C.POINTER(nxc_los_desc)),
+    'nxc_fit_rows': (_h, _int, _out, _i64p),
+    'nxc_fit_download': (_h, _dp),
+    'nxc_comm_unique_id': (_u8p,),
+    'nxc_comm_init': (_h, _u8p, _int, _int),
+    'nxc_comm_destroy': (_h,),
+    'nxc_image_allreduce': (_h,),
+    'nxc_allreduce_max_f64': (_h, _dp),
+    'nxc_allreduce_sum_f64': (_h, _dp),
+    'nxc_barrier': (_h,),
+    'nxc_allreduce_f64': (_h, _dp, _i64),
+    'nxc_comm_set_timeout': (_h, _dbl),
+    'nxc_comm_abort': (_h,),
+    'nxc_comm_request_abort': (_h,),
+    'nxc_comm_test_stall': (_h, _dbl),
+    'nxc_stream_copy_gbs': (_h, _i64, _int, _dp),
+    'nxc_shader_clock_mhz': (_h, _dp),
+    'nxc_pcg64_uniforms': (_h, _u64p, _u64p, _i64, _i64, _i64, _i32, _dp),
+    'nxc_math_batch': (_h, _int, _i64, _dp, _dp, _dp),
+}
+RESTYPES = {'nxc_last_error_string': C.c_char_p}       # every other function returns an int status
+EXPORTS = tuple(SIGNATURES)
+
 _lib = None
 
 
@@ -207,8 +293,11 @@ def load_library():
     # by the runtime when it initialises, i.e. at the first HIP call -- none has been made yet.
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     lib = C.CDLL(LIB_PATH)
-    lib.nxc_last_error_string.restype = C.c_char_p
-    missing = [name for name in EXPORTS if not hasattr(lib, name)]
+    missing = [name for name in SIGNATURES if not hasattr(lib, name)]
+    for name, argtypes in SIGNATURES.items():
+        if name not in missing:
+            entry = getattr(lib, name)
+            entry.argtypes, entry.restype = argtypes, RESTYPES.get(name, C.c_int)
     # (an explicitly named build -- experiments comparing library versions -- may lack the newest
     # entry points; the in-tree library may not)
     if missing and not os.environ.get('NEXOCLOM_HIP_LIB'):
@@ -273,7 +362,7 @@ class RowStore:
             if self._r is None:
                 raise HipError('the row store has been freed')
             self.ctx._check(self.ctx.lib.nxc_rows_download(
-                self.ctx._h, self._r, C.c_int64(first), C.c_int64(count),
+                self.ctx._h, self._r, first, count,
                 rows.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p) if index else None))
         return rows, idx
 
@@ -303,7 +392,7 @@ class PairList:
     def __init__(self, ctx, capacity):
         self.ctx, self.capacity = ctx, int(capacity)
         self._p = C.c_void_p()
-        ctx._check(ctx.lib.nxc_pairs_create(ctx._h, C.c_int64(self.capacity), C.byref(self._p)))
+        ctx._check(ctx.lib.nxc_pairs_create(ctx._h, self.capacity, C.byref(self._p)))
 
     @property
     def count(self):
@@ -315,10 +404,9 @@ class PairList:
         """(2, n) int64: spectrum, row of every pair, in the order the pass wrote them."""
         n = self.count
         out = np.zeros((2, n), dtype=np.int64)
-        i64p = C.POINTER(C.c_int64)
         self.ctx._check(self.ctx.lib.nxc_pairs_download(self.ctx._h, self._p,
-                                                        out[0].ctypes.data_as(i64p),
-                                                        out[1].ctypes.data_as(i64p)))
+                                                        out[0].ctypes.data_as(_i64p),
+                                                        out[1].ctypes.data_as(_i64p)))
         return out
 
     def free(self):
@@ -339,7 +427,7 @@ class Context:
     def __init__(self, device=0):
         self.lib = load_library()
         self._h = C.c_void_p()
-        self._check(self.lib.nxc_create(C.c_int(device), C.byref(self._h)))
+        self._check(self.lib.nxc_create(device, C.byref(self._h)))
         self.device = device
         self.n_packets = 0
         self.image_shape = None
@@ -383,12 +471,12 @@ class Context:
 
     def device_name(self):
         buf = C.create_string_buffer(256)
-        self._check(self.lib.nxc_device_name(self._h, buf, C.c_int(256)))
+        self._check(self.lib.nxc_device_name(self._h, buf, 256))
         return buf.value.decode()
 
     def bus_id(self):
         buf = C.create_string_buffer(64)
-        self._check(self.lib.nxc_device_bus_id(self._h, buf, C.c_int(64)))
+        self._check(self.lib.nxc_device_bus_id(self._h, buf, 64))
         return buf.value.decode()
 
     def synchronize(self):
@@ -501,15 +589,14 @@ class Context:
         self._check(self.lib.nxc_set_bodies(self._h, C.byref(d)))
 
     def set_first_index(self, first_index):
-        self._check(self.lib.nxc_set_first_index(self._h, C.c_int64(int(first_index))))
+        self._check(self.lib.nxc_set_first_index(self._h, first_index))
 
     # -- a-2 / a-1 --------------------------------------------------------------------------
     def state(self, x, y, z, vy):
         x, y, z, vy = map(_f64, (x, y, z, vy))
         n = len(x)
         out = [np.empty(n) for _ in range(4)]
-        self._check(self.lib.nxc_state(self._h, C.c_int64(n), _p(x), _p(y), _p(z), _p(vy),
-                                       *[_p(o) for o in out]))
+        self._check(self.lib.nxc_state(self._h, n, *[_p(a) for a in (x, y, z, vy, *out)]))
         return np.stack(out[:3], axis=1), out[3]
 
     def rk5_step(self, X0, h, want_delta=False):
@@ -520,7 +607,7 @@ class Context:
         hh = _f64(np.broadcast_to(np.asarray(h, dtype=np.float64), (n,)))
         out = np.empty((8, n))
         delta = np.empty((8, n)) if want_delta else None
-        self._check(self.lib.nxc_rk5_step(self._h, C.c_int64(n), _p(soa), _p(hh), _p(out),
+        self._check(self.lib.nxc_rk5_step(self._h, n, _p(soa), _p(hh), _p(out),
                                           _p(delta) if want_delta else None))
         return np.ascontiguousarray(out.T), (np.ascontiguousarray(delta.T) if want_delta else None)
 
@@ -533,7 +620,7 @@ class Context:
     def upload_soa(self, soa):
         soa = _f64(soa)
         assert soa.ndim == 2 and soa.shape[0] == 8
-        self._check(self.lib.nxc_packets_upload(self._h, C.c_int64(soa.shape[1]), _p(soa)))
+        self._check(self.lib.nxc_packets_upload(self._h, soa.shape[1], _p(soa)))
         self.n_packets = soa.shape[1]
 
     def upload_soa_pieces(self, pieces):
@@ -543,7 +630,7 @@ class Context:
         assert all(p.ndim == 2 and p.shape[0] == 8 for p in pieces)
         counts = (C.c_int64*len(pieces))(*[p.shape[1] for p in pieces])
         ptrs = (_dp*len(pieces))(*[_p(p) for p in pieces])
-        self._check(self.lib.nxc_packets_upload_pieces(self._h, C.c_int32(len(pieces)), counts, ptrs))
+        self._check(self.lib.nxc_packets_upload_pieces(self._h, len(pieces), counts, ptrs))
         self.n_packets = int(sum(p.shape[1] for p in pieces))
 
     def sample_packets(self, n, seed, first_index=0, download=False, speed_table=None,
@@ -617,10 +704,11 @@ class Context:
             setattr(d, f'n_node_{name}', len(axis))
             setattr(d, f'node_{name}_cdf', _p(cdf))
             setattr(d, 'node_speed_v' if name == 'speed' else f'node_{name}', _p(axis))
-        out = np.empty((8, int(n))) if download else None
-        self._check(self.lib.nxc_packets_sample(self._h, C.byref(d), C.c_int64(int(n)),
+        n = int(n)
+        out = np.empty((8, n)) if download else None
+        self._check(self.lib.nxc_packets_sample(self._h, C.byref(d), n,
                                                 _p(out) if download else None))
-        self.n_packets = int(n) if piece is None else int(piece[1])
+        self.n_packets = n if piece is None else int(piece[1])
         return out
 
     def image_clear(self):
@@ -630,8 +718,7 @@ class Context:
         nx, nz = self.image_shape
         image = np.empty((nx, nz))
         counts = np.empty((nx, nz), dtype=np.uint64)
-        self._check(self.lib.nxc_image_download(self._h, _p(image),
-                                                counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        self._check(self.lib.nxc_image_download(self._h, _p(image), counts.ctypes.data_as(_u64p)))
         return image, counts
 
     def counters(self):
@@ -664,10 +751,9 @@ class Context:
         final = np.empty((8, n)) if want_final else None
         steps = np.empty(n, dtype=np.int64) if want_steps else None
         self._check(self.lib.nxc_integrate_const(
-            self._h, C.c_double(step), C.c_int64(n_iter), C.c_double(outeredge),
-            C.c_uint32(NXC_RUN_IMAGE if image else 0), _p(traj) if nrec else None,
-            C.c_int64(nrec), _p(final) if want_final else None,
-            steps.ctypes.data_as(C.POINTER(C.c_int64)) if want_steps else None))
+            self._h, step, n_iter, outeredge, NXC_RUN_IMAGE if image else 0,
+            _p(traj) if nrec else None, nrec, _p(final) if want_final else None,
+            steps.ctypes.data_as(_i64p) if want_steps else None))
         return dict(traj=traj, final=None if final is None else np.ascontiguousarray(final.T),
                     steps=steps)
 
@@ -680,28 +766,26 @@ class Context:
         lengths = np.empty(n, dtype=np.int64)
         total = C.c_int64(0)
         self._check(self.lib.nxc_integrate_const_rows(
-            self._h, C.c_double(step), C.c_int64(n_iter), C.c_double(outeredge),
-            lengths.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(total)))
+            self._h, step, n_iter, outeredge, lengths.ctypes.data_as(_i64p), C.byref(total)))
         if resident:
             # records on their way (10 slots) + the columns that stay (9 + index)
             self.make_room(int(total.value) * 20 * (4 if narrow else 8))
             handle = C.c_void_p()
-            self._check(self.lib.nxc_rows_build(self._h, C.c_int(int(narrow)), C.byref(handle)))
+            self._check(self.lib.nxc_rows_build(self._h, int(narrow), C.byref(handle)))
             store = RowStore(self, handle)
             self._stores.append(weakref.ref(store))
             return dict(lengths=lengths, store=store)
         rows = np.empty((9, int(total.value)), dtype=np.float32 if narrow else np.float64)
         if narrow:
             self._check(self.lib.nxc_rows_fetch_f32(
-                self._h, rows.ctypes.data_as(C.POINTER(C.c_float)) if total.value else None))
+                self._h, rows.ctypes.data_as(_fp) if total.value else None))
         else:
             self._check(self.lib.nxc_rows_fetch(self._h, _p(rows) if total.value else None))
         return dict(lengths=lengths, rows=rows)
 
     def integrate_const_async(self, step, n_iter, outeredge, image=True):
-        self._check(self.lib.nxc_integrate_const_async(
-            self._h, C.c_double(step), C.c_int64(n_iter), C.c_double(outeredge),
-            C.c_uint32(NXC_RUN_IMAGE if image else 0)))
+        self._check(self.lib.nxc_integrate_const_async(self._h, step, n_iter, outeredge,
+                                                       NXC_RUN_IMAGE if image else 0))
 
     def integrate_const_streamed(self, soa, step, n_iter, outeredge, image=True, pieces=16):
         """Upload the (8, N) host array and integrate it in one pipelined pass (the next piece
@@ -712,8 +796,8 @@ class Context:
         assert soa.ndim == 2 and soa.shape[0] == 8
         self._keep = soa                      # the copies read it until the stream is drained
         self._check(self.lib.nxc_integrate_const_streamed(
-            self._h, C.c_int64(soa.shape[1]), _p(soa), C.c_int32(pieces), C.c_double(step),
-            C.c_int64(n_iter), C.c_double(outeredge), C.c_uint32(NXC_RUN_IMAGE if image else 0)))
+            self._h, soa.shape[1], _p(soa), pieces, step, n_iter, outeredge,
+            NXC_RUN_IMAGE if image else 0))
         self.n_packets = soa.shape[1]
 
     def integrate_var(self, resolution, outeredge, max_steps=10**6, resident=False):
@@ -722,13 +806,11 @@ class Context:
         n = self.n_packets
         hs = np.empty(n)
         if resident:
-            self._check(self.lib.nxc_integrate_var_resident(
-                self._h, C.c_double(resolution), C.c_double(outeredge), C.c_int64(max_steps),
-                _p(hs)))
+            self._check(self.lib.nxc_integrate_var_resident(self._h, resolution, outeredge,
+                                                            max_steps, _p(hs)))
             return hs
         final = np.empty((8, n))
-        self._check(self.lib.nxc_integrate_var(self._h, C.c_double(resolution),
-                                               C.c_double(outeredge), C.c_int64(max_steps),
+        self._check(self.lib.nxc_integrate_var(self._h, resolution, outeredge, max_steps,
                                                _p(final), _p(hs)))
         return np.ascontiguousarray(final.T), hs
 
@@ -741,8 +823,8 @@ class Context:
         handle = C.c_void_p()
         kept = np.zeros(n, dtype=np.uint8)
         self._check(self.lib.nxc_var_rows_build(
-            self._h, C.c_int(int(bool(narrow))), C.c_int(int(bool(compress))), C.byref(handle),
-            kept.ctypes.data_as(C.POINTER(C.c_uint8))))
+            self._h, int(bool(narrow)), int(bool(compress)), C.byref(handle),
+            kept.ctypes.data_as(_u8p)))
         store = RowStore(self, handle)
         self._stores.append(weakref.ref(store))
         return store, kept.view(np.bool_)
@@ -755,7 +837,7 @@ class Context:
         (suffix '_f32'); anything else is taken as float64 (suffix '')."""
         if all(getattr(c, 'dtype', None) == np.float32 for c in cols):
             cols = [np.ascontiguousarray(c) for c in cols]
-            return '_f32', [c.ctypes.data_as(C.POINTER(C.c_float)) for c in cols], cols
+            return '_f32', [c.ctypes.data_as(_fp) for c in cols], cols
         cols = [_f64(c) for c in cols]
         return '', [_p(c) for c in cols], cols
 
@@ -772,19 +854,19 @@ class Context:
         if rows is not None:
             store, first, count = rows
             self._check(getattr(self.lib, entry_name + '_rows')(
-                self._h, self._rows_handle(store), C.c_int64(first), C.c_int64(count)))
+                self._h, self._rows_handle(store), first, count))
             return
         suffix, ptrs, cols = self._columns(cols)
-        self._check(getattr(self.lib, entry_name + suffix)(self._h, C.c_int64(len(cols[0])), *ptrs))
+        self._check(getattr(self.lib, entry_name + suffix)(self._h, len(cols[0]), *ptrs))
 
     # a pixel image's velocity products; ``prefix``: 'image' or 'camera', as in nxc_<prefix>_...
     def _moments_enable(self, prefix, on):
-        self._check(getattr(self.lib, f'nxc_{prefix}_moments_enable')(self._h, C.c_int(int(bool(on)))))
+        self._check(getattr(self.lib, f'nxc_{prefix}_moments_enable')(self._h, int(bool(on))))
 
     def _cube_enable(self, prefix, nv, v_lo, v_hi):
-        self._check(getattr(self.lib, f'nxc_{prefix}_cube_enable')(
-            self._h, C.c_int64(int(nv)), C.c_double(v_lo), C.c_double(v_hi)))
-        setattr(self, f'_{prefix}_cube_nv', int(nv))
+        nv = int(nv)
+        self._check(getattr(self.lib, f'nxc_{prefix}_cube_enable')(self._h, nv, v_lo, v_hi))
+        setattr(self, f'_{prefix}_cube_nv', nv)
 
     def _pixel_sums_download(self, prefix, what):
         per_pixel = (4,) if what == 'moments' else (getattr(self, f'_{prefix}_cube_nv', 0) + 2, 2)
@@ -824,9 +906,8 @@ class Context:
         """How stored samples reach the image: 'atomics' (one global atomic pair per binned
         sample), 'tiles' (filed by image tile, summed in LDS, handed over once per pixel), or
         'auto' (tiles from 2^17 samples on).  Packet counts are identical either way."""
-        self._check(self.lib.nxc_image_mode(self._h, C.c_int(self.IMAGE_MODES.get(mode, mode)),
-                                            C.c_int(int(tile_pixels)),
-                                            C.c_int64(int(slab_samples))))
+        self._check(self.lib.nxc_image_mode(self._h, self.IMAGE_MODES.get(mode, mode),
+                                            tile_pixels, slab_samples))
 
     def image_accumulate_rows(self, store, first=0, count=None):
         """Bin rows [first, first + count) of a RowStore: no host round trip."""
@@ -879,28 +960,52 @@ class Context:
         ``vx`` and ``vz`` (a row store carries them)."""
         if profile and rows is None and (vx is None or vz is None):
             raise ValueError('profile=True over host columns needs vx and vz')
-        velocity = (vx, vz) if profile else None
-        if pairs is None:
-            return self._los_accumulate(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet,
-                                        unit_cm, g_tables, ladder, sc, x, y, z, vy, frac, index,
-                                        n_index, used_cap, rows, velocity)
-        if used_cap:
+        if pairs is not None and used_cap:
             raise ValueError('used_cap and pairs exclude each other')
-        self._check(self.lib.nxc_los_set_pairs(self._h, pairs._p))
+        name = 'nxc_los_profile_accumulate' if profile else 'nxc_los_accumulate'
+        d, keep = self._los_desc(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm,
+                                 g_tables, ladder)
+        sc = _f64(sc)
+        S = sc.shape[1]
+        if rows is not None:
+            store, first, count, shift = rows
+            entry = getattr(self.lib, name + '_rows')
+            samples = (self._rows_handle(store), first, count, shift)
+        else:
+            suffix, ptrs, cols = self._columns((x, y, z, vx, vy, vz, frac) if profile else
+                                               (x, y, z, vy, frac))
+            idx = None if index is None else np.ascontiguousarray(index, dtype=np.int64)
+            entry = getattr(self.lib, name + suffix)
+            samples = (len(cols[0]), *ptrs, idx.ctypes.data_as(_i64p) if idx is not None else None)
+        radiance = np.zeros(S)
+        npackets = np.zeros(S, dtype=np.int64)
+        included = np.zeros(n_index, dtype=np.uint8) if n_index else None
+        used = np.zeros((2, used_cap), dtype=np.int64) if used_cap else None
+        n_used = C.c_int64(0)
+        if pairs is not None:          # the pass writes its used pairs there, not to ``used``
+            self._check(self.lib.nxc_los_set_pairs(self._h, pairs._p))
         try:
-            return self._los_accumulate(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet,
-                                        unit_cm, g_tables, ladder, sc, x, y, z, vy, frac, index,
-                                        n_index, 0, rows, velocity)
+            self._check(entry(
+                self._h, C.byref(d), S, _p(sc), *samples, n_index, _p(radiance),
+                npackets.ctypes.data_as(_i64p),
+                included.ctypes.data_as(_u8p) if included is not None else None,
+                used_cap, used.ctypes.data_as(_i64p) if used is not None else None,
+                C.byref(n_used)))
         finally:
-            self.lib.nxc_los_set_pairs(self._h, None)
+            if pairs is not None:
+                self.lib.nxc_los_set_pairs(self._h, None)
+        m = min(int(n_used.value), used_cap)
+        return dict(radiance=radiance, npackets=npackets,
+                    included=None if included is None else included.astype(bool),
+                    used=None if used is None else used[:, :m], n_used=int(n_used.value))
 
     def los_profile_enable(self, S, nv, v_lo=0.0, v_hi=0.0):
         """Allocate and zero the line-of-sight profile of ``S`` spectra: ``nv`` bins over
         [v_lo, v_hi) [R/s] and four moment sums per spectrum (``nv`` 0 frees it; a second enable
         replaces and zeroes it)."""
-        self._check(self.lib.nxc_los_profile_enable(self._h, C.c_int64(int(S)), C.c_int64(int(nv)),
-                                                    C.c_double(v_lo), C.c_double(v_hi)))
-        self._los_profile_shape = (int(S), int(nv)) if int(nv) else None
+        S, nv = int(S), int(nv)
+        self._check(self.lib.nxc_los_profile_enable(self._h, S, nv, v_lo, v_hi))
+        self._los_profile_shape = (S, nv) if nv else None
 
     def los_profile_download(self):
         """(sums (S, nv + 2, 2), moments (S, 4)) float64: {sum w, sum w w} per spectrum and
@@ -924,43 +1029,6 @@ class Context:
         d.n_ladder, d.ladder = len(lad), _p(lad)
         return d, keep
 
-    def _los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm,
-                        g_tables, ladder, sc, x, y, z, vy, frac, index, n_index, used_cap, rows,
-                        velocity=None):
-        """``velocity``: None for the plain entries, (vx, vz) for the profile's."""
-        name = 'nxc_los_accumulate' if velocity is None else 'nxc_los_profile_accumulate'
-        d, keep = self._los_desc(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm,
-                                 g_tables, ladder)
-        sc = _f64(sc)
-        S = sc.shape[1]
-        i64p = C.POINTER(C.c_int64)
-        if rows is not None:
-            store, first, count, shift = rows
-            entry = getattr(self.lib, name + '_rows')
-            samples = (self._rows_handle(store), C.c_int64(first), C.c_int64(count), C.c_int64(shift))
-        else:
-            suffix, ptrs, cols = self._columns((x, y, z, vy, frac) if velocity is None else
-                                               (x, y, z, velocity[0], vy, velocity[1], frac))
-            idx = None if index is None else np.ascontiguousarray(index, dtype=np.int64)
-            entry = getattr(self.lib, name + suffix)
-            samples = (C.c_int64(len(cols[0])), *ptrs,
-                       idx.ctypes.data_as(i64p) if idx is not None else None)
-        radiance = np.zeros(S)
-        npackets = np.zeros(S, dtype=np.int64)
-        included = np.zeros(n_index, dtype=np.uint8) if n_index else None
-        used = np.zeros((2, used_cap), dtype=np.int64) if used_cap else None
-        n_used = C.c_int64(0)
-        self._check(entry(
-            self._h, C.byref(d), C.c_int64(S), _p(sc), *samples, C.c_int64(n_index),
-            _p(radiance), npackets.ctypes.data_as(i64p),
-            included.ctypes.data_as(C.POINTER(C.c_uint8)) if included is not None else None,
-            C.c_int64(used_cap), used.ctypes.data_as(i64p) if used is not None else None,
-            C.byref(n_used)))
-        m = min(int(n_used.value), used_cap)
-        return dict(radiance=radiance, npackets=npackets,
-                    included=None if included is None else included.astype(bool),
-                    used=None if used is None else used[:, :m], n_used=int(n_used.value))
-
     # -- ModelDensity -----------------------------------------------------------------------
     def density_set(self, points, cell_start, origin, h, dr, dims):
         """Upload a query-point index (ModelDensity.DensityIndex: points (Q, 3) sorted by cell,
@@ -973,7 +1041,7 @@ class Context:
         d.dims[:] = [int(v) for v in dims]
         d.n_points = len(pts)
         d.points = _p(pts) if len(pts) else None
-        d.cell_start = starts.ctypes.data_as(C.POINTER(C.c_int32))
+        d.cell_start = starts.ctypes.data_as(_i32p)
         self._check(self.lib.nxc_density_set(self._h, C.byref(d)))
         self._density_q = len(pts)
         self._density_spectrum_nv = 0            # the set switches the spectrum off
@@ -993,7 +1061,7 @@ class Context:
     def density_moments_enable(self, on=True):
         """After ``density_set``: allocate and zero the ten velocity-moment sums per indexed point
         (``on`` false switches them off; so does the next ``density_set``)."""
-        self._check(self.lib.nxc_density_moments_enable(self._h, C.c_int(int(bool(on)))))
+        self._check(self.lib.nxc_density_moments_enable(self._h, int(bool(on))))
 
     def density_moments_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
                                    frac=None, rows=None):
@@ -1077,7 +1145,7 @@ class Context:
         image = np.zeros(shape)
         counts = np.zeros(shape, dtype=np.uint64)
         self._check(self.lib.nxc_camera_download(
-            self._h, _p(image), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+            self._h, _p(image), counts.ctypes.data_as(_u64p)))
         return image, counts
 
     def camera_moments_enable(self, on=True):
@@ -1142,7 +1210,7 @@ class Context:
         counts = np.zeros((nlon, nlat), dtype=np.uint64)
         sums = np.zeros((2, nlon, nlat, nalt + 2, 2))
         self._check(self.lib.nxc_shell_download(
-            self._h, _p(column), counts.ctypes.data_as(C.POINTER(C.c_uint64)), _p(sums)))
+            self._h, _p(column), counts.ctypes.data_as(_u64p), _p(sums)))
         return column, counts, sums
 
     # -- LOSResultFitted ----------------------------------------------------------------------
@@ -1165,7 +1233,7 @@ class Context:
         if weight_mode == 'sigma':
             w = _f64(weight)
             d.weight = _p(w)
-        d.mask = mask.ctypes.data_as(C.POINTER(C.c_uint8))
+        d.mask = mask.ctypes.data_as(_u8p)
         self._check(self.lib.nxc_fit_set(self._h, C.byref(d)))
         self._fit_s = S
 
@@ -1176,14 +1244,13 @@ class Context:
             store, first, count, shift = rows
             r = self._rows_handle(store)
             self._fit_store = store
-            self._check(self.lib.nxc_fit_source_rows(self._h, r, C.c_int64(first),
-                                                     C.c_int64(count), C.c_int64(shift)))
+            self._check(self.lib.nxc_fit_source_rows(self._h, r, first, count, shift))
             return
         self._fit_store = None
         suffix, ptrs, cols = self._columns((x, y, z, vy, frac))
         idx = np.ascontiguousarray(index, dtype=np.int64)
         self._check(getattr(self.lib, 'nxc_fit_source' + suffix)(
-            self._h, C.c_int64(len(idx)), *ptrs, idx.ctypes.data_as(C.POINTER(C.c_int64))))
+            self._h, len(idx), *ptrs, idx.ctypes.data_as(_i64p)))
 
     def fit_packets(self, pairs, n_packets):
         """Per packet num, den, cnt and the multiplier mult over ``pairs`` (a PairList) and the
@@ -1193,9 +1260,8 @@ class Context:
         num, den, mult = np.zeros(n), np.zeros(n), np.zeros(n)
         cnt = np.zeros(n, dtype=np.int32)
         stats = np.zeros(2)
-        self._check(self.lib.nxc_fit_packets(
-            self._h, pairs._p, C.c_int64(n), _p(num), _p(den),
-            cnt.ctypes.data_as(C.POINTER(C.c_int32)), _p(mult), _p(stats)))
+        self._check(self.lib.nxc_fit_packets(self._h, pairs._p, n, _p(num), _p(den),
+                                             cnt.ctypes.data_as(_i32p), _p(mult), _p(stats)))
         return dict(num=num, den=den, cnt=cnt, mult=mult, f_sum=float(stats[0]),
                     n_seen=int(stats[1]))
 
@@ -1208,8 +1274,8 @@ class Context:
         """(RowStore of the fitted rows, rows kept per packet) for a row-store source."""
         lengths = np.zeros(int(n_packets), dtype=np.int64)
         handle = C.c_void_p()
-        self._check(self.lib.nxc_fit_rows(self._h, C.c_int(int(bool(compress))), C.byref(handle),
-                                          lengths.ctypes.data_as(C.POINTER(C.c_int64))))
+        self._check(self.lib.nxc_fit_rows(self._h, int(bool(compress)), C.byref(handle),
+                                          lengths.ctypes.data_as(_i64p)))
         store = RowStore(self, handle)
         self._stores.append(weakref.ref(store))
         return store, lengths
@@ -1234,8 +1300,8 @@ class Context:
         (d.alt_edges, d.az_edges, d.lon_edges, d.lat_edges, d.point_lon, d.point_lat,
          d.point_cos, d.threshold) = (_p(a) for a in keep)
         d.n_seg = len(seg)
-        d.seg = seg.ctypes.data_as(C.POINTER(C.c_int32)) if len(seg) else None
-        d.seg_off = seg_off.ctypes.data_as(C.POINTER(C.c_int32))
+        d.seg = seg.ctypes.data_as(_i32p) if len(seg) else None
+        d.seg_off = seg_off.ctypes.data_as(_i32p)
         self._check(self.lib.nxc_source_map_set(self._h, C.byref(d)))
         self._smap = (int(grid.nlon)*int(grid.nlat), int(grid.nvel), int(grid.nalt), int(grid.naz))
 
@@ -1256,8 +1322,8 @@ class Context:
                              'from the grid')
         ptr = [(_p(c) if n else None) for c in cols]
         self._check(self.lib.nxc_source_map_accumulate(
-            self._h, C.c_int64(n), *ptr, starts.ctypes.data_as(C.POINTER(C.c_int32)), _p(edges),
-            C.c_int32(int(bool(available))), C.c_double(float(factor)), _p(small)))
+            self._h, n, *ptr, starts.ctypes.data_as(_i32p), _p(edges),
+            int(bool(available)), factor, _p(small)))
         return dict(speed_dist=small[:nvel], altitude_dist=small[nvel:nvel + nalt],
                     azimuth_dist=small[nvel + nalt:nvel + nalt + naz],
                     speed_gridsum=small[nvel + nalt + naz:])
@@ -1278,7 +1344,7 @@ class Context:
 
     def comm_init(self, unique_id, rank, nranks):
         buf = (C.c_uint8*NXC_UNIQUE_ID_BYTES).from_buffer_copy(unique_id)
-        self._check(self.lib.nxc_comm_init(self._h, buf, C.c_int(rank), C.c_int(nranks)))
+        self._check(self.lib.nxc_comm_init(self._h, buf, rank, nranks))
 
     def comm_destroy(self):
         self._check(self.lib.nxc_comm_destroy(self._h))
@@ -1303,13 +1369,13 @@ class Context:
         """Sum over the ranks of a small float64 array (returned; LOSResult.py:264-266 across
         GPUs)."""
         v = np.array(values, dtype=np.float64).ravel()
-        self._check(self.lib.nxc_allreduce_f64(self._h, _p(v), C.c_int64(v.size)))
+        self._check(self.lib.nxc_allreduce_f64(self._h, _p(v), v.size))
         return v.reshape(np.shape(values))
 
     def comm_set_timeout(self, seconds):
         """Deadline of every wait on a collective (default 120 s): past it the communicator is
         aborted and the waiting call raises HipError (code NXC_ERR_RCCL)."""
-        self._check(self.lib.nxc_comm_set_timeout(self._h, C.c_double(seconds)))
+        self._check(self.lib.nxc_comm_set_timeout(self._h, seconds))
 
     def comm_abort(self):
         self._check(self.lib.nxc_comm_abort(self._h))
@@ -1322,14 +1388,13 @@ class Context:
 
     def comm_test_stall(self, seconds):
         """Fault injection: the stream is busy for ``seconds`` as if a collective hung."""
-        self._check(self.lib.nxc_comm_test_stall(self._h, C.c_double(seconds)))
+        self._check(self.lib.nxc_comm_test_stall(self._h, seconds))
 
     # -- measurement helpers ----------------------------------------------------------------
     def stream_copy_gbs(self, nbytes=1 << 31, reps=5):
         """The box's streaming-copy rate, GB/s of bytes read + written."""
         gbs = C.c_double(0)
-        self._check(self.lib.nxc_stream_copy_gbs(self._h, C.c_int64(nbytes), C.c_int(reps),
-                                                 C.byref(gbs)))
+        self._check(self.lib.nxc_stream_copy_gbs(self._h, nbytes, reps, C.byref(gbs)))
         return float(gbs.value)
 
     def shader_clock_mhz(self):
@@ -1344,8 +1409,7 @@ class Context:
         as the device sampler's generator 1 forms them."""
         state, inc = pcg64_words(seed)
         out = np.empty((nvec, count))
-        self._check(self.lib.nxc_pcg64_uniforms(self._h, state, inc, C.c_int64(n), C.c_int64(row0),
-                                                C.c_int64(count), C.c_int32(nvec), _p(out)))
+        self._check(self.lib.nxc_pcg64_uniforms(self._h, state, inc, n, row0, count, nvec, _p(out)))
         return out
 
     def math(self, which, x, y=None):
@@ -1353,6 +1417,6 @@ class Context:
         x = _f64(x)
         out = np.empty_like(x)
         y2 = _f64(y) if y is not None else None
-        self._check(self.lib.nxc_math_batch(self._h, C.c_int(code), C.c_int64(len(x)), _p(x),
+        self._check(self.lib.nxc_math_batch(self._h, code, len(x), _p(x),
                                             _p(y2) if y2 is not None else None, _p(out)))
         return out
