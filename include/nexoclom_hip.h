@@ -1027,7 +1027,12 @@ int nxc_los_profile_download(nxc_handle *h, double *sums, double *moments);
  * Map per point: [nvel speed | nalt altitude | naz azimuth | n_total | n_included | weight sum],
  * then hist2d[npoints]: the unsmeared lon/lat histogram (np.histogram2d of the included packets).
  * Included: frac > 0; weight: frac, or 1 when `available`.
- *   nxc_source_map_set         uploads the grid and segments and zeroes the resident map
+ *   nxc_source_map_set         uploads the grid and segments and zeroes the resident map.  A grid
+ *                              whose kernels would ask for more than 64 KiB of LDS -- a tile's
+ *                              histograms and segment table, 8 * tile * (nvel + nalt + naz + 3) +
+ *                              8 * (longest segment list + 1) bytes, or the staged edges and
+ *                              whole-planet histograms, 8 * (2 * (nvel + nalt + naz) + nlon + nlat
+ *                              + 5) bytes -- is refused (NXC_ERR_ARG, the resident map unchanged)
  *   nxc_source_map_accumulate  adds one Output: n packets' lat, lon, v [R/s], altitude, azimuth,
  *                              frac (sorted), cell_start[ncells + 1], its speed edges [nvel + 1]
  *                              (speed = v * r_km); the speed histograms of the map are added times

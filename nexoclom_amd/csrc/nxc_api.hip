@@ -29,6 +29,7 @@
 #include "nxc_cube_check.hpp"
 #include "nxc_los_profile_check.hpp"
 #include "nxc_desc_check.hpp"
+#include "nxc_source_map_check.hpp"
 #include "nxc_devbuf.hpp"
 #include "nxc_image_block.hpp"
 #include "nxc_kernels.hpp"
@@ -3660,14 +3661,6 @@ int nxc_shell_download(nxc_handle *h, double *column, uint64_t *counts, double *
 namespace {
 size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
-bool linspace_ok(const double *e, int64_t n)
-{
-    if (!e || n < 1) return false;
-    for (int64_t k = 0; k <= n; k++)
-        if (!std::isfinite(e[k]) || (k && !(e[k] >= e[k - 1]))) return false;
-    return e[n] > e[0];
-}
-
 void set_axis(const double *e, int64_t n, double &lo, double &hi, double &inv)
 {
     lo = e[0];
@@ -3675,40 +3668,26 @@ void set_axis(const double *e, int64_t n, double &lo, double &hi, double &inv)
     inv = (double)n / (hi - lo);
 }
 
+// the dynamic LDS of k_smap_points and k_smap_prep (nxc_source_map_check.hpp; nxc_source_map_set
+// has held both to NXC_SMAP_LDS_BYTES)
 size_t smap_points_lds(const SmapK &K)
 {
-    return (size_t)8 * K.tile * smap_stride(K) + (size_t)4 * 2 * (K.nseg_max + 1);
+    return smap_points_lds_bytes(K.tile, K.nvel, K.nalt, K.naz, K.nseg_max);
 }
+
+size_t smap_prep_lds(const SmapK &K) { return smap_prep_lds_bytes(K.nvel, K.nalt, K.naz, K.nlon, K.nlat); }
 }  // namespace
 
 int nxc_source_map_set(nxc_handle *h, const nxc_source_map_desc *d)
 {
     return guarded([&]() -> int {
     if (!h || !d) return fail(NXC_ERR_ARG, "null argument");
-    const int64_t nlon = d->nlon, nlat = d->nlat;
-    if (nlon < 1 || nlat < 1 || d->nvel < 1 || d->nalt < 1 || d->naz < 1 || nlon * nlat > (1 << 24) ||
-        d->nvel + d->nalt + d->naz > (1 << 16) || d->tile < 1 || d->tile > nlon ||
-        !(d->r_km > 0.0) || !std::isfinite(d->r_km))
-        return fail(NXC_ERR_ARG, "bad nxc_source_map_desc grid");
-    if (!linspace_ok(d->alt_edges, d->nalt) || !linspace_ok(d->az_edges, d->naz) ||
-        !linspace_ok(d->lon_edges, nlon) || !linspace_ok(d->lat_edges, nlat))
-        return fail(NXC_ERR_ARG, "nxc_source_map_desc: edges must be finite and increasing");
-    if (!d->point_lon || !d->point_lat || !d->point_cos || !d->threshold || !d->seg_off ||
-        (d->n_seg && !d->seg))
-        return fail(NXC_ERR_ARG, "nxc_source_map_desc: null table");
-    const int64_t tpr = (nlon + d->tile - 1) / d->tile, ntiles = tpr * nlat, ncells = nlon * nlat;
-    // every segment is a run of existing cells, and the tiles' lists tile the segment array
-    if (d->seg_off[0] != 0 || d->seg_off[ntiles] != d->n_seg || d->n_seg > INT32_MAX)
-        return fail(NXC_ERR_ARG, "nxc_source_map_desc: segment offsets do not span the segments");
+    // the grid, the tables, the segment lists and the LDS of both kernels (nxc_source_map_check.hpp)
     int64_t nseg_max = 0;
-    for (int64_t t = 0; t < ntiles; t++) {
-        const int64_t c = d->seg_off[t + 1] - d->seg_off[t];
-        if (c < 0) return fail(NXC_ERR_ARG, "nxc_source_map_desc: segment offsets are not sorted");
-        nseg_max = std::max(nseg_max, c);
-    }
-    for (int64_t s = 0; s < d->n_seg; s++)
-        if (d->seg[2 * s] < 0 || d->seg[2 * s] > d->seg[2 * s + 1] || d->seg[2 * s + 1] >= ncells)
-            return fail(NXC_ERR_ARG, "nxc_source_map_desc: segment outside the grid");
+    const std::string why = check_source_map_desc(d, &nseg_max);
+    if (!why.empty()) return fail(NXC_ERR_ARG, why);
+    const int64_t nlon = d->nlon, nlat = d->nlat;
+    const int64_t tpr = (nlon + d->tile - 1) / d->tile, ntiles = tpr * nlat, ncells = nlon * nlat;
     SmapK K{};
     K.r_km = d->r_km;
     K.nlon = (int)nlon; K.nlat = (int)nlat;
@@ -3718,8 +3697,6 @@ int nxc_source_map_set(nxc_handle *h, const nxc_source_map_desc *d)
     set_axis(d->az_edges, d->naz, K.az_lo, K.az_hi, K.az_inv);
     set_axis(d->lon_edges, nlon, K.lon_lo, K.lon_hi, K.lon_inv);
     set_axis(d->lat_edges, nlat, K.lat_lo, K.lat_hi, K.lat_inv);
-    if (smap_points_lds(K) > 64 * 1024)
-        return fail(NXC_ERR_ARG, "nxc_source_map_desc: a tile's histograms exceed 64 KiB of LDS");
     HIPCHK(hipSetDevice(h->device));
     h->have_smap = false;
     const int64_t npoints = ncells, stride = smap_stride(K);
@@ -3768,7 +3745,7 @@ int nxc_source_map_accumulate(nxc_handle *h, int64_t n, const double *lat, const
     if (n < 0 || n > INT32_MAX || !cell_start || !small ||
         (n && (!lat || !lon || !v || !alt || !az || !frac)) || !std::isfinite(factor))
         return fail(NXC_ERR_ARG, "bad arguments");
-    if (!linspace_ok(vel_edges, K.nvel))
+    if (!smap_linspace_ok(vel_edges, K.nvel))
         return fail(NXC_ERR_ARG, "speed edges must be finite and increasing");
     const int64_t nc = h->smap_ncells;
     if (cell_start[0] != 0 || cell_start[nc] > n)
@@ -3819,7 +3796,7 @@ int nxc_source_map_accumulate(nxc_handle *h, int64_t n, const double *lat, const
     const int2 *seg = reinterpret_cast<const int2 *>(gb + off_seg);
     if ((rc = begin_timed(h))) return rc;
     if (n) {
-        const size_t lds = 8 * (ne + (size_t)nh);
+        const size_t lds = smap_prep_lds(K);      // 8 * (ne + nh), within NXC_SMAP_LDS_BYTES since set
         const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((n + NXC_BLOCK - 1) / NXC_BLOCK,
                                                                     (int64_t)h->n_cu * 8));
         hipLaunchKernelGGL(k_smap_prep, dim3((unsigned)grid), dim3(NXC_BLOCK), lds, h->stream, K, (int)n,
