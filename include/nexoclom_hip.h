@@ -1178,6 +1178,51 @@ int nxc_pcg64_uniforms(nxc_handle *h, const uint64_t state[2], const uint64_t in
 int nxc_math_batch(nxc_handle *h, int which, int64_t n, const double *in, const double *in2,
                    double *out);
 
+/* ---- Moon-centred frame: stored rows moved into the frame that co-rotates with a moon -----------
+ * EXTENSION -- the reference stops at planets with moons (Output.py:153-155).  A constant-step run
+ * stores every step of every packet, and the stored-sample products read a row at t_remaining = t
+ * as a packet of age t0 - t seen at the epoch t_remaining = 0.  That steady-state reading holds in
+ * a frame in which the source stands still: for a run launched from a moon, the frame that
+ * co-rotates with the moon.  Moon m (nxc_bodies_desc) has radius rad and orbit radius a [R], rate
+ * omega [rad/s] and phase phi at t_remaining = 0; at t_remaining = t it is at
+ * a (-sin(phi - omega t), cos(phi - omega t), 0).  The host forms in fp64
+ *     M = a (-sin phi, cos phi, 0)               the moon at the epoch              [R]
+ *     U = a omega (-cos phi, -sin phi, 0)        its velocity at the epoch          [R/s]
+ *     scale = k = 1 / rad
+ * and every row (t, x, y, z, vx, vy, vz, frac, lossfrac, index) becomes
+ *     theta = omega * t  (one fp64 product),  (s, c) = sincos(theta)
+ *     q = (c x - s y,  s x + c y,  z)          p' = (q - M) * k
+ *     w = (c vx - s vy, s vx + c vy, vz)       v' = (w - U) * k
+ * with t, frac, lossfrac and index copied bit for bit: the rotation about z by +omega t carries the
+ * moon of the row's time onto the moon of the epoch.  One rounding per operation, in the order
+ * written; float32 stores are widened, computed in fp64 and rounded once.  Lengths come out in moon
+ * radii and velocities in moon radii per second relative to the moon; the axes stay parallel to the
+ * model frame (Sun at -y), so sub-observer angles, local time and the shadow test keep their
+ * meaning, with the unit sphere at the origin now the moon.  The Sun-relative radial velocity the
+ * g-values need is vy' + (vrplanet + U_y) in the moved unit: a consumer adds U_y * k to the vrplanet
+ * it is set with.  The planet neither occults nor shadows in this frame.
+ *   nxc_frame_rows         rows [first, first + count) of src as a new store of count rows of
+ *                          src's width (the caller frees it with nxc_rows_free)
+ *   nxc_frame_columns[_f32]  p rows of host columns; out [6][p]: x', y', z', vx', vy', vz'
+ * The three give identical bits for identical input (one kernel, k_frame_rows).  p = 0 or
+ * count = 0 does nothing (nxc_frame_rows then delivers a store without rows).  Refused with
+ * NXC_ERR_ARG (host-only code, nxc_frame_check.hpp): a null description, a field that is not
+ * finite, scale <= 0, first or count outside the store, a null column with p > 0. */
+typedef struct nxc_frame_desc {
+    double omega;             /* rad/s                                                             */
+    double M[3];              /* R: the moon at t_remaining = 0                                    */
+    double U[3];              /* R/s: its velocity then                                            */
+    double scale;             /* k = 1 / (the moon's radius in R)                                  */
+} nxc_frame_desc;
+int nxc_frame_rows(nxc_handle *h, const nxc_frame_desc *d, const nxc_rows *src, int64_t first,
+                   int64_t count, nxc_rows **out);
+int nxc_frame_columns(nxc_handle *h, const nxc_frame_desc *d, int64_t p, const double *t,
+                      const double *x, const double *y, const double *z, const double *vx,
+                      const double *vy, const double *vz, double *out);
+int nxc_frame_columns_f32(nxc_handle *h, const nxc_frame_desc *d, int64_t p, const float *t,
+                          const float *x, const float *y, const float *z, const float *vx,
+                          const float *vy, const float *vz, float *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,9 @@ operation by operation; the HIP kernel is k_camera.
     fov          'fx,fz'   full field of view along the image's x and z, degrees, each in (0, 180)
     dims         'nx,nz'   default '256,256'
     g / wavelength         as ModelResult
+    origin       the planet (default) or a moon among geometry.objects: the rows are moved into the
+                 frame that co-rotates with the moon (frames.MoonFrame); observer is then in moon
+                 radii from the moon's centre, and the moon is the sphere that occults and shadows
 
 Attributes: image, packet_image (nx x nz), uedges, vedges (tangent-plane bin edges), basis (rows
 right, boresight, up), observer, pixel_solid_angle (nx x nz, sr), totalsource, atoms_per_packet,
@@ -108,6 +111,7 @@ class CameraImage(ModelResult):
         self.type = 'camera image'
         if self.quantity not in ('column', 'radiance'):
             raise InputError('CameraImage.__init__', "quantity must be 'column' or 'radiance'")
+        self._set_origin()          # (npackets=, shard= and cp= are refused above, whatever the origin)
         self._frame()
         self._new_pixel_sums(moments, cube)
         self._ctx, self._device = context, device
@@ -119,10 +123,9 @@ class CameraImage(ModelResult):
         get = self.params.get
         if str(get('projection', 'gnomonic')).strip().lower() != 'gnomonic':
             raise NotImplementedError(UNSUPPORTED['projection'])
-        if get('origin', None) not in (None, self.inputs.geometry.planet):
-            raise NotImplementedError('moon-centred camera frames are out of scope')
         if 'observer' not in self.params:
-            raise InputError('CameraImage.__init__', "params need observer = 'x,y,z' [planet radii]")
+            raise InputError('CameraImage.__init__', "params need observer = 'x,y,z' [radii of the "
+                             "origin: the planet, or the moon of params['origin']]")
         self.observer = _vector(get('observer'), 'observer')
         if not np.dot(self.observer, self.observer) >= 1.0:
             raise InputError('CameraImage.__init__', 'the observer must be outside the planet (|o| >= 1)')
@@ -166,7 +169,8 @@ class CameraImage(ModelResult):
         velocity = self.moments or self.cube is not None
 
         def set_up(ctx, aplanet, vr_kms):
-            ctx.camera_set(self.observer, self.basis, vr_kms/self.unit_km, self.pix_area_cm2,
+            ctx.camera_set(self.observer, self.basis, self._vr_kms(vr_kms)/self.unit_km,
+                           self.pix_area_cm2,
                            self.quantity, self.uedges, self.vedges, self.g_tables(aplanet))
             self._enable_velocity(ctx, 'camera')
 
@@ -176,7 +180,7 @@ class CameraImage(ModelResult):
 
         sample_pass(self, list(self.inputs._catalogue), accumulate,
                     Output.MOMENT_COLS if velocity else Output.IMAGE_COLS, set_up,
-                    lambda ctx: self._collect_pixels(ctx, 'camera'))
+                    lambda ctx: self._collect_pixels(ctx, 'camera'), **self._frame_pass())
 
     def finalize(self):
         """Scale to a source rate of 1e23 atoms/s, as ModelImage.finalize does."""

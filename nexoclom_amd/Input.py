@@ -277,7 +277,11 @@ class Input:
         every rank bins the Outputs of its own catalogue and the image pairs and source totals
         are summed over the ranks (reduce='rccl': one ncclAllReduce; 'host': over the control
         plane, for tests) -- every rank gets the image of the whole run."""
-        from .ModelImage import ModelImage, refuse_cube_with, refuse_moments_with
+        from .ModelImage import ModelImage, read_params, refuse_cube_with, refuse_moments_with
+        if cp is not None:
+            from .frames import is_planet_origin, refuse_with_moon_origin
+            if not is_planet_origin(self, read_params(format_).get('origin')):
+                refuse_with_moon_origin(cp=cp)
         if kwargs.get('cube') is not None:
             refuse_cube_with(cp=cp, moments=kwargs.get('moments'))
         if kwargs.get('moments'):

@@ -36,6 +36,7 @@ from . import constants as const
 from .ModelImage import ModelResult
 from .atomicdata import atomicmass
 from .catalogue import sample_pass
+from .frames import MoonFrame, is_planet_origin, refuse_with_moon_origin
 from .units import Quantity
 
 MAX_CELLS = 1 << 24           # cells of the point grid (int32 starts; cell coordinates < 2^24)
@@ -255,7 +256,7 @@ def spectrum_from_sums(spectrum_sums, scale, unit_km, s_lo_kms, s_hi_kms, mass_k
 
 class ModelDensity:
     def __init__(self, inputs, xpts, ypts, zpts, dr=0.05, moments=False, *, cp=None,
-                 reduce='rccl', context=None, device=0, spectrum=None):
+                 reduce='rccl', context=None, device=0, spectrum=None, origin=None):
         """Number density at the points (xpts, ypts, zpts) [planet radii] from every catalogued
         Output of ``inputs`` (ModelDensity.py:18-85).  ``cp``: the control plane of a shared run
         (``Input.run(..., cp=cp)``): each rank sums its own Outputs, then the per-point sums and
@@ -276,12 +277,22 @@ class ModelDensity:
         velocity).  180 degrees or no boresight is the whole sky: ``density_in_view`` is then
         ``density`` up to the order of the additions.  Attributes: those of
         ``spectrum_from_sums`` and the raw ``spectrum_sums`` (2, Q, nbins + 2, 2).  It refuses
-        ``moments=True`` and ``cp=``."""
+        ``moments=True`` and ``cp=``.
+
+        ``origin=`` (EXTENSION): a moon among geometry.objects, by name or as an SSObject.  The
+        rows are moved into the frame that co-rotates with the moon (frames.MoonFrame) before they
+        are read: the points and ``dr`` are then in moon radii from the moon's centre, and the
+        velocities of ``moments=`` and ``spectrum=`` are relative to the moon (a spacecraft's
+        ``velocity`` likewise).  It refuses ``cp=``.  None or the planet: nothing changes."""
         if spectrum is not None:
             refuse_with_spectrum(moments=moments, cp=cp)
         self.type = 'density'
         self.inputs = inputs
         self.origin = inputs.geometry.planet
+        if not is_planet_origin(inputs, origin):
+            refuse_with_moon_origin(cp=cp)
+            self.frame = MoonFrame.from_inputs(inputs, origin)
+            self.origin = self.frame.origin
         self.unit = 'R_' + self.origin.object
         unit_km = float(self.origin.radius.value)
         dr = float(dr.to(self.unit)) if isinstance(dr, Quantity) and dr.unit else float(dr)
@@ -346,6 +357,8 @@ class ModelDensity:
                 setattr(self, name, value)
 
     context = ModelResult.context         # the catalogue's shared context, found once and kept
+    frame, slab_rows = None, ModelResult.slab_rows       # a moon's frame, as the images have it
+    _frame_pass = ModelResult._frame_pass
 
     def _accumulate(self, index, moments=False, frames=None):
         """(frac sums, counts, moment sums | spectrum sums | None) per indexed point over this
@@ -368,7 +381,8 @@ class ModelDensity:
         runs = list(self.inputs._catalogue)
         if runs:        # (without runs __init__ has raised, or a shared run leaves this rank none)
             # k_density* leave the context's counters alone: nothing to total
-            sample_pass(self, runs, lambda ctx, **samples: add(**samples), columns, counters=False)
+            sample_pass(self, runs, lambda ctx, **samples: add(**samples), columns, counters=False,
+                        **self._frame_pass())
         extra = ctx.density_spectrum_download() if frames is not None else \
             ctx.density_moments_download() if moments else None
         return (*ctx.density_download(), extra)

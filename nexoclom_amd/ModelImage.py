@@ -29,6 +29,14 @@ falls outside the range, ``velocity_edges`` / ``velocity_axis`` [km/s], ``cube_e
 (the error bars: ``cube / sqrt(cube_effective_packets)``) and the unscaled ``cube_sums``.
 include/nexoclom_hip.h ("Velocity cube") holds the definition.
 
+``params['origin']`` (catalogued Outputs only; an extension where the reference stops at planets
+with moons): the planet, or a moon among geometry.objects.  A moon makes ``center`` and ``width``
+lengths in moon radii around the moon, which then occults and shadows; the stored rows are moved
+into the frame that co-rotates with the moon before they are binned (frames.MoonFrame,
+catalogue.sample_pass(..., frame=), in slabs of ``slab_rows`` rows), and ``moments`` / ``cube``
+velocities are relative to the moon.  include/nexoclom_hip.h ("Moon-centred frame") holds the
+definition.
+
 Bokeh display / PostgreSQL caching of the reference are out of scope.
 """
 import copy
@@ -39,7 +47,8 @@ import os
 import numpy as np
 
 from .atomicdata import gValue
-from .catalogue import run_g_values, sample_pass, shared_context
+from .catalogue import framed_columns, framed_slabs, run_g_values, sample_pass, shared_context
+from .frames import MoonFrame, is_planet_origin, refuse_with_moon_origin
 from .input_classes import InputError
 from .units import Quantity
 
@@ -225,6 +234,37 @@ class ModelResult:
         self.unit = 'R_' + inputs.geometry.planet.object
         self.unit_km = inputs.geometry.planet.radius.value
 
+    frame = None              # a frames.MoonFrame: the rows are moved into it before they are read
+
+    def _set_origin(self, **refused):
+        """``params['origin']``: the planet (the default; nothing changes) or a moon among
+        geometry.objects.  A moon makes ``origin``, ``unit`` and ``unit_km`` the moon's -- every
+        length of ``params`` is then in moon radii, as the reference's ModelImage.__init__ has it
+        for ``origin`` -- and ``frame`` the frame the rows are moved into; it is refused together
+        with the keywords ``refused`` that are not None.  Any other origin: NotImplementedError."""
+        self.origin = self.params.get('origin', self.inputs.geometry.planet)
+        if is_planet_origin(self.inputs, self.origin):
+            return
+        try:
+            frame = MoonFrame.from_inputs(self.inputs, self.origin)
+        except ValueError as err:
+            raise NotImplementedError(f'{err}: a product is centred on the planet or on a moon '
+                                      'that takes part in the run') from None
+        refuse_with_moon_origin(**refused)
+        self.frame, self.origin = frame, frame.origin
+        self.unit, self.unit_km = frame.unit, frame.unit_km
+
+    slab_rows = 1 << 26       # rows moved into a moon's frame at a time (catalogue.framed_slabs)
+
+    def _frame_pass(self):
+        """What ``sample_pass`` is told beyond the planet-centred pass: nothing, or the frame."""
+        return {} if self.frame is None else dict(frame=self.frame, slab_rows=self.slab_rows)
+
+    def _vr_kms(self, vr_kms):
+        """The vrplanet [km/s] a kernel is set with: in a moon's frame the rows carry moon-relative
+        velocities, and the Sun-relative one of a row adds the moon's own (frames.MoonFrame)."""
+        return vr_kms if self.frame is None else vr_kms + self.frame.radvel_shift_kms
+
     def _lines(self, species):
         if 'wavelength' in self.params:
             return tuple(sorted(int(w.strip()) for w in str(self.params['wavelength']).split(',')))
@@ -297,7 +337,7 @@ class ModelImage(ModelResult):
     def __init__(self, inputs, params, overwrite=False, distribute=None, *, npackets=None,
                  seed=None, packs_per_it=None, downcast=True, device=0, context=None,
                  sampler='numpy', shard=None, finalize=True, generator='philox', moments=False,
-                 cube=None):
+                 cube=None, slab_rows=None):
         if cube is not None:
             refuse_cube_with(npackets=npackets, shard=shard, moments=moments)
             cube = parse_cube(cube)
@@ -305,10 +345,11 @@ class ModelImage(ModelResult):
             refuse_moments_with(npackets=npackets, shard=shard)
         super().__init__(inputs, params)
         self.type = 'image'
-        self.origin = self.params.get('origin', inputs.geometry.planet)
-        if self.origin != inputs.geometry.planet:
-            raise NotImplementedError('images centred on another object '
-                                      '(ModelResult.transform_reference_frame) are out of scope')
+        if slab_rows is not None:
+            if operator.index(slab_rows) < 1:
+                raise ValueError('slab_rows must be at least 1')
+            self.slab_rows = operator.index(slab_rows)
+        self._set_origin(npackets=npackets, shard=shard)
         self._frame()
         self._new_pixel_sums(moments, cube)
         self.blimits = None
@@ -378,11 +419,13 @@ class ModelImage(ModelResult):
             return False
 
         def set_up(ctx, aplanet, vr_kms):
-            self._set_image(ctx, aplanet, vr_kms/self.unit_km, downcast=False)      # clears it
+            vr = self._vr_kms(vr_kms)/self.unit_km
+            self._set_image(ctx, aplanet, vr, downcast=False)      # clears it
 
         # the Outputs of a launch group are consecutive slices of one store: one kernel launch per
         # run of adjacent slices instead of one per Output
-        sample_pass(self, runs, lambda ctx, rows: self._accumulate(ctx, rows=rows), (), set_up)
+        sample_pass(self, runs, lambda ctx, rows: self._accumulate(ctx, rows=rows), (), set_up,
+                    **self._frame_pass())
         image = self._collect_pixels(ctx, 'image')
         h = Histogram2dResult(image, self.xedges, self.zedges)
         self.xaxis, self.zaxis = h.x, h.y
@@ -436,18 +479,31 @@ class ModelImage(ModelResult):
         if view is not None and view[2] > 0:
             # the rows are still in HBM as save() would have stored them: bin them where they are
             aplanet, vrplanet_kms = float(output.aplanet), float(output.vrplanet)
-            self._set_image(ctx, aplanet, vrplanet_kms/self.unit_km, downcast=False)
-            self._accumulate(ctx, rows=tuple(view[:3]))
+            self._set_image(ctx, aplanet, self._vr_kms(vrplanet_kms)/self.unit_km, downcast=False)
+            if self.frame is None:
+                self._accumulate(ctx, rows=tuple(view[:3]))
+                self.counters = ctx.counters()
+            else:           # moved into the moon's frame slab by slab; every launch clears the counters
+                self.counters = {}
+                for moved in framed_slabs(ctx, self.frame, tuple(view[:3]), self.slab_rows):
+                    self._accumulate(ctx, rows=moved)
+                    for key, v in ctx.counters().items():
+                        self.counters[key] = self.counters.get(key, 0) + v
         else:
-            samples, aplanet, vrplanet_kms = Output.image_columns(
-                output, velocity=self.moments or self.cube is not None)
+            velocity = self.moments or self.cube is not None
+            if self.frame is None:
+                samples, aplanet, vrplanet_kms = Output.image_columns(output, velocity=velocity)
+            else:
+                samples = framed_columns(ctx, self.frame, output,
+                                         Output.MOMENT_COLS if velocity else Output.IMAGE_COLS)
+                aplanet, vrplanet_kms = run_g_values(output)
             if samples is None or len(samples[0]) == 0:
                 raise ValueError('this Output holds no trajectory (it was run with '
                                  'keep_trajectory=False); use ModelImage(..., npackets=N) instead')
-            vr = vrplanet_kms/self.unit_km                 # km/s -> R/s (ModelImage.py:242-243)
+            vr =self._vr_kms(vrplanet_kms)/self.unit_km   # km/s -> R/s (ModelImage.py:242-243)
             self._set_image(ctx, aplanet, vr, downcast=False)
             self._accumulate(ctx, samples)
-        self.counters = ctx.counters()
+            self.counters = ctx.counters()
         assert self.counters['nonfinite'] == 0, 'Non-finite weights'
         image, counts = ctx.image_download()
         if self.moments:

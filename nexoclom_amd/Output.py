@@ -371,6 +371,7 @@ class Output:
     def _bodies_config(self):
         """Arguments of hip_api.Context.set_bodies, or None for the reference's single-body
         model.  Moons are taken in the order of ``planet.moons``; geometry.phi follows it."""
+        from .frames import moon_table
         geo, opt = self.inputs.geometry, self.inputs.options
         included = [m for m in (self.planet.moons or []) if m in (geo.objects or ())]
         chx = getattr(opt, 'chx', None)
@@ -379,15 +380,7 @@ class Output:
         if opt.step_size == 0:
             raise NotImplementedError('moons / torus loss need the constant-step driver '
                                       '(options.step_size > 0)')
-        unit_m = self.unit_km*1e3
-        cfg = dict(moons=[], t0=float(opt.endtime.value), chx=None)
-        phis = [float(p) for p in (getattr(geo, 'phi', None) or ())]
-        assert len(phis) == len(included), 'The wrong number of orbital positions was given.'
-        for m, phi in zip(included, phis):
-            cfg['moons'].append(dict(name=m.object, gm=m.GM.value/unit_m**3,
-                                     radius=m.radius.value/self.unit_km,
-                                     a=m.a.value/self.unit_km,
-                                     omega=2*np.pi/(m.orbperiod.value*86400.), phi=phi))
+        cfg = dict(moons=moon_table(geo, self.unit_km), t0=float(opt.endtime.value), chx=None)
         if chx is not None:
             omega = 2*np.pi/(self.planet.rotperiod.value*3600.) if chx['corotation'] else 0.0
             cfg['chx'] = dict(k0=chx['k0'], rho0=chx['rho0'], width=chx['width'],

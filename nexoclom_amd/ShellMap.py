@@ -15,6 +15,9 @@ the definition operation by operation; the HIP kernel is k_shell.
     dims         'nlon,nlat'      default '72,36'
     altitude     'lo,hi,nbins'    planet radii above the surface, 0 <= lo < hi (required)
     g / wavelength                as ModelResult
+    origin       the planet (default) or a moon among geometry.objects: the rows are moved into the
+                 frame that co-rotates with the moon (frames.MoonFrame) and the shells lie around
+                 the moon, altitude in moon radii above its surface
 
 Attributes: longitude, local_time (hours; 12 at longitude 0, 18 at pi/2), latitude (asin of the
 band centres, rad), lon_edges, mu_edges, altitude_edges, altitude_axis (planet radii above the
@@ -128,6 +131,7 @@ class ShellMap(ModelResult):
         self.type = 'shell map'
         if self.quantity not in ('column', 'radiance'):
             raise InputError('ShellMap.__init__', "quantity must be 'column' or 'radiance'")
+        self._set_origin()          # (npackets=, shard= and cp= are refused above, whatever the origin)
         self._frame()
         self._column_sum = np.zeros(self.dims)
         self.packets = np.zeros(self.dims)
@@ -139,8 +143,6 @@ class ShellMap(ModelResult):
 
     def _frame(self):
         get = self.params.get
-        if get('origin', None) not in (None, self.inputs.geometry.planet):
-            raise NotImplementedError('moon-centred shells are out of scope')
         self.dims = parse_dims(get('dims', '72,36'))
         if 'altitude' not in self.params:
             raise InputError('ShellMap.__init__',
@@ -165,7 +167,7 @@ class ShellMap(ModelResult):
         columns.  The sums stay on the device while (aplanet, vrplanet) -- the g-values -- stay the
         same, and are summed on the host across such groups."""
         def set_up(ctx, aplanet, vr_kms):
-            ctx.shell_set(vr_kms/self.unit_km, self.quantity, self.lon_edges, self.mu_edges,
+            ctx.shell_set(self._vr_kms(vr_kms)/self.unit_km, self.quantity, self.lon_edges, self.mu_edges,
                           self.r_edges[0], self.r_edges[-1], self.altitude[2],
                           self.g_tables(aplanet))
 
@@ -177,7 +179,7 @@ class ShellMap(ModelResult):
 
         sample_pass(self, list(self.inputs._catalogue),
                     lambda ctx, **samples: ctx.shell_accumulate(**samples), Output.IMAGE_COLS,
-                    set_up, collect)
+                    set_up, collect, **self._frame_pass())
 
     def finalize(self):
         """Scale to a source rate of 1e23 atoms/s, as ModelImage.finalize does."""

@@ -78,7 +78,53 @@ def run_g_values(run):
         return float(data['aplanet']), float(data['vrplanet_kms'])
 
 
-def sample_pass(product, runs, accumulate, columns, set_up=None, collect=None, counters=True):
+FRAME_COLS = ('time', 'x', 'y', 'z', 'vx', 'vy', 'vz')      # what moving a row into a frame reads
+
+
+def framed_columns(ctx, frame, source, columns):
+    """The sample ``columns`` of a stored run without resident rows (a catalogued Output or an
+    .npz path) with its positions and velocities moved into ``frame``: time and the six state
+    columns go through ``ctx.frame_columns`` in the width they are stored in, the rest is handed
+    on as it is.  A restored Output holds save()'s float32 values widened (Output.py:555-570): it
+    is moved as the float32 rows it was, so that a run gives the same moved rows from HBM, from
+    its file and restored.  None: the run holds no trajectory."""
+    names = FRAME_COLS + tuple(c for c in columns if c not in FRAME_COLS)
+    samples = Output.sample_columns(source, names)
+    if samples is None or not len(samples[0]):
+        return None
+    table = dict(zip(names, samples))
+    state = [np.asarray(table[c]) for c in FRAME_COLS]
+    if all(c.dtype == np.float64 for c in state):
+        with np.errstate(over='ignore'):
+            narrow = [c.astype(np.float32) for c in state]
+        if all(np.array_equal(n, c) for n, c in zip(narrow, state)):
+            state = narrow
+    moved = ctx.frame_columns(frame, *state)
+    table.update(zip(FRAME_COLS[1:], moved))
+    return [table[c] for c in columns]
+
+
+def framed_slabs(ctx, frame, rows, slab_rows):
+    """``rows = (store, first, count)`` moved into ``frame`` slab by slab: yields ``(moved, 0, n)``
+    with ``moved`` a store of at most ``slab_rows`` rows that is freed when the caller comes back
+    for the next one, so the extra HBM is one slab whatever the size of the catalogue."""
+    store, first, count = rows
+    per_row = 40 if store.narrow else 80
+    for at in range(0, count, slab_rows):
+        n = min(slab_rows, count - at)
+        ctx.make_room(n*per_row)
+        if store._r is None:
+            raise MemoryError('no room on the device for a slab of moved rows beside the rows '
+                              'they are moved from; pass a smaller slab_rows')
+        moved = ctx.frame_rows(frame, store, first + at, n)
+        try:
+            yield moved, 0, n
+        finally:
+            moved.free()
+
+
+def sample_pass(product, runs, accumulate, columns, set_up=None, collect=None, counters=True,
+                frame=None, slab_rows=1 << 26):
     """Every stored sample of the catalogue ``runs`` through one consumer, on
     ``product.context()``.
 
@@ -90,12 +136,22 @@ def sample_pass(product, runs, accumulate, columns, set_up=None, collect=None, c
     [au], vrplanet [km/s]) -- the sums stay on the device over such a stretch -- and
     ``collect(ctx)`` at the end of each.
     ``counters``: the consumer's kernels clear the context's counters, so they are read after
-    every launch, totalled into ``product.counters`` and must show no non-finite weight."""
+    every launch, totalled into ``product.counters`` and must show no non-finite weight.
+    ``frame`` (a frames.MoonFrame): every row is moved into that frame first (k_frame_rows) and
+    the consumer runs unchanged on the moved rows -- resident spans in slabs of ``slab_rows``
+    rows (``framed_slabs``), other runs through ``framed_columns``.  None: nothing is moved, and
+    the pass is the same launches as ever."""
     if not runs:
         print('No model outputs found for these inputs.')
         return
     ctx = product.context()
     totals = {}
+
+    def launch(**samples):
+        accumulate(ctx, **samples)
+        if counters:
+            for key, v in ctx.counters().items():
+                totals[key] = totals.get(key, 0) + v
 
     def announced():
         for run in runs:
@@ -111,16 +167,17 @@ def sample_pass(product, runs, accumulate, columns, set_up=None, collect=None, c
             set_up(ctx, *item)
             is_set = True
             continue
-        if kind == 'rows':
-            accumulate(ctx, rows=item)
+        if kind == 'rows' and frame is None:
+            launch(rows=item)
+        elif kind == 'rows':
+            for moved in framed_slabs(ctx, frame, item, slab_rows):
+                launch(rows=moved)
         else:
-            samples = Output.sample_columns(item, columns)
+            samples = Output.sample_columns(item, columns) if frame is None else \
+                framed_columns(ctx, frame, item, columns)
             if samples is None or not len(samples[0]):
                 continue
-            accumulate(ctx, **dict(zip(columns, samples)))
-        if counters:
-            for key, v in ctx.counters().items():
-                totals[key] = totals.get(key, 0) + v
+            launch(**dict(zip(columns, samples)))
     if collect:
         collect(ctx)
     if counters:

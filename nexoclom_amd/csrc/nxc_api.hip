@@ -30,6 +30,7 @@
 #include "nxc_los_profile_check.hpp"
 #include "nxc_desc_check.hpp"
 #include "nxc_source_map_check.hpp"
+#include "nxc_frame_check.hpp"
 #include "nxc_devbuf.hpp"
 #include "nxc_image_block.hpp"
 #include "nxc_kernels.hpp"
@@ -4546,6 +4547,122 @@ int nxc_math_batch(nxc_handle *h, int which, int64_t n, const double *in, const 
     HIPCHK(stream_sync(h));
     return NXC_OK;
     });
+}
+
+}  // extern "C"
+
+// ---- moon-centred frame ------------------------------------------------------------------------
+namespace {
+
+FrameK frame_kernel_args(const nxc_frame_desc *d)
+{
+    return FrameK{d->omega, d->M[0], d->M[1], d->M[2], d->U[0], d->U[1], d->U[2], d->scale};
+}
+
+// k_frame_rows over n rows of the columns C, timed (nxc_last_kernel_ms).  16 bytes a thread and
+// column where every column that is used starts on a 16-byte boundary.
+template <typename T, typename I>
+int launch_frame(nxc_handle *h, const FrameK &F, const FrameCols &C, int64_t n)
+{
+    auto aligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+    bool wide = aligned(C.idx_in) && aligned(C.idx_out);
+    for (int c = 0; c < 9; c++) wide = wide && aligned(C.in[c]) && aligned(C.out[c]);
+    const int64_t V = 16 / (int64_t)sizeof(T);
+    const int64_t threads = wide ? n / V + V : n;
+    int rc;
+    if ((rc = begin_timed(h))) return rc;
+    hipLaunchKernelGGL((k_frame_rows<T, I>), dim3((unsigned)flat_grid(h, threads, NXC_BLOCK)),
+                       dim3(NXC_BLOCK), 0, h->stream, F, C, (long long)n, wide ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return end_timed(h);
+}
+
+// nxc_frame_columns / _f32: the seven columns up, one pass, the six moved ones back
+template <typename T, typename I>
+int frame_columns(nxc_handle *h, const nxc_frame_desc *d, int64_t p, const T *const in[7], T *out)
+{
+    return guarded([&]() -> int {
+    if (!h) return fail(NXC_ERR_ARG, "null handle");
+    std::string why = check_frame_desc(d);
+    const void *cols[8] = {in[0], in[1], in[2], in[3], in[4], in[5], in[6], out};
+    if (why.empty()) why = check_frame_columns(p, cols);
+    if (!why.empty()) return fail(NXC_ERR_ARG, why);
+    if (p == 0) return NXC_OK;
+    HIPCHK(hipSetDevice(h->device));
+    // device scratch: 7 columns in | 6 columns out, each 256-byte aligned
+    const size_t bytes = (size_t)p * sizeof(T), col = (bytes + 255) & ~size_t(255);
+    int rc = scratch_for(h, 13 * col);
+    if (rc) return rc;
+    unsigned char *base = reinterpret_cast<unsigned char *>(h->d_scratch.get());
+    FrameCols C{};
+    for (int c = 0; c < 7; c++) {
+        HIPCHK(hipMemcpyAsync(base + (size_t)c * col, in[c], bytes, hipMemcpyHostToDevice, h->stream));
+        C.in[c] = base + (size_t)c * col;
+    }
+    for (int c = 1; c < 7; c++) C.out[c] = base + (size_t)(6 + c) * col;
+    if ((rc = launch_frame<T, I>(h, frame_kernel_args(d), C, p))) return rc;
+    HIPCHK(hipMemcpy2DAsync(out, bytes, base + 7 * col, col, bytes, 6, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int nxc_frame_rows(nxc_handle *h, const nxc_frame_desc *d, const nxc_rows *src, int64_t first,
+                   int64_t count, nxc_rows **out)
+{
+    return guarded([&]() -> int {
+    if (!out) return fail(NXC_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (!h || !src) return fail(NXC_ERR_ARG, "null argument");
+    std::string why = check_frame_desc(d);
+    if (why.empty()) why = check_frame_range(src->total, first, count);
+    if (!why.empty()) return fail(NXC_ERR_ARG, why);
+    int rc = rows_check(h, src, first, count);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    nxc_rows *r = nullptr;
+    if ((rc = new_rows(h, count, src->f32, &r, "frame rows"))) return rc;
+    if (count > 0) {
+        const size_t vsz = src->f32 ? 4 : 8;
+        FrameCols C{};
+        for (int c = 0; c < 9; c++) {
+            C.in[c] = static_cast<const char *>(src->d_cols) + ((size_t)c * src->total + first) * vsz;
+            C.out[c] = static_cast<char *>(r->d_cols) + (size_t)c * count * vsz;
+        }
+        C.idx_in = static_cast<const char *>(src->d_index) + (size_t)first * vsz;
+        C.idx_out = r->d_index;
+        const FrameK F = frame_kernel_args(d);
+        rc = src->f32 ? launch_frame<float, int>(h, F, C, count)
+                      : launch_frame<double, long long>(h, F, C, count);
+        const hipError_t e = rc ? hipSuccess : stream_sync(h);
+        if (rc || e != hipSuccess) {
+            nxc_rows_free(h, r);
+            return rc ? rc : fail_hip("frame rows", e);
+        }
+    }
+    *out = r;
+    return NXC_OK;
+    });
+}
+
+int nxc_frame_columns(nxc_handle *h, const nxc_frame_desc *d, int64_t p, const double *t,
+                      const double *x, const double *y, const double *z, const double *vx,
+                      const double *vy, const double *vz, double *out)
+{
+    const double *const in[7] = {t, x, y, z, vx, vy, vz};
+    return frame_columns<double, long long>(h, d, p, in, out);
+}
+
+int nxc_frame_columns_f32(nxc_handle *h, const nxc_frame_desc *d, int64_t p, const float *t,
+                          const float *x, const float *y, const float *z, const float *vx,
+                          const float *vy, const float *vz, float *out)
+{
+    const float *const in[7] = {t, x, y, z, vx, vy, vz};
+    return frame_columns<float, int>(h, d, p, in, out);
 }
 
 }  // extern "C"

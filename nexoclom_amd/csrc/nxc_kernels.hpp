@@ -20,6 +20,7 @@
 //   k_density, k_density_moments, k_density_spectrum   stored samples within dr of query points
 //                   (density_walk -- loop, cull, candidate walk, membership -- with a load and a
 //                   per-trip lambda each; k_density_moments keeps the walk written out)
+//   k_frame_rows    stored rows moved into the frame that co-rotates with a moon (streaming)
 //
 // All lookup tables (radiation acceleration, g-values, bin edges) are staged once per workgroup
 // into LDS from one packed blob.
@@ -3494,4 +3495,91 @@ k_smap_gridsum(int ntiles, int nvel, const double *__restrict__ partial, double 
         __syncthreads();
     }
     if (threadIdx.x == 0) out[c] = red[0];
+}
+
+// ---- moon-centred frame (include/nexoclom_hip.h, "Moon-centred frame") ---------------------------
+// The frame as the host formed it, and the columns of one pass: in[] / out[] in the store's order
+// t, x, y, z, vx, vy, vz, frac, lossfrac.  A row store passes all nine and its index; host columns
+// pass in[0..6] and out[1..6] (a null out column is not written, nor is its in column read beyond
+// what the moved ones need).
+struct FrameK { double omega, Mx, My, Mz, Ux, Uy, Uz, k; };
+struct FrameCols {
+    const void *in[9];
+    void *out[9];
+    const void *idx_in;
+    void *idx_out;
+};
+
+// One row, in the definition's order, one rounding per operation (-ffp-contract=off)
+NXC_DEV void frame_row(const FrameK &F, double t, double &x, double &y, double &z, double &vx,
+                       double &vy, double &vz)
+{
+    double s, c;
+    sincos(F.omega * t, &s, &c);
+    const double qx = c * x - s * y, qy = s * x + c * y;
+    const double wx = c * vx - s * vy, wy = s * vx + c * vy;
+    x = (qx - F.Mx) * F.k;
+    y = (qy - F.My) * F.k;
+    z = (z - F.Mz) * F.k;
+    vx = (wx - F.Ux) * F.k;
+    vy = (wy - F.Uy) * F.k;
+    vz = (vz - F.Uz) * F.k;
+}
+
+// n rows into the frame F.  Streaming and HBM-bound: 40 (80) bytes a row in and as many out for
+// float32 (float64) stores, one sincos per row, no LDS, no atomics.  Grid-stride; the host caps
+// the grid at 8 blocks per CU.  `wide`: every column starts on a 16-byte boundary, and a thread
+// moves 16 bytes of each column per trip (4 float32 or 2 float64 rows); the n % V rows left over,
+// or all rows when a column is not aligned (a slice of a store from an odd row), go one per thread.
+// Both ways compute a row with frame_row, so the bits do not depend on the way.
+// <double, long long>: fp64 stores and host columns; <float, int>: float32 ones.
+template <typename T, typename I>
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_frame_rows(FrameK F, FrameCols C, long long n, int wide)
+{
+    static_assert(sizeof(T) == sizeof(I), "the index column is as wide as the values");
+    constexpr int V = 16 / (int)sizeof(T);
+    typedef T vec_t __attribute__((ext_vector_type(V)));
+    typedef I ivec_t __attribute__((ext_vector_type(V)));
+    const long long stride = (long long)gridDim.x * NXC_BLOCK;
+    const long long tid = (long long)blockIdx.x * NXC_BLOCK + threadIdx.x;
+    const long long groups = wide ? n / V : 0;
+    for (long long g = tid; g < groups; g += stride) {
+        vec_t v[7];
+#pragma unroll
+        for (int c = 0; c < 7; c++) v[c] = static_cast<const vec_t *>(C.in[c])[g];
+        vec_t o[6];
+#pragma unroll
+        for (int k = 0; k < V; k++) {
+            double x = v[1][k], y = v[2][k], z = v[3][k], vx = v[4][k], vy = v[5][k], vz = v[6][k];
+            frame_row(F, (double)v[0][k], x, y, z, vx, vy, vz);
+            o[0][k] = (T)x; o[1][k] = (T)y; o[2][k] = (T)z;
+            o[3][k] = (T)vx; o[4][k] = (T)vy; o[5][k] = (T)vz;
+        }
+#pragma unroll
+        for (int c = 0; c < 6; c++) static_cast<vec_t *>(C.out[c + 1])[g] = o[c];
+        if (C.out[0]) static_cast<vec_t *>(C.out[0])[g] = v[0];
+#pragma unroll
+        for (int c = 7; c < 9; c++)
+            if (C.out[c]) static_cast<vec_t *>(C.out[c])[g] = static_cast<const vec_t *>(C.in[c])[g];
+        if (C.idx_out) static_cast<ivec_t *>(C.idx_out)[g] = static_cast<const ivec_t *>(C.idx_in)[g];
+    }
+    for (long long r = groups * V + tid; r < n; r += stride) {
+        const T t = static_cast<const T *>(C.in[0])[r];
+        double x = static_cast<const T *>(C.in[1])[r], y = static_cast<const T *>(C.in[2])[r],
+               z = static_cast<const T *>(C.in[3])[r], vx = static_cast<const T *>(C.in[4])[r],
+               vy = static_cast<const T *>(C.in[5])[r], vz = static_cast<const T *>(C.in[6])[r];
+        frame_row(F, (double)t, x, y, z, vx, vy, vz);
+        static_cast<T *>(C.out[1])[r] = (T)x;
+        static_cast<T *>(C.out[2])[r] = (T)y;
+        static_cast<T *>(C.out[3])[r] = (T)z;
+        static_cast<T *>(C.out[4])[r] = (T)vx;
+        static_cast<T *>(C.out[5])[r] = (T)vy;
+        static_cast<T *>(C.out[6])[r] = (T)vz;
+        if (C.out[0]) static_cast<T *>(C.out[0])[r] = t;
+#pragma unroll
+        for (int c = 7; c < 9; c++)
+            if (C.out[c]) static_cast<T *>(C.out[c])[r] = static_cast<const T *>(C.in[c])[r];
+        if (C.idx_out) static_cast<I *>(C.idx_out)[r] = static_cast<const I *>(C.idx_in)[r];
+    }
 }

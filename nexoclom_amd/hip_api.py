@@ -141,6 +141,11 @@ class nxc_bodies_desc(C.Structure):
                 ('chx_omega', C.c_double)]
 
 
+class nxc_frame_desc(C.Structure):
+    _fields_ = [('omega', C.c_double), ('M', C.c_double*3), ('U', C.c_double*3),
+                ('scale', C.c_double)]
+
+
 class nxc_counters(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in
                 ('particle_steps', 'samples', 'samples_binned', 'nonfinite', 'bad_step',
@@ -273,6 +278,9 @@ SIGNATURES = {
     'nxc_shader_clock_mhz': (_h, _dp),
     'nxc_pcg64_uniforms': (_h, _u64p, _u64p, _i64, _i64, _i64, _i32, _dp),
     'nxc_math_batch': (_h, _int, _i64, _dp, _dp, _dp),
+    'nxc_frame_rows': (*_desc(nxc_frame_desc), _h, _i64, _i64, _out),
+    'nxc_frame_columns': (*_desc(nxc_frame_desc), _i64, *[_dp]*7, _dp),
+    'nxc_frame_columns_f32': (*_desc(nxc_frame_desc), _i64, *[_fp]*7, _fp),
 }
 RESTYPES = {'nxc_last_error_string': C.c_char_p}       # every other function returns an int status
 EXPORTS = tuple(SIGNATURES)
@@ -858,6 +866,48 @@ class Context:
             return
         suffix, ptrs, cols = self._columns(cols)
         self._check(getattr(self.lib, entry_name + suffix)(self._h, len(cols[0]), *ptrs))
+
+    # -- moon-centred frame: stored rows moved into the frame that co-rotates with a moon -----
+    @staticmethod
+    def frame_desc(frame):
+        """The nxc_frame_desc of ``frame``: one as it is, else built from the attributes omega
+        [rad/s], M [R], U [R/s] and scale (a frames.MoonFrame)."""
+        if isinstance(frame, nxc_frame_desc):
+            return frame
+        desc = nxc_frame_desc()
+        desc.omega, desc.scale = float(frame.omega), float(frame.scale)
+        desc.M[:], desc.U[:] = [float(v) for v in frame.M], [float(v) for v in frame.U]
+        return desc
+
+    def frame_rows(self, frame, store, first=0, count=None):
+        """Rows [first, first + count) of a RowStore moved into ``frame``: a new RowStore of
+        ``count`` rows of the same width, which the caller frees.  It is not entered among the
+        stores ``make_room`` may spill: nobody owns its rows."""
+        count = store.total - first if count is None else int(count)
+        handle = C.c_void_p()
+        self._check(self.lib.nxc_frame_rows(self._h, C.byref(self.frame_desc(frame)),
+                                            self._rows_handle(store), first, count,
+                                            C.byref(handle)))
+        return RowStore(self, handle)
+
+    def frame_columns(self, frame, t, x, y, z, vx, vy, vz):
+        """Host columns moved into ``frame``: (6, p) x', y', z', vx', vy', vz', float32 when all
+        seven columns are (they go over as they are, are widened on the device and rounded
+        once), else float64."""
+        suffix, ptrs, cols = self._columns((t, x, y, z, vx, vy, vz))
+        p = len(cols[0])
+        if any(len(c) != p for c in cols):
+            raise ValueError('frame_columns: the columns differ in length')
+        out = np.empty((6, p), dtype=np.float32 if suffix else np.float64)
+        self._check(getattr(self.lib, 'nxc_frame_columns' + suffix)(
+            self._h, C.byref(self.frame_desc(frame)), p, *ptrs,
+            out.ctypes.data_as(_fp if suffix else _dp)))
+        return out
+
+    def frame_columns_f32(self, frame, t, x, y, z, vx, vy, vz):
+        """``frame_columns`` of float32 columns (anything else is narrowed first)."""
+        return self.frame_columns(frame, *(np.asarray(c, dtype=np.float32)
+                                           for c in (t, x, y, z, vx, vy, vz)))
 
     # a pixel image's velocity products; ``prefix``: 'image' or 'camera', as in nxc_<prefix>_...
     def _moments_enable(self, prefix, on):
