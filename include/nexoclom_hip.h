@@ -1223,6 +1223,85 @@ int nxc_frame_columns_f32(nxc_handle *h, const nxc_frame_desc *d, int64_t p, con
                           const float *x, const float *y, const float *z, const float *vx,
                           const float *vy, const float *vz, float *out);
 
+/* ---- Age cube: the image's impulse response, and images for a time-varying source rate -----------
+ * EXTENSION -- every other product reads the stored rows as a steady state: a row at t_remaining =
+ * time is a packet of age t0 - time, t0 the run's endtime, and the image sums over all ages.  A row
+ * of age a stands for atoms launched a seconds before the epoch, so the image is linear in the
+ * source's history: filed by age, the weights give the image's response to a pulse of the source
+ * rate, and the image at any epoch for any history is one contraction of that cube.
+ * A block has na >= 1 bins over [a_lo, a_hi) seconds of age.  The host forms inv_da = na / (a_hi -
+ * a_lo) once in fp64.  A sample that reaches pixel pix with the final weight w -- exactly what is
+ * added to image[pix] -- and w != 0 is filed as follows, fp64, one rounding per operation, no
+ * contraction (time: the row's first column, widened when it is float32):
+ *   age = t0 - (double)time
+ *   u   = (age - a_lo) * inv_da
+ *   k = 0                 if u < 0                              (younger than the range)
+ *   k = 1 + (int)u        if 0 <= u < na                        (bin (int)u of the range)
+ *   k = na + 1            otherwise: at or above a_hi, or time not a number
+ * and the sample adds {w, w*w} to record pix*(na + 2) + k: one more atomic request per binned
+ * sample, pixel-major like the velocity cube.
+ *   - A sample with w == 0 adds nothing to the block; it is still counted in the packet image.  Its
+ *     time is not read.
+ *   - Nothing else is filtered: the na + 2 planes of a pixel sum to image[pix] up to the order of the
+ *     additions.
+ *   - The image pair, the counts and the counters of an ages pass are those of the plain pass.
+ *   nxc_image_ages_enable            after nxc_set_image: na >= 1 allocates and zeroes
+ *                                    nx*nz*(na + 2) 16-byte records (NXC_ERR_NOMEM when they cannot
+ *                                    be had), na == 0 frees them; nxc_set_image switches the block
+ *                                    off again; nxc_image_clear zeroes it with the image while it is
+ *                                    on.  NXC_ERR_ARG, before anything is allocated or freed, for
+ *                                    na < 0, t0, a_lo or a_hi not finite, a_lo >= a_hi (or a width
+ *                                    that is not finite), nx*nz*(na + 2) >= 2^31
+ *   nxc_image_ages_accumulate[_f32]  adds p host samples -- six columns, time first -- to the image
+ *                                    pair AND the block in one pass, never the tiles of
+ *                                    nxc_image_mode
+ *   nxc_image_ages_accumulate_rows   the same for rows [first, first + count) of a row store, whose
+ *                                    column 0 is the time
+ *   nxc_image_ages_download          sums[nx*nz][na + 2][2] = {w sum, w*w sum}, pixel index
+ *                                    ix*nz + iz, plane 0 below, planes 1..na the bins, na + 1 above
+ *   nxc_image_ages_upload            the block replaced by sums of that layout (for totals that were
+ *                                    added on the host)
+ *   nxc_image_ages_apply             ne >= 1 epochs: with K[na + 2][ne] (host, row-major, every value
+ *                                    finite) out[ne][nx*nz][2] (host) receives
+ *                                      out[e][pix] = { sum_k S[pix][k] * K[k][e],
+ *                                                      sum_k WW[pix][k] * (K[k][e] * K[k][e]) }
+ *                                    {S, WW} being the pixel's record of plane k.  Each sum runs over
+ *                                    k = 0, 1, .., na + 1 in that order from 0.0, one rounding per
+ *                                    operation, no contraction: a pure function of the block and K,
+ *                                    which a loop in the same order reproduces bit for bit.  The rows
+ *                                    of the two outer planes are applied like every other.
+ *                                    NXC_ERR_ARG for ne < 1, a null K or out, a value of K that is
+ *                                    not finite, planes that do not fit a workgroup's LDS even
+ *                                    at one pixel and one epoch, and more than 65535 epoch chunks
+ *                                    (of up to 64 epochs) -- all before anything is allocated
+ *   nxc_camera_ages_*                the same seven against the camera's own image buffer
+ * NXC_ERR_STATE names the missing call (the set first, then the enable), then NXC_ERR_ARG.  The age
+ * block, the velocity cube and the moments are independent states of a handle: enabling, clearing
+ * or freeing one never touches the others, and each pass adds to the image pair and its own block
+ * only. */
+int nxc_image_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi);
+int nxc_image_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
+                              const double *y, const double *z, const double *vy,
+                              const double *frac);
+int nxc_image_ages_accumulate_f32(nxc_handle *h, int64_t p, const float *time, const float *x,
+                                  const float *y, const float *z, const float *vy,
+                                  const float *frac);
+int nxc_image_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_image_ages_download(nxc_handle *h, double *sums);
+int nxc_image_ages_upload(nxc_handle *h, const double *sums);
+int nxc_image_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out);
+int nxc_camera_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi);
+int nxc_camera_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
+                               const double *y, const double *z, const double *vy,
+                               const double *frac);
+int nxc_camera_ages_accumulate_f32(nxc_handle *h, int64_t p, const float *time, const float *x,
+                                   const float *y, const float *z, const float *vy,
+                                   const float *frac);
+int nxc_camera_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_camera_ages_download(nxc_handle *h, double *sums);
+int nxc_camera_ages_upload(nxc_handle *h, const double *sums);
+int nxc_camera_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out);
+
 #ifdef __cplusplus
 }
 #endif

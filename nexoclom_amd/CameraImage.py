@@ -32,7 +32,10 @@ velocity_variance, velocity_dispersion, velocity_skewness, effective_packets) in
 (k_camera_moments), with the line-of-sight velocity taken along each sample's own ray from the
 camera, positive receding.  ``cube=(v_lo_kms, v_hi_kms, nbins)`` adds ModelImage's velocity cube
 (cube_sums, cube, cube_below, cube_above, velocity_edges, velocity_axis, cube_effective_packets)
-with the same velocity (k_camera_cube).
+with the same velocity (k_camera_cube).  ``ages=(a_lo_s, a_hi_s, nbins)`` adds ModelImage's age
+cube (age_sums, age_cube, age_below, age_above, age_edges, age_axis, age_effective_packets;
+k_camera_ages) and with it ``transient(epochs, history)``: the camera's images for a source whose
+rate changes with time (transient.py).
 
 Not supported, and refused: streaming (``npackets=``), shared runs (``cp=`` / ``shard=``), the
 LDS-tile accumulation, fisheye / all-sky projections (a gnomonic camera sees less than 180
@@ -41,6 +44,7 @@ degrees), moons as occulters.
 import numpy as np
 
 from .ModelImage import ModelImage, ModelResult, parse_cube, refuse_cube_with, refuse_moments_with
+from .transient import parse_ages, refuse_ages_of, refuse_ages_with
 from .Output import Output
 from .catalogue import sample_pass
 from .input_classes import InputError
@@ -96,7 +100,12 @@ def camera_basis(boresight, up):
 
 class CameraImage(ModelResult):
     def __init__(self, inputs, params, *, context=None, device=0, moments=False, cube=None,
-                 **unsupported):
+                 ages=None, **unsupported):
+        if ages is not None:
+            refuse_ages_with(moments=moments, cube=cube,
+                             **{key: unsupported.get(key) for key in ('npackets', 'shard', 'cp')})
+            ages = parse_ages(ages)
+            refuse_ages_of(inputs)
         if cube is not None:
             refuse_cube_with(moments=moments,
                              **{key: unsupported.get(key) for key in ('npackets', 'shard', 'cp')})
@@ -113,7 +122,7 @@ class CameraImage(ModelResult):
             raise InputError('CameraImage.__init__', "quantity must be 'column' or 'radiance'")
         self._set_origin()          # (npackets=, shard= and cp= are refused above, whatever the origin)
         self._frame()
-        self._new_pixel_sums(moments, cube)
+        self._new_pixel_sums(moments, cube, ages)
         self._ctx, self._device = context, device
         self.counters = {}
         self._from_catalogue()
@@ -172,16 +181,24 @@ class CameraImage(ModelResult):
             ctx.camera_set(self.observer, self.basis, self._vr_kms(vr_kms)/self.unit_km,
                            self.pix_area_cm2,
                            self.quantity, self.uedges, self.vedges, self.g_tables(aplanet))
+            if self.ages is not None:
+                self._ages_setup = lambda ctx: set_up(ctx, aplanet, vr_kms)
             self._enable_velocity(ctx, 'camera')
 
         def accumulate(ctx, **samples):
-            (ctx.camera_cube_accumulate if self.cube is not None else
+            (ctx.camera_ages_accumulate if self.ages is not None else
+             ctx.camera_cube_accumulate if self.cube is not None else
              ctx.camera_moments_accumulate if self.moments else ctx.camera_accumulate)(**samples)
 
         sample_pass(self, list(self.inputs._catalogue), accumulate,
+                    Output.AGE_COLS if self.ages is not None else
                     Output.MOMENT_COLS if velocity else Output.IMAGE_COLS, set_up,
                     lambda ctx: self._collect_pixels(ctx, 'camera'), **self._frame_pass())
 
     def finalize(self):
         """Scale to a source rate of 1e23 atoms/s, as ModelImage.finalize does."""
         ModelImage.finalize(self)
+
+    def transient(self, epochs, history):
+        """ModelResult.transient on the camera's age block (k_ages_apply)."""
+        return ModelResult.transient(self, epochs, history, prefix='camera')

@@ -282,6 +282,9 @@ class Input:
             from .frames import is_planet_origin, refuse_with_moon_origin
             if not is_planet_origin(self, read_params(format_).get('origin')):
                 refuse_with_moon_origin(cp=cp)
+        if kwargs.get('ages') is not None:
+            from .transient import refuse_ages_with
+            refuse_ages_with(cp=cp, moments=kwargs.get('moments'), cube=kwargs.get('cube'))
         if kwargs.get('cube') is not None:
             refuse_cube_with(cp=cp, moments=kwargs.get('moments'))
         if kwargs.get('moments'):

@@ -29,6 +29,14 @@ falls outside the range, ``velocity_edges`` / ``velocity_axis`` [km/s], ``cube_e
 (the error bars: ``cube / sqrt(cube_effective_packets)``) and the unscaled ``cube_sums``.
 include/nexoclom_hip.h ("Velocity cube") holds the definition.
 
+``ages=(a_lo_s, a_hi_s, nbins)`` (catalogued constant-step Outputs only; an extension) files every
+sample's weight under its age -- a row at t_remaining = t is a packet launched t0 - t seconds before
+the epoch, t0 = options.endtime -- in the same pass: ``age_cube`` (nx, nz, nbins), the image's
+response to a pulse of the source, ``age_below`` / ``age_above``, ``age_edges`` / ``age_axis`` [s],
+``age_effective_packets`` and the unscaled ``age_sums``; ``transient(epochs, history)`` contracts
+it with the response matrix of a source history into one image per epoch (transient.py).
+include/nexoclom_hip.h ("Age cube") holds the definition.
+
 ``params['origin']`` (catalogued Outputs only; an extension where the reference stops at planets
 with moons): the planet, or a moon among geometry.objects.  A moon makes ``center`` and ``width``
 lengths in moon radii around the moon, which then occults and shadows; the stored rows are moved
@@ -50,6 +58,8 @@ from .atomicdata import gValue
 from .catalogue import framed_columns, framed_slabs, run_g_values, sample_pass, shared_context
 from .frames import MoonFrame, is_planet_origin, refuse_with_moon_origin
 from .input_classes import InputError
+from .transient import (TransientImages, ages_from_sums, new_age_sums, parse_ages, refuse_ages_of,
+                        refuse_ages_with, response_matrix)
 from .units import Quantity
 
 HOST_SAMPLER_THREADS = 4        # chunks drawn ahead of the device by the streaming image
@@ -303,8 +313,12 @@ class ModelResult:
     # ---- the pixels of ModelImage and CameraImage; ``prefix``: the context's 'image' or 'camera'
     moments = False           # True: the pass over the rows also fills moment_sums
     cube = None               # (v_lo_kms, v_hi_kms, nbins): the pass also fills cube_sums
+    ages = None               # (a_lo_s, a_hi_s, nbins): the pass also fills age_sums
+    _ages_setup = None        # ctx -> None: the last set + enable of this object's age block
+    _ages_token = None        # what Context.ages_owner holds while the block is this object's total
+    _ages_collects = 0        # downloads added into age_sums
 
-    def _new_pixel_sums(self, moments, cube):
+    def _new_pixel_sums(self, moments, cube, ages=None):
         self.image = np.zeros(self.dims)
         self.packet_image = np.zeros(self.dims)
         self.moments = bool(moments)
@@ -313,6 +327,10 @@ class ModelResult:
         self.cube = cube
         if self.cube is not None:
             self.cube_sums = new_cube_sums(self.dims, self.cube)
+        self.ages = ages
+        if self.ages is not None:
+            self.age_sums = new_age_sums(self.dims, self.ages)
+            self._ages_token = object()
 
     def _enable_velocity(self, ctx, prefix):
         if self.moments:
@@ -320,6 +338,10 @@ class ModelResult:
         if self.cube is not None:
             v_lo, v_hi, nbins = self.cube
             getattr(ctx, prefix + '_cube_enable')(nbins, v_lo/self.unit_km, v_hi/self.unit_km)
+        if self.ages is not None:
+            a_lo, a_hi, nbins = self.ages
+            getattr(ctx, prefix + '_ages_enable')(nbins, float(self.inputs.options.endtime.value),
+                                                  a_lo, a_hi)
 
     def _collect_pixels(self, ctx, prefix):
         """Add the context's resident sums to the host's; the downloaded image."""
@@ -330,14 +352,58 @@ class ModelResult:
             self.moment_sums += getattr(ctx, prefix + '_moments_download')()
         if self.cube is not None:
             self.cube_sums += getattr(ctx, prefix + '_cube_download')()
+        if self.ages is not None:
+            self.age_sums += getattr(ctx, prefix + '_ages_download')()
+            self._collected_ages(ctx, prefix)
         return image
+
+    def _collected_ages(self, ctx, prefix):
+        """The resident block has just been added into ``age_sums``: after the first time it IS
+        this object's total, which the context is told (every set, clear, enable, pass and upload
+        there drops the claim); after a second one it is a part only."""
+        self._ages_collects += 1
+        if self._ages_collects == 1:
+            ctx.ages_owner[prefix] = self._ages_token
+        else:
+            ctx.ages_owner.pop(prefix, None)
+
+    def _publish_ages(self):
+        if self.ages is not None:
+            vars(self).update(ages_from_sums(self.age_sums, self.atoms_per_packet, *self.ages[:2]))
+
+    def transient(self, epochs, history, prefix='image'):
+        """The images at ``epochs`` [s] for a source whose rate relative to the nominal one was
+        ``history = (t_nodes_s, rate_nodes)`` (transient.response_matrix): a TransientImages with
+        epochs, kernel, images (E, nx, nz), effective_packets and light_curve.  The age block is
+        contracted where it is (k_ages_apply) while this object's sums are the ones resident in its
+        context; sums that were added on the host (several stretches of g-values) or that another
+        product has replaced since are set up again and uploaded once."""
+        if self.ages is None:
+            raise ValueError('transient() needs an object built with ages=(a_lo_s, a_hi_s, nbins)')
+        if not hasattr(self, 'age_edges'):
+            raise ValueError('transient() needs the finalized object (finalize())')
+        K = response_matrix(self.age_edges, epochs, history)
+        if self._ages_setup is None:                       # nothing was ever binned
+            sums = np.zeros((K.shape[1],) + tuple(self.dims) + (2,))
+        else:
+            ctx = self.context()
+            if ctx.ages_owner.get(prefix) is not self._ages_token:
+                self._ages_setup(ctx)
+                getattr(ctx, prefix + '_ages_upload')(self.age_sums)
+                ctx.ages_owner[prefix] = self._ages_token
+            sums = getattr(ctx, prefix + '_ages_apply')(K)
+        return TransientImages(epochs, K, sums, self.atoms_per_packet)
 
 
 class ModelImage(ModelResult):
     def __init__(self, inputs, params, overwrite=False, distribute=None, *, npackets=None,
                  seed=None, packs_per_it=None, downcast=True, device=0, context=None,
                  sampler='numpy', shard=None, finalize=True, generator='philox', moments=False,
-                 cube=None, slab_rows=None):
+                 cube=None, slab_rows=None, ages=None):
+        if ages is not None:
+            refuse_ages_with(npackets=npackets, shard=shard, moments=moments, cube=cube)
+            ages = parse_ages(ages)
+            refuse_ages_of(inputs)
         if cube is not None:
             refuse_cube_with(npackets=npackets, shard=shard, moments=moments)
             cube = parse_cube(cube)
@@ -351,7 +417,7 @@ class ModelImage(ModelResult):
             self.slab_rows = operator.index(slab_rows)
         self._set_origin(npackets=npackets, shard=shard)
         self._frame()
-        self._new_pixel_sums(moments, cube)
+        self._new_pixel_sums(moments, cube, ages)
         self.blimits = None
         self.xaxis = None
         self.zaxis = None
@@ -403,6 +469,9 @@ class ModelImage(ModelResult):
                 self.moment_sums += self._last_moment_sums
             if self.cube is not None:
                 self.cube_sums += self._last_cube_sums
+            if self.ages is not None:
+                self.age_sums += self._last_age_sums
+                self._collected_ages(self.context(), 'image')
             self.totalsource += run.totalsource
             self.xaxis, self.zaxis = weighted.x, weighted.y
 
@@ -424,6 +493,7 @@ class ModelImage(ModelResult):
 
         # the Outputs of a launch group are consecutive slices of one store: one kernel launch per
         # run of adjacent slices instead of one per Output
+        self._ages_collects = 0
         sample_pass(self, runs, lambda ctx, rows: self._accumulate(ctx, rows=rows), (), set_up,
                     **self._frame_pass())
         image = self._collect_pixels(ctx, 'image')
@@ -439,6 +509,7 @@ class ModelImage(ModelResult):
             vars(self).update(pixel_moments_from_sums(self.image, self.moment_sums, self.unit_km))
         if self.cube is not None:
             vars(self).update(cube_from_sums(self.cube_sums, self.atoms_per_packet, *self.cube[:2]))
+        self._publish_ages()
         self.image *= self.atoms_per_packet
 
     # ---- GPU plumbing ---------------------------------------------------------------------
@@ -456,12 +527,16 @@ class ModelImage(ModelResult):
     def _set_image(self, ctx, aplanet, vrplanet_Rs, downcast):
         ctx.set_image(self.image_rotation(), vrplanet_Rs, float(self.Apix), self.quantity,
                       self.xedges, self.zedges, self.g_tables(aplanet), downcast_f32=downcast)
+        if self.ages is not None:
+            self._ages_setup = lambda ctx: self._set_image(ctx, aplanet, vrplanet_Rs, downcast)
         self._enable_velocity(ctx, 'image')
 
     def _accumulate(self, ctx, samples=(), rows=None):
         """One pass over host columns or ``rows = (RowStore, first, count)`` through the entry this
         image asked for: the cube's, the moments' or the plain one."""
-        if self.cube is not None:
+        if self.ages is not None:
+            ctx.image_ages_accumulate(*samples, rows=rows)
+        elif self.cube is not None:
             ctx.image_cube_accumulate(*samples, rows=rows)
         elif self.moments:
             ctx.image_moments_accumulate(*samples, rows=rows)
@@ -491,12 +566,16 @@ class ModelImage(ModelResult):
                         self.counters[key] = self.counters.get(key, 0) + v
         else:
             velocity = self.moments or self.cube is not None
-            if self.frame is None:
-                samples, aplanet, vrplanet_kms = Output.image_columns(output, velocity=velocity)
-            else:
-                samples = framed_columns(ctx, self.frame, output,
-                                         Output.MOMENT_COLS if velocity else Output.IMAGE_COLS)
+            columns = Output.AGE_COLS if self.ages is not None else \
+                Output.MOMENT_COLS if velocity else Output.IMAGE_COLS
+            if self.frame is not None:
+                samples = framed_columns(ctx, self.frame, output, columns)
                 aplanet, vrplanet_kms = run_g_values(output)
+            elif self.ages is not None:
+                samples = Output.sample_columns(output, columns)
+                aplanet, vrplanet_kms = run_g_values(output)
+            else:
+                samples, aplanet, vrplanet_kms = Output.image_columns(output, velocity=velocity)
             if samples is None or len(samples[0]) == 0:
                 raise ValueError('this Output holds no trajectory (it was run with '
                                  'keep_trajectory=False); use ModelImage(..., npackets=N) instead')
@@ -510,6 +589,8 @@ class ModelImage(ModelResult):
             self._last_moment_sums = ctx.image_moments_download()
         if self.cube is not None:
             self._last_cube_sums = ctx.image_cube_download()
+        if self.ages is not None:
+            self._last_age_sums = ctx.image_ages_download()
         return (Histogram2dResult(image, self.xedges, self.zedges),
                 Histogram2dResult(counts.astype(float), self.xedges, self.zedges))
 

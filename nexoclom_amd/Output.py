@@ -766,6 +766,7 @@ class Output:
 
     IMAGE_COLS = ('x', 'y', 'z', 'vy', 'frac')
     MOMENT_COLS = ('x', 'y', 'z', 'vx', 'vy', 'vz', 'frac')
+    AGE_COLS = ('time', 'x', 'y', 'z', 'vy', 'frac')      # ages=: the row's time in front
     PATH = (str, os.PathLike)        # a stored run (.npz) where a catalogued Output may stand
 
     @staticmethod

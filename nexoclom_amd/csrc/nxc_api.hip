@@ -27,6 +27,7 @@
 #include "nxc_camera_check.hpp"
 #include "nxc_shell_check.hpp"
 #include "nxc_cube_check.hpp"
+#include "nxc_ages_check.hpp"
 #include "nxc_los_profile_check.hpp"
 #include "nxc_desc_check.hpp"
 #include "nxc_source_map_check.hpp"
@@ -326,7 +327,8 @@ struct nxc_pairs {
 };
 
 // What a pixel grid owns on the device, ModelImage's (nxc_set_image) and CameraImage's
-// (nxc_camera_set) alike.  The moments and the cube are there from their enable to the next set.
+// (nxc_camera_set) alike.  The moments, the cube and the age block are there from their enable to
+// the next set, each a state of its own.
 struct PixelSums {
     Dev<double> image;               // interleaved {weight sum, packet count} per pixel, fp64
     size_t npix = 0;
@@ -335,6 +337,9 @@ struct PixelSums {
     bool have_cube = false;          // nxc_X_cube_enable since the last set
     Dev<double> cube;                // the velocity cube: [npix][nv + 2] records (k_X_cube)
     CubeK cubeK{};
+    bool have_ages = false;          // nxc_X_ages_enable since the last set
+    Dev<double> ages;                // the age cube: [npix][na + 2] records (k_X_ages)
+    AgeK ageK{};
 };
 
 // Stored samples on the device, as every consumer (image, line of sight, density, fit) reads them:
@@ -342,7 +347,7 @@ struct PixelSums {
 struct Samples {
     bool f32 = false, index64 = true;
     int64_t n = 0, shift = 0;                // rows, index shift
-    const void *cols[7] = {};                // x, y, z, vy, frac, vx, vz (null where nobody reads it)
+    const void *cols[8] = {};                // x, y, z, vy, frac, vx, vz, time (null where nobody reads it)
     const void *index = nullptr;             // null where the entry allows it
     const nxc_rows *store = nullptr;         // stores: the store, column 0 of row 0 and the
     const void *col0 = nullptr;              // distance between columns (the fit's rows copy
@@ -1072,8 +1077,8 @@ int rows_check(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
 }
 
 // ---- sample views ------------------------------------------------------------------------------
-constexpr int N_SAMPLE_COLS = 7;
-constexpr int ROW_SAMPLE_COLS[N_SAMPLE_COLS] = {1, 2, 3, 5, 7, 4, 6};   // the store columns of x, y, z, vy, frac, vx, vz
+constexpr int N_SAMPLE_COLS = 8;
+constexpr int ROW_SAMPLE_COLS[N_SAMPLE_COLS] = {1, 2, 3, 5, 7, 4, 6, 0};   // the store columns of x, y, z, vy, frac, vx, vz, time
 
 // rows [first, first + count) of a store (its index is int32 beside float32 rows, else int64)
 int samples_from_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count, int64_t shift,
@@ -1680,6 +1685,30 @@ int camera_cube_run(nxc_handle *h, const Samples &s)
     });
 }
 
+// ModelImage(ages=...) over samples on the device (k_image_ages: atomics, never the tiles)
+int image_ages_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_image_ages<T>, NXC_IMAGE_MOMENTS_BLOCK, h->img_bytes, s.n,
+                                  h->d_blob_img, (int64_t)h->img_bytes, s.n, h->img.ageK,
+                                  s.col<T>(7), s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3),
+                                  s.col<T>(4), h->img.image, h->img.ages, h->d_ctr);
+    });
+}
+
+// CameraImage(ages=...) over samples on the device (k_camera_ages)
+int camera_ages_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_camera_ages<T>, NXC_CAMERA_BLOCK, h->cam_bytes, s.n, h->cam,
+                                  h->d_blob_cam, (int64_t)h->cam_bytes, s.n, h->cam_px.ageK,
+                                  s.col<T>(7), s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3),
+                                  s.col<T>(4), h->cam_px.image, h->cam_px.ages, h->d_ctr);
+    });
+}
+
 // What tells one consumer of stored samples from another at its entry points
 struct SampleConsumer {
     bool (*have)(const nxc_handle *);            // its nxc_*_set has been called ...
@@ -1689,6 +1718,7 @@ struct SampleConsumer {
     bool (*idle)(const nxc_handle *);            // nothing to add to, whatever the samples (or null)
     int (*run)(nxc_handle *, const Samples &);
     PixelSums nxc_handle::*px = nullptr;         // the pixel sums its moments and cube sit beside
+    bool needs_time = false;                     // reads the time column (host entries: an eighth array)
 };
 const SampleConsumer IMAGE_SAMPLES = {[](const nxc_handle *h) { return h->have_image; },
                                       "nxc_set_image has not been called",
@@ -1838,6 +1868,121 @@ int pixel_cube_download(nxc_handle *h, const SampleConsumer &base, const SampleC
     });
 }
 
+// the age block's state is its enable too, checked after the set's (pixel_moments_need_set); its
+// passes read the time column and neither vx nor vz
+const SampleConsumer IMAGE_AGES_SAMPLES = {[](const nxc_handle *h) { return h->img.have_ages; },
+                                           "nxc_image_ages_enable has not been called",
+                                           true, true, false, nullptr, image_ages_run, nullptr, true};
+const SampleConsumer CAMERA_AGES_SAMPLES = {[](const nxc_handle *h) { return h->cam_px.have_ages; },
+                                            "nxc_camera_ages_enable has not been called",
+                                            true, true, false, nullptr, camera_ages_run, nullptr, true};
+
+size_t ages_bytes(size_t npix, const AgeK &Q) { return npix * (size_t)(Q.na + 2) * 2 * sizeof(double); }
+
+// nxc_X_ages_enable: [npix][na + 2] zeroed records beside the image pair of `base`, or none; the
+// arguments are checked (check_ages_args) before the block there is is touched
+int pixel_ages_enable(nxc_handle *h, const SampleConsumer &base, int64_t na, double t0, double a_lo,
+                      double a_hi)
+{
+    if (int rc = pixel_moments_need_set(h, base)) return rc;
+    return guarded([&]() -> int {
+        PixelSums &px = h->*base.px;
+        if (na != 0) {
+            const std::string why = check_ages_args((int64_t)px.npix, na, t0, a_lo, a_hi);
+            if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
+        }
+        HIPCHK(hipSetDevice(h->device));
+        px.have_ages = false;
+        int rc = px.ages.release();
+        if (rc || na == 0) return rc;
+        px.ageK = AgeK{(int)na, t0, a_lo, ages_inv_da(na, a_lo, a_hi)};
+        const size_t bytes = ages_bytes(px.npix, px.ageK);
+        if ((rc = px.ages.ensure(bytes))) return rc;
+        HIPCHK(hipMemsetAsync(px.ages, 0, bytes, h->stream));
+        HIPCHK(stream_sync(h));
+        px.have_ages = true;
+        return NXC_OK;
+    });
+}
+
+// nxc_X_ages_download: sums[npix][na + 2][2], the device's own order
+int pixel_ages_download(nxc_handle *h, const SampleConsumer &base, const SampleConsumer &ages,
+                        double *sums)
+{
+    if (int rc = pixel_moments_need_set(h, base)) return rc;
+    return guarded([&]() -> int {
+        if (!ages.have(h)) return fail(NXC_ERR_STATE, ages.unset);
+        if (!sums) return fail(NXC_ERR_ARG, "bad arguments");
+        HIPCHK(hipSetDevice(h->device));
+        const PixelSums &px = h->*base.px;
+        HIPCHK(hipMemcpyAsync(sums, px.ages, ages_bytes(px.npix, px.ageK), hipMemcpyDeviceToHost,
+                              h->stream));
+        HIPCHK(stream_sync(h));
+        return NXC_OK;
+    });
+}
+
+// nxc_X_ages_upload: the block replaced by sums[npix][na + 2][2] (totals added on the host)
+int pixel_ages_upload(nxc_handle *h, const SampleConsumer &base, const SampleConsumer &ages,
+                      const double *sums)
+{
+    if (int rc = pixel_moments_need_set(h, base)) return rc;
+    return guarded([&]() -> int {
+        if (!ages.have(h)) return fail(NXC_ERR_STATE, ages.unset);
+        if (!sums) return fail(NXC_ERR_ARG, "bad arguments");
+        HIPCHK(hipSetDevice(h->device));
+        const PixelSums &px = h->*base.px;
+        HIPCHK(hipMemcpyAsync(px.ages, sums, ages_bytes(px.npix, px.ageK), hipMemcpyHostToDevice,
+                              h->stream));
+        HIPCHK(stream_sync(h));
+        return NXC_OK;
+    });
+}
+
+// nxc_X_ages_apply: out[ne][npix][2] (host) = the resident block contracted with K[na + 2][ne]
+// (host), k_ages_apply over pixel runs x epoch chunks cut to the device's LDS (ages_apply_plan)
+int pixel_ages_apply(nxc_handle *h, const SampleConsumer &base, const SampleConsumer &ages,
+                     int64_t ne, const double *K, double *out)
+{
+    if (int rc = pixel_moments_need_set(h, base)) return rc;
+    return guarded([&]() -> int {
+        if (!ages.have(h)) return fail(NXC_ERR_STATE, ages.unset);
+        const PixelSums &px = h->*base.px;
+        const int64_t planes = (int64_t)px.ageK.na + 2;
+        const std::string why = check_ages_apply(planes, ne, K);
+        if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
+        if (!out) return fail(NXC_ERR_ARG, "bad arguments");
+        HIPCHK(hipSetDevice(h->device));
+        int lds_per_block = 0;
+        HIPCHK(hipDeviceGetAttribute(&lds_per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device));
+        AgesPlan plan;
+        if (!ages_apply_plan(planes, ne, (size_t)std::max(lds_per_block, 0), &plan))
+            return fail(NXC_ERR_ARG, "age cube: one pixel's planes and one column of K exceed the "
+                                     "LDS of a workgroup");
+        const int64_t runs = ((int64_t)px.npix + plan.run - 1) / plan.run;
+        const int64_t chunks = (ne + plan.chunk - 1) / plan.chunk;
+        if (chunks > NXC_AGES_MAX_CHUNKS)
+            return fail(NXC_ERR_ARG, "age cube: more than 65535 epoch chunks in one call");
+        const size_t k_bytes = (size_t)planes * (size_t)ne * sizeof(double);
+        const size_t out_bytes = (size_t)ne * px.npix * 2 * sizeof(double);
+        Dev<double> d_K, d_out;
+        int rc;
+        if ((rc = d_K.ensure(k_bytes)) || (rc = d_out.ensure(out_bytes))) return rc;
+        HIPCHK(hipMemcpyAsync(d_K, K, k_bytes, hipMemcpyHostToDevice, h->stream));
+        const AgesApplyK A = {(int)planes, (int)plan.stride, (int)plan.run, (int)plan.chunk, (int)ne,
+                              (int64_t)px.npix};
+        if ((rc = prep_kernel(k_ages_apply, plan.bytes)) || (rc = begin_timed(h))) return rc;
+        hipLaunchKernelGGL(k_ages_apply, dim3((unsigned)runs, (unsigned)chunks), dim3(NXC_AGES_APPLY_BLOCK),
+                           plan.bytes, h->stream, A, reinterpret_cast<const double2 *>(px.ages.get()),
+                           d_K.get(), reinterpret_cast<double2 *>(d_out.get()));
+        HIPCHK(hipGetLastError());
+        if ((rc = end_timed(h))) return rc;
+        HIPCHK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(stream_sync(h));
+        return NXC_OK;
+    });
+}
+
 // What every accepted call does, samples or none
 int begin_sample_pass(nxc_handle *h, const SampleConsumer &c)
 {
@@ -1851,17 +1996,18 @@ int begin_sample_pass(nxc_handle *h, const SampleConsumer &c)
 template <typename T>
 int accumulate_columns(nxc_handle *h, const SampleConsumer &c, int64_t p, const T *x, const T *y,
                        const T *z, const T *vy, const T *frac, const T *vx = nullptr,
-                       const T *vz = nullptr)
+                       const T *vz = nullptr, const T *time = nullptr)
 {
     return guarded([&]() -> int {
         if (!h || !c.have(h)) return fail(NXC_ERR_STATE, c.unset);
         if (p < 0 || (p && (!x || !y || !z || (c.needs_vy && !vy) || !frac ||
-                            (c.needs_vxz && (!vx || !vz)))))
+                            (c.needs_vxz && (!vx || !vz)) || (c.needs_time && !time))))
             return fail(NXC_ERR_ARG, "bad arguments");
         int rc = begin_sample_pass(h, c);
         if (rc || p == 0 || (c.idle && c.idle(h))) return rc;
         const T *cols[N_SAMPLE_COLS] = {x, y, z, c.needs_vy ? vy : nullptr, frac,
-                                        c.needs_vxz ? vx : nullptr, c.needs_vxz ? vz : nullptr};
+                                        c.needs_vxz ? vx : nullptr, c.needs_vxz ? vz : nullptr,
+                                        c.needs_time ? time : nullptr};
         Samples s;
         rc = samples_upload(h, h->d_samples, p, cols, nullptr, &s);
         return rc ? rc : c.run(h, s);
@@ -2377,6 +2523,7 @@ int nxc_set_image(nxc_handle *h, const nxc_image_desc *d)
     h->have_image = false;
     h->img.have_mom = false;
     h->img.have_cube = false;
+    h->img.have_ages = false;
     h->image_block = append_image_block(part, G, d->nx, d->nz, d->xedges, d->zedges, nl, luts);
     h->image_part = std::move(part);
     h->G = G;
@@ -2527,6 +2674,8 @@ int nxc_image_clear(nxc_handle *h)
         HIPCHK(hipMemsetAsync(h->img.mom, 0, 4 * h->img.npix * sizeof(double), h->stream));
     if (h->img.have_cube)
         HIPCHK(hipMemsetAsync(h->img.cube, 0, cube_bytes(h->img.npix, h->img.cubeK), h->stream));
+    if (h->img.have_ages)
+        HIPCHK(hipMemsetAsync(h->img.ages, 0, ages_bytes(h->img.npix, h->img.ageK), h->stream));
     return NXC_OK;
 }
 
@@ -3453,6 +3602,7 @@ int nxc_camera_set(nxc_handle *h, const nxc_camera_desc *d)
     h->have_camera = false;
     h->cam_px.have_mom = false;
     h->cam_px.have_cube = false;
+    h->cam_px.have_ages = false;
     const size_t npix = (size_t)d->nx * (size_t)d->nz;
     if ((rc = h->d_blob_cam.ensure(blob.size())) ||
         (rc = h->cam_px.image.ensure(2 * npix * sizeof(double))))
@@ -3556,6 +3706,46 @@ int nxc_camera_cube_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t fi
 int nxc_camera_cube_download(nxc_handle *h, double *sums)
 {
     return pixel_cube_download(h, CAMERA_SAMPLES, CAMERA_CUBE_SAMPLES, sums);
+}
+
+int nxc_camera_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi)
+{
+    return pixel_ages_enable(h, CAMERA_SAMPLES, na, t0, a_lo, a_hi);
+}
+
+int nxc_camera_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
+                               const double *y, const double *z, const double *vy, const double *frac)
+{
+    if (int rc = pixel_moments_need_set(h, CAMERA_SAMPLES)) return rc;
+    return accumulate_columns<double>(h, CAMERA_AGES_SAMPLES, p, x, y, z, vy, frac, nullptr, nullptr, time);
+}
+
+int nxc_camera_ages_accumulate_f32(nxc_handle *h, int64_t p, const float *time, const float *x,
+                                   const float *y, const float *z, const float *vy, const float *frac)
+{
+    if (int rc = pixel_moments_need_set(h, CAMERA_SAMPLES)) return rc;
+    return accumulate_columns<float>(h, CAMERA_AGES_SAMPLES, p, x, y, z, vy, frac, nullptr, nullptr, time);
+}
+
+int nxc_camera_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    if (int rc = pixel_moments_need_set(h, CAMERA_SAMPLES)) return rc;
+    return accumulate_rows(h, CAMERA_AGES_SAMPLES, r, first, count);
+}
+
+int nxc_camera_ages_download(nxc_handle *h, double *sums)
+{
+    return pixel_ages_download(h, CAMERA_SAMPLES, CAMERA_AGES_SAMPLES, sums);
+}
+
+int nxc_camera_ages_upload(nxc_handle *h, const double *sums)
+{
+    return pixel_ages_upload(h, CAMERA_SAMPLES, CAMERA_AGES_SAMPLES, sums);
+}
+
+int nxc_camera_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out)
+{
+    return pixel_ages_apply(h, CAMERA_SAMPLES, CAMERA_AGES_SAMPLES, ne, K, out);
 }
 
 // ---- ShellMap --------------------------------------------------------------------------------------
@@ -4200,6 +4390,46 @@ int nxc_image_cube_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t fir
 int nxc_image_cube_download(nxc_handle *h, double *sums)
 {
     return pixel_cube_download(h, IMAGE_SAMPLES, IMAGE_CUBE_SAMPLES, sums);
+}
+
+int nxc_image_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi)
+{
+    return pixel_ages_enable(h, IMAGE_SAMPLES, na, t0, a_lo, a_hi);
+}
+
+int nxc_image_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
+                               const double *y, const double *z, const double *vy, const double *frac)
+{
+    if (int rc = pixel_moments_need_set(h, IMAGE_SAMPLES)) return rc;
+    return accumulate_columns<double>(h, IMAGE_AGES_SAMPLES, p, x, y, z, vy, frac, nullptr, nullptr, time);
+}
+
+int nxc_image_ages_accumulate_f32(nxc_handle *h, int64_t p, const float *time, const float *x,
+                                   const float *y, const float *z, const float *vy, const float *frac)
+{
+    if (int rc = pixel_moments_need_set(h, IMAGE_SAMPLES)) return rc;
+    return accumulate_columns<float>(h, IMAGE_AGES_SAMPLES, p, x, y, z, vy, frac, nullptr, nullptr, time);
+}
+
+int nxc_image_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    if (int rc = pixel_moments_need_set(h, IMAGE_SAMPLES)) return rc;
+    return accumulate_rows(h, IMAGE_AGES_SAMPLES, r, first, count);
+}
+
+int nxc_image_ages_download(nxc_handle *h, double *sums)
+{
+    return pixel_ages_download(h, IMAGE_SAMPLES, IMAGE_AGES_SAMPLES, sums);
+}
+
+int nxc_image_ages_upload(nxc_handle *h, const double *sums)
+{
+    return pixel_ages_upload(h, IMAGE_SAMPLES, IMAGE_AGES_SAMPLES, sums);
+}
+
+int nxc_image_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out)
+{
+    return pixel_ages_apply(h, IMAGE_SAMPLES, IMAGE_AGES_SAMPLES, ne, K, out);
 }
 
 int nxc_los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,

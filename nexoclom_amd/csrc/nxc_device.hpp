@@ -1210,6 +1210,34 @@ NXC_DEV int cube_plane(const CubeK &Q, double vlos)
     return k;
 }
 
+// ---- age cube: a sample's weight filed under its age ----------------------------------------------
+// (include/nexoclom_hip.h, "Age cube", holds the definition.)  na bins over [a_lo, a_hi) seconds of
+// age, inv_da = na / (a_hi - a_lo) from the host; a row's age is t0 - time, time being the row's
+// t_remaining.  A sample that reached pixel `pix` with the final weight w != 0 adds {w, w w} to
+// record pix (na + 2) + k of ages2,
+//     u = ((t0 - time) - a_lo) inv_da;   k = 0 if u < 0,   1 + (int)u if 0 <= u < na,   na + 1 otherwise
+// (otherwise: at or above a_hi, or time not a number).  The record index stays below 2^31
+// (check_ages_args).  A sample with w == 0 adds nothing and its time is not read.
+// Wave-cooperative: all 64 lanes call it from uniform control flow; one request per sample.
+struct AgeK {
+    int na;                     // bins; planes 0 and na + 1 hold what falls below and above
+    double t0, a_lo, inv_da;    // [s], [s], [1/s]
+};
+
+template <typename T>
+NXC_DEV void pixel_ages_add(const AgeK &Q, bool ok, int pix, double w, int64_t i,
+                            const T *__restrict__ time_col, double *__restrict__ ages2)
+{
+    const bool has = ok && w != 0.0;
+    double age = 0.0;
+    if (has) age = Q.t0 - (double)time_col[i];
+    const double u = (age - Q.a_lo) * Q.inv_da;
+    int k = Q.na + 1;
+    if (u < 0.0) k = 0;
+    else if (u < (double)Q.na) k = 1 + (int)u;
+    add_record_pairs(has, pix * (Q.na + 2) + k, w, w * w, ages2);
+}
+
 // ---- ShellMap: the same sample filed by local time, latitude and altitude --------------------------
 // (include/nexoclom_hip.h, "ShellMap", holds the definition; the operations below are in its
 // order.)  Everything the image has a place for -- g-value tables, the two edge arrays (longitude as

@@ -15,16 +15,19 @@
 //   k_camera        the same samples in the perspective image of a camera at a finite distance
 //   k_image_moments, k_camera_moments   either pass with four velocity-moment sums per pixel
 //   k_image_cube, k_camera_cube         either pass with the weight filed per pixel and Doppler bin
+//   k_image_ages, k_camera_ages         either pass with the weight filed per pixel and age bin
 //   k_shell         the same samples by solar-fixed longitude, sin(latitude) and altitude (ShellMap)
-//                   (all seven: pixel_pass -- staging, loop, loads, counters -- with a lambda each)
+//                   (all nine: pixel_pass -- staging, loop, loads, counters -- with a lambda each)
 //   k_density, k_density_moments, k_density_spectrum   stored samples within dr of query points
 //                   (density_walk -- loop, cull, candidate walk, membership -- with a load and a
 //                   per-trip lambda each; k_density_moments keeps the walk written out)
+//   k_ages_apply    an age cube contracted with a response matrix: one image per epoch (streaming)
 //   k_frame_rows    stored rows moved into the frame that co-rotates with a moon (streaming)
 //
 // All lookup tables (radiation acceleration, g-values, bin edges) are staged once per workgroup
 // into LDS from one packed blob.
 #pragma once
+#include "nxc_ages_check.hpp"
 #include "nxc_device.hpp"
 #include "nxc_fused_variant.hpp"
 #include "nxc_source_limits.hpp"
@@ -954,7 +957,7 @@ k_var(ForceK F, const unsigned char *__restrict__ blob, int64_t stage_bytes, int
 }
 
 // ---------------------------------------------------------------------------------------------
-// The pass of the seven pixel kernels over stored samples: the tables staged into LDS, a grid-stride
+// The pass of the nine pixel kernels over stored samples: the tables staged into LDS, a grid-stride
 // loop that hands `sample` one row per lane and trip (wave-cooperative: every lane calls it, with
 // or without a row), and the three counters flushed once per workgroup.  `sample` is the kernel's
 // own: (G, IR, PixelSample, binned, nonfinite) -> what the row adds.
@@ -1047,6 +1050,76 @@ k_image_cube(const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_
                    const PixelHit h = image_located(G, IR, s, acc2, binned, nonfinite);
                    pixel_cube_add(Q, h.ok, h.pix, h.w, image_vlos(G, IR, h, s, vx, vz), cube2);
                });
+}
+
+// ModelImage(ages=...): k_image_cube's pass with the sample's age in the place of its Doppler
+// velocity; a sample that reaches its pixel with w != 0 adds {w, w w} to the record of its pixel
+// and age bin in ages2, [n_pix][na + 2] 16-byte records (pixel_ages_add): at most two atomic
+// requests per binned sample.  Six columns: the time column is read by the lanes that file a
+// weight, vx and vz by nobody.  The scalars travel as a kernel argument; ImageK and the LDS blob
+// are k_image's.
+template <typename T>
+__global__ void __launch_bounds__(NXC_IMAGE_MOMENTS_BLOCK)
+k_image_ages(const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p, AgeK Q,
+             const T *__restrict__ time, const T *__restrict__ x, const T *__restrict__ y,
+             const T *__restrict__ z, const T *__restrict__ vy, const T *__restrict__ frac,
+             double *__restrict__ acc2, double *__restrict__ ages2, DevCounters *__restrict__ ctr)
+{
+    pixel_pass(blob, stage_bytes, p, x, y, z, vy, frac, ctr, (int64_t)blockIdx.x * blockDim.x,
+               (int64_t)gridDim.x * blockDim.x,
+               [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
+                   unsigned long long &binned, unsigned long long &nonfinite) {
+                   const PixelHit h = image_located(G, IR, s, acc2, binned, nonfinite);
+                   pixel_ages_add(Q, h.ok, h.pix, h.w, s.i, time, ages2);
+               });
+}
+
+// The image of every epoch from an age cube: out[e][pix] = {sum_k S[pix][k] K[k][e],
+// sum_k WW[pix][k] (K[k][e] K[k][e])} over k = 0 .. planes - 1 in that order from 0.0, one
+// rounding per operation -- a pure function of the cube and K.  Workgroup (bx, by) takes the pixels
+// [bx run, bx run + run) and the epochs [by chunk, by chunk + chunk): the pixels' records are one
+// contiguous block of the cube, loaded with coalesced 16-byte loads into LDS, [run][stride]
+// records with the odd stride of ages_apply_plan; beside it K's columns of the chunk,
+// [planes][chunk].  Each thread then forms (pixel, epoch) sums from LDS, consecutive threads
+// consecutive pixels, and writes out as [ne][npix] 16-byte records.  No atomics, no counters.
+// This kernel addresses its own dynamic LDS and does not go through stage_tables: the rule that the
+// table blob sits at LDS address 0 does not concern it.
+struct AgesApplyK {
+    int planes, stride, run, chunk, ne;
+    int64_t npix;
+};
+
+__global__ void __launch_bounds__(NXC_AGES_APPLY_BLOCK)
+k_ages_apply(AgesApplyK A, const double2 *__restrict__ cube2, const double *__restrict__ K,
+             double2 *__restrict__ out)
+{
+    double2 *const rec = reinterpret_cast<double2 *>(nxc_lds);                        // [run][stride]
+    double *const Kc = reinterpret_cast<double *>(rec + (size_t)A.run * A.stride);    // [planes][chunk]
+    const int64_t pix0 = (int64_t)blockIdx.x * A.run;
+    const int e0 = (int)blockIdx.y * A.chunk;
+    const int n = (int)(A.npix - pix0 < A.run ? A.npix - pix0 : A.run);
+    const int ce = A.ne - e0 < A.chunk ? A.ne - e0 : A.chunk;
+    const double2 *const src = cube2 + pix0 * A.planes;
+    for (int r = threadIdx.x; r < n * A.planes; r += blockDim.x) {
+        const int q = r / A.planes;
+        rec[q * A.stride + (r - q * A.planes)] = src[r];
+    }
+    for (int j = threadIdx.x; j < A.planes * ce; j += blockDim.x) {
+        const int k = j / ce;
+        Kc[k * A.chunk + (j - k * ce)] = K[(int64_t)k * A.ne + e0 + (j - k * ce)];
+    }
+    __syncthreads();
+    for (int item = threadIdx.x; item < n * ce; item += blockDim.x) {
+        const int e = item / n, q = item - e * n;
+        const double2 *const mine = rec + q * A.stride;
+        double s = 0.0, ww = 0.0;
+        for (int k = 0; k < A.planes; k++) {
+            const double c = Kc[k * A.chunk + e];
+            s = s + mine[k].x * c;
+            ww = ww + mine[k].y * (c * c);
+        }
+        out[(int64_t)(e0 + e) * A.npix + pix0 + q] = make_double2(s, ww);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3058,6 +3131,24 @@ k_camera_cube(CameraK K, const unsigned char *__restrict__ blob, int64_t stage_b
                    unsigned long long &binned, unsigned long long &nonfinite) {
                    const PixelHit h = camera_located(K, G, IR, s, acc2, binned, nonfinite);
                    pixel_cube_add(Q, h.ok, h.pix, h.w, camera_vlos(K, h, s, vx, vz), cube2);
+               });
+}
+
+// CameraImage(ages=...): k_camera's pass with k_image_ages' tail (pixel_ages_add); ages2 and Q as
+// in k_image_ages.
+template <typename T>
+__global__ void __launch_bounds__(NXC_CAMERA_BLOCK)
+k_camera_ages(CameraK K, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p,
+              AgeK Q, const T *__restrict__ time, const T *__restrict__ x, const T *__restrict__ y,
+              const T *__restrict__ z, const T *__restrict__ vy, const T *__restrict__ frac,
+              double *__restrict__ acc2, double *__restrict__ ages2, DevCounters *__restrict__ ctr)
+{
+    pixel_pass(blob, stage_bytes, p, x, y, z, vy, frac, ctr, (int64_t)blockIdx.x * blockDim.x,
+               (int64_t)gridDim.x * blockDim.x,
+               [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
+                   unsigned long long &binned, unsigned long long &nonfinite) {
+                   const PixelHit h = camera_located(K, G, IR, s, acc2, binned, nonfinite);
+                   pixel_ages_add(Q, h.ok, h.pix, h.w, s.i, time, ages2);
                });
 }
 

@@ -281,11 +281,38 @@ SIGNATURES = {
     'nxc_frame_rows': (*_desc(nxc_frame_desc), _h, _i64, _i64, _out),
     'nxc_frame_columns': (*_desc(nxc_frame_desc), _i64, *[_dp]*7, _dp),
     'nxc_frame_columns_f32': (*_desc(nxc_frame_desc), _i64, *[_fp]*7, _fp),
+    'nxc_image_ages_enable': (_h, _i64, _dbl, _dbl, _dbl),
+    **_sample_entries('nxc_image_ages_accumulate', 6),
+    'nxc_image_ages_download': (_h, _dp),
+    'nxc_image_ages_upload': (_h, _dp),
+    'nxc_image_ages_apply': (_h, _i64, _dp, _dp),
+    'nxc_camera_ages_enable': (_h, _i64, _dbl, _dbl, _dbl),
+    **_sample_entries('nxc_camera_ages_accumulate', 6),
+    'nxc_camera_ages_download': (_h, _dp),
+    'nxc_camera_ages_upload': (_h, _dp),
+    'nxc_camera_ages_apply': (_h, _i64, _dp, _dp),
 }
 RESTYPES = {'nxc_last_error_string': C.c_char_p}       # every other function returns an int status
 EXPORTS = tuple(SIGNATURES)
 
 _lib = None
+
+
+def ages_apply_plan(planes, ne, lds_bytes=64*1024):
+    """(stride, run, chunk) of a workgroup of k_ages_apply for ``planes`` = na + 2 planes and
+    ``ne`` epochs on a device with ``lds_bytes`` of LDS per workgroup: records from one pixel to the
+    next in LDS, pixels per workgroup, epochs per workgroup -- ages_apply_plan of
+    csrc/nxc_ages_check.hpp in Python, for what wants to know how often a call reads the block
+    (ceil(ne / chunk) times); tests/test_age_cube_cpu.py holds it against the C++.  None: one pixel
+    and one epoch do not fit."""
+    stride = planes | 1
+    least = stride*16 + planes*8
+    if planes < 3 or ne < 1 or least > lds_bytes:
+        return None
+    budget = min(lds_bytes, max(32*1024, least))
+    chunk = max(1, min(ne, 64, ((budget - stride*16)//2)//(planes*8)))
+    run = max(1, min(256, (budget - planes*chunk*8)//(stride*16)))
+    return stride, run, chunk
 
 
 def load_library():
@@ -439,6 +466,9 @@ class Context:
         self.device = device
         self.n_packets = 0
         self.image_shape = None
+        # 'image' / 'camera' -> the token of the product whose total the resident age block holds;
+        # whatever changes the block (a set, a clear, an enable, an ages pass, an upload) drops it
+        self.ages_owner = {}
         self._stores = []              # resident RowStores, oldest first (weak references)
 
     # -- plumbing ---------------------------------------------------------------------------
@@ -531,6 +561,7 @@ class Context:
             self._fill_lines(d, g_tables, keep)
         self._check(self.lib.nxc_set_image(self._h, C.byref(d)))
         self.image_shape = (int(d.nx), int(d.nz))
+        self.ages_owner.pop('image', None)          # the set switches the age block off
 
     def set_bounce(self, cfg):
         """cfg: dict from nexoclom_amd.surface.bounce_config, or None for perfect sticking.
@@ -721,6 +752,7 @@ class Context:
 
     def image_clear(self):
         self._check(self.lib.nxc_image_clear(self._h))
+        self.ages_owner.pop('image', None)          # zeroed with the image
 
     def image_download(self):
         nx, nz = self.image_shape
@@ -859,6 +891,8 @@ class Context:
     def _accumulate(self, entry_name, cols, rows):
         """One consumer's pass over stored samples: ``rows = (RowStore, first, count)`` through
         its ``_rows`` entry, else host columns through the entry of their width."""
+        if entry_name.endswith('_ages_accumulate'):
+            self.ages_owner.pop(entry_name.split('_')[1], None)
         if rows is not None:
             store, first, count = rows
             self._check(getattr(self.lib, entry_name + '_rows')(
@@ -918,8 +952,33 @@ class Context:
         self._check(getattr(self.lib, f'nxc_{prefix}_cube_enable')(self._h, nv, v_lo, v_hi))
         setattr(self, f'_{prefix}_cube_nv', nv)
 
+    def _ages_enable(self, prefix, na, t0, a_lo, a_hi):
+        na = int(na)
+        self._check(getattr(self.lib, f'nxc_{prefix}_ages_enable')(self._h, na, t0, a_lo, a_hi))
+        setattr(self, f'_{prefix}_ages_na', na)
+        self.ages_owner.pop(prefix, None)
+
+    def _ages_upload(self, prefix, sums):
+        shape = tuple(getattr(self, prefix + '_shape', None) or (0, 0)) + \
+            (getattr(self, f'_{prefix}_ages_na', 0) + 2, 2)
+        sums = _f64(sums)
+        if sums.shape != shape:
+            raise ValueError(f'ages_upload: sums of shape {sums.shape}, the block has {shape}')
+        self.ages_owner.pop(prefix, None)
+        self._check(getattr(self.lib, f'nxc_{prefix}_ages_upload')(self._h, _p(sums)))
+
+    def _ages_apply(self, prefix, K):
+        K = _f64(K)
+        if K.ndim != 2 or K.shape[0] != getattr(self, f'_{prefix}_ages_na', 0) + 2:
+            raise ValueError('ages_apply: K must have one row per plane, (na + 2, ne)')
+        ne = K.shape[1]
+        out = np.zeros((ne,) + tuple(getattr(self, prefix + '_shape', None) or (0, 0)) + (2,))
+        self._check(getattr(self.lib, f'nxc_{prefix}_ages_apply')(self._h, ne, _p(K), _p(out)))
+        return out
+
     def _pixel_sums_download(self, prefix, what):
-        per_pixel = (4,) if what == 'moments' else (getattr(self, f'_{prefix}_cube_nv', 0) + 2, 2)
+        bins = {'cube': f'_{prefix}_cube_nv', 'ages': f'_{prefix}_ages_na'}
+        per_pixel = (4,) if what == 'moments' else (getattr(self, bins[what], 0) + 2, 2)
         sums = np.zeros(tuple(getattr(self, prefix + '_shape', None) or (0, 0)) + per_pixel)
         self._check(getattr(self.lib, f'nxc_{prefix}_{what}_download')(self._h, _p(sums)))
         return sums
@@ -995,6 +1054,32 @@ class Context:
         """(nx, nz, nv + 2, 2) float64: {sum w, sum w w} per pixel and plane -- plane 0 below the
         range, 1..nv the bins, nv + 1 at or above it (or not a number)."""
         return self._pixel_sums_download('image', 'cube')
+
+    def image_ages_enable(self, na, t0=0.0, a_lo=0.0, a_hi=0.0):
+        """After ``set_image``: allocate and zero an age block of ``na`` bins over [a_lo, a_hi) [s]
+        for rows read at the epoch ``t0`` [s] beside the image pair (``na`` 0 frees it; the next
+        ``set_image`` switches it off)."""
+        self._ages_enable('image', na, t0, a_lo, a_hi)
+
+    def image_ages_accumulate(self, time=None, x=None, y=None, z=None, vy=None, frac=None,
+                              rows=None):
+        """Add samples to the image pair and to its age block in one pass: six host columns, the
+        time first (float32 ones go over as they are), or ``rows = (RowStore, first, count)``."""
+        self._accumulate('nxc_image_ages_accumulate', (time, x, y, z, vy, frac), rows)
+
+    def image_ages_download(self):
+        """(nx, nz, na + 2, 2) float64: {sum w, sum w w} per pixel and plane -- plane 0 younger
+        than the range, 1..na the bins, na + 1 at or above it (or a time that is not a number)."""
+        return self._pixel_sums_download('image', 'ages')
+
+    def image_ages_upload(self, sums):
+        """Replace the resident age block by ``sums`` (nx, nz, na + 2, 2)."""
+        self._ages_upload('image', sums)
+
+    def image_ages_apply(self, K):
+        """The resident age block contracted with ``K`` (na + 2, ne): (ne, nx, nz, 2) float64,
+        {sum_k S K, sum_k WW K K} per epoch and pixel, summed over the planes in their order."""
+        return self._ages_apply('image', K)
 
     # -- f-1: spacecraft lines of sight ------------------------------------------------------
     def los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables,
@@ -1183,6 +1268,7 @@ class Context:
             self._fill_lines(d, g_tables, keep)
         self._check(self.lib.nxc_camera_set(self._h, C.byref(d)))
         self.camera_shape = (int(d.nx), int(d.nz))
+        self.ages_owner.pop('camera', None)         # the set switches the age block off
 
     def camera_accumulate(self, x=None, y=None, z=None, vy=None, frac=None, rows=None):
         """Add samples to the camera image: five host columns (float32 ones go over as they are
@@ -1228,6 +1314,32 @@ class Context:
         """(nx, nz, nv + 2, 2) float64: {sum w, sum w w} per pixel and plane -- plane 0 below the
         range, 1..nv the bins, nv + 1 at or above it (or not a number)."""
         return self._pixel_sums_download('camera', 'cube')
+
+    def camera_ages_enable(self, na, t0=0.0, a_lo=0.0, a_hi=0.0):
+        """After ``camera_set``: allocate and zero an age block of ``na`` bins over [a_lo, a_hi) [s]
+        for rows read at the epoch ``t0`` [s] beside the camera image (``na`` 0 frees it; the next
+        ``camera_set`` switches it off)."""
+        self._ages_enable('camera', na, t0, a_lo, a_hi)
+
+    def camera_ages_accumulate(self, time=None, x=None, y=None, z=None, vy=None, frac=None,
+                              rows=None):
+        """Add samples to the camera image and to its age block in one pass: six host columns, the
+        time first (float32 ones go over as they are), or ``rows = (RowStore, first, count)``."""
+        self._accumulate('nxc_camera_ages_accumulate', (time, x, y, z, vy, frac), rows)
+
+    def camera_ages_download(self):
+        """(nx, nz, na + 2, 2) float64: {sum w, sum w w} per pixel and plane -- plane 0 younger
+        than the range, 1..na the bins, na + 1 at or above it (or a time that is not a number)."""
+        return self._pixel_sums_download('camera', 'ages')
+
+    def camera_ages_upload(self, sums):
+        """Replace the resident age block by ``sums`` (nx, nz, na + 2, 2)."""
+        self._ages_upload('camera', sums)
+
+    def camera_ages_apply(self, K):
+        """The resident age block contracted with ``K`` (na + 2, ne): (ne, nx, nz, 2) float64,
+        {sum_k S K, sum_k WW K K} per epoch and pixel, summed over the planes in their order."""
+        return self._ages_apply('camera', K)
 
     # -- ShellMap ---------------------------------------------------------------------------
     def shell_set(self, vrplanet, quantity, lon_edges, mu_edges, r_lo, r_hi, nalt, g_tables=()):
