@@ -1302,6 +1302,65 @@ int nxc_camera_ages_download(nxc_handle *h, double *sums);
 int nxc_camera_ages_upload(nxc_handle *h, const double *sums);
 int nxc_camera_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out);
 
+/* ---- Line-of-sight ages: radiance per age bin along each line of sight ---------------------------
+ * EXTENSION -- nxc_los_accumulate gives one radiance per spectrum, summed over all ages; this keeps
+ * the age ("Age cube" says what an age is and why the radiance is linear in the source's history).
+ * Per spectrum there are na >= 1 bins over [a_lo, a_hi) seconds of age, t0 being the run's endtime;
+ * the host forms inv_da = na / (a_hi - a_lo) once in fp64.  A (sample, spectrum) pair is decided
+ * and weighed exactly as in nxc_los_accumulate.  Where its wtemp = weight/Apix (times 0 when the foot
+ * point is in shadow) is added to radiance[spectrum], and wtemp != 0, the row's time is read and
+ * the pair is filed as follows, fp64, one rounding per operation, no contraction (time: the row's
+ * first column, widened exactly when it is float32):
+ *   age = t0 - (double)time
+ *   u   = (age - a_lo) * inv_da
+ *   k = 0                 if u < 0                              (younger than the range)
+ *   k = 1 + (int)u        if 0 <= u < na                        (bin (int)u of the range)
+ *   k = na + 1            otherwise: at or above a_hi, or time not a number
+ * -- the plane of "Age cube" -- and the pair adds {wtemp, wtemp*wtemp} to record
+ * spectrum*(na + 2) + k.
+ *   - A pair with wtemp == 0 (foot point in shadow, frac == 0, g == 0) adds nothing.  Its time is not
+ *     read.  It is still counted in npackets and `included`, as for the profile.
+ *   - Nothing else is filtered: the na + 2 planes of a spectrum sum to its radiance up to the order
+ *     of the additions.
+ *   - radiance, npackets, `included`, the used pairs and the counters of an ages pass are those of
+ *     the plain pass over the same samples, up to the fp64 addition order of radiance.
+ *   nxc_los_ages_enable             na >= 1 allocates and zeroes S*(na + 2) 16-byte records
+ *                                   (NXC_ERR_NOMEM when they cannot be had), na == 0 frees them; a
+ *                                   second enable replaces and zeroes.  NXC_ERR_ARG, before anything
+ *                                   is allocated or freed, for S < 1, na < 0, t0, a_lo or a_hi not
+ *                                   finite, a_lo >= a_hi (or a width that is not finite),
+ *                                   S*(na + 2) >= 2^31
+ *   nxc_los_ages_accumulate[_f32], _rows
+ *                                   nxc_los_accumulate[_f32], _rows with the time column in front (a
+ *                                   row store carries it: its column 0): everything the plain entry
+ *                                   returns, and the pairs' contributions added to the block.  Sums
+ *                                   accumulate over calls, slabs and Outputs until the next enable.
+ *                                   NXC_ERR_STATE without an enabled block; NXC_ERR_ARG when S is not
+ *                                   the enabled one, or time is null with P > 0; P == 0 adds nothing
+ *   nxc_los_ages_download           sums[S][na + 2][2] = {wtemp sum, wtemp*wtemp sum}, plane 0 below
+ *                                   the range, 1..na the bins, na + 1 above
+ * The block is a state of the handle of its own: nxc_los_accumulate* and nxc_los_profile_* never
+ * touch it, and these entries never touch the profile or the image's and camera's age blocks. */
+int nxc_los_ages_enable(nxc_handle *h, int64_t S, int64_t na, double t0, double a_lo, double a_hi);
+int nxc_los_ages_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                            int64_t P, const double *time, const double *x, const double *y,
+                            const double *z, const double *vy, const double *frac,
+                            const int64_t *index, int64_t n_index, double *radiance,
+                            int64_t *npackets, uint8_t *included, int64_t used_cap,
+                            int64_t *used_pairs, int64_t *n_used);
+int nxc_los_ages_accumulate_f32(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                                int64_t P, const float *time, const float *x, const float *y,
+                                const float *z, const float *vy, const float *frac,
+                                const int64_t *index, int64_t n_index, double *radiance,
+                                int64_t *npackets, uint8_t *included, int64_t used_cap,
+                                int64_t *used_pairs, int64_t *n_used);
+int nxc_los_ages_accumulate_rows(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                                 const nxc_rows *r, int64_t first, int64_t count,
+                                 int64_t index_shift, int64_t n_index, double *radiance,
+                                 int64_t *npackets, uint8_t *included, int64_t used_cap,
+                                 int64_t *used_pairs, int64_t *n_used);
+int nxc_los_ages_download(nxc_handle *h, double *sums);
+
 #ifdef __cplusplus
 }
 #endif

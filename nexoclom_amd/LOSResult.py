@@ -24,11 +24,18 @@ profile") adds the line profile of every spectrum -- its radiance per bin of the
 along the boresight -- and the line's shift, width, skewness and effective packet number, from the
 same pass over the samples.  Velocities are in the planet frame: the spacecraft's own velocity is not
 subtracted.
+
+``ages=(a_lo_s, a_hi_s, nbins)`` (an extension; include/nexoclom_hip.h, "Line-of-sight ages") files
+every pair's contribution under the age of its row as well: ``age_profile`` is each spectrum's
+response to a pulse of the source rate, and ``transient(history)`` gives the radiance of every
+spectrum at its own epoch for a source whose rate changed with time (transient.py).
 """
 import numpy as np
 import pandas as pd
 
 from .ModelImage import (ModelResult, cube_from_sums, parse_cube, pixel_moments_from_sums)
+from .transient import (TransientRadiance, ages_from_sums, parse_ages, refuse_ages_of,
+                        refuse_ages_with, spectrum_times)
 from .units import Quantity
 
 POSITION = ('x', 'y', 'z')
@@ -37,13 +44,15 @@ BORESIGHT = ('xbore', 'ybore', 'zbore')
 
 class SpacecraftData:
     """Minimal stand-in for MESSENGERuvvs.MESSENGERdata: positions and boresights per spectrum,
-    optionally the observed ``radiance`` [kR], its ``sigma`` and the tangent altitude ``alttan``
+    optionally the observed ``radiance`` [kR], its ``sigma``, the tangent altitude ``alttan`` and
+    the ``time`` [s] at which each spectrum was taken, on the clock of a source history
     (data columns of the same names), and the model results fitted to it (``model_result``)."""
 
     def __init__(self, x, y, z, xbore, ybore, zbore, species='Na', query='synthetic', *,
-                 radiance=None, sigma=None, alttan=None):
+                 radiance=None, sigma=None, alttan=None, time=None):
         columns = dict(zip(POSITION + BORESIGHT, (x, y, z, xbore, ybore, zbore)))
-        for name, values in (('radiance', radiance), ('sigma', sigma), ('alttan', alttan)):
+        for name, values in (('radiance', radiance), ('sigma', sigma), ('alttan', alttan),
+                             ('time', time)):
             if values is not None:
                 columns[name] = values
         self.data = pd.DataFrame(columns, dtype=float)
@@ -137,11 +146,28 @@ def parse_profile(profile, n_spectra):
     return v_lo, v_hi, nbins
 
 
+def parse_los_ages(ages, n_spectra):
+    """``(a_lo_s, a_hi_s, nbins)`` of an ``ages=`` argument, by parse_ages's rules; ValueError also
+    when ``n_spectra`` spectra would have more records than the device addresses
+    (S (nbins + 2) < 2^31)."""
+    a_lo, a_hi, nbins = parse_ages(ages)
+    if n_spectra*(nbins + 2) >= 2**31:
+        raise ValueError('ages=: len(scdata)*(nbins + 2) must stay below 2^31')
+    return a_lo, a_hi, nbins
+
+
 class LOSResult(ModelResult):
+    _ages = None              # (a_lo_s, a_hi_s, nbins): the passes also fill age_sums
+    _times = None             # the spectra's ``time`` column as simulate_data_from_inputs saw it
+
     def __init__(self, scdata, inputs, params=None, dphi=np.radians(1.), *, device=0,
-                 context=None, profile=None, **kwargs):
+                 context=None, profile=None, ages=None, **kwargs):
         scdata.set_frame('Model')
         self._profile = None if profile is None else parse_profile(profile, len(scdata.data))
+        if ages is not None:
+            refuse_ages_with(profile=profile)
+            self._ages = parse_los_ages(ages, len(scdata.data))
+            refuse_ages_of(inputs)
         super().__init__(inputs, {'quantity': 'radiance'} if params is None else params)
         if self.quantity != 'radiance':
             assert False, 'Other quantities not set up.'      # compute_iteration.py:213
@@ -162,10 +188,11 @@ class LOSResult(ModelResult):
         self.iterations = []
         self._geometry = None
 
-    def compute_iteration(self, output, scdata, used_cap=0, pairs=None, profile=False):
+    def compute_iteration(self, output, scdata, used_cap=0, pairs=None, profile=False, ages=False):
         """One catalogued Output against all spectra (compute_iteration.py:90-240).  ``pairs``: a
         device pair list (hip_api.PairList) that receives the pairs with weight > 0.  ``profile``:
-        the pass also adds to the context's enabled line-of-sight profile."""
+        the pass also adds to the context's enabled line-of-sight profile; ``ages``: to its enabled
+        line-of-sight ages."""
         from .Output import Output
         if not isinstance(output, Output):       # a file; a catalogued Output is used as stored:
             output = Output.restore(output)      # the binding widens just the columns it sends
@@ -185,6 +212,9 @@ class LOSResult(ModelResult):
         if profile:                            # the profile's entries, which read vx and vz too
             extra['profile'] = True
             velocity = ('vx', 'vz')
+        if ages:                               # the ages' entries, which read the rows' time too
+            extra['ages'] = True
+            velocity = ('time',)
         view = output.resident_rows(self.context())
         if view is not None:
             # the Output's rows are still in HBM: no host round trip
@@ -218,6 +248,8 @@ class LOSResult(ModelResult):
         if self._profile is not None and cp is not None:
             raise NotImplementedError('profile= does not support cp=: there is no all-reduce of the '
                                       'profile yet')
+        if self._ages is not None:
+            refuse_ages_with(cp=cp)
         self.outid, self.outputfiles, self.npackets, self.totalsource = self.inputs.search()
         print(f'LOSResult: {len(self.outid)} output files found.')
         shared = cp is not None and cp.world > 1
@@ -228,8 +260,20 @@ class LOSResult(ModelResult):
             v_lo, v_hi, nbins = self._profile
             self.context().los_profile_enable(len(scdata.data), nbins, v_lo/self.unit_km,
                                               v_hi/self.unit_km)
-        self.iterations = [self.compute_iteration(run, scdata, profile=self._profile is not None)
+        if self._ages is not None:
+            # one block for the whole run, like the profile's
+            a_lo, a_hi, nbins = self._ages
+            self.context().los_ages_enable(len(scdata.data), nbins,
+                                           float(self.inputs.options.endtime.value), a_lo, a_hi)
+            self._times = (np.array(scdata.data['time'], dtype=float) if 'time' in scdata.data
+                           else None)
+        modes = {key: True for key, on in (('profile', self._profile), ('ages', self._ages))
+                 if on is not None}
+        self.iterations = [self.compute_iteration(run, scdata, **modes)
                            for run in self.inputs._catalogue]
+        if self._ages is not None:
+            self.age_sums = self.context().los_ages_download()
+            self.context().los_ages_enable(len(scdata.data), 0)
         if self._profile is not None:
             self.profile_sums, self.moment_sums = self.context().los_profile_download()
             self.context().los_profile_enable(len(scdata.data), 0)
@@ -253,6 +297,8 @@ class LOSResult(ModelResult):
         self.atoms_per_packet = 1e23 / per_second
         if self._profile is not None:
             self._publish_profile(scdata.data.index)
+        if self._ages is not None:
+            self._publish_ages(scdata.data.index)
         self.radiance *= self.atoms_per_packet/1e3      # kR
 
     def _publish_profile(self, rows):
@@ -269,6 +315,41 @@ class LOSResult(ModelResult):
                 value = (pd.Series(value, index=rows) if value.ndim == 1
                          else pd.DataFrame(value, index=rows))
             setattr(self, name, value)
+
+    def _publish_ages(self, rows):
+        """The ages' attributes from ``age_sums`` (transient.ages_from_sums with the radiance's
+        scaling): ``age_profile`` (S, nbins), ``age_below``, ``age_above`` and
+        ``age_effective_packets``, indexed like ``radiance``; ``age_edges`` and ``age_axis`` [s]."""
+        for name, value in ages_from_sums(self.age_sums, self.atoms_per_packet/1e3,
+                                          *self._ages[:2]).items():
+            if name not in ('age_edges', 'age_axis'):
+                value = (pd.Series(value, index=rows) if value.ndim == 1
+                         else pd.DataFrame(value, index=rows))
+            setattr(self, name.replace('age_cube', 'age_profile'), value)
+
+    def transient(self, history, times=None):
+        """The radiance of every spectrum at its own epoch for a source whose rate relative to the
+        nominal one was ``history = (t_nodes_s, rate_nodes)`` (transient.response_matrix): a
+        TransientRadiance with times, kernel (nbins + 2, S), radiance [kR] and effective_packets.
+        ``times``: (S,) seconds on the history's clock, or one number for all spectra; by default
+        the ``time`` column the spacecraft data had in ``simulate_data_from_inputs``."""
+        if self._ages is None:
+            raise ValueError('transient() needs an object built with ages=(a_lo_s, a_hi_s, nbins)')
+        if not hasattr(self, 'age_sums'):
+            raise ValueError('transient() needs simulate_data_from_inputs first')
+        times = spectrum_times(times, self._times, self.age_sums.shape[0])
+        return TransientRadiance(times, self.age_edges, history, self.age_sums,
+                                 self.atoms_per_packet/1e3, self.radiance.index)
+
+    def transient_design(self, t_nodes, times=None):
+        """(S, J) matrix A with ``A @ rates == transient((t_nodes, rates)).radiance`` up to
+        rounding: column j is ``transient`` of the history with rate 1 at node j and 0 at the
+        others.  What a non-negative least-squares fit of a source history to an observed scan
+        needs; the fit itself is the caller's."""
+        nodes = np.atleast_1d(np.asarray(t_nodes, dtype=float))
+        columns = [np.asarray(self.transient((nodes, np.eye(len(nodes))[j]), times).radiance)
+                   for j in range(len(nodes))]
+        return np.stack(columns, axis=1)
 
     def make_mask(self, data):
         """(mask, sigma limit) of the ``masking`` keyword (LOSResult.py:171-200): ';'-separated

@@ -61,6 +61,9 @@ class LOSResultFitted(LOSResult):
         if kwargs.get('profile') is not None:
             raise NotImplementedError('profile= is not supported by LOSResultFitted: the profile '
                                       'carries no fitted weights')
+        if kwargs.get('ages') is not None:
+            raise NotImplementedError('ages= is not supported by LOSResultFitted: the age sums '
+                                      'carry no fitted weights')
         unfit = scdata.model_result[label_for_fitted]
         inputs = fitted_inputs(unfit.inputs)
         if 'context' not in kwargs and getattr(unfit, '_ctx', None) is not None:

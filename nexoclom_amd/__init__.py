@@ -18,6 +18,7 @@ from .CameraImage import CameraImage          # noqa: F401
 from .ShellMap import ShellMap                # noqa: F401
 from .LOSResultFitted import LOSResultFitted  # noqa: F401
 from .sourcemap import SourceMap              # noqa: F401
+from .transient import TransientImages, TransientRadiance, response_matrix   # noqa: F401
 from .solarsystem import SSObject, planet_dist    # noqa: F401
 from .atomicdata import gValue, RadPresConst, PhotoRate, atomicmass   # noqa: F401
 from .input_classes import InputError       # noqa: F401

@@ -28,6 +28,7 @@
 #include "nxc_shell_check.hpp"
 #include "nxc_cube_check.hpp"
 #include "nxc_ages_check.hpp"
+#include "nxc_los_ages_check.hpp"
 #include "nxc_los_profile_check.hpp"
 #include "nxc_desc_check.hpp"
 #include "nxc_source_map_check.hpp"
@@ -480,6 +481,11 @@ struct nxc_handle {
     int64_t los_prof_S = 0;          // spectra it was enabled for
     CubeK los_profK{};
     Dev<double> d_los_prof;          // [S][nv + 2] records {w, w w} | [S][4] sums m1 m2 m3 ww
+    // the line-of-sight ages (nxc_los_ages_enable): a block of their own, from enable to enable
+    bool have_los_ages = false;
+    int64_t los_ages_S = 0;          // spectra it was enabled for
+    AgeK los_agesK{};
+    Dev<double> d_los_ages;          // [S][na + 2] records {w, w w}
     bool have_fit = false;
     int64_t fit_S = 0, fit_np = -1;  // fit_np: packets whose multipliers are ready (nxc_fit_packets)
     int fit_mode = 0;
@@ -1153,6 +1159,8 @@ int rows_fetch(nxc_handle *h, void *rows_out, bool narrow)
 
 // records of the handle's line-of-sight profile
 size_t los_profile_records(const nxc_handle *h) { return (size_t)h->los_prof_S * (size_t)(h->los_profK.nv + 2); }
+// ... and of its line-of-sight ages
+size_t los_ages_records(const nxc_handle *h) { return (size_t)h->los_ages_S * (size_t)(h->los_agesK.na + 2); }
 
 // The pass constants and the LDS blob [header space | g-value tables] of a line-of-sight
 // descriptor (los_run, fit_radiance)
@@ -1195,12 +1203,14 @@ int los_tables(nxc_handle *h, const nxc_los_desc *d, LosK &K, std::vector<unsign
 }
 
 // f-1 over stored samples that are already on the device (64-bit, or 32-bit as save() keeps them)
-// PROFILE: the pass of nxc_los_profile_accumulate*, which also adds to the handle's line-of-sight
-// profile (dvx, dvz: the two columns only it reads); the plain pass launches what it always did
-template <bool PROFILE, typename T, typename I>
+// LOS_PROFILE: the pass of nxc_los_profile_accumulate*, which also adds to the handle's line-of-sight
+// profile (dvx, dvz: the two columns only it reads); LOS_AGES: the pass of nxc_los_ages_accumulate*,
+// which also adds to the handle's line-of-sight ages (dtime: the column only it reads); the plain
+// pass launches what it always did
+template <LosMode MODE, typename T, typename I>
 int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, int64_t P,
             const T *dx, const T *dy, const T *dz, const T *dvy, const T *dfrac, const T *dvx,
-            const T *dvz, const I *d_index,
+            const T *dvz, const T *dtime, const I *d_index,
             int64_t index_shift, int64_t n_index, double *radiance, int64_t *npackets, uint8_t *included,
             int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
 {
@@ -1256,7 +1266,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
     HIPCHK(hipMemsetAsync(base + o_nu, 0, 8, st));
     HIPCHK(hipMemsetAsync(h->d_ctr, 0, sizeof(DevCounters), st));
     if (P > 0) {
-        if ((rc = prep_kernel(k_los<T, I, PROFILE>, lds))) return rc;
+        if ((rc = prep_kernel(k_los<T, I, MODE>, lds))) return rc;
         const int tiles = (int)((S + K.tile_cap - 1) / K.tile_cap);
         constexpr int WPG = NXC_LOS_THREADS / 64;                  // waves per workgroup of k_los
         // the samples go through in slabs: the block scratch is sized for the worst case of one
@@ -1281,16 +1291,21 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
         size_t lds_pairs = ((stage_bytes + 31) & ~size_t(31)) + (size_t)((d->n_ladder + 3) & ~int64_t(3)) * 8;
         if (lds_pairs > 160 * 1024) return fail(NXC_ERR_ARG, "the ladder of ball centres exceeds the LDS");
         // the per-spectrum sums of a workgroup in LDS when they leave room for two workgroups per CU
-        // (a profile pass: radiance, count and the four moment sums)
-        const size_t sums_bytes = (size_t)S * (PROFILE ? 48 : 16);
+        // (a profile pass: radiance, count and the four moment sums; an ages pass has no sums of
+        // its own)
+        const size_t sums_bytes = (size_t)S * (MODE == LOS_PROFILE ? 48 : 16);
         const int lds_sums = lds_pairs + sums_bytes <= 80 * 1024 ? 1 : 0;
         if (lds_sums) lds_pairs += sums_bytes;
-        if ((rc = prep_kernel(k_los_pairs<T, I, PROFILE>, lds_pairs))) return rc;
-        LosProf<T, PROFILE> prof{};
-        if constexpr (PROFILE) {
+        if ((rc = prep_kernel(k_los_pairs<T, I, MODE>, lds_pairs))) return rc;
+        LosProf<T, MODE> prof{};
+        if constexpr (MODE == LOS_PROFILE) {
             prof.bins = h->los_profK;
             prof.rec = h->d_los_prof;
             prof.mom = h->d_los_prof + los_profile_records(h) * 2;
+        }
+        if constexpr (MODE == LOS_AGES) {
+            prof.bins = h->los_agesK;
+            prof.rec = h->d_los_ages;
         }
         unsigned *pair_used = reinterpret_cast<unsigned *>(h->d_losblk + o_n + 8);
         unsigned *pair_fill = reinterpret_cast<unsigned *>(h->d_losblk + o_fill);
@@ -1303,7 +1318,8 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
             const int64_t n = std::min<int64_t>(slab, P - first);
             const int64_t regions = (n + NXC_LOS_FORM - 1) / NXC_LOS_FORM;
             K.row_base = first;
-            if constexpr (PROFILE) { prof.vx = dvx + first; prof.vz = dvz + first; }
+            if constexpr (MODE == LOS_PROFILE) { prof.vx = dvx + first; prof.vz = dvz + first; }
+            if constexpr (MODE == LOS_AGES) prof.time = dtime + first;
             HIPCHK(hipMemsetAsync(n_slots, 0, 256 + (size_t)pair_cap * 4, st));   // counters + chunk fills
             hipLaunchKernelGGL((k_los_blocks<T, I>),
                                dim3((unsigned)((regions + NXC_LOS_BLOCKS_THREADS / 64 - 1) /
@@ -1313,7 +1329,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
             HIPCHK(hipGetLastError());
             // persistent waves, one workgroup per CU (its LDS holds all the spectra of a tile)
             const int64_t groups = std::max<int64_t>(1, std::min<int64_t>(h->n_cu, (n / 8 / 64 + WPG) / WPG));
-            hipLaunchKernelGGL((k_los<T, I, PROFILE>), dim3((unsigned)groups, tiles),
+            hipLaunchKernelGGL((k_los<T, I, MODE>), dim3((unsigned)groups, tiles),
                                dim3(NXC_LOS_THREADS), lds, st, K, base + o_blob,
                                (int64_t)stage_bytes, S, reinterpret_cast<const double *>(base + o_sc),
                                n_slots, bdesc, bsph, pair_list, pair_fill, pair_used, pair_chunks,
@@ -1325,7 +1341,7 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
                                included ? base + o_inc : nullptr, cap_used, d_used,
                                reinterpret_cast<unsigned long long *>(base + o_nu), h->d_ctr, prof);
             HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL((k_los_pairs<T, I, PROFILE>), dim3((unsigned)(h->n_cu * 2)), dim3(NXC_BLOCK),
+            hipLaunchKernelGGL((k_los_pairs<T, I, MODE>), dim3((unsigned)(h->n_cu * 2)), dim3(NXC_BLOCK),
                                lds_pairs, st, K, base + o_blob, (int64_t)stage_bytes, S,
                                reinterpret_cast<const double *>(base + o_sc), pair_list, pair_fill,
                                pair_used, pair_chunks, lds_sums, dx + first, dy + first, dz + first,
@@ -1377,16 +1393,16 @@ int los_check(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
 }
 
 // ... over a sample view
-template <bool PROFILE>
+template <LosMode MODE>
 int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, const Samples &s,
             int64_t n_index, double *radiance, int64_t *npackets, uint8_t *included, int64_t used_cap,
             int64_t *used_pairs, int64_t *n_used)
 {
     return with_sample_types(s, [&](auto t, auto i) {
         using T = decltype(t);
-        return los_run<PROFILE>(h, d, S, sc, s.n, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3),
-                                s.col<T>(4), s.col<T>(5), s.col<T>(6), s.idx<decltype(i)>(), s.shift,
-                                n_index, radiance, npackets, included, used_cap, used_pairs, n_used);
+        return los_run<MODE>(h, d, S, sc, s.n, s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3),
+                             s.col<T>(4), s.col<T>(5), s.col<T>(6), s.col<T>(7), s.idx<decltype(i)>(),
+                             s.shift, n_index, radiance, npackets, included, used_cap, used_pairs, n_used);
     });
 }
 
@@ -1401,26 +1417,38 @@ int los_profile_check(const nxc_handle *h, int64_t S)
     return NXC_OK;
 }
 
-// ... over samples in host memory: five columns, seven for a profile pass (+ the index column) go
-// to the device first
-template <bool PROFILE, typename T>
+// What an ages entry checks in front of the plain entry's own checks
+int los_ages_check(const nxc_handle *h, int64_t S)
+{
+    if (!h) return fail(NXC_ERR_ARG, "bad arguments");
+    if (!h->have_los_ages) return fail(NXC_ERR_STATE, "nxc_los_ages_enable has not been called");
+    if (S != h->los_ages_S)
+        return fail(NXC_ERR_ARG, "the ages were enabled for " + std::to_string(h->los_ages_S) +
+                                     " spectra, this call has " + std::to_string(S));
+    return NXC_OK;
+}
+
+// ... over samples in host memory: five columns, seven for a profile pass, six for an ages pass
+// (+ the index column) go to the device first
+template <LosMode MODE, typename T>
 int los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, int64_t P,
                    const T *x, const T *y, const T *z, const T *vx, const T *vy, const T *vz,
-                   const T *frac, const int64_t *index, int64_t n_index, double *radiance,
-                   int64_t *npackets, uint8_t *included, int64_t used_cap, int64_t *used_pairs,
-                   int64_t *n_used)
+                   const T *frac, const T *time, const int64_t *index, int64_t n_index,
+                   double *radiance, int64_t *npackets, uint8_t *included, int64_t used_cap,
+                   int64_t *used_pairs, int64_t *n_used)
 {
-    int rc = PROFILE ? los_profile_check(h, S) : NXC_OK;
+    int rc = MODE == LOS_PROFILE ? los_profile_check(h, S) : MODE == LOS_AGES ? los_ages_check(h, S) : NXC_OK;
     if (rc) return rc;
     rc = los_check(h, d, S, sc, P, radiance, npackets, included, n_index, used_cap, used_pairs, n_used);
     if (rc) return rc;
     if (P && (!x || !y || !z || !vy || !frac)) return fail(NXC_ERR_ARG, "bad arguments");
-    if (PROFILE && P && (!vx || !vz)) return fail(NXC_ERR_ARG, "bad arguments");
-    const T *cols[N_SAMPLE_COLS] = {x, y, z, vy, frac, vx, vz};
+    if (MODE == LOS_PROFILE && P && (!vx || !vz)) return fail(NXC_ERR_ARG, "bad arguments");
+    if (MODE == LOS_AGES && P && !time) return fail(NXC_ERR_ARG, "bad arguments");
+    const T *cols[N_SAMPLE_COLS] = {x, y, z, vy, frac, vx, vz, time};
     Samples s;
     if ((rc = samples_upload(h, h->d_samples, P, cols, index, &s))) return rc;
-    return los_run<PROFILE>(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs,
-                            n_used);
+    return los_run<MODE>(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs,
+                         n_used);
 }
 
 // nxc_los_profile_enable: S (nv + 2) zeroed records and S x 4 moment sums in one block, or none; the
@@ -1456,6 +1484,42 @@ int los_profile_download(nxc_handle *h, double *sums, double *moments)
     const size_t n_rec = los_profile_records(h) * 2;
     HIPCHK(hipMemcpyAsync(sums, h->d_los_prof, n_rec * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(moments, h->d_los_prof + n_rec, (size_t)h->los_prof_S * 4 * sizeof(double),
+                          hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+}
+
+// nxc_los_ages_enable: S (na + 2) zeroed records in a block of their own, or none; the arguments
+// are checked (check_los_ages_args) before the block there is is touched
+int los_ages_enable(nxc_handle *h, int64_t S, int64_t na, double t0, double a_lo, double a_hi)
+{
+    if (!h) return fail(NXC_ERR_ARG, "bad arguments");
+    if (na != 0) {
+        const std::string why = check_los_ages_args(S, na, t0, a_lo, a_hi);
+        if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
+    }
+    HIPCHK(hipSetDevice(h->device));
+    h->have_los_ages = false;
+    int rc = h->d_los_ages.release();
+    if (rc || na == 0) return rc;
+    h->los_ages_S = S;
+    h->los_agesK = AgeK{(int)na, t0, a_lo, ages_inv_da(na, a_lo, a_hi)};
+    const size_t bytes = los_ages_records(h) * 2 * sizeof(double);
+    if ((rc = h->d_los_ages.ensure(bytes))) return rc;
+    HIPCHK(hipMemsetAsync(h->d_los_ages, 0, bytes, h->stream));
+    HIPCHK(stream_sync(h));
+    h->have_los_ages = true;
+    return NXC_OK;
+}
+
+// nxc_los_ages_download: sums[S][na + 2][2], the device's own order
+int los_ages_download(nxc_handle *h, double *sums)
+{
+    if (!h) return fail(NXC_ERR_ARG, "bad arguments");
+    if (!h->have_los_ages) return fail(NXC_ERR_STATE, "nxc_los_ages_enable has not been called");
+    if (!sums) return fail(NXC_ERR_ARG, "bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(sums, h->d_los_ages, los_ages_records(h) * 2 * sizeof(double),
                           hipMemcpyDeviceToHost, h->stream));
     HIPCHK(stream_sync(h));
     return NXC_OK;
@@ -3336,8 +3400,8 @@ int nxc_los_accumulate_rows(nxc_handle *h, const nxc_los_desc *d, int64_t S, con
     if (rc) return rc;
     Samples s;
     if ((rc = samples_from_rows(h, r, first, count, index_shift, &s))) return rc;
-    return los_run<false>(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs,
-                          n_used);
+    return los_run<LOS_PLAIN>(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap,
+                              used_pairs, n_used);
     });
 }
 
@@ -3355,8 +3419,27 @@ int nxc_los_profile_accumulate_rows(nxc_handle *h, const nxc_los_desc *d, int64_
     if (rc) return rc;
     Samples s;
     if ((rc = samples_from_rows(h, r, first, count, index_shift, &s))) return rc;
-    return los_run<true>(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap, used_pairs,
-                         n_used);
+    return los_run<LOS_PROFILE>(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap,
+                                used_pairs, n_used);
+    });
+}
+
+int nxc_los_ages_accumulate_rows(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                                 const nxc_rows *r, int64_t first, int64_t count,
+                                 int64_t index_shift, int64_t n_index, double *radiance,
+                                 int64_t *npackets, uint8_t *included, int64_t used_cap,
+                                 int64_t *used_pairs, int64_t *n_used)
+{
+    return guarded([&]() -> int {
+    int rc = los_ages_check(h, S);
+    if (rc) return rc;
+    rc = los_check(h, d, S, sc, count, radiance, npackets, included, n_index, used_cap, used_pairs,
+                   n_used);
+    if (rc) return rc;
+    Samples s;
+    if ((rc = samples_from_rows(h, r, first, count, index_shift, &s))) return rc;
+    return los_run<LOS_AGES>(h, d, S, sc, s, n_index, radiance, npackets, included, used_cap,
+                             used_pairs, n_used);
     });
 }
 
@@ -4439,9 +4522,10 @@ int nxc_los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const do
                        int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
 {
     return guarded([&]() -> int {
-        return los_accumulate<false>(h, d, S, sc, P, x, y, z, decltype(x)(nullptr), vy,
-                                     decltype(x)(nullptr), frac, index, n_index, radiance, npackets,
-                                     included, used_cap, used_pairs, n_used);
+        return los_accumulate<LOS_PLAIN>(h, d, S, sc, P, x, y, z, decltype(x)(nullptr), vy,
+                                         decltype(x)(nullptr), frac, decltype(x)(nullptr), index,
+                                         n_index, radiance, npackets, included, used_cap, used_pairs,
+                                         n_used);
     });
 }
 
@@ -4452,9 +4536,10 @@ int nxc_los_accumulate_f32(nxc_handle *h, const nxc_los_desc *d, int64_t S, cons
                            int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
 {
     return guarded([&]() -> int {
-        return los_accumulate<false>(h, d, S, sc, P, x, y, z, decltype(x)(nullptr), vy,
-                                     decltype(x)(nullptr), frac, index, n_index, radiance, npackets,
-                                     included, used_cap, used_pairs, n_used);
+        return los_accumulate<LOS_PLAIN>(h, d, S, sc, P, x, y, z, decltype(x)(nullptr), vy,
+                                         decltype(x)(nullptr), frac, decltype(x)(nullptr), index,
+                                         n_index, radiance, npackets, included, used_cap, used_pairs,
+                                         n_used);
     });
 }
 
@@ -4471,8 +4556,9 @@ int nxc_los_profile_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, 
                                int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
 {
     return guarded([&]() -> int {
-        return los_accumulate<true>(h, d, S, sc, P, x, y, z, vx, vy, vz, frac, index, n_index, radiance,
-                                    npackets, included, used_cap, used_pairs, n_used);
+        return los_accumulate<LOS_PROFILE>(h, d, S, sc, P, x, y, z, vx, vy, vz, frac,
+                                           decltype(x)(nullptr), index, n_index, radiance, npackets,
+                                           included, used_cap, used_pairs, n_used);
     });
 }
 
@@ -4484,14 +4570,53 @@ int nxc_los_profile_accumulate_f32(nxc_handle *h, const nxc_los_desc *d, int64_t
                                    int64_t used_cap, int64_t *used_pairs, int64_t *n_used)
 {
     return guarded([&]() -> int {
-        return los_accumulate<true>(h, d, S, sc, P, x, y, z, vx, vy, vz, frac, index, n_index, radiance,
-                                    npackets, included, used_cap, used_pairs, n_used);
+        return los_accumulate<LOS_PROFILE>(h, d, S, sc, P, x, y, z, vx, vy, vz, frac,
+                                           decltype(x)(nullptr), index, n_index, radiance, npackets,
+                                           included, used_cap, used_pairs, n_used);
     });
 }
 
 int nxc_los_profile_download(nxc_handle *h, double *sums, double *moments)
 {
     return guarded([&]() -> int { return los_profile_download(h, sums, moments); });
+}
+
+int nxc_los_ages_enable(nxc_handle *h, int64_t S, int64_t na, double t0, double a_lo, double a_hi)
+{
+    return guarded([&]() -> int { return los_ages_enable(h, S, na, t0, a_lo, a_hi); });
+}
+
+int nxc_los_ages_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                            int64_t P, const double *time, const double *x, const double *y,
+                            const double *z, const double *vy, const double *frac,
+                            const int64_t *index, int64_t n_index, double *radiance,
+                            int64_t *npackets, uint8_t *included, int64_t used_cap,
+                            int64_t *used_pairs, int64_t *n_used)
+{
+    return guarded([&]() -> int {
+        return los_accumulate<LOS_AGES>(h, d, S, sc, P, x, y, z, decltype(x)(nullptr), vy,
+                                        decltype(x)(nullptr), frac, time, index, n_index, radiance,
+                                        npackets, included, used_cap, used_pairs, n_used);
+    });
+}
+
+int nxc_los_ages_accumulate_f32(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
+                                int64_t P, const float *time, const float *x, const float *y,
+                                const float *z, const float *vy, const float *frac,
+                                const int64_t *index, int64_t n_index, double *radiance,
+                                int64_t *npackets, uint8_t *included, int64_t used_cap,
+                                int64_t *used_pairs, int64_t *n_used)
+{
+    return guarded([&]() -> int {
+        return los_accumulate<LOS_AGES>(h, d, S, sc, P, x, y, z, decltype(x)(nullptr), vy,
+                                        decltype(x)(nullptr), frac, time, index, n_index, radiance,
+                                        npackets, included, used_cap, used_pairs, n_used);
+    });
+}
+
+int nxc_los_ages_download(nxc_handle *h, double *sums)
+{
+    return guarded([&]() -> int { return los_ages_download(h, sums); });
 }
 
 // ---- RCCL -------------------------------------------------------------------------------------

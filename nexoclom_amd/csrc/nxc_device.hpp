@@ -1238,6 +1238,19 @@ NXC_DEV void pixel_ages_add(const AgeK &Q, bool ok, int pix, double w, int64_t i
     add_record_pairs(has, pix * (Q.na + 2) + k, w, w * w, ages2);
 }
 
+// The same rule on its own, for the line-of-sight ages (k_los_pairs, k_los; include/nexoclom_hip.h,
+// "Line-of-sight ages"), which file a pair under spectrum (na + 2) + k with per-lane atomics.
+// (pixel_ages_add keeps its own copy, for cube_plane's reason.)
+NXC_DEV int age_plane(const AgeK &Q, double time)
+{
+    const double age = Q.t0 - time;
+    const double u = (age - Q.a_lo) * Q.inv_da;
+    int k = Q.na + 1;
+    if (u < 0.0) k = 0;
+    else if (u < (double)Q.na) k = 1 + (int)u;
+    return k;
+}
+
 // ---- ShellMap: the same sample filed by local time, latitude and altitude --------------------------
 // (include/nexoclom_hip.h, "ShellMap", holds the definition; the operations below are in its
 // order.)  Everything the image has a place for -- g-value tables, the two edge arrays (longitude as

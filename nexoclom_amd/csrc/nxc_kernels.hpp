@@ -1559,36 +1559,49 @@ NXC_DEV double los_wtemp(const LosK &K, double vy_p, double frac_p, double dist,
     return nxc_div(weight, apix);
 }
 
-// What a profile pass (include/nexoclom_hip.h, "Line-of-sight profile") hands its kernels besides
-// the plain pass's arguments; the plain instantiations carry nothing.
-template <typename T, bool PROFILE>
+// The three line-of-sight passes: k_los, k_los_pairs and los_pair are instantiated once per mode.
+enum LosMode { LOS_PLAIN = 0, LOS_PROFILE = 1, LOS_AGES = 2 };
+
+// What a profile pass (include/nexoclom_hip.h, "Line-of-sight profile") or an ages pass
+// ("Line-of-sight ages") hands its kernels besides the plain pass's arguments; the plain
+// instantiations carry nothing.
+template <typename T, LosMode MODE>
 struct LosProf {};
 template <typename T>
-struct LosProf<T, true> {
+struct LosProf<T, LOS_PROFILE> {
     CubeK bins;                              // the cube's bin rule over the spectrum's own boresight
     const T *vx, *vz;                        // read for decided pairs with wtemp != 0 only
     double *rec;                             // [S][nv + 2] records {wtemp, wtemp wtemp}: always memory
     double *mom;                             // [S][4] sums m1 m2 m3 ww in memory
 };
+template <typename T>
+struct LosProf<T, LOS_AGES> {
+    AgeK bins;                               // the age cube's bin rule
+    const T *time;                           // read for decided pairs with wtemp != 0 only
+    double *rec;                             // [S][na + 2] records {wtemp, wtemp wtemp}: always memory
+};
 
-template <typename T> NXC_DEV double *profile_moments(const LosProf<T, false> &) { return nullptr; }
-template <typename T> NXC_DEV double *profile_moments(const LosProf<T, true> &Q) { return Q.mom; }
+template <typename T, LosMode MODE>
+NXC_DEV double *profile_moments(const LosProf<T, MODE> &) { return nullptr; }
+template <typename T> NXC_DEV double *profile_moments(const LosProf<T, LOS_PROFILE> &Q) { return Q.mom; }
 
 // One (stored sample, spectrum) pair, exactly as the reference decides and weighs it
 // (compute_iteration.py:177-213).  sp: the spectrum's eight tile values.
 // (vy_p, frac_p, idx_p: the sample's radial velocity, fraction and slot in `included`, loaded by the
 // caller together with its coordinates; ladder: global or LDS)
-// PROFILE: a pair that adds wtemp != 0 to the radiance also files {wtemp, wtemp wtemp} under its
+// LOS_PROFILE: a pair that adds wtemp != 0 to the radiance also files {wtemp, wtemp wtemp} under its
 // Doppler bin in Q.rec and adds its four moment terms to mom[4 spectrum ...] (Q.mom, or a
 // workgroup's LDS copy) -- per-lane atomics like the radiance's: the lanes got here one by one.
-template <bool PROFILE = false, typename T = double>
+// LOS_AGES: such a pair files {wtemp, wtemp wtemp} under its age bin in Q.rec (age_plane of the row's
+// time, read here and only here); there are no moment sums.
+template <LosMode MODE = LOS_PLAIN, typename T = double>
 NXC_DEV void los_pair(const LosK &K, const double *__restrict__ sp, int64_t spectrum, int64_t p,
                       double px, double py, double pz, double vy_p, double frac_p, long long idx_p,
                       const double *ladder, double *radiance, unsigned long long *npackets,
                       unsigned char *__restrict__ included, long long used_cap,
                       long long *__restrict__ used_pairs, unsigned long long *__restrict__ n_used,
                       double rs_1e6, unsigned long long &my_pairs, unsigned long long &my_nonfinite,
-                      const LosProf<T, PROFILE> &Q = {}, double *mom = nullptr)
+                      const LosProf<T, MODE> &Q = {}, double *mom = nullptr)
 {
     const double xs = sp[0], ys = sp[1], zs = sp[2], bx = sp[3], by = sp[4], bz = sp[5];
     const double rx = px - xs, ry = py - ys, rz = pz - zs;
@@ -1625,7 +1638,7 @@ NXC_DEV void los_pair(const LosK &K, const double *__restrict__ sp, int64_t spec
     const bool lit = ((hx * hx + hz * hz) > 0x1.0000000000001p+0) || (hy < 0.0);
     wtemp = lit ? wtemp : wtemp * 0.0;
     if (wtemp != 0.0) unsafeAtomicAdd(&radiance[spectrum], wtemp);     // (global, or a workgroup's LDS copy)
-    if constexpr (PROFILE) {
+    if constexpr (MODE == LOS_PROFILE) {
         if (wtemp != 0.0) {
             const double vlos = ((double)Q.vx[p] * bx + vy_p * by) + (double)Q.vz[p] * bz;
             double *const r = Q.rec + 2 * (spectrum * (Q.bins.nv + 2) + cube_plane(Q.bins, vlos));
@@ -1638,6 +1651,14 @@ NXC_DEV void los_pair(const LosK &K, const double *__restrict__ sp, int64_t spec
             unsafeAtomicAdd(m + 1, m2);
             unsafeAtomicAdd(m + 2, m2 * vlos);
             unsafeAtomicAdd(m + 3, ww);
+        }
+    }
+    if constexpr (MODE == LOS_AGES) {
+        if (wtemp != 0.0) {
+            const int k = age_plane(Q.bins, (double)Q.time[p]);
+            double *const r = Q.rec + 2 * (spectrum * (Q.bins.na + 2) + k);
+            unsafeAtomicAdd(r, wtemp);
+            unsafeAtomicAdd(r + 1, wtemp * wtemp);
         }
     }
     atomicAdd(&npackets[spectrum], 1ull);
@@ -1984,7 +2005,7 @@ constexpr int NXC_LOS_WAVE_BYTES = NXC_LOSQ_BYTES + 64 * 32 + 16 * 32 + 8 * 32 +
 #ifndef NXC_LOS_THREADS
 #define NXC_LOS_THREADS 1024
 #endif
-template <typename T, typename I, bool PROFILE = false>
+template <typename T, typename I, LosMode MODE = LOS_PLAIN>
 __global__ void __launch_bounds__(NXC_LOS_THREADS)
 k_los(LosK K, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t S,
       const double *__restrict__ sc, const unsigned long long *__restrict__ n_slots,
@@ -1997,7 +2018,7 @@ k_los(LosK K, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64
       unsigned long long *__restrict__ npackets, unsigned char *__restrict__ included,
       long long used_cap, long long *__restrict__ used_pairs,
       unsigned long long *__restrict__ n_used, DevCounters *__restrict__ ctr,
-      LosProf<T, PROFILE> prof = {})
+      LosProf<T, MODE> prof = {})
 {
     static_assert(NXC_LOS_TILE <= 512, "a (group, spectrum) pair is 3 + 9 bits");
     stage_tables(blob, stage_bytes);
@@ -2247,7 +2268,7 @@ k_los(LosK K, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64
 
 // The pairs k_los found near a cone, decided and weighed as the reference does it
 // (compute_iteration.py:177-213) -- 64 of them per wave instruction.
-template <typename T, typename I, bool PROFILE = false>
+template <typename T, typename I, LosMode MODE = LOS_PLAIN>
 __global__ void __launch_bounds__(NXC_BLOCK)
 k_los_pairs(LosK K, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t S,
             const double *__restrict__ sc, const unsigned long long *__restrict__ pair_list,
@@ -2258,7 +2279,7 @@ k_los_pairs(LosK K, const unsigned char *__restrict__ blob, int64_t stage_bytes,
             double *__restrict__ radiance, unsigned long long *__restrict__ npackets,
             unsigned char *__restrict__ included, long long used_cap,
             long long *__restrict__ used_pairs, unsigned long long *__restrict__ n_used,
-            DevCounters *__restrict__ ctr, LosProf<T, PROFILE> prof = {})
+            DevCounters *__restrict__ ctr, LosProf<T, MODE> prof = {})
 {
     stage_tables(blob, stage_bytes);                   // g-value tables; nxc_log's table in the header
     // the ladder of ball centres next to them: a pair walks seven of its rungs
@@ -2271,11 +2292,12 @@ k_los_pairs(LosK K, const unsigned char *__restrict__ blob, int64_t stage_bytes,
     double *const racc = lad + ((K.n_ladder + 3) & ~3);
     unsigned long long *const nacc = reinterpret_cast<unsigned long long *>(racc + (lds_sums ? S : 0));
     // (a profile pass: the four moment sums per spectrum behind them, S * 48 bytes in all; the bin
-    // records are spread over nv + 2 addresses per spectrum and go to memory)
+    // records are spread over nv + 2 addresses per spectrum and go to memory; an ages pass has its
+    // records only, so its LDS sums are the plain pass's)
     double *const macc = reinterpret_cast<double *>(nacc + S);
     if (lds_sums)
         for (int k = threadIdx.x; k < S; k += blockDim.x) { racc[k] = 0.0; nacc[k] = 0ull; }
-    if constexpr (PROFILE)
+    if constexpr (MODE == LOS_PROFILE)
         if (lds_sums)
             for (int k = threadIdx.x; k < 4 * S; k += blockDim.x) macc[k] = 0.0;
     __syncthreads();
@@ -2306,7 +2328,7 @@ k_los_pairs(LosK K, const unsigned char *__restrict__ blob, int64_t stage_bytes,
         for (int k = threadIdx.x; k < S; k += blockDim.x) {
             if (nacc[k]) atomicAdd(&npackets[k], nacc[k]);
             if (racc[k] != 0.0) unsafeAtomicAdd(&radiance[k], racc[k]);
-            if constexpr (PROFILE) {
+            if constexpr (MODE == LOS_PROFILE) {
                 if (nacc[k])
                     for (int c = 0; c < 4; c++)
                         if (macc[4 * k + c] != 0.0) unsafeAtomicAdd(&prof.mom[4 * k + c], macc[4 * k + c]);

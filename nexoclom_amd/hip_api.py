@@ -291,6 +291,10 @@ SIGNATURES = {
     'nxc_camera_ages_download': (_h, _dp),
     'nxc_camera_ages_upload': (_h, _dp),
     'nxc_camera_ages_apply': (_h, _i64, _dp, _dp),
+    'nxc_los_ages_enable': (_h, _i64, _i64, _dbl, _dbl, _dbl),
+    **_sample_entries('nxc_los_ages_accumulate', 6, (C.POINTER(nxc_los_desc), _i64, _dp), True,
+                      _los_results),
+    'nxc_los_ages_download': (_h, _dp),
 }
 RESTYPES = {'nxc_last_error_string': C.c_char_p}       # every other function returns an int status
 EXPORTS = tuple(SIGNATURES)
@@ -1085,19 +1089,26 @@ class Context:
     def los_accumulate(self, dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables,
                        ladder, sc, x=None, y=None, z=None, vy=None, frac=None, index=None,
                        n_index=0, used_cap=0, rows=None, pairs=None, vx=None, vz=None,
-                       profile=False):
+                       profile=False, ages=False, time=None):
         """sc: (8, S) array x,y,z,xbore,ybore,zbore,dist_from_plan,ladder_len.  Samples: five host
         columns (+ index), or ``rows = (RowStore, first, count, index_shift)`` for rows that are
         already in HBM.  Returns dict(radiance, npackets, included|None, used (2, m)|None,
         n_used).  ``pairs``: a PairList that receives the used pairs on the device instead of
         ``used`` (HipError with code NXC_ERR_OVERFLOW when they do not fit).  ``profile``: the
         pass also adds to the profile of ``los_profile_enable``; host columns then come with
-        ``vx`` and ``vz`` (a row store carries them)."""
+        ``vx`` and ``vz`` (a row store carries them).  ``ages``: the pass also adds to the block of
+        ``los_ages_enable``; host columns then come with ``time`` (a row store carries it).  One
+        pass does one of the two."""
+        if profile and ages:
+            raise ValueError('profile=True and ages=True exclude each other: one pass does one')
         if profile and rows is None and (vx is None or vz is None):
             raise ValueError('profile=True over host columns needs vx and vz')
+        if ages and rows is None and time is None:
+            raise ValueError('ages=True over host columns needs time')
         if pairs is not None and used_cap:
             raise ValueError('used_cap and pairs exclude each other')
-        name = 'nxc_los_profile_accumulate' if profile else 'nxc_los_accumulate'
+        name = ('nxc_los_profile_accumulate' if profile else
+                'nxc_los_ages_accumulate' if ages else 'nxc_los_accumulate')
         d, keep = self._los_desc(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm,
                                  g_tables, ladder)
         sc = _f64(sc)
@@ -1108,6 +1119,7 @@ class Context:
             samples = (self._rows_handle(store), first, count, shift)
         else:
             suffix, ptrs, cols = self._columns((x, y, z, vx, vy, vz, frac) if profile else
+                                               (time, x, y, z, vy, frac) if ages else
                                                (x, y, z, vy, frac))
             idx = None if index is None else np.ascontiguousarray(index, dtype=np.int64)
             entry = getattr(self.lib, name + suffix)
@@ -1150,6 +1162,22 @@ class Context:
         sums, moments = np.zeros((S, nv + 2, 2)), np.zeros((S, 4))
         self._check(self.lib.nxc_los_profile_download(self._h, _p(sums), _p(moments)))
         return sums, moments
+
+    def los_ages_enable(self, S, na, t0=0.0, a_lo=0.0, a_hi=0.0):
+        """Allocate and zero the line-of-sight ages of ``S`` spectra: ``na`` bins over
+        [a_lo, a_hi) seconds of age at the epoch ``t0`` (``na`` 0 frees them; a second enable
+        replaces and zeroes them)."""
+        S, na = int(S), int(na)
+        self._check(self.lib.nxc_los_ages_enable(self._h, S, na, t0, a_lo, a_hi))
+        self._los_ages_shape = (S, na) if na else None
+
+    def los_ages_download(self):
+        """sums (S, na + 2, 2) float64: {sum w, sum w w} per spectrum and plane -- plane 0 younger
+        than the range, 1..na the bins, na + 1 at or above it (or a time that is not a number)."""
+        S, na = getattr(self, '_los_ages_shape', None) or (0, 0)
+        sums = np.zeros((S, na + 2, 2))
+        self._check(self.lib.nxc_los_ages_download(self._h, _p(sums)))
+        return sums
 
     @staticmethod
     def _los_desc(dphi, sin_dphi, sin_2dphi, cos_threshold, vrplanet, unit_cm, g_tables, ladder):

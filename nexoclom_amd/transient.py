@@ -49,7 +49,9 @@ def refuse_ages_with(**given):
            'moments': 'ages= does not support moments=True: each is a pass of its own that adds to '
                       'the image, so two passes would add it twice; make two objects',
            'cube': 'ages= does not support cube=: each is a pass of its own that adds to the '
-                   'image, so two passes would add it twice; make two objects'}
+                   'image, so two passes would add it twice; make two objects',
+           'profile': 'ages= does not support profile=: a line-of-sight pass files its pairs by '
+                      'age or by velocity, not both; make two objects'}
     for key, value in given.items():
         if value is not None and value is not False:
             raise NotImplementedError(why[key])
@@ -177,3 +179,52 @@ class TransientImages:
         self.images = S*atoms_per_packet
         self.effective_packets = np.where(filled, S*S/np.where(filled, ww, 1.0), 0.0)
         self.light_curve = self.images.sum(axis=(1, 2))
+
+
+def spectrum_times(times, default, n_spectra):
+    """(S,) epochs of ``n_spectra`` spectra from ``times``: one per spectrum, one number for all of
+    them, or -- None -- ``default`` (the spacecraft data's ``time`` column).  ValueError when there
+    is neither, for another length and for a time that is not finite."""
+    if times is None:
+        if default is None:
+            raise ValueError('transient: times is missing and the spacecraft data had no time '
+                             'column')
+        times = default
+    try:
+        times = np.asarray(times, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError('transient: times are numbers') from None
+    if times.ndim == 0:
+        times = np.full(n_spectra, float(times))
+    if times.shape != (n_spectra,):
+        raise ValueError(f'transient: times of shape {times.shape} for {n_spectra} spectra')
+    if not np.all(np.isfinite(times)):
+        raise ValueError('transient: all times must be finite')
+    return times
+
+
+class TransientRadiance:
+    """What ``los.transient(history, times)`` returns:
+
+      times              (S,) [s]: the epoch of every spectrum
+      kernel             (nbins + 2, S): column s is the response at the epoch of spectrum s
+      radiance           (S,) Series [kR], indexed like the result's ``radiance``:
+                         sum_k S[s][k] K[k][s]
+      effective_packets  (S,) Series: (sum)^2 / sum_k WW[s][k] K[k][s]^2, 0 where a spectrum is
+                         empty -- the error bars are radiance / sqrt(effective_packets)
+
+    Both sums run over k = 0 .. nbins + 1 in that order from 0.0, one rounding per operation: a
+    pure function of ``age_sums`` and the kernel."""
+
+    def __init__(self, times, age_edges, history, age_sums, scale, rows):
+        import pandas as pd
+        self.times = times
+        self.kernel = K = response_matrix(age_edges, times, history)
+        total, ww = np.zeros(len(times)), np.zeros(len(times))
+        for k in range(K.shape[0]):
+            total = total + age_sums[:, k, 0]*K[k]
+            ww = ww + age_sums[:, k, 1]*(K[k]*K[k])
+        filled = ww != 0
+        self.radiance = pd.Series(total*scale, index=rows)
+        self.effective_packets = pd.Series(
+            np.where(filled, total*total/np.where(filled, ww, 1.0), 0.0), index=rows)
