@@ -897,6 +897,16 @@ int launch_fused(nxc_handle *h, bool image, int rows, int64_t n_iter, double out
     const size_t tables = v.image ? h->all_bytes : h->force_bytes, lds = persist_lds(tables, v);
     int grid = 1, block = BLOCK_PERSIST, rc;
     if ((rc = prepare_persistent_launch(h, kernel, &block, lds, h->n_packets, &grid))) return rc;
+    // tests: "<blocks>x<waves per block>" -- fewer lanes than packets at small sizes, so that lanes
+    // take second packets; anything else is ignored.  lds stays sized for a full block.
+    if (const char *t = std::getenv("NXC_TEST_FUSED_WAVES")) {
+        int b = 0, w = 0;
+        char rest = 0;
+        if (std::sscanf(t, "%dx%d%c", &b, &w, &rest) == 2 && b >= 1 && b <= h->n_cu && w >= 1 &&
+            w <= BLOCK_PERSIST / 64) {
+            grid = b; block = w * 64;
+        }
+    }
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, h->stream, h->F, h->d_blob,
                        (int64_t)tables, h->n_packets, job.soa, job.order, h->first_id, n_iter,
                        sqrt_threshold(outeredge), job.final, job.steps,

@@ -14,6 +14,37 @@ from oracle import np_oracle as O
 from oracle.c_oracle import COracle
 
 
+def compact_rows(traj, narrow=False):
+    """traj (8, nrec, n), a dense trajectory -> (rows (9, total), index (total,), lengths (n,)): its
+    frac > 0 records, packet-major, with lossfrac in the reference's association
+    (Output.py:420-421) from 0."""
+    n = traj.shape[2]
+    frac = traj[7].T                                     # (n, nrec)
+    lossfrac = np.zeros_like(frac)
+    for ct in range(1, frac.shape[1]):
+        act = frac[:, ct - 1] > 0
+        if not act.any():
+            break
+        lossfrac[act, ct] = (lossfrac[act, ct - 1] + frac[act, ct - 1]) - frac[act, ct]
+    live = frac > 0
+    rows = np.stack([traj[c].T[live] for c in range(8)] + [lossfrac[live]])
+    index = np.repeat(np.arange(n), live.sum(axis=1))
+    if narrow:
+        rows, index = rows.astype(np.float32), index.astype(np.int32)
+    return rows, index, live.sum(axis=1).astype(np.int64)
+
+
+def bodies_of(cfg):
+    """The oracle's Bodies for what hip_api.Context.set_bodies takes (moons only: no torus)."""
+    if cfg is None:
+        return None
+    assert cfg.get('chx') is None, 'the stand-in covers moons without the plasma torus'
+    m = cfg['moons']
+    return O.Bodies(gm=tuple(x['gm'] for x in m), radius=tuple(x['radius'] for x in m),
+                    a=tuple(x['a'] for x in m), omega=tuple(x['omega'] for x in m),
+                    phi=tuple(x['phi'] for x in m), t0=cfg['t0'])
+
+
 class OracleRowStore:
     """Stand-in for hip_api.RowStore: the rows save() keeps, held on the host."""
 
@@ -54,6 +85,7 @@ class OracleContext:
         self.image_shape = None
         self._forces = None
         self._desc = None
+        self._bodies = None
         self._soa = None
         self._image = None
         self._counts = None
@@ -82,7 +114,7 @@ class OracleContext:
         assert cfg is None, 'the stand-in only covers perfect sticking'
 
     def set_bodies(self, cfg):
-        assert cfg is None, 'the stand-in only covers the single-body model'
+        self._bodies = bodies_of(cfg)
 
     def set_first_index(self, first_index):
         self._first = int(first_index)
@@ -180,7 +212,8 @@ class OracleContext:
         t0 = time.perf_counter()
         X0 = np.ascontiguousarray(self._soa.T)
         res = self.co.integrate_const(self._forces, X0, step, n_iter, outeredge,
-                                      img=self._desc if image else None, threads=self.threads)
+                                      img=self._desc if image else None, threads=self.threads,
+                                      bodies=self._bodies)
         if image:
             self._image += res['image']
             self._counts += res['counts']
@@ -206,24 +239,11 @@ class OracleContext:
         X0 = np.ascontiguousarray(self._soa.T)
         n, nrec = self.n_packets, n_iter + 1
         res = self.co.integrate_const(self._forces, X0, step, n_iter, outeredge, nrec=nrec,
-                                      threads=self.threads)
-        traj = res['traj']                                   # (8, nrec, n)
-        frac = traj[7].T                                     # (n, nrec)
-        lossfrac = np.zeros_like(frac)
-        for ct in range(1, nrec):
-            act = frac[:, ct - 1] > 0
-            if not act.any():
-                break
-            lossfrac[act, ct] = (lossfrac[act, ct - 1] + frac[act, ct - 1]) - frac[act, ct]
-        live = frac > 0
-        rows = np.stack([traj[c].T[live] for c in range(8)] + [lossfrac[live]])
-        index = np.repeat(np.arange(n), live.sum(axis=1))
-        if narrow:
-            rows, index = rows.astype(np.float32), index.astype(np.int32)
+                                      threads=self.threads, bodies=self._bodies)
+        rows, index, lengths = compact_rows(res['traj'], narrow)
         self._ctr = dict(particle_steps=res['work'], samples=0, samples_binned=0, nonfinite=0,
                          bad_step=0, neg_frac=0, unfinished=0)
         self.calls.append((self.n_packets, self._first))
-        lengths = live.sum(axis=1).astype(np.int64)
         if resident:
             return dict(lengths=lengths, store=OracleRowStore(self, rows, index, narrow))
         return dict(lengths=lengths, rows=rows)
