@@ -689,6 +689,57 @@ int nxc_density_spectrum_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64
                                          int64_t count);
 int nxc_density_spectrum_download(nxc_handle *h, double *sums);
 
+/* ---- Density ages: density per age bin at the points, for a time-varying source rate --------------
+ * EXTENSION -- nxc_density_accumulate sums a point's ball over all ages; this keeps the age ("Age
+ * cube" says what an age is and why the density is linear in the source's history).  A block has
+ * na >= 1 bins over [a_lo, a_hi) seconds of age at the epoch t0, the run's endtime.  The host forms
+ * inv_da = na / (a_hi - a_lo) once in fp64.  A row that is a member of point q's ball (the membership
+ * of nxc_density_set, unchanged) is filed as follows with f = (double)frac, fp64, one rounding per
+ * operation, no contraction (time: the row's first column, widened when it is float32):
+ *   age = t0 - (double)time
+ *   u   = (age - a_lo) * inv_da
+ *   k = 0                 if u < 0                              (younger than the range)
+ *   k = 1 + (int)u        if 0 <= u < na                        (bin (int)u of the range)
+ *   k = na + 1            otherwise: at or above a_hi, or time not a number
+ * -- the plane of "Age cube" -- and the member row adds
+ *   {f, 1}     to point q's {sum_frac, count} pair, as nxc_density_accumulate does
+ *   {f, f*f}   to record q*(na + 2) + k of the block.
+ *   - Nothing is filtered.  A member with f == 0 adds zeros and is still counted (nxc_density_* count
+ *     every member; the image's age cube, where w == 0 adds nothing, differs).  A non-finite f
+ *     poisons the record it reaches.
+ *   - So the na + 2 planes of a point sum to its sum_frac up to the order of the additions, which is
+ *     not fixed.
+ *   - time and frac are read only for a row that passed the cell cull.
+ *   nxc_density_ages_enable          after nxc_density_set: na >= 1 allocates and zeroes Q*(na + 2)
+ *                                    16-byte records (NXC_ERR_NOMEM when they cannot be had), na == 0
+ *                                    frees them; nxc_density_set switches the block off again and
+ *                                    frees it, as it does the spectrum.  NXC_ERR_ARG, before anything
+ *                                    is allocated or freed, for Q < 1, na < 0, t0, a_lo or a_hi not
+ *                                    finite, a_lo >= a_hi (or a width that is not finite),
+ *                                    Q*(na + 2) >= 2^31
+ *   nxc_density_ages_accumulate[_f32] adds p host samples -- five columns, time first -- to
+ *                                    {sum_frac, count} AND the block in one pass
+ *   nxc_density_ages_accumulate_rows the same for rows [first, first + count) of a row store, whose
+ *                                    column 0 is the time
+ *   nxc_density_ages_download        sums[Q][na + 2][2] = {f sum, f*f sum}, point (index order), plane
+ *                                    0 below, planes 1..na the bins, na + 1 above
+ *   nxc_density_ages_upload          the block replaced by sums of that layout
+ *   nxc_density_ages_apply           nxc_image_ages_apply over the Q points in place of the pixels:
+ *                                    out[ne][Q][2], the same sums in the same order, the same refusals
+ * NXC_ERR_STATE names the missing call (nxc_density_set, then the enable), then NXC_ERR_ARG for p < 0,
+ * a null column with p > 0 or a null sums; p = 0 adds nothing.  The age block, the moments and the
+ * spectrum are independent states of a handle: the ages entries add to {sum_frac, count} and the
+ * block only, and the plain, moments and spectrum entries never touch the block. */
+int nxc_density_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi);
+int nxc_density_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
+                                const double *y, const double *z, const double *frac);
+int nxc_density_ages_accumulate_f32(nxc_handle *h, int64_t p, const float *time, const float *x,
+                                    const float *y, const float *z, const float *frac);
+int nxc_density_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_density_ages_download(nxc_handle *h, double *sums);
+int nxc_density_ages_upload(nxc_handle *h, const double *sums);
+int nxc_density_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out);
+
 /* ---- CameraImage: perspective image from a position inside or near the cloud ----------------------
  * EXTENSION -- the reference images from infinity only (ModelImage.create_image); this is the same
  * weighting seen by a pinhole (gnomonic) camera at a finite distance.  Samples are x, y, z [R],

@@ -27,6 +27,14 @@ EXTENSION (``spectrum=dict(...)``): what an in-situ mass spectrometer counts.  T
 given velocity at that point, if the direction it arrives from lies within a cone around a
 boresight: per point and speed bin the density of the atoms in view and their number flux
 (``parse_spectrum``, ``spectrum_from_sums``).
+
+EXTENSION (``ages=(a_lo_s, a_hi_s, nbins)``): the density for a source whose rate changes with time.
+The pass (k_density_ages; include/nexoclom_hip.h, "Density ages") files every hit under the age of
+its row as well: per point and age bin the density that atoms launched that long ago contribute.
+``transient(epochs, history)`` contracts the block with the response matrix of a source history
+(transient.py) into the density at every point per epoch, ``transient_track(history, times)`` reads
+each point at its own time -- a spacecraft crossing the cloud -- and ``transient_design`` gives the
+matrix a fit of the history to such a track needs.
 """
 import operator
 
@@ -37,6 +45,8 @@ from .ModelImage import ModelResult
 from .atomicdata import atomicmass
 from .catalogue import sample_pass
 from .frames import MoonFrame, is_planet_origin, refuse_with_moon_origin
+from .transient import (TransientDensity, TransientTrack, ages_from_sums, parse_ages,
+                        refuse_ages_of, refuse_ages_with, response_matrix, spectrum_times)
 from .units import Quantity
 
 MAX_CELLS = 1 << 24           # cells of the point grid (int32 starts; cell coordinates < 2^24)
@@ -129,6 +139,7 @@ def moments_from_sums(s0, sums, unit_km, mass_kg):
 
 SPECTRUM_KEYS = ('speed', 'velocity', 'boresight', 'half_angle')
 MAX_SPECTRUM_RECORDS = 2**31      # the device's record index is an int
+MAX_AGE_RECORDS = 2**31           # likewise
 
 
 def _vectors(value, Q, name):
@@ -256,7 +267,7 @@ def spectrum_from_sums(spectrum_sums, scale, unit_km, s_lo_kms, s_hi_kms, mass_k
 
 class ModelDensity:
     def __init__(self, inputs, xpts, ypts, zpts, dr=0.05, moments=False, *, cp=None,
-                 reduce='rccl', context=None, device=0, spectrum=None, origin=None):
+                 reduce='rccl', context=None, device=0, spectrum=None, origin=None, ages=None):
         """Number density at the points (xpts, ypts, zpts) [planet radii] from every catalogued
         Output of ``inputs`` (ModelDensity.py:18-85).  ``cp``: the control plane of a shared run
         (``Input.run(..., cp=cp)``): each rank sums its own Outputs, then the per-point sums and
@@ -283,7 +294,22 @@ class ModelDensity:
         rows are moved into the frame that co-rotates with the moon (frames.MoonFrame) before they
         are read: the points and ``dr`` are then in moon radii from the moon's centre, and the
         velocities of ``moments=`` and ``spectrum=`` are relative to the moon (a spacecraft's
-        ``velocity`` likewise).  It refuses ``cp=``.  None or the planet: nothing changes."""
+        ``velocity`` likewise).  It refuses ``cp=``.  None or the planet: nothing changes.
+
+        ``ages=(a_lo_s, a_hi_s, nbins)`` (EXTENSION; catalogued constant-step Outputs only) also
+        files every hit under the age of its row, options.endtime minus its t_remaining: ``nbins``
+        bins over [a_lo_s, a_hi_s) seconds.  Attributes: the raw ``age_sums`` (Q, nbins + 2, 2) =
+        {sum f, sum f f} per point and plane (0 younger than the range, 1..nbins the bins,
+        nbins + 1 at or above it; zeros at a point left out of the index) and, scaled as
+        ``density`` is, ``age_density`` (Q, nbins), ``age_below``, ``age_above`` (Q,), with
+        ``age_edges``, ``age_axis`` [s] and ``age_effective_packets`` (Q, nbins):
+        ``age_density.sum(1) + age_below + age_above`` is ``density`` up to the order of the
+        additions.  ``transient``, ``transient_track`` and ``transient_design`` read them.  It
+        refuses ``moments=True``, ``spectrum=`` and ``cp=``; a moon's ``origin=`` is allowed."""
+        if ages is not None:
+            refuse_ages_with(moments=moments, spectrum=spectrum, cp=cp)
+            ages = parse_ages(ages)
+            refuse_ages_of(inputs)
         if spectrum is not None:
             refuse_with_spectrum(moments=moments, cp=cp)
         self.type = 'density'
@@ -303,6 +329,9 @@ class ModelDensity:
             raise ValueError('xpts, ypts and zpts must have the same length')
         Q = len(xyz[0])
         self._spectrum = None if spectrum is None else parse_spectrum(spectrum, Q)
+        if ages is not None and Q*(ages[2] + 2) >= MAX_AGE_RECORDS:
+            raise ValueError('ages=: points * (nbins + 2) must stay below 2^31')
+        self._ages = ages
         self.density = np.zeros(Q)
         self.packets = np.zeros(Q)
         self.totalsource = 0.
@@ -318,6 +347,11 @@ class ModelDensity:
         frames = None if self._spectrum is None else spectrum_frames(self._spectrum, unit_km,
                                                                       index.order)
         sums, counts, extra = self._accumulate(index, self._moments, frames)
+        if self._ages is not None:
+            self._index = index                   # transient() sets it up again with it
+            self.age_sums = np.zeros((Q, self._ages[2] + 2, 2))
+            if extra is not None:
+                self.age_sums[index.order] = extra
         if self._spectrum is not None:
             self.spectrum_sums = np.zeros((2, Q, self._spectrum['speed'][2] + 2, 2))
             self.spectrum_sums[:, index.order] = extra
@@ -355,20 +389,29 @@ class ModelDensity:
                                                   self.atoms_per_packet/float(self.Vpix), unit_km,
                                                   s_lo, s_hi, mass_kg).items():
                 setattr(self, name, value)
+        if self._ages is not None:
+            for name, value in ages_from_sums(self.age_sums, self.atoms_per_packet/float(self.Vpix),
+                                              *self._ages[:2]).items():
+                setattr(self, name.replace('age_cube', 'age_density'), value)
 
     context = ModelResult.context         # the catalogue's shared context, found once and kept
     frame, slab_rows = None, ModelResult.slab_rows       # a moon's frame, as the images have it
     _frame_pass = ModelResult._frame_pass
+    _ages = None              # (a_lo_s, a_hi_s, nbins): the pass also fills age_sums
+    _ages_token = None        # what Context.ages_owner holds while the block is this object's total
 
     def _accumulate(self, index, moments=False, frames=None):
-        """(frac sums, counts, moment sums | spectrum sums | None) per indexed point over this
-        process's catalogue (ModelDensity.py:62-82).  Rows in HBM are read where they are, one
-        launch per run of adjacent slices of a store; other Outputs upload X's x, y, z, frac (with
-        moments or a spectrum -- ``frames``, the indexed points' frame records: and vx, vy, vz)."""
+        """(frac sums, counts, moment sums | spectrum sums | age sums | None) per indexed point
+        over this process's catalogue (ModelDensity.py:62-82).  Rows in HBM are read where they
+        are, one launch per run of adjacent slices of a store; other Outputs upload X's x, y, z,
+        frac (with moments or a spectrum -- ``frames``, the indexed points' frame records: and vx,
+        vy, vz; with ages: and time)."""
         ctx = self.context()
-        ctx.density_set(index.points, index.cell_start, index.origin, index.h, index.dr,
-                        index.dims)
+        self._set_index(ctx, index)
         columns, add = ('x', 'y', 'z', 'frac'), ctx.density_accumulate
+        ages = self._ages is not None and len(index.points) > 0    # no block without a point
+        if ages:
+            columns, add = ('time', 'x', 'y', 'z', 'frac'), ctx.density_ages_accumulate
         if moments:
             ctx.density_moments_enable()
             columns, add = ('x', 'y', 'z', 'vx', 'vy', 'vz', 'frac'), ctx.density_moments_accumulate
@@ -385,4 +428,61 @@ class ModelDensity:
                         **self._frame_pass())
         extra = ctx.density_spectrum_download() if frames is not None else \
             ctx.density_moments_download() if moments else None
+        if ages:       # the resident block is this object's total until the context says otherwise
+            extra = ctx.density_ages_download()
+            ctx.ages_owner['density'] = self._ages_token = object()
         return (*ctx.density_download(), extra)
+
+    def _set_index(self, ctx, index):
+        """The point index and, with ``ages=``, a zeroed age block in the context."""
+        ctx.density_set(index.points, index.cell_start, index.origin, index.h, index.dr,
+                        index.dims)
+        if self._ages is not None and len(index.points):
+            a_lo, a_hi, nbins = self._ages
+            ctx.density_ages_enable(nbins, float(self.inputs.options.endtime.value), a_lo, a_hi)
+
+    def _need_ages(self, what):
+        if self._ages is None:
+            raise ValueError(f'{what}() needs an object built with ages=(a_lo_s, a_hi_s, nbins)')
+        return self.atoms_per_packet/float(self.Vpix)
+
+    def transient(self, epochs, history):
+        """The density at every point at ``epochs`` [s] for a source whose rate relative to the
+        nominal one was ``history = (t_nodes_s, rate_nodes)`` (transient.response_matrix): a
+        TransientDensity with epochs, kernel (nbins + 2, E), density (E, Q), scaled as ``density``
+        is, and effective_packets (E, Q).  The age block is contracted where it is (k_ages_apply)
+        while this object's sums are the ones resident in its context; when another product has
+        replaced them since, the index is set up again and ``age_sums`` uploaded once.  The device
+        works in the index's point order; the result is in the input's."""
+        scale = self._need_ages('transient')
+        K = response_matrix(self.age_edges, epochs, history)
+        index, Q = self._index, len(self.age_sums)
+        sums = np.zeros((K.shape[1], Q, 2))
+        if len(index.points):
+            ctx = self.context()
+            if ctx.ages_owner.get('density') is not self._ages_token:
+                self._set_index(ctx, index)
+                ctx.density_ages_upload(self.age_sums[index.order])
+                ctx.ages_owner['density'] = self._ages_token
+            sums[:, index.order] = ctx.density_ages_apply(K)
+        return TransientDensity(epochs, K, sums, scale)
+
+    def transient_track(self, history, times):
+        """The trajectory's product: point q read at its own time.  ``times``: (Q,) seconds on the
+        history's clock, or one number for all points.  A TransientTrack with times, kernel
+        (nbins + 2, Q) -- column q the response at the time of point q --, density (Q,) =
+        scale * sum_k S[q][k] K[k][q], scaled as ``density`` is, and effective_packets (Q,).  The
+        sums run over the planes from 0 upwards, from 0.0, on the host: a track has 1e4 points."""
+        scale = self._need_ages('transient_track')
+        times = spectrum_times(times, None, len(self.age_sums))
+        return TransientTrack(times, self.age_edges, history, self.age_sums, scale)
+
+    def transient_design(self, t_nodes, times):
+        """(Q, J) matrix A with ``A @ rates == transient_track((t_nodes, rates), times).density``
+        up to rounding: column j is ``transient_track`` of the history with rate 1 at node j and
+        0 at the others.  What a non-negative least-squares fit of a source history to the
+        densities measured along a track needs; the fit itself is the caller's."""
+        nodes = np.atleast_1d(np.asarray(t_nodes, dtype=float))
+        columns = [self.transient_track((nodes, np.eye(len(nodes))[j]), times).density
+                   for j in range(len(nodes))]
+        return np.stack(columns, axis=1)

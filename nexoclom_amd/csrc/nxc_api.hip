@@ -28,6 +28,7 @@
 #include "nxc_shell_check.hpp"
 #include "nxc_cube_check.hpp"
 #include "nxc_ages_check.hpp"
+#include "nxc_density_ages_check.hpp"
 #include "nxc_los_ages_check.hpp"
 #include "nxc_los_profile_check.hpp"
 #include "nxc_desc_check.hpp"
@@ -454,6 +455,9 @@ struct nxc_handle {
     SpectrumK dens_spec{};
     Dev<double> d_dens_spec;         // the spectrum: [2][Q][nv + 2] records (k_density_spectrum)
     Dev<double> d_dens_frames;       // [Q][8]: ux uy uz 0 bx by bz 0 per indexed point
+    bool have_dens_ages = false;     // nxc_density_ages_enable since the last nxc_density_set
+    AgeK dens_ageK{};
+    Dev<double> d_dens_ages;         // the ages: [Q][na + 2] records {f, f f} (k_density_ages)
 
     // CameraImage (nxc_camera_set): the camera, its LDS blob [LdsHeader | g tables | u edges |
     // v edges] and its own {weight sum, count} image
@@ -1688,6 +1692,17 @@ int spectrum_run(nxc_handle *h, const Samples &s)
     });
 }
 
+// ModelDensity(ages=...) over samples on the device (k_density_ages: time, x, y, z, frac)
+int density_ages_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_density_ages<T>, NXC_BLOCK, 0, s.n, h->dens, h->dens_ageK, s.n,
+                                  s.col<T>(7), s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(4),
+                                  h->d_dens_pts, h->d_dens_cell, h->d_dens_acc, h->d_dens_ages);
+    });
+}
+
 // CameraImage over samples on the device (k_camera)
 int camera_run(nxc_handle *h, const Samples &s)
 {
@@ -1827,6 +1842,35 @@ int spectrum_free(nxc_handle *h)
     h->have_dens_spec = false;
     const int rc = h->d_dens_spec.release(), rc2 = h->d_dens_frames.release();
     return rc ? rc : rc2;
+}
+// the density ages' state is their enable too, checked after nxc_density_set's (moments_need_set);
+// the pass reads the time column and no velocity
+const SampleConsumer DENSITY_AGES_SAMPLES = {[](const nxc_handle *h) { return h->have_dens_ages; },
+                                             "nxc_density_ages_enable has not been called",
+                                             false, false, false,
+                                             [](const nxc_handle *h) { return h->dens_q == 0; },
+                                             density_ages_run, nullptr, true};
+// bytes of the age block over Q points
+size_t density_ages_bytes(const nxc_handle *h)
+{
+    return (size_t)h->dens_q * (size_t)(h->dens_ageK.na + 2) * 2 * sizeof(double);
+}
+
+// the density ages off, their records back to the device
+int density_ages_free(nxc_handle *h)
+{
+    h->have_dens_ages = false;
+    return h->d_dens_ages.release();
+}
+
+// the state checks of the block's download, upload and apply (nxc_density_set is named first), and
+// their null check
+int density_ages_ready(const nxc_handle *h, const void *host)
+{
+    if (!h || !h->have_density) return fail(NXC_ERR_STATE, DENSITY_SAMPLES.unset);
+    if (!h->have_dens_ages) return fail(NXC_ERR_STATE, DENSITY_AGES_SAMPLES.unset);
+    if (!host) return fail(NXC_ERR_ARG, "bad arguments");
+    return NXC_OK;
 }
 const SampleConsumer CAMERA_SAMPLES = {[](const nxc_handle *h) { return h->have_camera; },
                                        "nxc_camera_set has not been called",
@@ -2013,8 +2057,47 @@ int pixel_ages_upload(nxc_handle *h, const SampleConsumer &base, const SampleCon
     });
 }
 
+// out[ne][n_rec][2] (host) = a resident block of n_rec records of `planes` planes contracted with
+// K[planes][ne] (host), k_ages_apply over record runs x epoch chunks cut to the device's LDS
+// (ages_apply_plan).  Called inside guarded(), after the state checks of the entry.
+int ages_block_apply(nxc_handle *h, size_t n_rec, int64_t planes, const double *d_block, int64_t ne,
+                     const double *K, double *out)
+{
+    const std::string why = check_ages_apply(planes, ne, K);
+    if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
+    if (!out) return fail(NXC_ERR_ARG, "bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    int lds_per_block = 0;
+    HIPCHK(hipDeviceGetAttribute(&lds_per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device));
+    AgesPlan plan;
+    if (!ages_apply_plan(planes, ne, (size_t)std::max(lds_per_block, 0), &plan))
+        return fail(NXC_ERR_ARG, "age cube: one pixel's planes and one column of K exceed the "
+                                 "LDS of a workgroup");
+    const int64_t runs = ((int64_t)n_rec + plan.run - 1) / plan.run;
+    const int64_t chunks = (ne + plan.chunk - 1) / plan.chunk;
+    if (chunks > NXC_AGES_MAX_CHUNKS)
+        return fail(NXC_ERR_ARG, "age cube: more than 65535 epoch chunks in one call");
+    const size_t k_bytes = (size_t)planes * (size_t)ne * sizeof(double);
+    const size_t out_bytes = (size_t)ne * n_rec * 2 * sizeof(double);
+    Dev<double> d_K, d_out;
+    int rc;
+    if ((rc = d_K.ensure(k_bytes)) || (rc = d_out.ensure(out_bytes))) return rc;
+    HIPCHK(hipMemcpyAsync(d_K, K, k_bytes, hipMemcpyHostToDevice, h->stream));
+    const AgesApplyK A = {(int)planes, (int)plan.stride, (int)plan.run, (int)plan.chunk, (int)ne,
+                          (int64_t)n_rec};
+    if ((rc = prep_kernel(k_ages_apply, plan.bytes)) || (rc = begin_timed(h))) return rc;
+    hipLaunchKernelGGL(k_ages_apply, dim3((unsigned)runs, (unsigned)chunks), dim3(NXC_AGES_APPLY_BLOCK),
+                       plan.bytes, h->stream, A, reinterpret_cast<const double2 *>(d_block),
+                       d_K.get(), reinterpret_cast<double2 *>(d_out.get()));
+    HIPCHK(hipGetLastError());
+    if ((rc = end_timed(h))) return rc;
+    HIPCHK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+}
+
 // nxc_X_ages_apply: out[ne][npix][2] (host) = the resident block contracted with K[na + 2][ne]
-// (host), k_ages_apply over pixel runs x epoch chunks cut to the device's LDS (ages_apply_plan)
+// (host) (ages_block_apply)
 int pixel_ages_apply(nxc_handle *h, const SampleConsumer &base, const SampleConsumer &ages,
                      int64_t ne, const double *K, double *out)
 {
@@ -2022,38 +2105,7 @@ int pixel_ages_apply(nxc_handle *h, const SampleConsumer &base, const SampleCons
     return guarded([&]() -> int {
         if (!ages.have(h)) return fail(NXC_ERR_STATE, ages.unset);
         const PixelSums &px = h->*base.px;
-        const int64_t planes = (int64_t)px.ageK.na + 2;
-        const std::string why = check_ages_apply(planes, ne, K);
-        if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
-        if (!out) return fail(NXC_ERR_ARG, "bad arguments");
-        HIPCHK(hipSetDevice(h->device));
-        int lds_per_block = 0;
-        HIPCHK(hipDeviceGetAttribute(&lds_per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device));
-        AgesPlan plan;
-        if (!ages_apply_plan(planes, ne, (size_t)std::max(lds_per_block, 0), &plan))
-            return fail(NXC_ERR_ARG, "age cube: one pixel's planes and one column of K exceed the "
-                                     "LDS of a workgroup");
-        const int64_t runs = ((int64_t)px.npix + plan.run - 1) / plan.run;
-        const int64_t chunks = (ne + plan.chunk - 1) / plan.chunk;
-        if (chunks > NXC_AGES_MAX_CHUNKS)
-            return fail(NXC_ERR_ARG, "age cube: more than 65535 epoch chunks in one call");
-        const size_t k_bytes = (size_t)planes * (size_t)ne * sizeof(double);
-        const size_t out_bytes = (size_t)ne * px.npix * 2 * sizeof(double);
-        Dev<double> d_K, d_out;
-        int rc;
-        if ((rc = d_K.ensure(k_bytes)) || (rc = d_out.ensure(out_bytes))) return rc;
-        HIPCHK(hipMemcpyAsync(d_K, K, k_bytes, hipMemcpyHostToDevice, h->stream));
-        const AgesApplyK A = {(int)planes, (int)plan.stride, (int)plan.run, (int)plan.chunk, (int)ne,
-                              (int64_t)px.npix};
-        if ((rc = prep_kernel(k_ages_apply, plan.bytes)) || (rc = begin_timed(h))) return rc;
-        hipLaunchKernelGGL(k_ages_apply, dim3((unsigned)runs, (unsigned)chunks), dim3(NXC_AGES_APPLY_BLOCK),
-                           plan.bytes, h->stream, A, reinterpret_cast<const double2 *>(px.ages.get()),
-                           d_K.get(), reinterpret_cast<double2 *>(d_out.get()));
-        HIPCHK(hipGetLastError());
-        if ((rc = end_timed(h))) return rc;
-        HIPCHK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(stream_sync(h));
-        return NXC_OK;
+        return ages_block_apply(h, px.npix, (int64_t)px.ageK.na + 2, px.ages.get(), ne, K, out);
     });
 }
 
@@ -3478,6 +3530,7 @@ int nxc_density_set(nxc_handle *h, const nxc_density_desc *d)
     h->have_density = false;
     h->have_dens_mom = false;
     if (int rc = spectrum_free(h)) return rc;      // up to gigabytes: not kept for a set that may never enable one
+    if (int rc = density_ages_free(h)) return rc;  // likewise
     std::vector<double> pts((size_t)Q * 4, 0.0);
     for (int64_t j = 0; j < Q; j++)
         for (int a = 0; a < 3; a++) pts[4 * j + a] = d->points[3 * j + a];
@@ -3659,6 +3712,80 @@ int nxc_density_spectrum_download(nxc_handle *h, double *sums)
                           hipMemcpyDeviceToHost, h->stream));
     HIPCHK(stream_sync(h));
     return NXC_OK;
+    });
+}
+
+int nxc_density_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_density) return fail(NXC_ERR_STATE, DENSITY_SAMPLES.unset);
+    if (na != 0) {     // before anything is freed or allocated
+        const std::string why = check_density_ages_args(h->dens_q, na, t0, a_lo, a_hi);
+        if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
+    }
+    HIPCHK(hipSetDevice(h->device));
+    int rc = density_ages_free(h);
+    if (rc || na == 0) return rc;
+    h->dens_ageK = AgeK{(int)na, t0, a_lo, ages_inv_da(na, a_lo, a_hi)};
+    const size_t bytes = density_ages_bytes(h);
+    if ((rc = h->d_dens_ages.ensure(bytes))) return rc;
+    HIPCHK(hipMemsetAsync(h->d_dens_ages, 0, bytes, h->stream));
+    HIPCHK(stream_sync(h));
+    h->have_dens_ages = true;
+    return NXC_OK;
+    });
+}
+
+int nxc_density_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
+                                const double *y, const double *z, const double *frac)
+{
+    if (int rc = moments_need_set(h)) return rc;
+    return accumulate_columns<double>(h, DENSITY_AGES_SAMPLES, p, x, y, z, nullptr, frac, nullptr,
+                                      nullptr, time);
+}
+
+int nxc_density_ages_accumulate_f32(nxc_handle *h, int64_t p, const float *time, const float *x,
+                                    const float *y, const float *z, const float *frac)
+{
+    if (int rc = moments_need_set(h)) return rc;
+    return accumulate_columns<float>(h, DENSITY_AGES_SAMPLES, p, x, y, z, nullptr, frac, nullptr,
+                                     nullptr, time);
+}
+
+int nxc_density_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    if (int rc = moments_need_set(h)) return rc;
+    return accumulate_rows(h, DENSITY_AGES_SAMPLES, r, first, count);
+}
+
+int nxc_density_ages_download(nxc_handle *h, double *sums)
+{
+    return guarded([&]() -> int {
+    if (int rc = density_ages_ready(h, sums)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(sums, h->d_dens_ages, density_ages_bytes(h), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+    });
+}
+
+int nxc_density_ages_upload(nxc_handle *h, const double *sums)
+{
+    return guarded([&]() -> int {
+    if (int rc = density_ages_ready(h, sums)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(h->d_dens_ages, sums, density_ages_bytes(h), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+    });
+}
+
+int nxc_density_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out)
+{
+    return guarded([&]() -> int {
+    if (int rc = density_ages_ready(h, out)) return rc;
+    return ages_block_apply(h, (size_t)h->dens_q, (int64_t)h->dens_ageK.na + 2, h->d_dens_ages.get(), ne,
+                            K, out);
     });
 }
 

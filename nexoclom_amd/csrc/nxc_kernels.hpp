@@ -18,7 +18,8 @@
 //   k_image_ages, k_camera_ages         either pass with the weight filed per pixel and age bin
 //   k_shell         the same samples by solar-fixed longitude, sin(latitude) and altitude (ShellMap)
 //                   (all nine: pixel_pass -- staging, loop, loads, counters -- with a lambda each)
-//   k_density, k_density_moments, k_density_spectrum   stored samples within dr of query points
+//   k_density, k_density_moments, k_density_spectrum, k_density_ages
+//                   stored samples within dr of query points
 //                   (density_walk -- loop, cull, candidate walk, membership -- with a load and a
 //                   per-trip lambda each; k_density_moments keeps the walk written out)
 //   k_ages_apply    an age cube contracted with a response matrix: one image per epoch (streaming)
@@ -3091,6 +3092,39 @@ k_density_spectrum(DensityK K, SpectrumK S, int64_t n, int64_t n_points, const T
                      add_record_pairs(hit, q, w, 1.0, acc2);
                      add_record_pairs(hit && seen, rec, w, w * w, spec2);
                      add_record_pairs(hit && seen, rec, g, g * g, flux2);
+                 });
+}
+
+// ModelDensity(ages=...): k_density's pass with every hit filed under the age of its row
+// (include/nexoclom_hip.h, "Density ages", holds the definition).  time and frac are read only for a
+// row the cull passed.  With f = frac and the plane k of pixel_ages_add's rule (age_plane),
+//     u = ((t0 - time) - a_lo) inv_da;   k = 0 if u < 0,   1 + (int)u if 0 <= u < na,   na + 1 otherwise
+// a hit adds
+//     {f, 1}      to record q of acc2 (k_density's own pair array)
+//     {f, f f}    to record q (na + 2) + k of ages2, [Q][na + 2] records.
+// The two pair adds are made from uniform control flow (add_record_pairs), and a trip in which no
+// lane of the wave hits makes none.  The record index stays below 2^31 (check_density_ages_args).
+// Nothing is filtered: f == 0 adds zeros and is counted, a non-finite f poisons what it reaches.
+template <typename T>
+__global__ void __launch_bounds__(NXC_BLOCK)
+k_density_ages(DensityK K, AgeK Q, int64_t n, const T *__restrict__ time, const T *__restrict__ x,
+               const T *__restrict__ y, const T *__restrict__ z, const T *__restrict__ frac,
+               const double *__restrict__ pts, const int *__restrict__ cell_start,
+               double *__restrict__ acc2, double *__restrict__ ages2)
+{
+    double t = 0.0, w = 0.0;
+    density_walk<true>(K, n, x, y, z, pts, cell_start, (int64_t)blockIdx.x * blockDim.x,
+                 (int64_t)gridDim.x * blockDim.x,
+                 [&](int64_t i) {
+                     t = (double)time[i];
+                     w = (double)frac[i];
+                 },
+                 [&](bool hit, int q) {
+                     if (__ballot(hit) == 0) return;
+                     int rec = 0;
+                     if (hit) rec = q * (Q.na + 2) + age_plane(Q, t);
+                     add_record_pairs(hit, q, w, 1.0, acc2);
+                     add_record_pairs(hit, rec, w, w * w, ages2);
                  });
 }
 

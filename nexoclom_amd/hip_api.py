@@ -226,6 +226,11 @@ SIGNATURES = {
     'nxc_density_spectrum_enable': _desc(nxc_density_spectrum_desc),
     **_sample_entries('nxc_density_spectrum_accumulate', 7),
     'nxc_density_spectrum_download': (_h, _dp),
+    'nxc_density_ages_enable': (_h, _i64, _dbl, _dbl, _dbl),
+    **_sample_entries('nxc_density_ages_accumulate', 5),
+    'nxc_density_ages_download': (_h, _dp),
+    'nxc_density_ages_upload': (_h, _dp),
+    'nxc_density_ages_apply': (_h, _i64, _dp, _dp),
     'nxc_camera_set': _desc(nxc_camera_desc),
     **_sample_entries('nxc_camera_accumulate', 5),
     'nxc_camera_download': (_h, _dp, _u64p),
@@ -1208,6 +1213,9 @@ class Context:
         self._check(self.lib.nxc_density_set(self._h, C.byref(d)))
         self._density_q = len(pts)
         self._density_spectrum_nv = 0            # the set switches the spectrum off
+        self.density_shape = (len(pts),)         # what the age block's helpers call the pixels
+        self._density_ages_na = 0                # ... and the age block
+        self.ages_owner.pop('density', None)
 
     def density_accumulate(self, x=None, y=None, z=None, frac=None, rows=None):
         """Add samples to the per-point sums: four host columns (float32 ones go over as they
@@ -1276,6 +1284,32 @@ class Context:
         sums = np.zeros((2, getattr(self, '_density_q', 0), nv + 2, 2))
         self._check(self.lib.nxc_density_spectrum_download(self._h, _p(sums)))
         return sums
+
+    def density_ages_enable(self, na, t0=0.0, a_lo=0.0, a_hi=0.0):
+        """After ``density_set``: allocate and zero an age block of ``na`` bins over [a_lo, a_hi)
+        seconds of age at the epoch ``t0`` [s] per indexed point (``na = 0`` frees it; the next
+        ``density_set`` switches it off)."""
+        self._ages_enable('density', na, t0, a_lo, a_hi)
+
+    def density_ages_accumulate(self, time=None, x=None, y=None, z=None, frac=None, rows=None):
+        """Add samples to the per-point {frac sum, count} and to the age block in one pass: five
+        host columns, time first (float32 ones go over as they are), or ``rows = (RowStore, first,
+        count)``."""
+        self._accumulate('nxc_density_ages_accumulate', (time, x, y, z, frac), rows)
+
+    def density_ages_download(self):
+        """(Q, na + 2, 2) float64 in the index's point order: {sum f, sum f f} per age plane (0
+        below, 1..na the bins, na + 1 above) over the samples within dr."""
+        return self._pixel_sums_download('density', 'ages')
+
+    def density_ages_upload(self, sums):
+        """Replace the age block by ``sums`` (Q, na + 2, 2), in the index's point order."""
+        self._ages_upload('density', sums)
+
+    def density_ages_apply(self, K):
+        """(ne, Q, 2) = the resident age block contracted with ``K`` (na + 2, ne), as
+        ``image_ages_apply`` does it for pixels."""
+        return self._ages_apply('density', K)
 
     # -- CameraImage ------------------------------------------------------------------------
     def camera_set(self, observer, basis, vrplanet, pix_area_cm2, quantity, uedges, vedges,

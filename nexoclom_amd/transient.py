@@ -12,6 +12,8 @@ whose rate was ``rate(t)`` times the nominal one is
 
 -- one contraction of the cube with a small matrix (``response_matrix``; k_ages_apply on the
 device).  Only the rate changes: where and how fast the source launches stays as the run had it.
+LOSResult files the pairs of its lines of sight and ModelDensity the members of its points' balls
+the same way; their ``transient`` reads each spectrum or point at an epoch of its own.
 Host only, NumPy only."""
 import operator
 
@@ -51,7 +53,9 @@ def refuse_ages_with(**given):
            'cube': 'ages= does not support cube=: each is a pass of its own that adds to the '
                    'image, so two passes would add it twice; make two objects',
            'profile': 'ages= does not support profile=: a line-of-sight pass files its pairs by '
-                      'age or by velocity, not both; make two objects'}
+                      'age or by velocity, not both; make two objects',
+           'spectrum': 'ages= does not support spectrum=: each is a pass of its own that adds to '
+                       'the density, so two passes would add it twice; make two objects'}
     for key, value in given.items():
         if value is not None and value is not False:
             raise NotImplementedError(why[key])
@@ -220,11 +224,53 @@ class TransientRadiance:
         import pandas as pd
         self.times = times
         self.kernel = K = response_matrix(age_edges, times, history)
-        total, ww = np.zeros(len(times)), np.zeros(len(times))
-        for k in range(K.shape[0]):
-            total = total + age_sums[:, k, 0]*K[k]
-            ww = ww + age_sums[:, k, 1]*(K[k]*K[k])
-        filled = ww != 0
+        total, effective = track_sums(age_sums, K)
         self.radiance = pd.Series(total*scale, index=rows)
-        self.effective_packets = pd.Series(
-            np.where(filled, total*total/np.where(filled, ww, 1.0), 0.0), index=rows)
+        self.effective_packets = pd.Series(effective, index=rows)
+
+
+def track_sums(age_sums, K):
+    """(sum_k S[n][k] K[k][n], its effective packets) per record n of ``age_sums`` (N, nbins + 2,
+    2) read with its own column of ``K`` (nbins + 2, N): both sums over k = 0 .. nbins + 1 in that
+    order from 0.0, one rounding per operation; the effective packets are (sum)^2 /
+    sum_k WW[n][k] K[k][n]^2, 0 where a record is empty."""
+    total, ww = np.zeros(K.shape[1]), np.zeros(K.shape[1])
+    for k in range(K.shape[0]):
+        total = total + age_sums[:, k, 0]*K[k]
+        ww = ww + age_sums[:, k, 1]*(K[k]*K[k])
+    filled = ww != 0
+    return total, np.where(filled, total*total/np.where(filled, ww, 1.0), 0.0)
+
+
+class TransientDensity:
+    """What ``dens.transient(epochs, history)`` returns:
+
+      epochs             (E,) [s]
+      kernel             (nbins + 2, E): the response matrix used
+      density            (E, Q), scaled as ``density`` is
+      effective_packets  (E, Q): (sum)^2 / (ww sum), 0 where a point is empty -- the error bars
+                         are density / sqrt(effective_packets)"""
+
+    def __init__(self, epochs, kernel, sums, scale):
+        self.epochs = np.atleast_1d(np.asarray(epochs, dtype=float))
+        self.kernel = kernel
+        S, ww = sums[..., 0], sums[..., 1]
+        filled = ww != 0
+        self.density = S*scale
+        self.effective_packets = np.where(filled, S*S/np.where(filled, ww, 1.0), 0.0)
+
+
+class TransientTrack:
+    """What ``dens.transient_track(history, times)`` returns:
+
+      times              (Q,) [s]: the epoch of every point
+      kernel             (nbins + 2, Q): column q is the response at the epoch of point q
+      density            (Q,), scaled as ``density`` is: scale * sum_k S[q][k] K[k][q]
+      effective_packets  (Q,): ``track_sums``' -- the error bars are density /
+                         sqrt(effective_packets)"""
+
+    def __init__(self, times, age_edges, history, age_sums, scale):
+        self.times = times
+        self.kernel = response_matrix(age_edges, times, history)
+        total, self.effective_packets = track_sums(age_sums, self.kernel)
+        self.density = total*scale

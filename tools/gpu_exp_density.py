@@ -19,6 +19,11 @@ Median and [min, max] per kernel, and the spectrum's two floors: 28 B per row pl
 frame record) at the k_stream_copy rate, and one request per hit plus two per seen hit at 2.4e10
 requests/s.  The seen hits of the cone are counted by one more pass over the same rows with
 frac = 1 (downloaded and handed back as host columns), where plane 0 of the spectrum holds them.
+
+``--ages [--out FILE]``: the same with k_density, k_density_spectrum (whole sky, 16 bins) and
+k_density_ages (16 age bins over the run) alternated, and on the grid k_ages_apply for 1 and 64
+epochs (2 warm-up and 5 timed calls).  The ages' floors: 12 B of position per float32 row and 20 B
+where the cull passes it, at the k_stream_copy rate, and two requests per hit at 2.4e10 requests/s.
 """
 import contextlib
 import io
@@ -175,7 +180,64 @@ def spectrum_leg(out_path, warm=3, timed=9):
     ctx.close()
 
 
+def ages_leg(out_path, warm=3, timed=9, na=16):
+    ctx = hip_api.Context(0)
+    copy_bps = ctx.stream_copy_gbs() * 1e9
+    inputs = Input(os.path.join(ROOT, 'nexoclom_amd', 'inputfiles', 'Na.mercury.bench.input'))
+    with contextlib.redirect_stdout(io.StringIO()):
+        inputs.run(1e6, seed=7, context=ctx)
+    launches = spans(inputs, ctx)
+    rows = sum(s[2] for s in launches)
+    t0 = float(inputs.options.endtime.value)
+    unit_km = float(inputs.geometry.planet.radius.value)
+    for name, pts in point_sets().items():
+        index = DensityIndex(pts, DR)
+        ctx.density_set(index.points, index.cell_start, index.origin, index.h, index.dr,
+                        index.dims)
+        ctx.density_spectrum_enable(na, 0.0, 8.0/unit_km)            # the whole sky, 16 bins
+        ctx.density_ages_enable(na, t0, 0.0, t0)
+        times = {'k_density': [], 'k_density_spectrum': [], 'k_density_ages': []}
+        passes = (ctx.density_accumulate, ctx.density_spectrum_accumulate,
+                  ctx.density_ages_accumulate)
+        for rep in range(warm + timed):
+            for key, accumulate in zip(times, passes):
+                ms = kernel_ms(ctx, launches, accumulate)
+                if rep >= warm:
+                    times[key].append(ms)
+        hits = float(ctx.density_download()[1].sum()) / (3*(warm + timed))
+        ctx.density_spectrum_enable(0)
+        record = dict(npackets=1e6, points=name, rows=rows, launches=len(launches), hits=hits,
+                      na=na, record_bytes=len(index.points)*(na + 2)*16,
+                      stream_copy_gbs=round(copy_bps/1e9, 1),
+                      # 12 B of position per float32 row, 20 B where the cull passes it
+                      floor_bytes_ms=[round(rows*b/copy_bps*1e3, 3) for b in (12, 20)],
+                      floor_atomics_ms=round(2*hits/ATOMIC_RPS*1e3, 3))
+        for key, values in times.items():
+            record[key + '_ms'] = [round(v, 3) for v in values]
+            record[key] = spread(values)
+        if name.startswith('grid'):            # transient(): the block contracted for 1 and 64 epochs
+            for ne in (1, 64):
+                K = np.ones((na + 2, ne))
+                apply_ms = []
+                for rep in range(2 + 5):
+                    ctx.density_ages_apply(K)
+                    if rep >= 2:
+                        apply_ms.append(ctx.last_kernel_ms())
+                record[f'k_ages_apply_{ne}_ms'] = [round(v, 3) for v in apply_ms]
+                record[f'k_ages_apply_{ne}'] = spread(apply_ms)
+        line = json.dumps(record)
+        print(line, flush=True)
+        if out_path:
+            with open(out_path, 'a') as f:
+                f.write(line + '\n')
+        ctx.density_ages_enable(0)
+    ctx.close()
+
+
 def main():
+    if '--ages' in sys.argv:
+        out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else None
+        return ages_leg(out)
     if '--spectrum' in sys.argv:
         out = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else None
         return spectrum_leg(out)
