@@ -995,6 +995,52 @@ int nxc_shell_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const flo
 int nxc_shell_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
 int nxc_shell_download(nxc_handle *h, double *column, uint64_t *counts, double *sums);
 
+/* ---- ShellMap moments: bulk velocity, temperature and fluxes per cell and altitude record ----------
+ * EXTENSION.  In the same single pass as "ShellMap", every sample that step 8 there files (w != 0)
+ * also files its velocity, resolved in the local spherical basis at the sample, under the same
+ * record cell * (nalt + 2) + k.  Samples are x, y, z [R], vx, vy, vz [R/s], frac; they are relative
+ * to whatever the rows are relative to (a moon, after nxc_frame_rows).  vrplanet is not added to
+ * the velocity: it enters radvel for the g-value alone.  cell, k, w and has = (step 7 reached &&
+ * w != 0) are exactly those of "ShellMap", and column, packets and planes A and B are filled exactly
+ * as there.  Per sample with `has`, fp64, one rounding per operation, no contraction, sqrt and /
+ * correctly rounded, in this order:
+ *   1. p2 = x*x + y*y;  r2 = p2 + z*z;  r = sqrt(r2);  p = sqrt(p2);  h = x*vx + y*vy
+ *   2. v_r = (h + z*vz) / r                  positive is upward
+ *   3. v_e = (x*vy - y*vx) / p               positive is toward increasing solar-fixed longitude
+ *                                            (lon = atan2(x, -y): 0 at noon, pi/2 at dusk)
+ *   4. v_n = (p2*vz - z*h) / (r*p)           positive is northward
+ *   5. p2 == 0 (exactly on the polar axis, where east and north are 0/0): nothing more is added
+ *   6. u_r = w*v_r, u_e = w*v_e, u_n = w*v_n;  up = v_r > 0 ? u_r : 0;  dn = v_r < 0 ? -u_r : 0
+ *   7. twelve sums go to the sample's record of six planes of 16-byte records,
+ *      [6][nlon*nlat][nalt + 2][2]:
+ *        plane 0  {u_r, u_e}            plane 3  {u_r*v_e, u_r*v_n}
+ *        plane 1  {u_n, u_r*v_r}        plane 4  {u_e*v_n, up}
+ *        plane 2  {u_e*v_e, u_n*v_n}    plane 5  {up*up, dn*dn}
+ * Non-finite vx or vz are not filtered: they reach the sums of their record, as in "Density
+ * moments" (a NaN vy makes radvel a NaN and is dropped by step 5 of "ShellMap").  up and dn*dn are
+ * continuous at v_r = 0.  Six more atomic requests per filed sample, each made by lanes l and
+ * l + 32 of one instruction; a trip of a wave in which no lane files makes none.  The order of
+ * addition is not fixed.
+ *   nxc_shell_moments_enable          after nxc_shell_set: on != 0 allocates and zeroes the six planes
+ *                                     (NXC_ERR_NOMEM when they cannot be had), on == 0 frees them;
+ *                                     the next nxc_shell_set switches them off again
+ *   nxc_shell_moments_accumulate[_f32] adds p host samples to everything nxc_shell_accumulate adds
+ *                                     to AND to the six planes, in one pass
+ *   nxc_shell_moments_accumulate_rows the same for rows [first, first + count) of a row store
+ *   nxc_shell_moments_download        sums[6][nlon*nlat][nalt + 2][2]
+ * NXC_ERR_STATE naming nxc_shell_set before it, then NXC_ERR_STATE "moments not enabled" before the
+ * enable; NXC_ERR_ARG for p < 0, a null column with p > 0 or a null `sums`.  nxc_shell_accumulate*
+ * and nxc_shell_download serve unchanged beside them and never touch the six planes. */
+int nxc_shell_moments_enable(nxc_handle *h, int on);
+int nxc_shell_moments_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                                 const double *z, const double *vx, const double *vy,
+                                 const double *vz, const double *frac);
+int nxc_shell_moments_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                     const float *z, const float *vx, const float *vy,
+                                     const float *vz, const float *frac);
+int nxc_shell_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_shell_moments_download(nxc_handle *h, double *sums);
+
 /* ---- Line-of-sight profile: radiance per Doppler bin along each line of sight ----------------------
  * EXTENSION -- nxc_los_accumulate gives one radiance per spectrum; the profile keeps the line: per
  * spectrum nv >= 1 bins over [v_lo, v_hi), in the rows' velocity unit (planet radii per second), and

@@ -30,12 +30,27 @@ column_profile (the zenith column per shell) with column_below and column_above
 column_effective_packets ((sum a)^2 / sum a^2 per cell and shell, 0 where a shell is empty),
 shell_sums (the unscaled download), totalsource, atoms_per_packet, sourcerate, counters.
 
+``ShellMap(inputs, params, moments=True)``: the same single pass (k_shell_moments; "ShellMap
+moments" in the header) also files every sample's velocity, resolved in the local basis (radial up,
+east toward increasing longitude, north), under its cell and altitude bin.  Then also: velocity
+(nlon, nlat, nalt, 3) [km/s], velocity_covariance (..., 3, 3) [km^2/s^2], temperature [K],
+shell_moment_sums (the unscaled download, ``SHELL_MOMENT_COLUMNS``), and for 'column' flux_up,
+flux_down, flux_net [atoms cm^-2 s^-1] with flux_up_effective_packets and
+flux_down_effective_packets, and shell_rate_up, shell_rate_down, shell_rate_net (nalt,) [atoms/s]:
+the number rate through each shell -- at the top shell the escape rate, ``down`` at the bottom
+shell the return rate to the surface (``shell_moments_from_sums``).  For 'radiance' the moments are
+emission-weighted and the fluxes and rates are None.  With ``origin`` a moon the velocities are
+relative to the moon.
+
 Not supported, and refused: streaming (``npackets=``), shared runs (``cp=`` / ``shard=``).
 """
 import numpy as np
 
+from . import constants as const
+from .ModelDensity import moments_from_sums
 from .ModelImage import ModelResult
 from .Output import Output
+from .atomicdata import atomicmass
 from .catalogue import sample_pass
 from .input_classes import InputError
 
@@ -121,8 +136,60 @@ def shell_from_sums(column_sum, shell_sums, atoms_per_packet, solid_angle, volum
             'column_effective_packets': _effective(B[..., 1:-1, 0], B[..., 1:-1, 1])}
 
 
+# the twelve sums of ``shell_moment_sums`` per cell and altitude record, plane by plane and half by
+# half: u_a = w v_a in the local basis (r up, e east, n north), up = u_r where v_r > 0, dn = -u_r
+# where v_r < 0 (include/nexoclom_hip.h, "ShellMap moments")
+SHELL_MOMENT_COLUMNS = ('ur', 'ue', 'un', 'urr', 'uee', 'unn', 'ure', 'urn', 'uen', 'up', 'upup',
+                        'dndn')
+
+
+def shell_moments_from_sums(shell_sums, moment_sums, atoms_per_packet, volume, r_edges, unit_km,
+                            mass_kg, quantity='column'):
+    """What ``ShellMap(moments=True)`` publishes, from ``shell_sums`` (2, nlon, nlat, nalt + 2, 2,
+    plane A = {sum w, sum w w}) and ``moment_sums`` (6, nlon, nlat, nalt + 2, 2), the twelve sums of
+    ``SHELL_MOMENT_COLUMNS`` with velocities in R/s, R = ``unit_km``; ``volume`` (nalt) in R^3,
+    ``r_edges`` (nalt + 1) in R, ``mass_kg`` the atom's.
+
+    Per cell and altitude bin, over plane A's sum w of the same record (NaN where it is not > 0), as
+    ModelDensity.moments_from_sums forms them: ``velocity`` (..., 3) [km/s] in the order (radial,
+    east, north), ``velocity_covariance`` (..., 3, 3) [km^2/s^2], ``temperature`` [K] =
+    m tr C / (3 k_B).  For ``quantity`` 'column' also the fluxes [atoms cm^-2 s^-1]
+    atoms_per_packet S / (V_k R_cm^2) with S = sum up (``flux_up``), sum up - sum u_r
+    (``flux_down``) and sum u_r (``flux_net``); their effective packets (sum)^2 / sum of squares, 0
+    where empty; and per shell the number rates [atoms/s] through it, atoms_per_packet sum_cells S /
+    dr (``shell_rate_up``, ``shell_rate_down``, ``shell_rate_net``): the volume estimator.  For
+    'radiance' the moments are emission-weighted and the fluxes and rates are None."""
+    A = np.asarray(shell_sums, dtype=float)[0][..., 1:-1, :]
+    M = np.moveaxis(np.asarray(moment_sums, dtype=float), 0, -2)[..., 1:-1, :, :]
+    shape = A.shape[:-1]
+    M = M.reshape(shape + (12,))
+    col = {name: M[..., k] for k, name in enumerate(SHELL_MOMENT_COLUMNS)}
+    ten = np.stack([col[c] for c in ('ur', 'ue', 'un', 'urr', 'uee', 'unn', 'ure', 'urn', 'uen')]
+                   + [A[..., 1]], axis=-1)
+    u, cov, temperature, _ = moments_from_sums(A[..., 0].reshape(-1), ten.reshape(-1, 10), unit_km,
+                                               mass_kg)
+    out = {'velocity': u.reshape(shape + (3,)), 'velocity_covariance': cov.reshape(shape + (3, 3)),
+           'temperature': temperature.reshape(shape)}
+    names = ('flux_up', 'flux_down', 'flux_net', 'flux_up_effective_packets',
+             'flux_down_effective_packets', 'shell_rate_up', 'shell_rate_down', 'shell_rate_net')
+    if quantity != 'column':
+        out.update(dict.fromkeys(names))
+        return out
+    R_cm = unit_km*1e5
+    S = {'up': col['up'], 'down': col['up'] - col['ur'], 'net': col['ur']}
+    dr = np.diff(np.asarray(r_edges, dtype=float))
+    for name, value in S.items():
+        out['flux_' + name] = value*atoms_per_packet/(np.asarray(volume)*R_cm**2)
+        out['shell_rate_' + name] = atoms_per_packet*value.sum(axis=(0, 1))/dr
+    out['flux_up_effective_packets'] = _effective(S['up'], col['upup'])
+    out['flux_down_effective_packets'] = _effective(S['down'], col['dndn'])
+    return out
+
+
 class ShellMap(ModelResult):
-    def __init__(self, inputs, params, *, context=None, device=0, **unsupported):
+    moments = False           # True: the pass over the rows also fills shell_moment_sums
+
+    def __init__(self, inputs, params, *, moments=False, context=None, device=0, **unsupported):
         for key in unsupported:
             if key in UNSUPPORTED:
                 raise NotImplementedError(UNSUPPORTED[key])
@@ -136,6 +203,9 @@ class ShellMap(ModelResult):
         self._column_sum = np.zeros(self.dims)
         self.packets = np.zeros(self.dims)
         self.shell_sums = np.zeros((2,) + tuple(self.dims) + (self.altitude[2] + 2, 2))
+        self.moments = bool(moments)
+        if self.moments:
+            self.shell_moment_sums = np.zeros((6,) + self.shell_sums.shape[1:])
         self._ctx, self._device = context, device
         self.counters = {}
         self._from_catalogue()
@@ -162,23 +232,33 @@ class ShellMap(ModelResult):
         self.altitude_axis_km = self.altitude_axis*self.unit_km
 
     def _from_catalogue(self):
-        """Every catalogued Output through k_shell.  Rows in HBM are read where they are, one
-        launch per run of adjacent slices of a store; other Outputs upload their five sample
-        columns.  The sums stay on the device while (aplanet, vrplanet) -- the g-values -- stay the
-        same, and are summed on the host across such groups."""
+        """Every catalogued Output through k_shell (with ``moments``: k_shell_moments).  Rows in HBM
+        are read where they are, one launch per run of adjacent slices of a store; other Outputs
+        upload their five (seven) sample columns.  The sums stay on the device while (aplanet,
+        vrplanet) -- the g-values -- stay the same, and are summed on the host across such groups."""
         def set_up(ctx, aplanet, vr_kms):
             ctx.shell_set(self._vr_kms(vr_kms)/self.unit_km, self.quantity, self.lon_edges, self.mu_edges,
                           self.r_edges[0], self.r_edges[-1], self.altitude[2],
                           self.g_tables(aplanet))
+            if self.moments:
+                ctx.shell_moments_enable()
 
         def collect(ctx):
             column, counts, sums = ctx.shell_download()
             self._column_sum += column
             self.packets += counts.astype(float)
             self.shell_sums += sums
+            if self.moments:
+                self.shell_moment_sums += ctx.shell_moments_download()
 
-        sample_pass(self, list(self.inputs._catalogue),
-                    lambda ctx, **samples: ctx.shell_accumulate(**samples), Output.IMAGE_COLS,
+        def accumulate(ctx, **samples):
+            if self.moments:
+                ctx.shell_moments_accumulate(**samples)
+            else:
+                ctx.shell_accumulate(**samples)
+
+        sample_pass(self, list(self.inputs._catalogue), accumulate,
+                    Output.MOMENT_COLS if self.moments else Output.IMAGE_COLS,
                     set_up, collect, **self._frame_pass())
 
     def finalize(self):
@@ -188,3 +268,8 @@ class ShellMap(ModelResult):
                                    self.solid_angle, self._volume, self.unit_km*1e5)
         for name, value in products.items():
             setattr(self, name, value)
+        if self.moments:
+            mass_kg = atomicmass(self.inputs.options.species).value * const.AMU
+            vars(self).update(shell_moments_from_sums(
+                self.shell_sums, self.shell_moment_sums, self.atoms_per_packet, self._volume,
+                self.r_edges, self.unit_km, mass_kg, self.quantity))

@@ -26,6 +26,7 @@
 #include "../../include/nexoclom_hip.h"
 #include "nxc_camera_check.hpp"
 #include "nxc_shell_check.hpp"
+#include "nxc_shell_moments_check.hpp"
 #include "nxc_cube_check.hpp"
 #include "nxc_ages_check.hpp"
 #include "nxc_density_ages_check.hpp"
@@ -476,6 +477,8 @@ struct nxc_handle {
     PixelSums shell_px;              // shell.replicas copies of the pair per cell, summed by the
                                      // download (its moments and cube stay off)
     Dev<double> d_shell_planes;      // [2][cells][nalt + 2] records: {w, w w} | {c, c c} (k_shell)
+    bool have_shell_mom = false;     // nxc_shell_moments_enable since the last nxc_shell_set
+    Dev<double> d_shell_mom;         // [6][cells][nalt + 2] records: the twelve sums (k_shell_moments)
 
     // LOSResultFitted: the pair list the line-of-sight passes fill (nxc_los_set_pairs); the fit's
     // per-spectrum data, its sample source and per-packet sums (nxc_fit_*)
@@ -1726,6 +1729,19 @@ int shell_run(nxc_handle *h, const Samples &s)
     });
 }
 
+// ShellMap(moments=True) over samples on the device (k_shell_moments)
+int shell_moments_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_shell_moments<T>, NXC_SHELL_BLOCK, h->shell_bytes, s.n, h->shell,
+                                  h->d_blob_shell, (int64_t)h->shell_bytes, s.n, s.col<T>(0),
+                                  s.col<T>(1), s.col<T>(2), s.col<T>(5), s.col<T>(3), s.col<T>(6),
+                                  s.col<T>(4), h->shell_px.image, h->d_shell_planes, h->d_shell_mom,
+                                  h->d_ctr);
+    });
+}
+
 // ModelImage(moments=True) over samples on the device (k_image_moments: atomics, never the tiles)
 int image_moments_run(nxc_handle *h, const Samples &s)
 {
@@ -1878,6 +1894,23 @@ const SampleConsumer CAMERA_SAMPLES = {[](const nxc_handle *h) { return h->have_
 const SampleConsumer SHELL_SAMPLES = {[](const nxc_handle *h) { return h->have_shell; },
                                       "nxc_shell_set has not been called",
                                       true, true, false, nullptr, shell_run, &nxc_handle::shell_px};
+// the shell moments' state is their enable, checked after nxc_shell_set's (shell_moments_state,
+// check_shell_moments_ready)
+const SampleConsumer SHELL_MOMENT_SAMPLES = {[](const nxc_handle *h) { return h->have_shell_mom; },
+                                             NXC_SHELL_MOMENTS_UNSET,
+                                             true, true, true, nullptr, shell_moments_run};
+ShellMomentsState shell_moments_state(const nxc_handle *h)
+{
+    if (!h) return {false, false, false, 0};
+    return {true, h->have_shell, h->have_shell_mom, h->shell.plane};
+}
+// the state checks in front of SHELL_MOMENT_SAMPLES' entries: the set is named first
+int shell_moments_ready(const nxc_handle *h)
+{
+    const ShellMomentsRefusal r = check_shell_moments_ready(shell_moments_state(h));
+    if (r.code == NXC_OK) return NXC_OK;
+    return guarded([&]() -> int { return fail(r.code, r.why); });
+}
 // the pixel moments' state is their enable, checked after the set's (pixel_moments_need_set)
 const SampleConsumer IMAGE_MOMENT_SAMPLES = {[](const nxc_handle *h) { return h->img.have_mom; },
                                              "nxc_image_moments_enable has not been called",
@@ -4002,6 +4035,8 @@ int nxc_shell_set(nxc_handle *h, const nxc_shell_desc *d)
     K.pairs = 2 * d->nlon * d->nlat;
 
     h->have_shell = false;
+    h->have_shell_mom = false;                 // the moments go with the map they were enabled on
+    if ((rc = h->d_shell_mom.release())) return rc;
     const size_t cells = (size_t)d->nlon * (size_t)d->nlat;
     const size_t pair_bytes = (size_t)K.replicas * 2 * cells * sizeof(double);
     const size_t plane_bytes = 2 * (size_t)K.plane * sizeof(double);
@@ -4064,6 +4099,60 @@ int nxc_shell_download(nxc_handle *h, double *column, uint64_t *counts, double *
         if (column) column[q] = c;
         if (counts) counts[q] = (uint64_t)n;
     }
+    return NXC_OK;
+    });
+}
+
+// ---- ShellMap moments ------------------------------------------------------------------------------
+int nxc_shell_moments_enable(nxc_handle *h, int on)
+{
+    return guarded([&]() -> int {
+    const ShellMomentsRefusal r = check_shell_moments_enable(shell_moments_state(h));
+    if (r.code != NXC_OK) return fail(r.code, r.why);
+    HIPCHK(hipSetDevice(h->device));
+    h->have_shell_mom = false;
+    int rc = h->d_shell_mom.release();
+    if (rc || !on) return rc;
+    const size_t bytes = shell_moments_bytes(h->shell.plane);
+    if ((rc = h->d_shell_mom.ensure(bytes))) return rc;
+    HIPCHK(hipMemsetAsync(h->d_shell_mom, 0, bytes, h->stream));
+    HIPCHK(stream_sync(h));
+    h->have_shell_mom = true;
+    return NXC_OK;
+    });
+}
+
+int nxc_shell_moments_accumulate(nxc_handle *h, int64_t p, const double *x, const double *y,
+                                 const double *z, const double *vx, const double *vy,
+                                 const double *vz, const double *frac)
+{
+    if (int rc = shell_moments_ready(h)) return rc;
+    return accumulate_columns<double>(h, SHELL_MOMENT_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_shell_moments_accumulate_f32(nxc_handle *h, int64_t p, const float *x, const float *y,
+                                     const float *z, const float *vx, const float *vy,
+                                     const float *vz, const float *frac)
+{
+    if (int rc = shell_moments_ready(h)) return rc;
+    return accumulate_columns<float>(h, SHELL_MOMENT_SAMPLES, p, x, y, z, vy, frac, vx, vz);
+}
+
+int nxc_shell_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    if (int rc = shell_moments_ready(h)) return rc;
+    return accumulate_rows(h, SHELL_MOMENT_SAMPLES, r, first, count);
+}
+
+int nxc_shell_moments_download(nxc_handle *h, double *sums)
+{
+    return guarded([&]() -> int {
+    const ShellMomentsRefusal r = check_shell_moments_download(shell_moments_state(h), sums);
+    if (r.code != NXC_OK) return fail(r.code, r.why);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(sums, h->d_shell_mom, shell_moments_bytes(h->shell.plane),
+                          hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
     return NXC_OK;
     });
 }

@@ -1310,6 +1310,93 @@ NXC_DEV void shell_located(const ShellK &S, const ImageK &G, const ImageRegs &R,
     add_record_pairs(has, rec, c, c * c, planes2 + S.plane);
 }
 
+// What the front of the shell moments' pass hands to its tail: did the sample file a weight
+// w != 0 under a record of the planes, which record, and the weight.
+struct ShellHit {
+    bool has;
+    int rec;
+    double w;
+};
+
+// shell_located, operation by operation, handing on what it filed: the front of k_shell_moments.
+// (A copy: with shell_located calling this and dropping the result, k_shell compiles to another
+// instruction order -- pixel_cube_add's reason.)
+NXC_DEV ShellHit shell_front(const ShellK &S, const ImageK &G, const ImageRegs &R, const PixelSample &s,
+                             double *__restrict__ acc2, double *__restrict__ planes2,
+                             unsigned long long &binned, unsigned long long &nonfinite)
+{
+    bool ok = false;
+    int cell = -1;
+    double w = 0.0, c = 0.0, r = 1.0;
+    if (s.has) {
+        const double radvel = s.vy + R.vrplanet;
+        const double r2 = (s.x * s.x + s.y * s.y) + s.z * s.z;
+        r = nxc_sqrt(r2);
+        const double mu = nxc_div(s.z, r);
+        double lon = atan2(s.x, -s.y);
+        if (lon < 0.0) lon = lon + 0x1.921fb54442d18p+2;
+        const int ix = bin_index(lon, R.xedges, R.nx, R.x_lo, R.x_hi, R.x_inv_step);
+        const int iz = bin_index(mu, R.zedges, R.nz, R.z_lo, R.z_hi, R.z_inv_step);
+        if (ix < 0 || iz < 0) {
+            if (!(__builtin_fabs(s.frac) <= 1.7976931348623157e308) || radvel != radvel) nonfinite++;
+        } else {
+            cell = ix * R.nz + iz;
+            double f = s.frac;
+            if (R.quantity != 0) f = sunlit(s.x, s.y, s.z) ? f : f * 0.0;
+            ok = image_weight(G, R, radvel, f, w);
+            if (ok) {
+                c = nxc_div(w, r2);
+                ok = __builtin_fabs(c) <= 1.7976931348623157e308;
+            }
+            if (!ok) nonfinite++;
+        }
+    }
+    binned += ok;
+    image_add_pairs(ok, cell, c, acc2);
+    const bool has = ok && w != 0.0;
+    const double t = (r - S.r_lo) * S.inv_dr;
+    int k = S.nalt + 1;
+    if (t < 0.0) k = 0;
+    else if (t < (double)S.nalt) k = 1 + (int)t;
+    const int rec = cell * (S.nalt + 2) + k;
+    add_record_pairs(has, rec, w, w * w, planes2);
+    add_record_pairs(has, rec, c, c * c, planes2 + S.plane);
+    return {has, rec, w};
+}
+
+// ---- ShellMap moments: the velocity of a filed sample in the local spherical basis ------------------
+// (include/nexoclom_hip.h, "ShellMap moments", holds the definition; the operations below are in its
+// order.)  A sample that shell_front filed under record `rec` with w != 0, and that is not exactly
+// on the polar axis (p2 != 0), adds twelve sums to the same record of six planes of mom2,
+// [6][cells][nalt + 2] 16-byte records S.plane doubles apart.  vx and vz are read only by a lane
+// with h.has (0 otherwise).  Non-finite velocities are not filtered.  Wave-cooperative: all 64 lanes
+// call it from uniform control flow; six requests per filed sample, none in a trip without one.
+template <typename T>
+NXC_DEV void shell_moments_add(const ShellK &S, const ShellHit &h, const PixelSample &s,
+                               const T *__restrict__ vx_col, const T *__restrict__ vz_col,
+                               double *__restrict__ mom2)
+{
+    double vx = 0.0, vz = 0.0;
+    if (h.has) { vx = (double)vx_col[s.i]; vz = (double)vz_col[s.i]; }
+    const double p2 = s.x * s.x + s.y * s.y;
+    const double r2 = p2 + s.z * s.z;
+    const double r = nxc_sqrt(r2), p = nxc_sqrt(p2);
+    const double hv = s.x * vx + s.y * s.vy;
+    const double v_r = nxc_div(hv + s.z * vz, r);
+    const double v_e = nxc_div(s.x * s.vy - s.y * vx, p);
+    const double v_n = nxc_div(p2 * vz - s.z * hv, r * p);
+    const bool has = h.has && p2 != 0.0;
+    const double u_r = h.w * v_r, u_e = h.w * v_e, u_n = h.w * v_n;
+    const double up = v_r > 0.0 ? u_r : 0.0;
+    const double dn = v_r < 0.0 ? -u_r : 0.0;
+    add_record_pairs(has, h.rec, u_r, u_e, mom2);
+    add_record_pairs(has, h.rec, u_n, u_r * v_r, mom2 + S.plane);
+    add_record_pairs(has, h.rec, u_e * v_e, u_n * v_n, mom2 + 2 * S.plane);
+    add_record_pairs(has, h.rec, u_r * v_e, u_r * v_n, mom2 + 3 * S.plane);
+    add_record_pairs(has, h.rec, u_e * v_n, up, mom2 + 4 * S.plane);
+    add_record_pairs(has, h.rec, up * up, dn * dn, mom2 + 5 * S.plane);
+}
+
 // Per-wave compaction queue between image_locate and image_weight: a ring of 128 located samples
 // {pixel, radial velocity, masked fraction} in LDS.  push() appends the lanes' samples in lane
 // order (ballot + prefix rank); once 64 are waiting, pop() hands one to every lane.  All calls

@@ -249,6 +249,9 @@ SIGNATURES = {
     'nxc_shell_set': _desc(nxc_shell_desc),
     **_sample_entries('nxc_shell_accumulate', 5),
     'nxc_shell_download': (_h, _dp, _u64p, _dp),
+    'nxc_shell_moments_enable': (_h, _int),
+    **_sample_entries('nxc_shell_moments_accumulate', 7),
+    'nxc_shell_moments_download': (_h, _dp),
     'nxc_los_profile_enable': (_h, _i64, _i64, _dbl, _dbl),
     **_sample_entries('nxc_los_profile_accumulate', 7, (C.POINTER(nxc_los_desc), _i64, _dp), True,
                       _los_results),
@@ -1436,6 +1439,25 @@ class Context:
         self._check(self.lib.nxc_shell_download(
             self._h, _p(column), counts.ctypes.data_as(_u64p), _p(sums)))
         return column, counts, sums
+
+    def shell_moments_enable(self, on=True):
+        """After ``shell_set``: allocate and zero the six planes of velocity sums per cell and
+        altitude record (``on`` false frees them; the next ``shell_set`` switches them off)."""
+        self._check(self.lib.nxc_shell_moments_enable(self._h, int(bool(on))))
+
+    def shell_moments_accumulate(self, x=None, y=None, z=None, vx=None, vy=None, vz=None,
+                                 frac=None, rows=None):
+        """Add samples to the shell map and to its velocity sums in one pass: seven host columns
+        (float32 ones go over as they are), or ``rows = (RowStore, first, count)``."""
+        self._accumulate('nxc_shell_moments_accumulate', (x, y, z, vx, vy, vz, frac), rows)
+
+    def shell_moments_download(self):
+        """(6, nlon, nlat, nalt + 2, 2) float64: the twelve sums of ShellMap.SHELL_MOMENT_COLUMNS
+        per cell and altitude record, plane by plane (include/nexoclom_hip.h, "ShellMap moments")."""
+        nlon, nlat, nalt = getattr(self, 'shell_shape', None) or (0, 0, 0)
+        sums = np.zeros((6, nlon, nlat, nalt + 2, 2))
+        self._check(self.lib.nxc_shell_moments_download(self._h, _p(sums)))
+        return sums
 
     # -- LOSResultFitted ----------------------------------------------------------------------
     def pairs_create(self, capacity):

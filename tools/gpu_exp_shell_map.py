@@ -16,6 +16,13 @@ over the same rows on a finer grid (720 x 360 x 32) and on coarser ones (72 x 36
 the requests are the same, the records they fall on are not.  No time is a gate.
 
     python tools/gpu_exp_shell_map.py [--out FILE] [N]          (default: 1e6)
+
+``--moments``: k_shell against k_shell_moments (ShellMap(moments=True)) instead, alternated in the
+same way over the same rows, on 72 x 36 x 32 and on 720 x 360 x 32: per grid and kernel median
+[min, max], the requests (k_shell_moments: six more per sample with w != 0), requests/s and the
+share of the atomic floor in the kernel's time.
+
+    python tools/gpu_exp_shell_map.py --moments [--out FILE] [N]
 """
 import contextlib
 import io
@@ -51,13 +58,78 @@ def lit_counts(launches, image):
     return count
 
 
+MOMENT_GRIDS = (('72,36', '0,4,32'), ('720,360', '0,4,32'))
+
+
+def main_moments(n, out_path):
+    """``--moments``: k_shell against k_shell_moments over the same resident rows, alternated, on
+    the two grids of the table above.  k_shell makes one request per binned sample and two more
+    for one with w != 0; k_shell_moments makes six more for those (the samples exactly on the polar
+    axis, which make none of the six, are not told apart: none is expected among float32 rows)."""
+    ctx = hip_api.Context(0)
+    inputs = Input(os.path.join(ROOT, 'nexoclom_amd', 'inputfiles', 'Na.mercury.bench.input'))
+    with contextlib.redirect_stdout(io.StringIO()):
+        inputs.run(n, seed=7, context=ctx)
+    launches = [span for _, span in sample_spans(inputs._catalogue, ctx)]
+    rows = sum(s[2] for s in launches)
+    lit = 0
+    for store, first, total in launches:
+        for at in range(first, first + total, CHUNK):
+            got, _ = store.download(at, min(CHUNK, first + total - at), index=False)
+            x, y, z = got[1], got[2], got[3]
+            lit += int(np.count_nonzero(((x*x + z*z > 1) | (y < 0)) & (x*x + y*y + z*z > 0)))
+    kernels = {'k_shell': lambda span: ctx.shell_accumulate(rows=span),
+               'k_shell_moments': lambda span: ctx.shell_moments_accumulate(rows=span)}
+    grids = {}
+    for dims, altitude in MOMENT_GRIDS:
+        params = dict(quantity='radiance', dims=dims, altitude=altitude)
+        with contextlib.redirect_stdout(io.StringIO()):
+            # the class checks the whole path once and leaves its description set and enabled
+            ShellMap(inputs, params, context=ctx, moments=True)
+        times = {name: [] for name in kernels}
+        binned = {}
+        for rnd in range(WARMUP + ROUNDS):
+            for name, accumulate in kernels.items():
+                ms, hit = 0.0, 0
+                for span in launches:
+                    accumulate(span)
+                    ms += ctx.last_kernel_ms()
+                    hit += ctx.counters()['samples_binned']
+                binned[name] = hit
+                if rnd >= WARMUP:
+                    times[name].append(ms)
+        med = {name: float(np.median(t)) for name, t in times.items()}
+        requests = {'k_shell': binned['k_shell'] + 2*lit,
+                    'k_shell_moments': binned['k_shell_moments'] + 8*lit}
+        grids[f'{dims} x {altitude.split(",")[2]}'] = {
+            'binned': binned, 'requests': requests,
+            **{name + '_ms': spread(t) for name, t in times.items()},
+            'moments_over_shell': round(med['k_shell_moments']/med['k_shell'], 3),
+            'requests_per_s': {name: round(requests[name]/med[name]*1e3, 0) for name in kernels},
+            'atomic_floor_ms': {name: round(requests[name]/ATOMIC_RPS*1e3, 3) for name in kernels},
+            'floor_share_of_kernel_time': {name: round(requests[name]/ATOMIC_RPS*1e3/med[name], 3)
+                                           for name in kernels}}
+    line = json.dumps({'npackets': n, 'rows': rows, 'launches': len(launches),
+                       'binned_nonzero': lit, 'warmup': WARMUP, 'rounds': ROUNDS, 'grids': grids})
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, 'a') as f:
+            f.write(line + '\n')
+    ctx.close()
+
+
 def main():
     args = sys.argv[1:]
     out_path = None
     if '--out' in args:
         out_path = args[args.index('--out') + 1]
         del args[args.index('--out'):args.index('--out') + 2]
+    moments = '--moments' in args
+    if moments:
+        args.remove('--moments')
     n = float(args[0]) if args else 1e6
+    if moments:
+        return main_moments(n, out_path)
     ctx = hip_api.Context(0)
     copy_bps = ctx.stream_copy_gbs()*1e9
     inputs = Input(os.path.join(ROOT, 'nexoclom_amd', 'inputfiles', 'Na.mercury.bench.input'))
