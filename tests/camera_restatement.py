@@ -3,7 +3,8 @@ written from that text, operation by operation, one IEEE rounding per operation.
 the library.
 
 ``camera_image(...)`` returns a ``CameraResult``: image, counts (nx, nz), the number of samples
-offered and binned, and two guards that say how far the inputs are from any decision the device
+offered and binned, ``nonfinite`` as steps 3, 6 and 8 count it, and two guards that say how far
+the inputs are from any decision the device
 could take differently by a rounding:
 
 * ``edge_guard``: the smallest distance of any tangent-plane coordinate (u, v of a sample in front
@@ -11,12 +12,20 @@ could take differently by a rounding:
 * ``margin_guard``: the smallest relative margin of ``dc > 0`` (all samples) and of the three
   occultation inequalities (binned samples): |dc| / r, |b| / (|o| r), |b - r2| / max(|b|, r2),
   |c2 - r2| / max(c2, r2).
+
+``camera_samples(...)`` takes the same arguments and returns the per-sample intermediates of the
+same arithmetic as a dict of arrays: dc, front, u, v, ix, iz (-1: not located), located, pix, b, r2,
+c2, b_r2 = b - r2 and c2_r2 = c2 - r2 (0 iff the two are equal), hidden, s = x*x + z*z, sunlit (all
+true for quantity 'column', which does not take the decision), w (the final weight of step 7) and
+keep (step 8 reached with a finite weight), and the count ``nonfinite``.
+tests/threshold_cases.py places samples on the thresholds with them.
 """
 from collections import namedtuple
 
 import numpy as np
 
-CameraResult = namedtuple('CameraResult', 'image counts samples binned edge_guard margin_guard')
+CameraResult = namedtuple('CameraResult', 'image counts samples binned edge_guard margin_guard '
+                                          'nonfinite')
 
 
 def _bins(value, edges):
@@ -38,8 +47,7 @@ def _edge_distance(value, edges):
     return float(np.min(near / np.maximum(np.abs(value), edges[-1])))
 
 
-def camera_image(x, y, z, vy, frac, o, C, uedges, vedges, vrplanet, pix_area_cm2, quantity,
-                 g_tables=()):
+def _camera(x, y, z, vy, frac, o, C, uedges, vedges, vrplanet, pix_area_cm2, quantity, g_tables):
     x, y, z, vy, frac = (np.asarray(c).astype(np.float64) for c in (x, y, z, vy, frac))
     o = np.asarray(o, dtype=np.float64)
     C = np.asarray(C, dtype=np.float64).reshape(9)
@@ -66,6 +74,7 @@ def camera_image(x, y, z, vy, frac, o, C, uedges, vedges, vrplanet, pix_area_cm2
         hidden = (b > 0) & (b < r2) & (c2 < r2)
         f = np.where(hidden, frac*0.0, frac)
         # 5
+        sunlit = np.ones(len(f), dtype=bool)
         if quantity == 'radiance':
             sunlit = (x*x + z*z > 1.0 + 2.0**-52) | (y < 0)
             f = np.where(sunlit, f, f*0.0)
@@ -85,7 +94,27 @@ def camera_image(x, y, z, vy, frac, o, C, uedges, vedges, vrplanet, pix_area_cm2
         foot = ((dc*dc)*dc)/r
         w = w/(foot*pix_area_cm2)
         # 8
+        outside_bad = ~located & (~np.isfinite(frac) | np.isnan(radvel))
         keep &= np.isfinite(w)
+    return dict(dc=dc, u=u, v=v, ix=ix, iz=iz, located=located, b=b, r2=r2, c2=c2, hidden=hidden,
+                b_r2=b - r2, c2_r2=c2 - r2,
+                sunlit=sunlit, s=x*x + z*z, w=w, keep=keep, pix=ix*nz + iz, front=front,
+                nonfinite=int(outside_bad.sum() + (located & ~keep).sum()))
+
+
+def camera_samples(x, y, z, vy, frac, o, C, uedges, vedges, vrplanet, pix_area_cm2, quantity,
+                   g_tables=()):
+    return _camera(x, y, z, vy, frac, o, C, uedges, vedges, vrplanet, pix_area_cm2, quantity, g_tables)
+
+
+def camera_image(x, y, z, vy, frac, o, C, uedges, vedges, vrplanet, pix_area_cm2, quantity,
+                 g_tables=()):
+    d = _camera(x, y, z, vy, frac, o, C, uedges, vedges, vrplanet, pix_area_cm2, quantity, g_tables)
+    o = np.asarray(o, dtype=np.float64)
+    uedges, vedges = np.asarray(uedges, dtype=np.float64), np.asarray(vedges, dtype=np.float64)
+    nx, nz = len(uedges) - 1, len(vedges) - 1
+    dc, u, v, ix, iz, located, b, r2, c2, w, keep, front = (d[k] for k in (
+        'dc', 'u', 'v', 'ix', 'iz', 'located', 'b', 'r2', 'c2', 'w', 'keep', 'front'))
     pix = (ix*nz + iz)[keep]
     image = np.bincount(pix, weights=w[keep], minlength=nx*nz).reshape(nx, nz)
     counts = np.bincount(pix, minlength=nx*nz).reshape(nx, nz)
@@ -100,4 +129,5 @@ def camera_image(x, y, z, vy, frac, o, C, uedges, vedges, vrplanet, pix_area_cm2
                         np.abs(bl - r2l)/np.maximum(np.abs(bl), r2l),
                         np.abs(c2l - r2l)/np.maximum(c2l, r2l)]
         margin_guard = min((float(np.min(m)) for m in margins if len(m)), default=np.inf)
-    return CameraResult(image, counts, len(x), int(keep.sum()), edge_guard, margin_guard)
+    return CameraResult(image, counts, len(dc), int(keep.sum()), edge_guard, margin_guard,
+                        d['nonfinite'])

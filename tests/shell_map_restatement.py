@@ -14,6 +14,12 @@ rounded; np.arctan2 decides a bin only).  It does not call the library.
   take the decision);
 * ``bin_guard``: the smallest distance of any t in [0, nalt] of a filed sample to an integer (inf
   when there is none): how far the nearest sample is from changing its altitude record.
+
+``shell_samples(...)`` takes the same arguments and returns the per-sample intermediates of the same
+arithmetic as a dict of arrays: lon, mu, r, r2, ix, iz (-1: outside), located, cell, s = x*x + z*z,
+sunlit (all true for quantity 'column'), w, c, keep (step 7 reached), filed (keep and w != 0), t and
+k, the altitude record of step 8 (NaN and -1 where nothing is filed), and the count ``nonfinite``.
+tests/threshold_cases.py places samples on the thresholds with them.
 """
 from collections import namedtuple
 
@@ -38,7 +44,13 @@ def _edge_distance(value, edge, length):
     return float(np.min(near))/length
 
 
-def shell_map(x, y, z, vy, frac, vrplanet, quantity, g_tables, nlon, nlat, r_lo, r_hi, nalt):
+def shell_samples(x, y, z, vy, frac, vrplanet, quantity, g_tables, nlon, nlat, r_lo, r_hi, nalt):
+    return shell_map(x, y, z, vy, frac, vrplanet, quantity, g_tables, nlon, nlat, r_lo, r_hi, nalt,
+                     samples=True)
+
+
+def shell_map(x, y, z, vy, frac, vrplanet, quantity, g_tables, nlon, nlat, r_lo, r_hi, nalt,
+              samples=False):
     x, y, z, vy, frac = (np.asarray(c).astype(np.float64) for c in (x, y, z, vy, frac))
     lon_edges, mu_edges = edges(nlon, nlat)
     nalt = int(nalt)
@@ -59,6 +71,7 @@ def shell_map(x, y, z, vy, frac, vrplanet, quantity, g_tables, nlon, nlat, r_lo,
         # 4
         f = frac
         s = x*x + z*z
+        sunlit = np.ones(len(f), dtype=bool)
         if quantity == 'radiance':
             sunlit = (s > 1.0 + 2.0**-52) | (y < 0)
             f = np.where(sunlit, f, f*0.0)
@@ -90,6 +103,12 @@ def shell_map(x, y, z, vy, frac, vrplanet, quantity, g_tables, nlon, nlat, r_lo,
         k[t < 0] = 0
         k[inside] = 1 + t[inside].astype(np.int64)
         rec = (ix*nlat + iz)[filed]*(nalt + 2) + k
+        if samples:
+            t_all, k_all = np.full(len(x), np.nan), np.full(len(x), -1, dtype=np.int64)
+            t_all[filed], k_all[filed] = t, k
+            return dict(lon=lon, mu=mu, r=r, r2=r2, t=t_all, ix=ix, iz=iz, located=located,
+                        cell=ix*nlat + iz, sunlit=sunlit, s=s, w=w, c=c, keep=keep, filed=filed, k=k_all,
+                        nonfinite=nonfinite)
         n = ncell*(nalt + 2)
         wf, cf = w[filed], c[filed]
         terms = [[wf, wf*wf], [cf, cf*cf]]

@@ -6,7 +6,9 @@ that close to a bin edge, no decision that close to its threshold).  That is a c
 inputs, far above the few-ulp differences possible between the device and NumPy, and it is what
 makes the exact comparison of packet counts legitimate.  Weighted pixels then agree to rtol 1e-11
 (the project's figure for images summed in another order; the camera weight adds about ten
-roundings), counts and counters exactly."""
+roundings), counts and counters exactly.  The thresholds themselves, which the guards keep
+away from, are covered by tests/test_gpu_camera_thresholds.py on the inputs of
+tests/threshold_cases.py."""
 import contextlib
 import io
 import os

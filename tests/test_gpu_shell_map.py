@@ -12,7 +12,9 @@ per (plane, cell, record, half), and on the downloaded result plane B summed ove
 cell must equal its column at rtol 1e-11.
 
 Every case's inputs come from CASES, so that the guards of all of them can be checked without a
-GPU: ``python -m tests.test_gpu_shell_map`` restates every case and prints its guards."""
+GPU: ``python -m tests.test_gpu_shell_map`` restates every case and prints its guards.  The
+thresholds themselves, which the guards keep away from, are covered by
+tests/test_gpu_shell_thresholds.py on the inputs of tests/threshold_cases.py."""
 import contextlib
 import io
 

@@ -13,7 +13,10 @@ of the guards, and the grid of their case has an odd number of longitude bins, w
 longitude pi in the middle of one.
 
 Every case's inputs come from CASES, so that the guards of all of them can be checked without a GPU:
-``python -m tests.test_gpu_shell_moments`` restates every case and prints its guards."""
+``python -m tests.test_gpu_shell_moments`` restates every case and prints its guards.  The
+thresholds themselves, which the guards keep away from, are covered by
+tests/test_gpu_shell_thresholds.py, which runs the inputs of tests/threshold_cases.py through
+shell_front as well."""
 import contextlib
 import io
 
