@@ -1041,6 +1041,63 @@ int nxc_shell_moments_accumulate_f32(nxc_handle *h, int64_t p, const float *x, c
 int nxc_shell_moments_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
 int nxc_shell_moments_download(nxc_handle *h, double *sums);
 
+/* ---- ShellMap ages: density and zenith column per age bin, for a time-varying source rate ----------
+ * EXTENSION -- nxc_shell_accumulate sums a record over all ages; this keeps the age ("Age cube" says
+ * what an age is and why the sums are linear in the source's history).  A block has na >= 1 bins over
+ * [a_lo, a_hi) seconds of age at the epoch t0, the run's endtime.  The host forms inv_da =
+ * na / (a_hi - a_lo) once in fp64.  Samples are time, x, y, z, vy, frac (time: the row's first column,
+ * widened when it is float32).  A sample goes through steps 1 to 7 of "ShellMap" unchanged: column and
+ * packets of its cell, the counters, `nonfinite` and the replicas of the pair array are what
+ * nxc_shell_accumulate makes them.  If step 8 files the sample (w != 0) under record rec =
+ * cell * (nalt + 2) + k, it adds to planes A and B exactly as there, and it forms the plane ka, fp64,
+ * one rounding per operation, no contraction:
+ *   age = t0 - (double)time
+ *   u   = (age - a_lo) * inv_da
+ *   ka = 0                if u < 0                              (younger than the range)
+ *   ka = 1 + (int)u       if 0 <= u < na                        (bin (int)u of the range)
+ *   ka = na + 1           otherwise: at or above a_hi, or time not a number
+ * -- the plane of "Age cube" -- and adds
+ *   {w, w*w}   to record rec * (na + 2) + ka of age plane A
+ *   {c, c*c}   to the same record of age plane B.
+ *   - Five atomic requests per filed sample at most, each made from uniform control flow; a trip of
+ *     a wave in which no lane files makes none of the four record requests.
+ *   - A sample with w == 0, or one that was not binned, adds nothing to the block, and its time is
+ *     not read.
+ *   - So the na + 2 planes of a record sum to that record of plane A (and of plane B), and age plane
+ *     B summed over a cell's nalt + 2 records is the cell's column per age, both up to the order of
+ *     the additions, which is not fixed.
+ * The block is [2][R][na + 2] 16-byte records, R = nlon*nlat*(nalt + 2), a buffer of its own on the
+ * handle.  The age block and the moments are independent states of a shell map.
+ *   nxc_shell_ages_enable            after nxc_shell_set: na >= 1 allocates and zeroes the block
+ *                                    (NXC_ERR_NOMEM when the two planes cannot be had), na == 0 frees
+ *                                    it; nxc_shell_set switches the block off again and frees it, as
+ *                                    it does the moments' planes.  NXC_ERR_ARG, before anything is
+ *                                    allocated or freed, for na < 0, t0, a_lo or a_hi not finite,
+ *                                    a_lo >= a_hi (or a width that is not finite), R*(na + 2) >= 2^31
+ *   nxc_shell_ages_accumulate[_f32]  adds p host samples -- six columns, time first -- to everything
+ *                                    nxc_shell_accumulate adds to AND to the block, in one pass
+ *   nxc_shell_ages_accumulate_rows   the same for rows [first, first + count) of a row store, whose
+ *                                    column 0 is the time
+ *   nxc_shell_ages_download          sums[2][R][na + 2][2]: age plane A = {w sum, w*w sum}, age plane
+ *                                    B = {c sum, c*c sum}; plane 0 below, 1..na the bins, na + 1 above
+ *   nxc_shell_ages_upload            the block replaced by sums of that layout
+ *   nxc_shell_ages_apply             K[na + 2][ne], out[2][ne][R][2]: per plane nxc_image_ages_apply
+ *                                    over the R records in place of the pixels, the same sums in the
+ *                                    same order, the same refusals
+ * NXC_ERR_STATE names the missing call (nxc_shell_set, then the enable), then NXC_ERR_ARG for p < 0, a
+ * null column with p > 0 or a null sums / out; p = 0 adds nothing but still zeroes the counters.
+ * nxc_shell_accumulate*, nxc_shell_moments_* and nxc_shell_download serve unchanged beside them and
+ * never touch the block. */
+int nxc_shell_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi);
+int nxc_shell_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
+                              const double *y, const double *z, const double *vy, const double *frac);
+int nxc_shell_ages_accumulate_f32(nxc_handle *h, int64_t p, const float *time, const float *x,
+                                  const float *y, const float *z, const float *vy, const float *frac);
+int nxc_shell_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count);
+int nxc_shell_ages_download(nxc_handle *h, double *sums);
+int nxc_shell_ages_upload(nxc_handle *h, const double *sums);
+int nxc_shell_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out);
+
 /* ---- Line-of-sight profile: radiance per Doppler bin along each line of sight ----------------------
  * EXTENSION -- nxc_los_accumulate gives one radiance per spectrum; the profile keeps the line: per
  * spectrum nv >= 1 bins over [v_lo, v_hi), in the rows' velocity unit (planet radii per second), and

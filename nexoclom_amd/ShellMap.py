@@ -42,6 +42,21 @@ shell the return rate to the surface (``shell_moments_from_sums``).  For 'radian
 emission-weighted and the fluxes and rates are None.  With ``origin`` a moon the velocities are
 relative to the moon.
 
+``ShellMap(inputs, params, ages=(a_lo_s, a_hi_s, nbins))`` (catalogued constant-step Outputs only):
+the same single pass (k_shell_ages; "ShellMap ages" in the header) also files both records of every
+sample under its age, options.endtime minus the row's t_remaining: ``nbins`` bins over [a_lo_s,
+a_hi_s) seconds.  Then also (``shell_ages_from_sums``): shell_age_sums (2, nlon, nlat, nalt + 2,
+nbins + 2, 2; the unscaled block), age_density (nlon, nlat, nalt, nbins) with age_density_below and
+age_density_above (the ages outside the range), age_column_profile (nlon, nlat, nalt, nbins),
+age_column (nlon, nlat, nbins) with age_column_below and age_column_above, age_edges, age_axis [s],
+age_density_effective_packets and age_column_effective_packets: age_density.sum(-1) +
+age_density_below + age_density_above is density and age_column.sum(-1) + age_column_below +
+age_column_above is column, up to the order of the additions.  ``transient(epochs, history)``
+contracts the block with the response matrix of a source history (transient.py) on the device: the
+density, the zenith column and the content inside the altitude range per epoch (a
+transient.TransientShells).  It refuses ``moments=True`` (make two objects); a moon's ``origin`` is
+allowed.
+
 Not supported, and refused: streaming (``npackets=``), shared runs (``cp=`` / ``shard=``).
 """
 import numpy as np
@@ -53,6 +68,8 @@ from .Output import Output
 from .atomicdata import atomicmass
 from .catalogue import sample_pass
 from .input_classes import InputError
+from .transient import (TransientShells, parse_ages, refuse_ages_of, refuse_ages_with,
+                        response_matrix)
 
 MAX_DIM = 8192
 UNSUPPORTED = {
@@ -186,10 +203,56 @@ def shell_moments_from_sums(shell_sums, moment_sums, atoms_per_packet, volume, r
     return out
 
 
+MAX_AGE_RECORDS = 2**31           # the device's record index is an int
+
+
+def shell_ages_from_sums(shell_age_sums, atoms_per_packet, solid_angle, volume, R_cm, a_lo, a_hi):
+    """What ``ShellMap(ages=...)`` publishes, from ``shell_age_sums`` (2, nlon, nlat, nalt + 2,
+    nbins + 2, 2) = {sum w, sum w w} (age plane A) and {sum c, sum c c}, c = w/r^2 (age plane B) per
+    cell, altitude record and age plane (plane 0 younger than the range, 1..nbins the bins,
+    nbins + 1 at or above it); ``volume`` (nalt) in R^3, ``R_cm`` the planet's radius.  Scaled as
+    ``shell_from_sums`` scales density and column:
+      age_density (nlon, nlat, nalt, nbins), age_density_below, age_density_above (nlon, nlat, nalt)
+      age_column_profile (nlon, nlat, nalt, nbins)
+      age_column (nlon, nlat, nbins), age_column_below, age_column_above (nlon, nlat): plane B summed
+                 over all nalt + 2 records of a cell, from record 0 upwards
+      age_edges, age_axis [s]
+      age_density_effective_packets (as age_density), age_column_effective_packets (as age_column):
+                 (sum)^2 / sum of squares, 0 where empty"""
+    sums = np.asarray(shell_age_sums, dtype=float)
+    A, B = sums[0], sums[1]
+    nbins = sums.shape[-2] - 2
+    per_area = atoms_per_packet/(solid_angle*R_cm**2)
+    volume_cm3 = np.asarray(volume)*R_cm**3               # density: sum * atoms_per_packet / V, as
+                                                          # shell_from_sums forms it
+    cell = np.zeros(B.shape[:2] + B.shape[3:])           # (nlon, nlat, nbins + 2, 2)
+    for k in range(B.shape[2]):
+        cell = cell + B[:, :, k]
+    edges = a_lo + np.arange(nbins + 1)*(a_hi - a_lo)/nbins
+    return {'age_density': A[:, :, 1:-1, 1:-1, 0]*atoms_per_packet/volume_cm3[:, None],
+            'age_density_below': A[:, :, 1:-1, 0, 0]*atoms_per_packet/volume_cm3,
+            'age_density_above': A[:, :, 1:-1, -1, 0]*atoms_per_packet/volume_cm3,
+            'age_column_profile': B[:, :, 1:-1, 1:-1, 0]*per_area,
+            'age_column': cell[:, :, 1:-1, 0]*per_area,
+            'age_column_below': cell[:, :, 0, 0]*per_area,
+            'age_column_above': cell[:, :, -1, 0]*per_area,
+            'age_edges': edges,
+            'age_axis': (edges[:-1] + edges[1:])/2,
+            'age_density_effective_packets': _effective(A[:, :, 1:-1, 1:-1, 0],
+                                                        A[:, :, 1:-1, 1:-1, 1]),
+            'age_column_effective_packets': _effective(cell[:, :, 1:-1, 0], cell[:, :, 1:-1, 1])}
+
+
 class ShellMap(ModelResult):
     moments = False           # True: the pass over the rows also fills shell_moment_sums
 
-    def __init__(self, inputs, params, *, moments=False, context=None, device=0, **unsupported):
+    def __init__(self, inputs, params, *, moments=False, ages=None, context=None, device=0,
+                 **unsupported):
+        if ages is not None:
+            refuse_ages_with(moments=moments,
+                             **{key: unsupported.get(key) for key in ('npackets', 'shard', 'cp')})
+            ages = parse_ages(ages)
+            refuse_ages_of(inputs)
         for key in unsupported:
             if key in UNSUPPORTED:
                 raise NotImplementedError(UNSUPPORTED[key])
@@ -206,6 +269,15 @@ class ShellMap(ModelResult):
         self.moments = bool(moments)
         if self.moments:
             self.shell_moment_sums = np.zeros((6,) + self.shell_sums.shape[1:])
+        self.ages = ages
+        if self.ages is not None:
+            records = self.dims[0]*self.dims[1]*(self.altitude[2] + 2)
+            if records*(self.ages[2] + 2) >= MAX_AGE_RECORDS:
+                raise ValueError('ages=: nlon*nlat*(altitude bins + 2)*(nbins + 2) must stay below '
+                                 '2^31')
+            self.shell_age_sums = np.zeros((2,) + tuple(self.dims) +
+                                           (self.altitude[2] + 2, self.ages[2] + 2, 2))
+            self._ages_token = object()
         self._ctx, self._device = context, device
         self.counters = {}
         self._from_catalogue()
@@ -232,9 +304,9 @@ class ShellMap(ModelResult):
         self.altitude_axis_km = self.altitude_axis*self.unit_km
 
     def _from_catalogue(self):
-        """Every catalogued Output through k_shell (with ``moments``: k_shell_moments).  Rows in HBM
-        are read where they are, one launch per run of adjacent slices of a store; other Outputs
-        upload their five (seven) sample columns.  The sums stay on the device while (aplanet,
+        """Every catalogued Output through k_shell (with ``moments``: k_shell_moments, with ``ages``:
+        k_shell_ages).  Rows in HBM are read where they are, one launch per run of adjacent slices
+        of a store; other Outputs upload their five (seven, six) sample columns.  The sums stay on the device while (aplanet,
         vrplanet) -- the g-values -- stay the same, and are summed on the host across such groups."""
         def set_up(ctx, aplanet, vr_kms):
             ctx.shell_set(self._vr_kms(vr_kms)/self.unit_km, self.quantity, self.lon_edges, self.mu_edges,
@@ -242,6 +314,10 @@ class ShellMap(ModelResult):
                           self.g_tables(aplanet))
             if self.moments:
                 ctx.shell_moments_enable()
+            if self.ages is not None:
+                self._ages_setup = lambda ctx: set_up(ctx, aplanet, vr_kms)
+                a_lo, a_hi, nbins = self.ages
+                ctx.shell_ages_enable(nbins, float(self.inputs.options.endtime.value), a_lo, a_hi)
 
         def collect(ctx):
             column, counts, sums = ctx.shell_download()
@@ -250,15 +326,21 @@ class ShellMap(ModelResult):
             self.shell_sums += sums
             if self.moments:
                 self.shell_moment_sums += ctx.shell_moments_download()
+            if self.ages is not None:
+                self.shell_age_sums += ctx.shell_ages_download()
+                self._collected_ages(ctx, 'shell')
 
         def accumulate(ctx, **samples):
             if self.moments:
                 ctx.shell_moments_accumulate(**samples)
+            elif self.ages is not None:
+                ctx.shell_ages_accumulate(**samples)
             else:
                 ctx.shell_accumulate(**samples)
 
         sample_pass(self, list(self.inputs._catalogue), accumulate,
-                    Output.MOMENT_COLS if self.moments else Output.IMAGE_COLS,
+                    Output.MOMENT_COLS if self.moments else
+                    Output.AGE_COLS if self.ages is not None else Output.IMAGE_COLS,
                     set_up, collect, **self._frame_pass())
 
     def finalize(self):
@@ -273,3 +355,32 @@ class ShellMap(ModelResult):
             vars(self).update(shell_moments_from_sums(
                 self.shell_sums, self.shell_moment_sums, self.atoms_per_packet, self._volume,
                 self.r_edges, self.unit_km, mass_kg, self.quantity))
+        if self.ages is not None:
+            vars(self).update(shell_ages_from_sums(
+                self.shell_age_sums, self.atoms_per_packet, self.solid_angle, self._volume,
+                self.unit_km*1e5, *self.ages[:2]))
+
+    def transient(self, epochs, history):
+        """The shell map at ``epochs`` [s] for a source whose rate relative to the nominal one was
+        ``history = (t_nodes_s, rate_nodes)`` (transient.response_matrix): a TransientShells with
+        epochs, kernel (nbins + 2, E), density (E, nlon, nlat, nalt), column_profile, column (E,
+        nlon, nlat), their effective packets and content (E,).  The age block is contracted where
+        it is (k_ages_apply) while this object's sums are the ones resident in its context; sums
+        that were added on the host (several stretches of g-values) or that another product has
+        replaced since are set up again and uploaded once."""
+        if self.ages is None:
+            raise ValueError('transient() needs an object built with ages=(a_lo_s, a_hi_s, nbins)')
+        if not hasattr(self, 'age_edges'):
+            raise ValueError('transient() needs the finalized object (finalize())')
+        K = response_matrix(self.age_edges, epochs, history)
+        if self._ages_setup is None:                       # nothing was ever binned
+            sums = np.zeros((2, K.shape[1]) + self.shell_age_sums.shape[1:4] + (2,))
+        else:
+            ctx = self.context()
+            if ctx.ages_owner.get('shell') is not self._ages_token:
+                self._ages_setup(ctx)
+                ctx.shell_ages_upload(self.shell_age_sums)
+                ctx.ages_owner['shell'] = self._ages_token
+            sums = ctx.shell_ages_apply(K)
+        return TransientShells(epochs, K, sums, self.atoms_per_packet, self.solid_angle,
+                               self._volume, self.unit_km*1e5, self.quantity)

@@ -27,6 +27,7 @@
 #include "nxc_camera_check.hpp"
 #include "nxc_shell_check.hpp"
 #include "nxc_shell_moments_check.hpp"
+#include "nxc_shell_ages_check.hpp"
 #include "nxc_cube_check.hpp"
 #include "nxc_ages_check.hpp"
 #include "nxc_density_ages_check.hpp"
@@ -479,6 +480,9 @@ struct nxc_handle {
     Dev<double> d_shell_planes;      // [2][cells][nalt + 2] records: {w, w w} | {c, c c} (k_shell)
     bool have_shell_mom = false;     // nxc_shell_moments_enable since the last nxc_shell_set
     Dev<double> d_shell_mom;         // [6][cells][nalt + 2] records: the twelve sums (k_shell_moments)
+    bool have_shell_ages = false;    // nxc_shell_ages_enable since the last nxc_shell_set
+    AgeK shell_ageK{};
+    Dev<double> d_shell_ages;        // [2][cells (nalt + 2)][na + 2] records: {w, w w} | {c, c c} (k_shell_ages)
 
     // LOSResultFitted: the pair list the line-of-sight passes fill (nxc_los_set_pairs); the fit's
     // per-spectrum data, its sample source and per-packet sums (nxc_fit_*)
@@ -1742,6 +1746,19 @@ int shell_moments_run(nxc_handle *h, const Samples &s)
     });
 }
 
+// ShellMap(ages=...) over samples on the device (k_shell_ages: time, x, y, z, vy, frac)
+int shell_ages_run(nxc_handle *h, const Samples &s)
+{
+    return with_sample_types(s, [&](auto t, auto) -> int {
+        using T = decltype(t);
+        return launch_sample_pass(h, k_shell_ages<T>, NXC_SHELL_BLOCK, h->shell_bytes, s.n, h->shell,
+                                  h->shell_ageK, h->d_blob_shell, (int64_t)h->shell_bytes, s.n,
+                                  s.col<T>(7), s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3),
+                                  s.col<T>(4), h->shell_px.image, h->d_shell_planes, h->d_shell_ages,
+                                  h->d_ctr);
+    });
+}
+
 // ModelImage(moments=True) over samples on the device (k_image_moments: atomics, never the tiles)
 int image_moments_run(nxc_handle *h, const Samples &s)
 {
@@ -1910,6 +1927,37 @@ int shell_moments_ready(const nxc_handle *h)
     const ShellMomentsRefusal r = check_shell_moments_ready(shell_moments_state(h));
     if (r.code == NXC_OK) return NXC_OK;
     return guarded([&]() -> int { return fail(r.code, r.why); });
+}
+// the shell ages' state is their enable too, checked after nxc_shell_set's (shell_ages_need_set);
+// the pass reads the time column and neither vx nor vz
+const SampleConsumer SHELL_AGES_SAMPLES = {[](const nxc_handle *h) { return h->have_shell_ages; },
+                                           "nxc_shell_ages_enable has not been called",
+                                           true, true, false, nullptr, shell_ages_run, nullptr, true};
+// records of one plane of the shell map: cells (nalt + 2)
+int64_t shell_records(const nxc_handle *h) { return h->shell.plane / 2; }
+
+// the shell ages off, their records back to the device
+int shell_ages_free(nxc_handle *h)
+{
+    h->have_shell_ages = false;
+    return h->d_shell_ages.release();
+}
+
+// the state check in front of SHELL_AGES_SAMPLES' entries: nxc_shell_set is the missing call
+int shell_ages_need_set(const nxc_handle *h)
+{
+    if (h && h->have_shell) return NXC_OK;
+    return guarded([&]() -> int { return fail(NXC_ERR_STATE, SHELL_SAMPLES.unset); });
+}
+
+// the state checks of the block's download, upload and apply (nxc_shell_set is named first), and
+// their null check
+int shell_ages_ready(const nxc_handle *h, const void *host)
+{
+    if (!h || !h->have_shell) return fail(NXC_ERR_STATE, SHELL_SAMPLES.unset);
+    if (!h->have_shell_ages) return fail(NXC_ERR_STATE, SHELL_AGES_SAMPLES.unset);
+    if (!host) return fail(NXC_ERR_ARG, "bad arguments");
+    return NXC_OK;
 }
 // the pixel moments' state is their enable, checked after the set's (pixel_moments_need_set)
 const SampleConsumer IMAGE_MOMENT_SAMPLES = {[](const nxc_handle *h) { return h->img.have_mom; },
@@ -4037,6 +4085,7 @@ int nxc_shell_set(nxc_handle *h, const nxc_shell_desc *d)
     h->have_shell = false;
     h->have_shell_mom = false;                 // the moments go with the map they were enabled on
     if ((rc = h->d_shell_mom.release())) return rc;
+    if ((rc = shell_ages_free(h))) return rc;  // likewise the ages
     const size_t cells = (size_t)d->nlon * (size_t)d->nlat;
     const size_t pair_bytes = (size_t)K.replicas * 2 * cells * sizeof(double);
     const size_t plane_bytes = 2 * (size_t)K.plane * sizeof(double);
@@ -4154,6 +4203,85 @@ int nxc_shell_moments_download(nxc_handle *h, double *sums)
                           hipMemcpyDeviceToHost, h->stream));
     HIPCHK(stream_sync(h));
     return NXC_OK;
+    });
+}
+
+// ---- ShellMap ages ---------------------------------------------------------------------------------
+int nxc_shell_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi)
+{
+    return guarded([&]() -> int {
+    if (!h || !h->have_shell) return fail(NXC_ERR_STATE, SHELL_SAMPLES.unset);
+    if (na != 0) {     // before anything is freed or allocated
+        const std::string why = check_shell_ages_args(shell_records(h), na, t0, a_lo, a_hi);
+        if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
+    }
+    HIPCHK(hipSetDevice(h->device));
+    int rc = shell_ages_free(h);
+    if (rc || na == 0) return rc;
+    h->shell_ageK = AgeK{(int)na, t0, a_lo, ages_inv_da(na, a_lo, a_hi)};
+    const size_t bytes = shell_ages_bytes(shell_records(h), na);
+    if ((rc = h->d_shell_ages.ensure(bytes))) return rc;
+    HIPCHK(hipMemsetAsync(h->d_shell_ages, 0, bytes, h->stream));
+    HIPCHK(stream_sync(h));
+    h->have_shell_ages = true;
+    return NXC_OK;
+    });
+}
+
+int nxc_shell_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
+                              const double *y, const double *z, const double *vy, const double *frac)
+{
+    if (int rc = shell_ages_need_set(h)) return rc;
+    return accumulate_columns<double>(h, SHELL_AGES_SAMPLES, p, x, y, z, vy, frac, nullptr, nullptr, time);
+}
+
+int nxc_shell_ages_accumulate_f32(nxc_handle *h, int64_t p, const float *time, const float *x,
+                                  const float *y, const float *z, const float *vy, const float *frac)
+{
+    if (int rc = shell_ages_need_set(h)) return rc;
+    return accumulate_columns<float>(h, SHELL_AGES_SAMPLES, p, x, y, z, vy, frac, nullptr, nullptr, time);
+}
+
+int nxc_shell_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
+{
+    if (int rc = shell_ages_need_set(h)) return rc;
+    return accumulate_rows(h, SHELL_AGES_SAMPLES, r, first, count);
+}
+
+int nxc_shell_ages_download(nxc_handle *h, double *sums)
+{
+    return guarded([&]() -> int {
+    if (int rc = shell_ages_ready(h, sums)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(sums, h->d_shell_ages, shell_ages_bytes(shell_records(h), h->shell_ageK.na),
+                          hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+    });
+}
+
+int nxc_shell_ages_upload(nxc_handle *h, const double *sums)
+{
+    return guarded([&]() -> int {
+    if (int rc = shell_ages_ready(h, sums)) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(h->d_shell_ages, sums, shell_ages_bytes(shell_records(h), h->shell_ageK.na),
+                          hipMemcpyHostToDevice, h->stream));
+    HIPCHK(stream_sync(h));
+    return NXC_OK;
+    });
+}
+
+int nxc_shell_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out)
+{
+    return guarded([&]() -> int {
+    if (int rc = shell_ages_ready(h, out)) return rc;
+    // age plane A, then age plane B: each the image's contraction over the R records
+    const size_t R = (size_t)shell_records(h);
+    const int64_t planes = (int64_t)h->shell_ageK.na + 2;
+    if (int rc = ages_block_apply(h, R, planes, h->d_shell_ages.get(), ne, K, out)) return rc;
+    return ages_block_apply(h, R, planes, h->d_shell_ages.get() + R * (size_t)planes * 2, ne, K,
+                            out + (size_t)ne * R * 2);
     });
 }
 

@@ -1397,6 +1397,83 @@ NXC_DEV void shell_moments_add(const ShellK &S, const ShellHit &h, const PixelSa
     add_record_pairs(has, h.rec, up * up, dn * dn, mom2 + 5 * S.plane);
 }
 
+// ---- ShellMap ages: a filed sample's two records under its age --------------------------------------
+// (include/nexoclom_hip.h, "ShellMap ages", holds the definition.)  What the front of the ages' pass
+// hands to its tail: ShellHit and the column term c = w / r2 of plane B.
+struct ShellAgesHit {
+    bool has;
+    int rec;
+    double w, c;
+};
+
+// shell_located, operation by operation, handing on what it filed: the front of k_shell_ages.  (A
+// copy of its own, for shell_front's reason: ShellHit with a fourth member, or shell_front calling
+// this, would change k_shell_moments' instruction stream.)
+NXC_DEV ShellAgesHit shell_ages_front(const ShellK &S, const ImageK &G, const ImageRegs &R,
+                                      const PixelSample &s, double *__restrict__ acc2,
+                                      double *__restrict__ planes2, unsigned long long &binned,
+                                      unsigned long long &nonfinite)
+{
+    bool ok = false;
+    int cell = -1;
+    double w = 0.0, c = 0.0, r = 1.0;
+    if (s.has) {
+        const double radvel = s.vy + R.vrplanet;
+        const double r2 = (s.x * s.x + s.y * s.y) + s.z * s.z;
+        r = nxc_sqrt(r2);
+        const double mu = nxc_div(s.z, r);
+        double lon = atan2(s.x, -s.y);
+        if (lon < 0.0) lon = lon + 0x1.921fb54442d18p+2;
+        const int ix = bin_index(lon, R.xedges, R.nx, R.x_lo, R.x_hi, R.x_inv_step);
+        const int iz = bin_index(mu, R.zedges, R.nz, R.z_lo, R.z_hi, R.z_inv_step);
+        if (ix < 0 || iz < 0) {
+            if (!(__builtin_fabs(s.frac) <= 1.7976931348623157e308) || radvel != radvel) nonfinite++;
+        } else {
+            cell = ix * R.nz + iz;
+            double f = s.frac;
+            if (R.quantity != 0) f = sunlit(s.x, s.y, s.z) ? f : f * 0.0;
+            ok = image_weight(G, R, radvel, f, w);
+            if (ok) {
+                c = nxc_div(w, r2);
+                ok = __builtin_fabs(c) <= 1.7976931348623157e308;
+            }
+            if (!ok) nonfinite++;
+        }
+    }
+    binned += ok;
+    image_add_pairs(ok, cell, c, acc2);
+    const bool has = ok && w != 0.0;
+    const double t = (r - S.r_lo) * S.inv_dr;
+    int k = S.nalt + 1;
+    if (t < 0.0) k = 0;
+    else if (t < (double)S.nalt) k = 1 + (int)t;
+    const int rec = cell * (S.nalt + 2) + k;
+    add_record_pairs(has, rec, w, w * w, planes2);
+    add_record_pairs(has, rec, c, c * c, planes2 + S.plane);
+    return {has, rec, w, c};
+}
+
+// A sample that shell_ages_front filed under record `rec` adds {w, w w} to record
+// rec (na + 2) + ka of age plane A and {c, c c} to the same record of age plane B, S.plane (na + 2)
+// doubles further on; ka is pixel_ages_add's plane of the row's time, which only a lane with h.has
+// reads.  The record index stays below 2^31 (check_shell_ages_args); a lane without h.has forms
+// none.  Wave-cooperative: all 64 lanes call it from uniform control flow; two requests per filed
+// sample, none in a trip without one.
+template <typename T>
+NXC_DEV void shell_ages_add(const ShellK &S, const AgeK &Q, const ShellAgesHit &h, int64_t i,
+                            const T *__restrict__ time_col, double *__restrict__ ages2)
+{
+    double age = 0.0;
+    if (h.has) age = Q.t0 - (double)time_col[i];
+    const double u = (age - Q.a_lo) * Q.inv_da;
+    int ka = Q.na + 1;
+    if (u < 0.0) ka = 0;
+    else if (u < (double)Q.na) ka = 1 + (int)u;
+    const int rec = h.has ? h.rec * (Q.na + 2) + ka : 0;
+    add_record_pairs(h.has, rec, h.w, h.w * h.w, ages2);
+    add_record_pairs(h.has, rec, h.c, h.c * h.c, ages2 + S.plane * (int64_t)(Q.na + 2));
+}
+
 // Per-wave compaction queue between image_locate and image_weight: a ring of 128 located samples
 // {pixel, radial velocity, masked fraction} in LDS.  push() appends the lanes' samples in lane
 // order (ballot + prefix rank); once 64 are waiting, pop() hands one to every lane.  All calls

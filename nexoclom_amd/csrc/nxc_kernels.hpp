@@ -18,7 +18,8 @@
 //   k_image_ages, k_camera_ages         either pass with the weight filed per pixel and age bin
 //   k_shell         the same samples by solar-fixed longitude, sin(latitude) and altitude (ShellMap)
 //   k_shell_moments k_shell's pass with twelve velocity sums per cell and altitude record
-//                   (all ten: pixel_pass -- staging, loop, loads, counters -- with a lambda each)
+//   k_shell_ages    k_shell's pass with both records of a sample filed under its age bin as well
+//                   (all eleven: pixel_pass -- staging, loop, loads, counters -- with a lambda each)
 //   k_density, k_density_moments, k_density_spectrum, k_density_ages
 //                   stored samples within dr of query points
 //                   (density_walk -- loop, cull, candidate walk, membership -- with a load and a
@@ -959,7 +960,7 @@ k_var(ForceK F, const unsigned char *__restrict__ blob, int64_t stage_bytes, int
 }
 
 // ---------------------------------------------------------------------------------------------
-// The pass of the ten pixel kernels over stored samples: the tables staged into LDS, a grid-stride
+// The pass of the eleven pixel kernels over stored samples: the tables staged into LDS, a grid-stride
 // loop that hands `sample` one row per lane and trip (wave-cooperative: every lane calls it, with
 // or without a row), and the three counters flushed once per workgroup.  `sample` is the kernel's
 // own: (G, IR, PixelSample, binned, nonfinite) -> what the row adds.
@@ -3257,6 +3258,30 @@ k_shell_moments(ShellK S, const unsigned char *__restrict__ blob, int64_t stage_
                    unsigned long long &binned, unsigned long long &nonfinite) {
                    const ShellHit h = shell_front(S, G, IR, s, own2, planes2, binned, nonfinite);
                    shell_moments_add(S, h, s, vx, vz, mom2);
+               });
+}
+
+// ShellMap(ages=...): k_shell's pass over six columns, time first; a sample filed under its record
+// with w != 0 also adds {w, w w} and {c, c c} to that record's plane of its age in the two planes
+// of ages2, [2][cells (nalt + 2)][na + 2] 16-byte records (shell_ages_front, shell_ages_add): at
+// most five atomic requests per binned sample.  The time column is read by the lanes that file a
+// weight.  The age scalars travel as a kernel argument of their own; block size, LDS blob and the
+// copies of the pair array are k_shell's.
+template <typename T>
+__global__ void __launch_bounds__(NXC_SHELL_BLOCK)
+k_shell_ages(ShellK S, AgeK Q, const unsigned char *__restrict__ blob, int64_t stage_bytes, int64_t p,
+             const T *__restrict__ time, const T *__restrict__ x, const T *__restrict__ y,
+             const T *__restrict__ z, const T *__restrict__ vy, const T *__restrict__ frac,
+             double *__restrict__ acc2, double *__restrict__ planes2, double *__restrict__ ages2,
+             DevCounters *__restrict__ ctr)
+{
+    double *__restrict__ own2 = acc2 + (int64_t)(blockIdx.x % (unsigned)S.replicas) * S.pairs;
+    pixel_pass(blob, stage_bytes, p, x, y, z, vy, frac, ctr, (int64_t)blockIdx.x * blockDim.x,
+               (int64_t)gridDim.x * blockDim.x,
+               [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
+                   unsigned long long &binned, unsigned long long &nonfinite) {
+                   const ShellAgesHit h = shell_ages_front(S, G, IR, s, own2, planes2, binned, nonfinite);
+                   shell_ages_add(S, Q, h, s.i, time, ages2);
                });
 }
 

@@ -252,6 +252,11 @@ SIGNATURES = {
     'nxc_shell_moments_enable': (_h, _int),
     **_sample_entries('nxc_shell_moments_accumulate', 7),
     'nxc_shell_moments_download': (_h, _dp),
+    'nxc_shell_ages_enable': (_h, _i64, _dbl, _dbl, _dbl),
+    **_sample_entries('nxc_shell_ages_accumulate', 6),
+    'nxc_shell_ages_download': (_h, _dp),
+    'nxc_shell_ages_upload': (_h, _dp),
+    'nxc_shell_ages_apply': (_h, _i64, _dp, _dp),
     'nxc_los_profile_enable': (_h, _i64, _i64, _dbl, _dbl),
     **_sample_entries('nxc_los_profile_accumulate', 7, (C.POINTER(nxc_los_desc), _i64, _dp), True,
                       _los_results),
@@ -1422,6 +1427,8 @@ class Context:
             self._fill_lines(d, g_tables, keep)
         self._check(self.lib.nxc_shell_set(self._h, C.byref(d)))
         self.shell_shape = (int(d.nlon), int(d.nlat), int(d.nalt))
+        self._shell_ages_na = 0                  # the set switches the age block off
+        self.ages_owner.pop('shell', None)
 
     def shell_accumulate(self, x=None, y=None, z=None, vy=None, frac=None, rows=None):
         """Add samples to the shell map: five host columns (float32 ones go over as they are and
@@ -1458,6 +1465,51 @@ class Context:
         sums = np.zeros((6, nlon, nlat, nalt + 2, 2))
         self._check(self.lib.nxc_shell_moments_download(self._h, _p(sums)))
         return sums
+
+    def _shell_records(self):
+        nlon, nlat, nalt = getattr(self, 'shell_shape', None) or (0, 0, 0)
+        return (nlon, nlat, nalt + 2 if nlon else 0)
+
+    def shell_ages_enable(self, na, t0=0.0, a_lo=0.0, a_hi=0.0):
+        """After ``shell_set``: allocate and zero an age block of ``na`` bins over [a_lo, a_hi)
+        seconds of age at the epoch ``t0`` [s] per cell and altitude record, two planes (``na = 0``
+        frees it; the next ``shell_set`` switches it off)."""
+        self._ages_enable('shell', na, t0, a_lo, a_hi)
+
+    def shell_ages_accumulate(self, time=None, x=None, y=None, z=None, vy=None, frac=None,
+                              rows=None):
+        """Add samples to the shell map and to its age block in one pass: six host columns, time
+        first (float32 ones go over as they are), or ``rows = (RowStore, first, count)``."""
+        self._accumulate('nxc_shell_ages_accumulate', (time, x, y, z, vy, frac), rows)
+
+    def shell_ages_download(self):
+        """(2, nlon, nlat, nalt + 2, na + 2, 2) float64: {sum w, sum w w} and {sum c, sum c c},
+        c = w / r^2, per cell, altitude record and age plane (0 below, 1..na the bins, na + 1
+        above; include/nexoclom_hip.h, "ShellMap ages")."""
+        sums = np.zeros((2,) + self._shell_records() + (getattr(self, '_shell_ages_na', 0) + 2, 2))
+        self._check(self.lib.nxc_shell_ages_download(self._h, _p(sums)))
+        return sums
+
+    def shell_ages_upload(self, sums):
+        """Replace the age block by ``sums`` (2, nlon, nlat, nalt + 2, na + 2, 2)."""
+        shape = (2,) + self._shell_records() + (getattr(self, '_shell_ages_na', 0) + 2, 2)
+        sums = _f64(sums)
+        if sums.shape != shape:
+            raise ValueError(f'ages_upload: sums of shape {sums.shape}, the block has {shape}')
+        self.ages_owner.pop('shell', None)
+        self._check(self.lib.nxc_shell_ages_upload(self._h, _p(sums)))
+
+    def shell_ages_apply(self, K):
+        """(2, ne, nlon, nlat, nalt + 2, 2) = both planes of the resident age block contracted
+        with ``K`` (na + 2, ne), as ``image_ages_apply`` does it for pixels: {sum_k S K,
+        sum_k WW K K} per epoch and record, summed over the age planes in their order."""
+        K = _f64(K)
+        if K.ndim != 2 or K.shape[0] != getattr(self, '_shell_ages_na', 0) + 2:
+            raise ValueError('ages_apply: K must have one row per plane, (na + 2, ne)')
+        ne = K.shape[1]
+        out = np.zeros((2, ne) + self._shell_records() + (2,))
+        self._check(self.lib.nxc_shell_ages_apply(self._h, ne, _p(K), _p(out)))
+        return out
 
     # -- LOSResultFitted ----------------------------------------------------------------------
     def pairs_create(self, capacity):

@@ -13,7 +13,8 @@ whose rate was ``rate(t)`` times the nominal one is
 -- one contraction of the cube with a small matrix (``response_matrix``; k_ages_apply on the
 device).  Only the rate changes: where and how fast the source launches stays as the run had it.
 LOSResult files the pairs of its lines of sight and ModelDensity the members of its points' balls
-the same way; their ``transient`` reads each spectrum or point at an epoch of its own.
+the same way; their ``transient`` reads each spectrum or point at an epoch of its own.  ShellMap
+files both records of a sample (k_shell_ages); its ``transient`` gives the shells per epoch.
 Host only, NumPy only."""
 import operator
 
@@ -49,7 +50,7 @@ def refuse_ages_with(**given):
            'shard': 'ages= does not support shard=: the age sums are not reduced over shards',
            'cp': 'ages= does not support cp=: there is no all-reduce of the age sums yet',
            'moments': 'ages= does not support moments=True: each is a pass of its own that adds to '
-                      'the image, so two passes would add it twice; make two objects',
+                      'the same sums, so two passes would add them twice; make two objects',
            'cube': 'ages= does not support cube=: each is a pass of its own that adds to the '
                    'image, so two passes would add it twice; make two objects',
            'profile': 'ages= does not support profile=: a line-of-sight pass files its pairs by '
@@ -274,3 +275,44 @@ class TransientTrack:
         self.kernel = response_matrix(age_edges, times, history)
         total, self.effective_packets = track_sums(age_sums, self.kernel)
         self.density = total*scale
+
+
+class TransientShells:
+    """What ``shell.transient(epochs, history)`` returns, from ``sums`` (2, E, nlon, nlat, nalt + 2,
+    2), both planes of the shell map's age block contracted with the kernel ({sum_k S K,
+    sum_k WW K K} per epoch, cell and altitude record):
+
+      epochs                     (E,) [s]
+      kernel                     (nbins + 2, E): the response matrix used
+      density                    (E, nlon, nlat, nalt), scaled as the map's ``density`` is
+      column_profile             (E, nlon, nlat, nalt), scaled as ``column`` is
+      column                     (E, nlon, nlat): plane B summed over all nalt + 2 records of a
+                                 cell from record 0 upwards, scaled as ``column`` is
+      density_effective_packets  (E, nlon, nlat, nalt): (sum)^2 / (ww sum), 0 where empty
+      column_effective_packets   (E, nlon, nlat): the same of the cell's sums
+      content                    (E,): for 'column' the atoms inside the altitude range,
+                                 atoms_per_packet times plane A's sums over the bins 1..nalt of all
+                                 cells; None for 'radiance'"""
+
+    def __init__(self, epochs, kernel, sums, atoms_per_packet, solid_angle, volume, R_cm,
+                 quantity='column'):
+        self.epochs = np.atleast_1d(np.asarray(epochs, dtype=float))
+        self.kernel = kernel
+        sums = np.asarray(sums, dtype=float)
+        A, B = sums[0][..., 1:-1, :], sums[1]
+        per_area = atoms_per_packet/(solid_angle*R_cm**2)
+        cell = np.zeros(B.shape[:3] + (2,))
+        for k in range(B.shape[3]):
+            cell = cell + B[:, :, :, k]
+
+        def effective(S, ww):
+            filled = ww != 0
+            return np.where(filled, S*S/np.where(filled, ww, 1.0), 0.0)
+
+        self.density = A[..., 0]*atoms_per_packet/(np.asarray(volume)*R_cm**3)
+        self.column_profile = B[..., 1:-1, 0]*per_area
+        self.column = cell[..., 0]*per_area
+        self.density_effective_packets = effective(A[..., 0], A[..., 1])
+        self.column_effective_packets = effective(cell[..., 0], cell[..., 1])
+        self.content = atoms_per_packet*A[..., 0].sum(axis=(1, 2, 3)) if quantity == 'column' \
+            else None

@@ -23,6 +23,13 @@ same way over the same rows, on 72 x 36 x 32 and on 720 x 360 x 32: per grid and
 share of the atomic floor in the kernel's time.
 
     python tools/gpu_exp_shell_map.py --moments [--out FILE] [N]
+
+``--ages``: k_shell against k_shell_ages (ShellMap(ages=...), 32 age bins over the run) in the same
+way, 1 warm-up round and 10 timed ones, on 72 x 36 x 32 and on 720 x 360 x 1: per grid and kernel
+median [min, max], the requests (k_shell_ages: two more per sample with w != 0, five in all),
+requests/s, the atomic floor and its share of the kernel's time, and the bytes of the block.
+
+    python tools/gpu_exp_shell_map.py --ages [--out FILE] [N]
 """
 import contextlib
 import io
@@ -118,6 +125,68 @@ def main_moments(n, out_path):
     ctx.close()
 
 
+AGE_GRIDS = (('72,36', '0,4,32'), ('720,360', '0,4,1'))
+AGE_BINS = 32
+
+
+def main_ages(n, out_path, warmup=1, rounds=10):
+    """``--ages``: k_shell against k_shell_ages over the same resident rows, alternated, on the two
+    grids above.  k_shell makes one request per binned sample and two more for one with w != 0;
+    k_shell_ages makes two more again for those, to (nbins + 2) times as many records."""
+    ctx = hip_api.Context(0)
+    inputs = Input(os.path.join(ROOT, 'nexoclom_amd', 'inputfiles', 'Na.mercury.bench.input'))
+    with contextlib.redirect_stdout(io.StringIO()):
+        inputs.run(n, seed=7, context=ctx)
+    launches = [span for _, span in sample_spans(inputs._catalogue, ctx)]
+    rows = sum(s[2] for s in launches)
+    lit = 0
+    for store, first, total in launches:
+        for at in range(first, first + total, CHUNK):
+            got, _ = store.download(at, min(CHUNK, first + total - at), index=False)
+            x, y, z = got[1], got[2], got[3]
+            lit += int(np.count_nonzero(((x*x + z*z > 1) | (y < 0)) & (x*x + y*y + z*z > 0)))
+    kernels = {'k_shell': lambda span: ctx.shell_accumulate(rows=span),
+               'k_shell_ages': lambda span: ctx.shell_ages_accumulate(rows=span)}
+    endtime = float(inputs.options.endtime.value)
+    grids = {}
+    for dims, altitude in AGE_GRIDS:
+        params = dict(quantity='radiance', dims=dims, altitude=altitude)
+        with contextlib.redirect_stdout(io.StringIO()):
+            # the class checks the whole path once and leaves its description set and enabled
+            sm = ShellMap(inputs, params, context=ctx, ages=(0., endtime, AGE_BINS))
+        times = {name: [] for name in kernels}
+        binned = {}
+        for rnd in range(warmup + rounds):
+            for name, accumulate in kernels.items():
+                ms, hit = 0.0, 0
+                for span in launches:
+                    accumulate(span)
+                    ms += ctx.last_kernel_ms()
+                    hit += ctx.counters()['samples_binned']
+                binned[name] = hit
+                if rnd >= warmup:
+                    times[name].append(ms)
+        med = {name: float(np.median(t)) for name, t in times.items()}
+        requests = {'k_shell': binned['k_shell'] + 2*lit,
+                    'k_shell_ages': binned['k_shell_ages'] + 4*lit}
+        grids[f'{dims} x {altitude.split(",")[2]}'] = {
+            'age_bins': AGE_BINS, 'block_bytes': int(sm.shell_age_sums.size*8),
+            'binned': binned, 'requests': requests,
+            **{name + '_ms': spread(t) for name, t in times.items()},
+            'ages_over_shell': round(med['k_shell_ages']/med['k_shell'], 3),
+            'requests_per_s': {name: round(requests[name]/med[name]*1e3, 0) for name in kernels},
+            'atomic_floor_ms': {name: round(requests[name]/ATOMIC_RPS*1e3, 3) for name in kernels},
+            'floor_share_of_kernel_time': {name: round(requests[name]/ATOMIC_RPS*1e3/med[name], 3)
+                                           for name in kernels}}
+    line = json.dumps({'npackets': n, 'rows': rows, 'launches': len(launches),
+                       'binned_nonzero': lit, 'warmup': warmup, 'rounds': rounds, 'grids': grids})
+    print(line, flush=True)
+    if out_path:
+        with open(out_path, 'a') as f:
+            f.write(line + '\n')
+    ctx.close()
+
+
 def main():
     args = sys.argv[1:]
     out_path = None
@@ -127,9 +196,14 @@ def main():
     moments = '--moments' in args
     if moments:
         args.remove('--moments')
+    ages = '--ages' in args
+    if ages:
+        args.remove('--ages')
     n = float(args[0]) if args else 1e6
     if moments:
         return main_moments(n, out_path)
+    if ages:
+        return main_ages(n, out_path)
     ctx = hip_api.Context(0)
     copy_bps = ctx.stream_copy_gbs()*1e9
     inputs = Input(os.path.join(ROOT, 'nexoclom_amd', 'inputfiles', 'Na.mercury.bench.input'))
