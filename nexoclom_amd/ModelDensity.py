@@ -397,6 +397,7 @@ class ModelDensity:
     context = ModelResult.context         # the catalogue's shared context, found once and kept
     frame, slab_rows = None, ModelResult.slab_rows       # a moon's frame, as the images have it
     _frame_pass = ModelResult._frame_pass
+    _ages_transient = ModelResult._ages_transient
     _ages = None              # (a_lo_s, a_hi_s, nbins): the pass also fills age_sums
     _ages_token = None        # what Context.ages_owner holds while the block is this object's total
 
@@ -459,12 +460,9 @@ class ModelDensity:
         index, Q = self._index, len(self.age_sums)
         sums = np.zeros((K.shape[1], Q, 2))
         if len(index.points):
-            ctx = self.context()
-            if ctx.ages_owner.get('density') is not self._ages_token:
-                self._set_index(ctx, index)
-                ctx.density_ages_upload(self.age_sums[index.order])
-                ctx.ages_owner['density'] = self._ages_token
-            sums[:, index.order] = ctx.density_ages_apply(K)
+            sums[:, index.order] = self._ages_transient(
+                'density', lambda ctx: self._set_index(ctx, index),
+                lambda: self.age_sums[index.order], K)
         return TransientDensity(epochs, K, sums, scale)
 
     def transient_track(self, history, times):

@@ -371,6 +371,13 @@ class ModelResult:
         if self.ages is not None:
             vars(self).update(ages_from_sums(self.age_sums, self.atoms_per_packet, *self.ages[:2]))
 
+    def _ages_transient(self, prefix, setup, sums, K):
+        """``Context.ages_transient`` on this object's context for its token.  Called through the
+        class: any context that answers ``<prefix>_ages_upload`` / ``_apply`` and keeps an
+        ``ages_owner`` is re-seated by the one rule."""
+        from .hip_api import Context
+        return Context.ages_transient(self.context(), prefix, self._ages_token, setup, sums, K)
+
     def transient(self, epochs, history, prefix='image'):
         """The images at ``epochs`` [s] for a source whose rate relative to the nominal one was
         ``history = (t_nodes_s, rate_nodes)`` (transient.response_matrix): a TransientImages with
@@ -386,12 +393,7 @@ class ModelResult:
         if self._ages_setup is None:                       # nothing was ever binned
             sums = np.zeros((K.shape[1],) + tuple(self.dims) + (2,))
         else:
-            ctx = self.context()
-            if ctx.ages_owner.get(prefix) is not self._ages_token:
-                self._ages_setup(ctx)
-                getattr(ctx, prefix + '_ages_upload')(self.age_sums)
-                ctx.ages_owner[prefix] = self._ages_token
-            sums = getattr(ctx, prefix + '_ages_apply')(K)
+            sums = self._ages_transient(prefix, self._ages_setup, lambda: self.age_sums, K)
         return TransientImages(epochs, K, sums, self.atoms_per_packet)
 
 

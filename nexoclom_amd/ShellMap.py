@@ -376,11 +376,6 @@ class ShellMap(ModelResult):
         if self._ages_setup is None:                       # nothing was ever binned
             sums = np.zeros((2, K.shape[1]) + self.shell_age_sums.shape[1:4] + (2,))
         else:
-            ctx = self.context()
-            if ctx.ages_owner.get('shell') is not self._ages_token:
-                self._ages_setup(ctx)
-                ctx.shell_ages_upload(self.shell_age_sums)
-                ctx.ages_owner['shell'] = self._ages_token
-            sums = ctx.shell_ages_apply(K)
+            sums = self._ages_transient('shell', self._ages_setup, lambda: self.shell_age_sums, K)
         return TransientShells(epochs, K, sums, self.atoms_per_packet, self.solid_angle,
                                self._volume, self.unit_km*1e5, self.quantity)

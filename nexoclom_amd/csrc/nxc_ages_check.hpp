@@ -1,8 +1,11 @@
-// Host-only side of the age cube (include/nexoclom_hip.h, "Age cube"): what nxc_*_ages_enable and
-// nxc_*_ages_apply must find before anything is allocated or freed, and how nxc_*_ages_apply cuts
-// its work to the LDS of a workgroup.  Plain C++ without a device call or a handle: a refusal is a
-// text, which nxc_api.hip hands to fail().  So it can also be built into a stand-alone program and
-// run under the host sanitizers (tests/tools/ages_check.cpp).
+// Host-only side of the age blocks (include/nexoclom_hip.h, "Age cube", "Density ages",
+// "Line-of-sight ages", "ShellMap ages"): what nxc_*_ages_enable and nxc_*_ages_apply must find
+// before anything is allocated or freed, the size of a block, and how nxc_*_ages_apply cuts its work
+// to the LDS of a workgroup.  One check serves the four subjects; what differs between them is the
+// words of the refusal (AgesSubject).  Plain C++ without a device call or a handle: a refusal is a
+// text, which nxc_api.hip hands to fail().  So it can also be built into stand-alone programs and
+// run under the host sanitizers (tests/tools/ages_check.cpp, density_ages_check.cpp,
+// los_ages_check.cpp, shell_ages_check.cpp).
 #pragma once
 
 #include <algorithm>
@@ -11,23 +14,48 @@
 #include <cstdint>
 #include <string>
 
-// add_record_pairs takes the record index as an int: n_pix * (na + 2) records must stay below this
+// add_record_pairs takes the record index as an int: records * (na + 2) must stay below this
 constexpr int64_t NXC_AGES_MAX_RECORDS = int64_t(1) << 31;
 
-// "" or why the enable refuses na >= 1 age bins over [a_lo, a_hi) at the epoch t0 on an image of
-// n_pix >= 1 pixels
-inline std::string check_ages_args(int64_t n_pix, int64_t na, double t0, double a_lo, double a_hi)
+constexpr int NXC_SHELL_AGE_PLANES = 2;             // age plane A {w, w w}, age plane B {c, c c}
+
+// What is given ages, in the words of its refusals
+struct AgesSubject {
+    const char *label;      // what every refusal starts with
+    const char *empty;      // the sentence for a subject without a record
+    const char *records;    // how the number of 16-byte records of one set is spelled
+};
+constexpr AgesSubject AGES_OF_PIXELS = {"age cube", "the image has no pixels", "n_pix * (na + 2)"};
+constexpr AgesSubject AGES_OF_POINTS = {"density ages", "the index has no points",
+                                        "n_points * (na + 2)"};
+constexpr AgesSubject AGES_OF_SPECTRA = {"line-of-sight ages", "S must be at least 1", "S * (na + 2)"};
+constexpr AgesSubject AGES_OF_SHELLS = {"shell ages", "the map has no records",
+                                        "nlon * nlat * (nalt + 2) * (na + 2)"};
+
+// "" or why the enable refuses na >= 1 age bins over [a_lo, a_hi) at the epoch t0 for a subject of
+// n >= 1 records (pixels, points, spectra, records of the shell map) per set
+inline std::string check_ages_args(const AgesSubject &who, int64_t n, int64_t na, double t0,
+                                   double a_lo, double a_hi)
 {
-    if (n_pix < 1) return "age cube: the image has no pixels";
-    if (na < 1) return "age cube: na must be at least 1";
-    if (!std::isfinite(t0)) return "age cube: t0 must be finite";
-    if (!std::isfinite(a_lo) || !std::isfinite(a_hi)) return "age cube: a_lo and a_hi must be finite";
-    if (!(a_lo < a_hi)) return "age cube: a_lo must be below a_hi";
-    if (!std::isfinite(a_hi - a_lo)) return "age cube: a_hi - a_lo must be finite";
-    // n_pix * (na + 2) < 2^31 without forming the product: na + 2 <= floor((2^31 - 1) / n_pix)
-    if (na >= NXC_AGES_MAX_RECORDS || na + 2 > (NXC_AGES_MAX_RECORDS - 1) / n_pix)
-        return "age cube: n_pix * (na + 2) must be below 2^31 records";
+    const std::string label = std::string(who.label) + ": ";
+    if (n < 1) return label + who.empty;
+    if (na < 1) return label + "na must be at least 1";
+    if (!std::isfinite(t0)) return label + "t0 must be finite";
+    if (!std::isfinite(a_lo) || !std::isfinite(a_hi)) return label + "a_lo and a_hi must be finite";
+    if (!(a_lo < a_hi)) return label + "a_lo must be below a_hi";
+    if (!std::isfinite(a_hi - a_lo)) return label + "a_hi - a_lo must be finite";
+    // n * (na + 2) < 2^31 without forming the product: na + 2 <= floor((2^31 - 1) / n)
+    if (na >= NXC_AGES_MAX_RECORDS || na + 2 > (NXC_AGES_MAX_RECORDS - 1) / n)
+        return label + who.records + " must be below 2^31 records";
     return "";
+}
+
+// bytes of `sets` sets (NXC_SHELL_AGE_PLANES for the shell map, 1 elsewhere) of records * (na + 2)
+// records {sum, sum of squares}; the arguments are ones check_ages_args accepted, so the records of
+// a set stay below 2^31 and the bytes below 2^36
+inline size_t ages_block_bytes(int sets, int64_t records, int64_t na)
+{
+    return (size_t)sets * (size_t)records * (size_t)(na + 2) * 2 * sizeof(double);
 }
 
 // bins per second of age, formed once in fp64 on the host

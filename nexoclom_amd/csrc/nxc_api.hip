@@ -27,11 +27,8 @@
 #include "nxc_camera_check.hpp"
 #include "nxc_shell_check.hpp"
 #include "nxc_shell_moments_check.hpp"
-#include "nxc_shell_ages_check.hpp"
 #include "nxc_cube_check.hpp"
 #include "nxc_ages_check.hpp"
-#include "nxc_density_ages_check.hpp"
-#include "nxc_los_ages_check.hpp"
 #include "nxc_los_profile_check.hpp"
 #include "nxc_desc_check.hpp"
 #include "nxc_source_map_check.hpp"
@@ -330,6 +327,19 @@ struct nxc_pairs {
     Dev<long long> d;
 };
 
+// An age block on the device: `sets` sets of records x (na + 2) 16-byte records {sum, sum of
+// squares}, there from its enable (ages_enable) to the next set of what owns it.  One type for the
+// image, the camera, the density, the shell map and the lines of sight.
+struct AgeBlock {
+    bool have = false;               // nxc_X_ages_enable since the owner's last set
+    AgeK K{};
+    int64_t records = 0;             // per set: pixels, points, spectra, records of the shell map
+    int sets = 1;                    // NXC_SHELL_AGE_PLANES for the shell map: {w, w w} | {c, c c}
+    Dev<double> d;                   // [sets][records][na + 2] records
+    size_t bytes() const { return ages_block_bytes(sets, records, K.na); }
+    int release() { have = false; return d.release(); }     // off, its records back to the device
+};
+
 // What a pixel grid owns on the device, ModelImage's (nxc_set_image) and CameraImage's
 // (nxc_camera_set) alike.  The moments, the cube and the age block are there from their enable to
 // the next set, each a state of its own.
@@ -341,9 +351,7 @@ struct PixelSums {
     bool have_cube = false;          // nxc_X_cube_enable since the last set
     Dev<double> cube;                // the velocity cube: [npix][nv + 2] records (k_X_cube)
     CubeK cubeK{};
-    bool have_ages = false;          // nxc_X_ages_enable since the last set
-    Dev<double> ages;                // the age cube: [npix][na + 2] records (k_X_ages)
-    AgeK ageK{};
+    AgeBlock ages;                   // the age cube: [npix][na + 2] records (k_X_ages)
 };
 
 // Stored samples on the device, as every consumer (image, line of sight, density, fit) reads them:
@@ -457,9 +465,7 @@ struct nxc_handle {
     SpectrumK dens_spec{};
     Dev<double> d_dens_spec;         // the spectrum: [2][Q][nv + 2] records (k_density_spectrum)
     Dev<double> d_dens_frames;       // [Q][8]: ux uy uz 0 bx by bz 0 per indexed point
-    bool have_dens_ages = false;     // nxc_density_ages_enable since the last nxc_density_set
-    AgeK dens_ageK{};
-    Dev<double> d_dens_ages;         // the ages: [Q][na + 2] records {f, f f} (k_density_ages)
+    AgeBlock dens_ages;              // the ages: [Q][na + 2] records {f, f f} (k_density_ages)
 
     // CameraImage (nxc_camera_set): the camera, its LDS blob [LdsHeader | g tables | u edges |
     // v edges] and its own {weight sum, count} image
@@ -480,9 +486,7 @@ struct nxc_handle {
     Dev<double> d_shell_planes;      // [2][cells][nalt + 2] records: {w, w w} | {c, c c} (k_shell)
     bool have_shell_mom = false;     // nxc_shell_moments_enable since the last nxc_shell_set
     Dev<double> d_shell_mom;         // [6][cells][nalt + 2] records: the twelve sums (k_shell_moments)
-    bool have_shell_ages = false;    // nxc_shell_ages_enable since the last nxc_shell_set
-    AgeK shell_ageK{};
-    Dev<double> d_shell_ages;        // [2][cells (nalt + 2)][na + 2] records: {w, w w} | {c, c c} (k_shell_ages)
+    AgeBlock shell_ages;             // [2][cells (nalt + 2)][na + 2] records: {w, w w} | {c, c c} (k_shell_ages)
 
     // LOSResultFitted: the pair list the line-of-sight passes fill (nxc_los_set_pairs); the fit's
     // per-spectrum data, its sample source and per-packet sums (nxc_fit_*)
@@ -493,10 +497,7 @@ struct nxc_handle {
     CubeK los_profK{};
     Dev<double> d_los_prof;          // [S][nv + 2] records {w, w w} | [S][4] sums m1 m2 m3 ww
     // the line-of-sight ages (nxc_los_ages_enable): a block of their own, from enable to enable
-    bool have_los_ages = false;
-    int64_t los_ages_S = 0;          // spectra it was enabled for
-    AgeK los_agesK{};
-    Dev<double> d_los_ages;          // [S][na + 2] records {w, w w}
+    AgeBlock los_ages;               // [S][na + 2] records {w, w w}; records: the S it was enabled for
     bool have_fit = false;
     int64_t fit_S = 0, fit_np = -1;  // fit_np: packets whose multipliers are ready (nxc_fit_packets)
     int fit_mode = 0;
@@ -1180,8 +1181,6 @@ int rows_fetch(nxc_handle *h, void *rows_out, bool narrow)
 
 // records of the handle's line-of-sight profile
 size_t los_profile_records(const nxc_handle *h) { return (size_t)h->los_prof_S * (size_t)(h->los_profK.nv + 2); }
-// ... and of its line-of-sight ages
-size_t los_ages_records(const nxc_handle *h) { return (size_t)h->los_ages_S * (size_t)(h->los_agesK.na + 2); }
 
 // The pass constants and the LDS blob [header space | g-value tables] of a line-of-sight
 // descriptor (los_run, fit_radiance)
@@ -1325,8 +1324,8 @@ int los_run(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc, i
             prof.mom = h->d_los_prof + los_profile_records(h) * 2;
         }
         if constexpr (MODE == LOS_AGES) {
-            prof.bins = h->los_agesK;
-            prof.rec = h->d_los_ages;
+            prof.bins = h->los_ages.K;
+            prof.rec = h->los_ages.d;
         }
         unsigned *pair_used = reinterpret_cast<unsigned *>(h->d_losblk + o_n + 8);
         unsigned *pair_fill = reinterpret_cast<unsigned *>(h->d_losblk + o_fill);
@@ -1439,12 +1438,13 @@ int los_profile_check(const nxc_handle *h, int64_t S)
 }
 
 // What an ages entry checks in front of the plain entry's own checks
+constexpr const char *LOS_AGES_UNSET = "nxc_los_ages_enable has not been called";
 int los_ages_check(const nxc_handle *h, int64_t S)
 {
     if (!h) return fail(NXC_ERR_ARG, "bad arguments");
-    if (!h->have_los_ages) return fail(NXC_ERR_STATE, "nxc_los_ages_enable has not been called");
-    if (S != h->los_ages_S)
-        return fail(NXC_ERR_ARG, "the ages were enabled for " + std::to_string(h->los_ages_S) +
+    if (!h->los_ages.have) return fail(NXC_ERR_STATE, LOS_AGES_UNSET);
+    if (S != h->los_ages.records)
+        return fail(NXC_ERR_ARG, "the ages were enabled for " + std::to_string(h->los_ages.records) +
                                      " spectra, this call has " + std::to_string(S));
     return NXC_OK;
 }
@@ -1505,42 +1505,6 @@ int los_profile_download(nxc_handle *h, double *sums, double *moments)
     const size_t n_rec = los_profile_records(h) * 2;
     HIPCHK(hipMemcpyAsync(sums, h->d_los_prof, n_rec * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(moments, h->d_los_prof + n_rec, (size_t)h->los_prof_S * 4 * sizeof(double),
-                          hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(stream_sync(h));
-    return NXC_OK;
-}
-
-// nxc_los_ages_enable: S (na + 2) zeroed records in a block of their own, or none; the arguments
-// are checked (check_los_ages_args) before the block there is is touched
-int los_ages_enable(nxc_handle *h, int64_t S, int64_t na, double t0, double a_lo, double a_hi)
-{
-    if (!h) return fail(NXC_ERR_ARG, "bad arguments");
-    if (na != 0) {
-        const std::string why = check_los_ages_args(S, na, t0, a_lo, a_hi);
-        if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
-    }
-    HIPCHK(hipSetDevice(h->device));
-    h->have_los_ages = false;
-    int rc = h->d_los_ages.release();
-    if (rc || na == 0) return rc;
-    h->los_ages_S = S;
-    h->los_agesK = AgeK{(int)na, t0, a_lo, ages_inv_da(na, a_lo, a_hi)};
-    const size_t bytes = los_ages_records(h) * 2 * sizeof(double);
-    if ((rc = h->d_los_ages.ensure(bytes))) return rc;
-    HIPCHK(hipMemsetAsync(h->d_los_ages, 0, bytes, h->stream));
-    HIPCHK(stream_sync(h));
-    h->have_los_ages = true;
-    return NXC_OK;
-}
-
-// nxc_los_ages_download: sums[S][na + 2][2], the device's own order
-int los_ages_download(nxc_handle *h, double *sums)
-{
-    if (!h) return fail(NXC_ERR_ARG, "bad arguments");
-    if (!h->have_los_ages) return fail(NXC_ERR_STATE, "nxc_los_ages_enable has not been called");
-    if (!sums) return fail(NXC_ERR_ARG, "bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(sums, h->d_los_ages, los_ages_records(h) * 2 * sizeof(double),
                           hipMemcpyDeviceToHost, h->stream));
     HIPCHK(stream_sync(h));
     return NXC_OK;
@@ -1704,9 +1668,9 @@ int density_ages_run(nxc_handle *h, const Samples &s)
 {
     return with_sample_types(s, [&](auto t, auto) -> int {
         using T = decltype(t);
-        return launch_sample_pass(h, k_density_ages<T>, NXC_BLOCK, 0, s.n, h->dens, h->dens_ageK, s.n,
+        return launch_sample_pass(h, k_density_ages<T>, NXC_BLOCK, 0, s.n, h->dens, h->dens_ages.K, s.n,
                                   s.col<T>(7), s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(4),
-                                  h->d_dens_pts, h->d_dens_cell, h->d_dens_acc, h->d_dens_ages);
+                                  h->d_dens_pts, h->d_dens_cell, h->d_dens_acc, h->dens_ages.d);
     });
 }
 
@@ -1752,9 +1716,9 @@ int shell_ages_run(nxc_handle *h, const Samples &s)
     return with_sample_types(s, [&](auto t, auto) -> int {
         using T = decltype(t);
         return launch_sample_pass(h, k_shell_ages<T>, NXC_SHELL_BLOCK, h->shell_bytes, s.n, h->shell,
-                                  h->shell_ageK, h->d_blob_shell, (int64_t)h->shell_bytes, s.n,
+                                  h->shell_ages.K, h->d_blob_shell, (int64_t)h->shell_bytes, s.n,
                                   s.col<T>(7), s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3),
-                                  s.col<T>(4), h->shell_px.image, h->d_shell_planes, h->d_shell_ages,
+                                  s.col<T>(4), h->shell_px.image, h->d_shell_planes, h->shell_ages.d,
                                   h->d_ctr);
     });
 }
@@ -1813,9 +1777,9 @@ int image_ages_run(nxc_handle *h, const Samples &s)
     return with_sample_types(s, [&](auto t, auto) -> int {
         using T = decltype(t);
         return launch_sample_pass(h, k_image_ages<T>, NXC_IMAGE_MOMENTS_BLOCK, h->img_bytes, s.n,
-                                  h->d_blob_img, (int64_t)h->img_bytes, s.n, h->img.ageK,
+                                  h->d_blob_img, (int64_t)h->img_bytes, s.n, h->img.ages.K,
                                   s.col<T>(7), s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3),
-                                  s.col<T>(4), h->img.image, h->img.ages, h->d_ctr);
+                                  s.col<T>(4), h->img.image, h->img.ages.d, h->d_ctr);
     });
 }
 
@@ -1825,9 +1789,9 @@ int camera_ages_run(nxc_handle *h, const Samples &s)
     return with_sample_types(s, [&](auto t, auto) -> int {
         using T = decltype(t);
         return launch_sample_pass(h, k_camera_ages<T>, NXC_CAMERA_BLOCK, h->cam_bytes, s.n, h->cam,
-                                  h->d_blob_cam, (int64_t)h->cam_bytes, s.n, h->cam_px.ageK,
+                                  h->d_blob_cam, (int64_t)h->cam_bytes, s.n, h->cam_px.ages.K,
                                   s.col<T>(7), s.col<T>(0), s.col<T>(1), s.col<T>(2), s.col<T>(3),
-                                  s.col<T>(4), h->cam_px.image, h->cam_px.ages, h->d_ctr);
+                                  s.col<T>(4), h->cam_px.image, h->cam_px.ages.d, h->d_ctr);
     });
 }
 
@@ -1878,33 +1842,11 @@ int spectrum_free(nxc_handle *h)
 }
 // the density ages' state is their enable too, checked after nxc_density_set's (moments_need_set);
 // the pass reads the time column and no velocity
-const SampleConsumer DENSITY_AGES_SAMPLES = {[](const nxc_handle *h) { return h->have_dens_ages; },
+const SampleConsumer DENSITY_AGES_SAMPLES = {[](const nxc_handle *h) { return h->dens_ages.have; },
                                              "nxc_density_ages_enable has not been called",
                                              false, false, false,
                                              [](const nxc_handle *h) { return h->dens_q == 0; },
                                              density_ages_run, nullptr, true};
-// bytes of the age block over Q points
-size_t density_ages_bytes(const nxc_handle *h)
-{
-    return (size_t)h->dens_q * (size_t)(h->dens_ageK.na + 2) * 2 * sizeof(double);
-}
-
-// the density ages off, their records back to the device
-int density_ages_free(nxc_handle *h)
-{
-    h->have_dens_ages = false;
-    return h->d_dens_ages.release();
-}
-
-// the state checks of the block's download, upload and apply (nxc_density_set is named first), and
-// their null check
-int density_ages_ready(const nxc_handle *h, const void *host)
-{
-    if (!h || !h->have_density) return fail(NXC_ERR_STATE, DENSITY_SAMPLES.unset);
-    if (!h->have_dens_ages) return fail(NXC_ERR_STATE, DENSITY_AGES_SAMPLES.unset);
-    if (!host) return fail(NXC_ERR_ARG, "bad arguments");
-    return NXC_OK;
-}
 const SampleConsumer CAMERA_SAMPLES = {[](const nxc_handle *h) { return h->have_camera; },
                                        "nxc_camera_set has not been called",
                                        true, true, false, nullptr, camera_run, &nxc_handle::cam_px};
@@ -1928,37 +1870,14 @@ int shell_moments_ready(const nxc_handle *h)
     if (r.code == NXC_OK) return NXC_OK;
     return guarded([&]() -> int { return fail(r.code, r.why); });
 }
-// the shell ages' state is their enable too, checked after nxc_shell_set's (shell_ages_need_set);
+// the shell ages' state is their enable too, checked after nxc_shell_set's (pixel_moments_need_set);
 // the pass reads the time column and neither vx nor vz
-const SampleConsumer SHELL_AGES_SAMPLES = {[](const nxc_handle *h) { return h->have_shell_ages; },
+const SampleConsumer SHELL_AGES_SAMPLES = {[](const nxc_handle *h) { return h->shell_ages.have; },
                                            "nxc_shell_ages_enable has not been called",
                                            true, true, false, nullptr, shell_ages_run, nullptr, true};
 // records of one plane of the shell map: cells (nalt + 2)
 int64_t shell_records(const nxc_handle *h) { return h->shell.plane / 2; }
 
-// the shell ages off, their records back to the device
-int shell_ages_free(nxc_handle *h)
-{
-    h->have_shell_ages = false;
-    return h->d_shell_ages.release();
-}
-
-// the state check in front of SHELL_AGES_SAMPLES' entries: nxc_shell_set is the missing call
-int shell_ages_need_set(const nxc_handle *h)
-{
-    if (h && h->have_shell) return NXC_OK;
-    return guarded([&]() -> int { return fail(NXC_ERR_STATE, SHELL_SAMPLES.unset); });
-}
-
-// the state checks of the block's download, upload and apply (nxc_shell_set is named first), and
-// their null check
-int shell_ages_ready(const nxc_handle *h, const void *host)
-{
-    if (!h || !h->have_shell) return fail(NXC_ERR_STATE, SHELL_SAMPLES.unset);
-    if (!h->have_shell_ages) return fail(NXC_ERR_STATE, SHELL_AGES_SAMPLES.unset);
-    if (!host) return fail(NXC_ERR_ARG, "bad arguments");
-    return NXC_OK;
-}
 // the pixel moments' state is their enable, checked after the set's (pixel_moments_need_set)
 const SampleConsumer IMAGE_MOMENT_SAMPLES = {[](const nxc_handle *h) { return h->img.have_mom; },
                                              "nxc_image_moments_enable has not been called",
@@ -2069,69 +1988,94 @@ int pixel_cube_download(nxc_handle *h, const SampleConsumer &base, const SampleC
 
 // the age block's state is its enable too, checked after the set's (pixel_moments_need_set); its
 // passes read the time column and neither vx nor vz
-const SampleConsumer IMAGE_AGES_SAMPLES = {[](const nxc_handle *h) { return h->img.have_ages; },
+const SampleConsumer IMAGE_AGES_SAMPLES = {[](const nxc_handle *h) { return h->img.ages.have; },
                                            "nxc_image_ages_enable has not been called",
                                            true, true, false, nullptr, image_ages_run, nullptr, true};
-const SampleConsumer CAMERA_AGES_SAMPLES = {[](const nxc_handle *h) { return h->cam_px.have_ages; },
+const SampleConsumer CAMERA_AGES_SAMPLES = {[](const nxc_handle *h) { return h->cam_px.ages.have; },
                                             "nxc_camera_ages_enable has not been called",
                                             true, true, false, nullptr, camera_ages_run, nullptr, true};
 
-size_t ages_bytes(size_t npix, const AgeK &Q) { return npix * (size_t)(Q.na + 2) * 2 * sizeof(double); }
+// Who owns an age block, for the entries that enable, copy and contract it (ages_*)
+struct AgesOwner {
+    AgeBlock &(*block)(nxc_handle *);
+    const SampleConsumer *base;      // its "has not been called" comes first; null (the lines of
+                                     // sight): no set to wait for, and a null handle is NXC_ERR_ARG
+    const char *unset;               // the ages consumer's "has not been called"
+    const AgesSubject &subject;      // the words of the enable's refusals
+    int64_t (*records)(const nxc_handle *);     // records per set; null: the enable's argument S
+    int sets;
+    bool out_first;                  // the apply refuses a null `out` before it looks at K
+};
+const AgesOwner IMAGE_AGES = {[](nxc_handle *h) -> AgeBlock & { return h->img.ages; }, &IMAGE_SAMPLES,
+                              IMAGE_AGES_SAMPLES.unset, AGES_OF_PIXELS,
+                              [](const nxc_handle *h) { return (int64_t)h->img.npix; }, 1, false};
+const AgesOwner CAMERA_AGES = {[](nxc_handle *h) -> AgeBlock & { return h->cam_px.ages; },
+                               &CAMERA_SAMPLES, CAMERA_AGES_SAMPLES.unset, AGES_OF_PIXELS,
+                               [](const nxc_handle *h) { return (int64_t)h->cam_px.npix; }, 1, false};
+const AgesOwner DENSITY_AGES = {[](nxc_handle *h) -> AgeBlock & { return h->dens_ages; },
+                                &DENSITY_SAMPLES, DENSITY_AGES_SAMPLES.unset, AGES_OF_POINTS,
+                                [](const nxc_handle *h) { return h->dens_q; }, 1, true};
+const AgesOwner SHELL_AGES = {[](nxc_handle *h) -> AgeBlock & { return h->shell_ages; }, &SHELL_SAMPLES,
+                              SHELL_AGES_SAMPLES.unset, AGES_OF_SHELLS, shell_records,
+                              NXC_SHELL_AGE_PLANES, true};
+const AgesOwner LOS_AGES_BLOCK = {[](nxc_handle *h) -> AgeBlock & { return h->los_ages; }, nullptr,
+                                  LOS_AGES_UNSET, AGES_OF_SPECTRA, nullptr, 1, false};
 
-// nxc_X_ages_enable: [npix][na + 2] zeroed records beside the image pair of `base`, or none; the
-// arguments are checked (check_ages_args) before the block there is is touched
-int pixel_ages_enable(nxc_handle *h, const SampleConsumer &base, int64_t na, double t0, double a_lo,
-                      double a_hi)
+// the state check every entry of an owner starts with: its set is the missing call
+int ages_need_set(const nxc_handle *h, const AgesOwner &o)
 {
-    if (int rc = pixel_moments_need_set(h, base)) return rc;
+    if (!o.base) return h ? NXC_OK : fail(NXC_ERR_ARG, "bad arguments");
+    if (!h || !o.base->have(h)) return fail(NXC_ERR_STATE, o.base->unset);
+    return NXC_OK;
+}
+
+// ... and the download, the upload and the apply go on with: the enable is
+int ages_need_enable(nxc_handle *h, const AgesOwner &o)
+{
+    if (int rc = ages_need_set(h, o)) return rc;
+    if (!o.block(h).have) return fail(NXC_ERR_STATE, o.unset);
+    return NXC_OK;
+}
+
+// nxc_X_ages_enable: sets x records x (na + 2) zeroed records, or none (na == 0); the arguments are
+// checked (check_ages_args) before the block there is is touched
+int ages_enable(nxc_handle *h, const AgesOwner &o, int64_t S, int64_t na, double t0, double a_lo,
+                double a_hi)
+{
     return guarded([&]() -> int {
-        PixelSums &px = h->*base.px;
+        if (int rc = ages_need_set(h, o)) return rc;
+        const int64_t records = o.records ? o.records(h) : S;
         if (na != 0) {
-            const std::string why = check_ages_args((int64_t)px.npix, na, t0, a_lo, a_hi);
+            const std::string why = check_ages_args(o.subject, records, na, t0, a_lo, a_hi);
             if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
         }
         HIPCHK(hipSetDevice(h->device));
-        px.have_ages = false;
-        int rc = px.ages.release();
+        AgeBlock &b = o.block(h);
+        int rc = b.release();
         if (rc || na == 0) return rc;
-        px.ageK = AgeK{(int)na, t0, a_lo, ages_inv_da(na, a_lo, a_hi)};
-        const size_t bytes = ages_bytes(px.npix, px.ageK);
-        if ((rc = px.ages.ensure(bytes))) return rc;
-        HIPCHK(hipMemsetAsync(px.ages, 0, bytes, h->stream));
+        b.K = AgeK{(int)na, t0, a_lo, ages_inv_da(na, a_lo, a_hi)};
+        b.records = records;
+        b.sets = o.sets;
+        const size_t bytes = b.bytes();
+        if ((rc = b.d.ensure(bytes))) return rc;
+        HIPCHK(hipMemsetAsync(b.d, 0, bytes, h->stream));
         HIPCHK(stream_sync(h));
-        px.have_ages = true;
+        b.have = true;
         return NXC_OK;
     });
 }
 
-// nxc_X_ages_download: sums[npix][na + 2][2], the device's own order
-int pixel_ages_download(nxc_handle *h, const SampleConsumer &base, const SampleConsumer &ages,
-                        double *sums)
+// nxc_X_ages_download: sums[sets][records][na + 2][2], the device's own order; nxc_X_ages_upload:
+// the block replaced by such sums (totals added on the host)
+int ages_copy(nxc_handle *h, const AgesOwner &o, double *sums, hipMemcpyKind kind)
 {
-    if (int rc = pixel_moments_need_set(h, base)) return rc;
     return guarded([&]() -> int {
-        if (!ages.have(h)) return fail(NXC_ERR_STATE, ages.unset);
+        if (int rc = ages_need_enable(h, o)) return rc;
         if (!sums) return fail(NXC_ERR_ARG, "bad arguments");
         HIPCHK(hipSetDevice(h->device));
-        const PixelSums &px = h->*base.px;
-        HIPCHK(hipMemcpyAsync(sums, px.ages, ages_bytes(px.npix, px.ageK), hipMemcpyDeviceToHost,
-                              h->stream));
-        HIPCHK(stream_sync(h));
-        return NXC_OK;
-    });
-}
-
-// nxc_X_ages_upload: the block replaced by sums[npix][na + 2][2] (totals added on the host)
-int pixel_ages_upload(nxc_handle *h, const SampleConsumer &base, const SampleConsumer &ages,
-                      const double *sums)
-{
-    if (int rc = pixel_moments_need_set(h, base)) return rc;
-    return guarded([&]() -> int {
-        if (!ages.have(h)) return fail(NXC_ERR_STATE, ages.unset);
-        if (!sums) return fail(NXC_ERR_ARG, "bad arguments");
-        HIPCHK(hipSetDevice(h->device));
-        const PixelSums &px = h->*base.px;
-        HIPCHK(hipMemcpyAsync(px.ages, sums, ages_bytes(px.npix, px.ageK), hipMemcpyHostToDevice,
+        AgeBlock &b = o.block(h);
+        const bool down = kind == hipMemcpyDeviceToHost;
+        HIPCHK(hipMemcpyAsync(down ? sums : b.d.get(), down ? b.d.get() : sums, b.bytes(), kind,
                               h->stream));
         HIPCHK(stream_sync(h));
         return NXC_OK;
@@ -2177,16 +2121,21 @@ int ages_block_apply(nxc_handle *h, size_t n_rec, int64_t planes, const double *
     return NXC_OK;
 }
 
-// nxc_X_ages_apply: out[ne][npix][2] (host) = the resident block contracted with K[na + 2][ne]
-// (host) (ages_block_apply)
-int pixel_ages_apply(nxc_handle *h, const SampleConsumer &base, const SampleConsumer &ages,
-                     int64_t ne, const double *K, double *out)
+// nxc_X_ages_apply: out[sets][ne][records][2] (host) = each set of the resident block contracted
+// with K[na + 2][ne] (host) (ages_block_apply), the shell map's plane A first
+int ages_apply(nxc_handle *h, const AgesOwner &o, int64_t ne, const double *K, double *out)
 {
-    if (int rc = pixel_moments_need_set(h, base)) return rc;
     return guarded([&]() -> int {
-        if (!ages.have(h)) return fail(NXC_ERR_STATE, ages.unset);
-        const PixelSums &px = h->*base.px;
-        return ages_block_apply(h, px.npix, (int64_t)px.ageK.na + 2, px.ages.get(), ne, K, out);
+        if (int rc = ages_need_enable(h, o)) return rc;
+        if (o.out_first && !out) return fail(NXC_ERR_ARG, "bad arguments");
+        const AgeBlock &b = o.block(h);
+        const size_t R = (size_t)b.records;
+        const int64_t planes = (int64_t)b.K.na + 2;
+        for (size_t set = 0; set < (size_t)b.sets; set++)
+            if (int rc = ages_block_apply(h, R, planes, b.d.get() + set * R * (size_t)planes * 2, ne, K,
+                                          out + set * (size_t)ne * R * 2))
+                return rc;
+        return NXC_OK;
     });
 }
 
@@ -2730,7 +2679,7 @@ int nxc_set_image(nxc_handle *h, const nxc_image_desc *d)
     h->have_image = false;
     h->img.have_mom = false;
     h->img.have_cube = false;
-    h->img.have_ages = false;
+    h->img.ages.have = false;
     h->image_block = append_image_block(part, G, d->nx, d->nz, d->xedges, d->zedges, nl, luts);
     h->image_part = std::move(part);
     h->G = G;
@@ -2881,8 +2830,8 @@ int nxc_image_clear(nxc_handle *h)
         HIPCHK(hipMemsetAsync(h->img.mom, 0, 4 * h->img.npix * sizeof(double), h->stream));
     if (h->img.have_cube)
         HIPCHK(hipMemsetAsync(h->img.cube, 0, cube_bytes(h->img.npix, h->img.cubeK), h->stream));
-    if (h->img.have_ages)
-        HIPCHK(hipMemsetAsync(h->img.ages, 0, ages_bytes(h->img.npix, h->img.ageK), h->stream));
+    if (h->img.ages.have)
+        HIPCHK(hipMemsetAsync(h->img.ages.d, 0, h->img.ages.bytes(), h->stream));
     return NXC_OK;
 }
 
@@ -3611,7 +3560,7 @@ int nxc_density_set(nxc_handle *h, const nxc_density_desc *d)
     h->have_density = false;
     h->have_dens_mom = false;
     if (int rc = spectrum_free(h)) return rc;      // up to gigabytes: not kept for a set that may never enable one
-    if (int rc = density_ages_free(h)) return rc;  // likewise
+    if (int rc = h->dens_ages.release()) return rc; // likewise
     std::vector<double> pts((size_t)Q * 4, 0.0);
     for (int64_t j = 0; j < Q; j++)
         for (int a = 0; a < 3; a++) pts[4 * j + a] = d->points[3 * j + a];
@@ -3798,23 +3747,7 @@ int nxc_density_spectrum_download(nxc_handle *h, double *sums)
 
 int nxc_density_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi)
 {
-    return guarded([&]() -> int {
-    if (!h || !h->have_density) return fail(NXC_ERR_STATE, DENSITY_SAMPLES.unset);
-    if (na != 0) {     // before anything is freed or allocated
-        const std::string why = check_density_ages_args(h->dens_q, na, t0, a_lo, a_hi);
-        if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
-    }
-    HIPCHK(hipSetDevice(h->device));
-    int rc = density_ages_free(h);
-    if (rc || na == 0) return rc;
-    h->dens_ageK = AgeK{(int)na, t0, a_lo, ages_inv_da(na, a_lo, a_hi)};
-    const size_t bytes = density_ages_bytes(h);
-    if ((rc = h->d_dens_ages.ensure(bytes))) return rc;
-    HIPCHK(hipMemsetAsync(h->d_dens_ages, 0, bytes, h->stream));
-    HIPCHK(stream_sync(h));
-    h->have_dens_ages = true;
-    return NXC_OK;
-    });
+    return ages_enable(h, DENSITY_AGES, 0, na, t0, a_lo, a_hi);
 }
 
 int nxc_density_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
@@ -3841,33 +3774,17 @@ int nxc_density_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t f
 
 int nxc_density_ages_download(nxc_handle *h, double *sums)
 {
-    return guarded([&]() -> int {
-    if (int rc = density_ages_ready(h, sums)) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(sums, h->d_dens_ages, density_ages_bytes(h), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(stream_sync(h));
-    return NXC_OK;
-    });
+    return ages_copy(h, DENSITY_AGES, sums, hipMemcpyDeviceToHost);
 }
 
 int nxc_density_ages_upload(nxc_handle *h, const double *sums)
 {
-    return guarded([&]() -> int {
-    if (int rc = density_ages_ready(h, sums)) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(h->d_dens_ages, sums, density_ages_bytes(h), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(stream_sync(h));
-    return NXC_OK;
-    });
+    return ages_copy(h, DENSITY_AGES, const_cast<double *>(sums), hipMemcpyHostToDevice);
 }
 
 int nxc_density_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out)
 {
-    return guarded([&]() -> int {
-    if (int rc = density_ages_ready(h, out)) return rc;
-    return ages_block_apply(h, (size_t)h->dens_q, (int64_t)h->dens_ageK.na + 2, h->d_dens_ages.get(), ne,
-                            K, out);
-    });
+    return ages_apply(h, DENSITY_AGES, ne, K, out);
 }
 
 // ---- CameraImage ---------------------------------------------------------------------------------
@@ -3903,7 +3820,7 @@ int nxc_camera_set(nxc_handle *h, const nxc_camera_desc *d)
     h->have_camera = false;
     h->cam_px.have_mom = false;
     h->cam_px.have_cube = false;
-    h->cam_px.have_ages = false;
+    h->cam_px.ages.have = false;
     const size_t npix = (size_t)d->nx * (size_t)d->nz;
     if ((rc = h->d_blob_cam.ensure(blob.size())) ||
         (rc = h->cam_px.image.ensure(2 * npix * sizeof(double))))
@@ -4011,7 +3928,7 @@ int nxc_camera_cube_download(nxc_handle *h, double *sums)
 
 int nxc_camera_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi)
 {
-    return pixel_ages_enable(h, CAMERA_SAMPLES, na, t0, a_lo, a_hi);
+    return ages_enable(h, CAMERA_AGES, 0, na, t0, a_lo, a_hi);
 }
 
 int nxc_camera_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
@@ -4036,17 +3953,17 @@ int nxc_camera_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t fi
 
 int nxc_camera_ages_download(nxc_handle *h, double *sums)
 {
-    return pixel_ages_download(h, CAMERA_SAMPLES, CAMERA_AGES_SAMPLES, sums);
+    return ages_copy(h, CAMERA_AGES, sums, hipMemcpyDeviceToHost);
 }
 
 int nxc_camera_ages_upload(nxc_handle *h, const double *sums)
 {
-    return pixel_ages_upload(h, CAMERA_SAMPLES, CAMERA_AGES_SAMPLES, sums);
+    return ages_copy(h, CAMERA_AGES, const_cast<double *>(sums), hipMemcpyHostToDevice);
 }
 
 int nxc_camera_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out)
 {
-    return pixel_ages_apply(h, CAMERA_SAMPLES, CAMERA_AGES_SAMPLES, ne, K, out);
+    return ages_apply(h, CAMERA_AGES, ne, K, out);
 }
 
 // ---- ShellMap --------------------------------------------------------------------------------------
@@ -4085,7 +4002,7 @@ int nxc_shell_set(nxc_handle *h, const nxc_shell_desc *d)
     h->have_shell = false;
     h->have_shell_mom = false;                 // the moments go with the map they were enabled on
     if ((rc = h->d_shell_mom.release())) return rc;
-    if ((rc = shell_ages_free(h))) return rc;  // likewise the ages
+    if ((rc = h->shell_ages.release())) return rc;  // likewise the ages
     const size_t cells = (size_t)d->nlon * (size_t)d->nlat;
     const size_t pair_bytes = (size_t)K.replicas * 2 * cells * sizeof(double);
     const size_t plane_bytes = 2 * (size_t)K.plane * sizeof(double);
@@ -4209,80 +4126,42 @@ int nxc_shell_moments_download(nxc_handle *h, double *sums)
 // ---- ShellMap ages ---------------------------------------------------------------------------------
 int nxc_shell_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi)
 {
-    return guarded([&]() -> int {
-    if (!h || !h->have_shell) return fail(NXC_ERR_STATE, SHELL_SAMPLES.unset);
-    if (na != 0) {     // before anything is freed or allocated
-        const std::string why = check_shell_ages_args(shell_records(h), na, t0, a_lo, a_hi);
-        if (!why.empty()) return fail(NXC_ERR_ARG, why.c_str());
-    }
-    HIPCHK(hipSetDevice(h->device));
-    int rc = shell_ages_free(h);
-    if (rc || na == 0) return rc;
-    h->shell_ageK = AgeK{(int)na, t0, a_lo, ages_inv_da(na, a_lo, a_hi)};
-    const size_t bytes = shell_ages_bytes(shell_records(h), na);
-    if ((rc = h->d_shell_ages.ensure(bytes))) return rc;
-    HIPCHK(hipMemsetAsync(h->d_shell_ages, 0, bytes, h->stream));
-    HIPCHK(stream_sync(h));
-    h->have_shell_ages = true;
-    return NXC_OK;
-    });
+    return ages_enable(h, SHELL_AGES, 0, na, t0, a_lo, a_hi);
 }
 
 int nxc_shell_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
                               const double *y, const double *z, const double *vy, const double *frac)
 {
-    if (int rc = shell_ages_need_set(h)) return rc;
+    if (int rc = pixel_moments_need_set(h, SHELL_SAMPLES)) return rc;
     return accumulate_columns<double>(h, SHELL_AGES_SAMPLES, p, x, y, z, vy, frac, nullptr, nullptr, time);
 }
 
 int nxc_shell_ages_accumulate_f32(nxc_handle *h, int64_t p, const float *time, const float *x,
                                   const float *y, const float *z, const float *vy, const float *frac)
 {
-    if (int rc = shell_ages_need_set(h)) return rc;
+    if (int rc = pixel_moments_need_set(h, SHELL_SAMPLES)) return rc;
     return accumulate_columns<float>(h, SHELL_AGES_SAMPLES, p, x, y, z, vy, frac, nullptr, nullptr, time);
 }
 
 int nxc_shell_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t first, int64_t count)
 {
-    if (int rc = shell_ages_need_set(h)) return rc;
+    if (int rc = pixel_moments_need_set(h, SHELL_SAMPLES)) return rc;
     return accumulate_rows(h, SHELL_AGES_SAMPLES, r, first, count);
 }
 
 int nxc_shell_ages_download(nxc_handle *h, double *sums)
 {
-    return guarded([&]() -> int {
-    if (int rc = shell_ages_ready(h, sums)) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(sums, h->d_shell_ages, shell_ages_bytes(shell_records(h), h->shell_ageK.na),
-                          hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(stream_sync(h));
-    return NXC_OK;
-    });
+    return ages_copy(h, SHELL_AGES, sums, hipMemcpyDeviceToHost);
 }
 
 int nxc_shell_ages_upload(nxc_handle *h, const double *sums)
 {
-    return guarded([&]() -> int {
-    if (int rc = shell_ages_ready(h, sums)) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpyAsync(h->d_shell_ages, sums, shell_ages_bytes(shell_records(h), h->shell_ageK.na),
-                          hipMemcpyHostToDevice, h->stream));
-    HIPCHK(stream_sync(h));
-    return NXC_OK;
-    });
+    return ages_copy(h, SHELL_AGES, const_cast<double *>(sums), hipMemcpyHostToDevice);
 }
 
 int nxc_shell_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out)
 {
-    return guarded([&]() -> int {
-    if (int rc = shell_ages_ready(h, out)) return rc;
-    // age plane A, then age plane B: each the image's contraction over the R records
-    const size_t R = (size_t)shell_records(h);
-    const int64_t planes = (int64_t)h->shell_ageK.na + 2;
-    if (int rc = ages_block_apply(h, R, planes, h->d_shell_ages.get(), ne, K, out)) return rc;
-    return ages_block_apply(h, R, planes, h->d_shell_ages.get() + R * (size_t)planes * 2, ne, K,
-                            out + (size_t)ne * R * 2);
-    });
+    return ages_apply(h, SHELL_AGES, ne, K, out);
 }
 
 // ---- source maps ---------------------------------------------------------------------------------
@@ -4831,7 +4710,7 @@ int nxc_image_cube_download(nxc_handle *h, double *sums)
 
 int nxc_image_ages_enable(nxc_handle *h, int64_t na, double t0, double a_lo, double a_hi)
 {
-    return pixel_ages_enable(h, IMAGE_SAMPLES, na, t0, a_lo, a_hi);
+    return ages_enable(h, IMAGE_AGES, 0, na, t0, a_lo, a_hi);
 }
 
 int nxc_image_ages_accumulate(nxc_handle *h, int64_t p, const double *time, const double *x,
@@ -4856,17 +4735,17 @@ int nxc_image_ages_accumulate_rows(nxc_handle *h, const nxc_rows *r, int64_t fir
 
 int nxc_image_ages_download(nxc_handle *h, double *sums)
 {
-    return pixel_ages_download(h, IMAGE_SAMPLES, IMAGE_AGES_SAMPLES, sums);
+    return ages_copy(h, IMAGE_AGES, sums, hipMemcpyDeviceToHost);
 }
 
 int nxc_image_ages_upload(nxc_handle *h, const double *sums)
 {
-    return pixel_ages_upload(h, IMAGE_SAMPLES, IMAGE_AGES_SAMPLES, sums);
+    return ages_copy(h, IMAGE_AGES, const_cast<double *>(sums), hipMemcpyHostToDevice);
 }
 
 int nxc_image_ages_apply(nxc_handle *h, int64_t ne, const double *K, double *out)
 {
-    return pixel_ages_apply(h, IMAGE_SAMPLES, IMAGE_AGES_SAMPLES, ne, K, out);
+    return ages_apply(h, IMAGE_AGES, ne, K, out);
 }
 
 int nxc_los_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
@@ -4937,7 +4816,7 @@ int nxc_los_profile_download(nxc_handle *h, double *sums, double *moments)
 
 int nxc_los_ages_enable(nxc_handle *h, int64_t S, int64_t na, double t0, double a_lo, double a_hi)
 {
-    return guarded([&]() -> int { return los_ages_enable(h, S, na, t0, a_lo, a_hi); });
+    return ages_enable(h, LOS_AGES_BLOCK, S, na, t0, a_lo, a_hi);
 }
 
 int nxc_los_ages_accumulate(nxc_handle *h, const nxc_los_desc *d, int64_t S, const double *sc,
@@ -4970,7 +4849,7 @@ int nxc_los_ages_accumulate_f32(nxc_handle *h, const nxc_los_desc *d, int64_t S,
 
 int nxc_los_ages_download(nxc_handle *h, double *sums)
 {
-    return guarded([&]() -> int { return los_ages_download(h, sums); });
+    return ages_copy(h, LOS_AGES_BLOCK, sums, hipMemcpyDeviceToHost);
 }
 
 // ---- RCCL -------------------------------------------------------------------------------------

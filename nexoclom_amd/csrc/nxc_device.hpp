@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "nxc_math.hpp"
 #include "nxc_fused_variant.hpp"
 
@@ -1187,27 +1188,34 @@ struct CubeK {
     double v_lo, inv_dv;    // [R/s], [s/R]
 };
 
+// The under/over bin rule of every binned axis here (Doppler, age, altitude, speed): the record of
+// the bin coordinate t among n bins with one record below and one above them,
+//     0 if t < 0,   1 + (int)t if 0 <= t < n,   n + 1 otherwise
+// (otherwise: at or above the last edge, or t not a number -- both comparisons are false for a NaN).
+NXC_DEV int record_bin(double t, int n)
+{
+    int k = n + 1;
+    if (t < 0.0) k = 0;
+    else if (t < (double)n) k = 1 + (int)t;
+    return k;
+}
+
 NXC_DEV void pixel_cube_add(const CubeK &Q, bool ok, int pix, double w, double vlos,
                             double *__restrict__ cube2)
 {
     const bool has = ok && w != 0.0;
     const double t = (vlos - Q.v_lo) * Q.inv_dv;
-    int k = Q.nv + 1;
-    if (t < 0.0) k = 0;
-    else if (t < (double)Q.nv) k = 1 + (int)t;
+    const int k = record_bin(t, Q.nv);
     add_record_pairs(has, pix * (Q.nv + 2) + k, w, w * w, cube2);
 }
 
-// The same rule on its own, for the line-of-sight profile (k_los_pairs, k_los), which files a pair
-// under spectrum (nv + 2) + k with per-lane atomics.  (pixel_cube_add keeps its own copy: taken
-// from here its kernels compile to another instruction order.)
+// The same bin on its own, for the line-of-sight profile (k_los_pairs, k_los), which files a pair
+// under spectrum (nv + 2) + k with per-lane atomics.  (pixel_cube_add forms t itself and shares only
+// record_bin: calling this, which takes the CubeK by reference, was tried and changes the
+// instruction stream of k_image_cube and k_camera_cube.)
 NXC_DEV int cube_plane(const CubeK &Q, double vlos)
 {
-    const double t = (vlos - Q.v_lo) * Q.inv_dv;
-    int k = Q.nv + 1;
-    if (t < 0.0) k = 0;
-    else if (t < (double)Q.nv) k = 1 + (int)t;
-    return k;
+    return record_bin((vlos - Q.v_lo) * Q.inv_dv, Q.nv);
 }
 
 // ---- age cube: a sample's weight filed under its age ----------------------------------------------
@@ -1232,23 +1240,19 @@ NXC_DEV void pixel_ages_add(const AgeK &Q, bool ok, int pix, double w, int64_t i
     double age = 0.0;
     if (has) age = Q.t0 - (double)time_col[i];
     const double u = (age - Q.a_lo) * Q.inv_da;
-    int k = Q.na + 1;
-    if (u < 0.0) k = 0;
-    else if (u < (double)Q.na) k = 1 + (int)u;
+    const int k = record_bin(u, Q.na);
     add_record_pairs(has, pix * (Q.na + 2) + k, w, w * w, ages2);
 }
 
-// The same rule on its own, for the line-of-sight ages (k_los_pairs, k_los; include/nexoclom_hip.h,
+// The same bin on its own, for the line-of-sight ages (k_los_pairs, k_los; include/nexoclom_hip.h,
 // "Line-of-sight ages"), which file a pair under spectrum (na + 2) + k with per-lane atomics.
-// (pixel_ages_add keeps its own copy, for cube_plane's reason.)
+// (pixel_ages_add and shell_ages_add form u themselves and share only record_bin: one function of
+// the AgeK by reference for both was tried and changes the instruction stream of k_image_ages and
+// k_camera_ages -- cube_plane's finding.)
 NXC_DEV int age_plane(const AgeK &Q, double time)
 {
     const double age = Q.t0 - time;
-    const double u = (age - Q.a_lo) * Q.inv_da;
-    int k = Q.na + 1;
-    if (u < 0.0) k = 0;
-    else if (u < (double)Q.na) k = 1 + (int)u;
-    return k;
+    return record_bin((age - Q.a_lo) * Q.inv_da, Q.na);
 }
 
 // ---- ShellMap: the same sample filed by local time, latitude and altitude --------------------------
@@ -1265,65 +1269,30 @@ struct ShellK {
     int64_t pairs;          // doubles from one copy to the next: cells 2
 };
 
-// locate + weight + count + add of one sample per lane, and its two records: k_shell's sample.
-// Wave-cooperative like image_located.  The atan2 is the only value here that is not correctly
-// rounded; it reaches nothing but bin_index.
-NXC_DEV void shell_located(const ShellK &S, const ImageK &G, const ImageRegs &R, const PixelSample &s,
-                           double *__restrict__ acc2, double *__restrict__ planes2,
-                           unsigned long long &binned, unsigned long long &nonfinite)
-{
-    bool ok = false;
-    int cell = -1;
-    double w = 0.0, c = 0.0, r = 1.0;
-    if (s.has) {
-        const double radvel = s.vy + R.vrplanet;
-        const double r2 = (s.x * s.x + s.y * s.y) + s.z * s.z;
-        r = nxc_sqrt(r2);
-        const double mu = nxc_div(s.z, r);
-        double lon = atan2(s.x, -s.y);
-        if (lon < 0.0) lon = lon + 0x1.921fb54442d18p+2;
-        const int ix = bin_index(lon, R.xedges, R.nx, R.x_lo, R.x_hi, R.x_inv_step);
-        const int iz = bin_index(mu, R.zedges, R.nz, R.z_lo, R.z_hi, R.z_inv_step);
-        if (ix < 0 || iz < 0) {
-            if (!(__builtin_fabs(s.frac) <= 1.7976931348623157e308) || radvel != radvel) nonfinite++;
-        } else {
-            cell = ix * R.nz + iz;
-            double f = s.frac;
-            if (R.quantity != 0) f = sunlit(s.x, s.y, s.z) ? f : f * 0.0;
-            ok = image_weight(G, R, radvel, f, w);
-            if (ok) {
-                c = nxc_div(w, r2);
-                ok = __builtin_fabs(c) <= 1.7976931348623157e308;
-            }
-            if (!ok) nonfinite++;
-        }
-    }
-    binned += ok;
-    image_add_pairs(ok, cell, c, acc2);
-    const bool has = ok && w != 0.0;
-    const double t = (r - S.r_lo) * S.inv_dr;
-    int k = S.nalt + 1;
-    if (t < 0.0) k = 0;
-    else if (t < (double)S.nalt) k = 1 + (int)t;
-    const int rec = cell * (S.nalt + 2) + k;
-    add_record_pairs(has, rec, w, w * w, planes2);
-    add_record_pairs(has, rec, c, c * c, planes2 + S.plane);
-}
-
-// What the front of the shell moments' pass hands to its tail: did the sample file a weight
-// w != 0 under a record of the planes, which record, and the weight.
+// What the front of a shell pass hands to its tail.  ShellHit, for the moments: did the sample file
+// a weight w != 0 under a record of the planes, which record, and the weight.  ShellAgesHit, for the
+// ages (include/nexoclom_hip.h, "ShellMap ages"): the same and the column term c = w / r2 of plane B.
 struct ShellHit {
     bool has;
     int rec;
     double w;
 };
 
-// shell_located, operation by operation, handing on what it filed: the front of k_shell_moments.
-// (A copy: with shell_located calling this and dropping the result, k_shell compiles to another
-// instruction order -- pixel_cube_add's reason.)
-NXC_DEV ShellHit shell_front(const ShellK &S, const ImageK &G, const ImageRegs &R, const PixelSample &s,
-                             double *__restrict__ acc2, double *__restrict__ planes2,
-                             unsigned long long &binned, unsigned long long &nonfinite)
+struct ShellAgesHit {
+    bool has;
+    int rec;
+    double w, c;
+};
+
+// locate + weight + count + add of one sample per lane, and its two records: the shell sample.
+// Hit says what is handed on: void for k_shell, ShellHit for the front of k_shell_moments,
+// ShellAgesHit for the front of k_shell_ages; the operations are the same, and each kernel compiles
+// to the instructions it had with a front of its own.  Wave-cooperative like image_located.  The
+// atan2 is the only value here that is not correctly rounded; it reaches nothing but bin_index.
+template <typename Hit>
+NXC_DEV Hit shell_located(const ShellK &S, const ImageK &G, const ImageRegs &R, const PixelSample &s,
+                          double *__restrict__ acc2, double *__restrict__ planes2,
+                          unsigned long long &binned, unsigned long long &nonfinite)
 {
     bool ok = false;
     int cell = -1;
@@ -1355,18 +1324,17 @@ NXC_DEV ShellHit shell_front(const ShellK &S, const ImageK &G, const ImageRegs &
     image_add_pairs(ok, cell, c, acc2);
     const bool has = ok && w != 0.0;
     const double t = (r - S.r_lo) * S.inv_dr;
-    int k = S.nalt + 1;
-    if (t < 0.0) k = 0;
-    else if (t < (double)S.nalt) k = 1 + (int)t;
+    const int k = record_bin(t, S.nalt);
     const int rec = cell * (S.nalt + 2) + k;
     add_record_pairs(has, rec, w, w * w, planes2);
     add_record_pairs(has, rec, c, c * c, planes2 + S.plane);
-    return {has, rec, w};
+    if constexpr (std::is_same_v<Hit, ShellHit>) return {has, rec, w};
+    else if constexpr (std::is_same_v<Hit, ShellAgesHit>) return {has, rec, w, c};
 }
 
 // ---- ShellMap moments: the velocity of a filed sample in the local spherical basis ------------------
 // (include/nexoclom_hip.h, "ShellMap moments", holds the definition; the operations below are in its
-// order.)  A sample that shell_front filed under record `rec` with w != 0, and that is not exactly
+// order.)  A sample that shell_located<ShellHit> filed under record `rec` with w != 0, and that is not exactly
 // on the polar axis (p2 != 0), adds twelve sums to the same record of six planes of mom2,
 // [6][cells][nalt + 2] 16-byte records S.plane doubles apart.  vx and vz are read only by a lane
 // with h.has (0 otherwise).  Non-finite velocities are not filtered.  Wave-cooperative: all 64 lanes
@@ -1398,65 +1366,11 @@ NXC_DEV void shell_moments_add(const ShellK &S, const ShellHit &h, const PixelSa
 }
 
 // ---- ShellMap ages: a filed sample's two records under its age --------------------------------------
-// (include/nexoclom_hip.h, "ShellMap ages", holds the definition.)  What the front of the ages' pass
-// hands to its tail: ShellHit and the column term c = w / r2 of plane B.
-struct ShellAgesHit {
-    bool has;
-    int rec;
-    double w, c;
-};
-
-// shell_located, operation by operation, handing on what it filed: the front of k_shell_ages.  (A
-// copy of its own, for shell_front's reason: ShellHit with a fourth member, or shell_front calling
-// this, would change k_shell_moments' instruction stream.)
-NXC_DEV ShellAgesHit shell_ages_front(const ShellK &S, const ImageK &G, const ImageRegs &R,
-                                      const PixelSample &s, double *__restrict__ acc2,
-                                      double *__restrict__ planes2, unsigned long long &binned,
-                                      unsigned long long &nonfinite)
-{
-    bool ok = false;
-    int cell = -1;
-    double w = 0.0, c = 0.0, r = 1.0;
-    if (s.has) {
-        const double radvel = s.vy + R.vrplanet;
-        const double r2 = (s.x * s.x + s.y * s.y) + s.z * s.z;
-        r = nxc_sqrt(r2);
-        const double mu = nxc_div(s.z, r);
-        double lon = atan2(s.x, -s.y);
-        if (lon < 0.0) lon = lon + 0x1.921fb54442d18p+2;
-        const int ix = bin_index(lon, R.xedges, R.nx, R.x_lo, R.x_hi, R.x_inv_step);
-        const int iz = bin_index(mu, R.zedges, R.nz, R.z_lo, R.z_hi, R.z_inv_step);
-        if (ix < 0 || iz < 0) {
-            if (!(__builtin_fabs(s.frac) <= 1.7976931348623157e308) || radvel != radvel) nonfinite++;
-        } else {
-            cell = ix * R.nz + iz;
-            double f = s.frac;
-            if (R.quantity != 0) f = sunlit(s.x, s.y, s.z) ? f : f * 0.0;
-            ok = image_weight(G, R, radvel, f, w);
-            if (ok) {
-                c = nxc_div(w, r2);
-                ok = __builtin_fabs(c) <= 1.7976931348623157e308;
-            }
-            if (!ok) nonfinite++;
-        }
-    }
-    binned += ok;
-    image_add_pairs(ok, cell, c, acc2);
-    const bool has = ok && w != 0.0;
-    const double t = (r - S.r_lo) * S.inv_dr;
-    int k = S.nalt + 1;
-    if (t < 0.0) k = 0;
-    else if (t < (double)S.nalt) k = 1 + (int)t;
-    const int rec = cell * (S.nalt + 2) + k;
-    add_record_pairs(has, rec, w, w * w, planes2);
-    add_record_pairs(has, rec, c, c * c, planes2 + S.plane);
-    return {has, rec, w, c};
-}
-
-// A sample that shell_ages_front filed under record `rec` adds {w, w w} to record
+// (include/nexoclom_hip.h, "ShellMap ages", holds the definition.)
+// A sample that shell_located<ShellAgesHit> filed under record `rec` adds {w, w w} to record
 // rec (na + 2) + ka of age plane A and {c, c c} to the same record of age plane B, S.plane (na + 2)
 // doubles further on; ka is pixel_ages_add's plane of the row's time, which only a lane with h.has
-// reads.  The record index stays below 2^31 (check_shell_ages_args); a lane without h.has forms
+// reads.  The record index stays below 2^31 (check_ages_args); a lane without h.has forms
 // none.  Wave-cooperative: all 64 lanes call it from uniform control flow; two requests per filed
 // sample, none in a trip without one.
 template <typename T>
@@ -1466,9 +1380,7 @@ NXC_DEV void shell_ages_add(const ShellK &S, const AgeK &Q, const ShellAgesHit &
     double age = 0.0;
     if (h.has) age = Q.t0 - (double)time_col[i];
     const double u = (age - Q.a_lo) * Q.inv_da;
-    int ka = Q.na + 1;
-    if (u < 0.0) ka = 0;
-    else if (u < (double)Q.na) ka = 1 + (int)u;
+    const int ka = record_bin(u, Q.na);
     const int rec = h.has ? h.rec * (Q.na + 2) + ka : 0;
     add_record_pairs(h.has, rec, h.w, h.w * h.w, ages2);
     add_record_pairs(h.has, rec, h.c, h.c * h.c, ages2 + S.plane * (int64_t)(Q.na + 2));

@@ -3084,11 +3084,7 @@ k_density_spectrum(DensityK K, SpectrumK S, int64_t n, int64_t n_points, const T
                          const double s = __builtin_sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
                          const double a = -((c[0] * fr[4] + c[1] * fr[5]) + c[2] * fr[6]);
                          seen = S.all_sky != 0 || a >= S.cos_half * s;
-                         const double t = (s - S.s_lo) * S.inv_ds;
-                         int k = S.nv + 1;
-                         if (t < 0.0) k = 0;
-                         else if (t < (double)S.nv) k = 1 + (int)t;
-                         rec = q * (S.nv + 2) + k;
+                         rec = q * (S.nv + 2) + record_bin((s - S.s_lo) * S.inv_ds, S.nv);
                          g = w * s;
                      }
                      add_record_pairs(hit, q, w, 1.0, acc2);
@@ -3105,7 +3101,7 @@ k_density_spectrum(DensityK K, SpectrumK S, int64_t n, int64_t n_points, const T
 //     {f, 1}      to record q of acc2 (k_density's own pair array)
 //     {f, f f}    to record q (na + 2) + k of ages2, [Q][na + 2] records.
 // The two pair adds are made from uniform control flow (add_record_pairs), and a trip in which no
-// lane of the wave hits makes none.  The record index stays below 2^31 (check_density_ages_args).
+// lane of the wave hits makes none.  The record index stays below 2^31 (check_ages_args).
 // Nothing is filtered: f == 0 adds zeros and is counted, a non-finite f poisons what it reaches.
 template <typename T>
 __global__ void __launch_bounds__(NXC_BLOCK)
@@ -3234,13 +3230,13 @@ k_shell(ShellK S, const unsigned char *__restrict__ blob, int64_t stage_bytes, i
                (int64_t)gridDim.x * blockDim.x,
                [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
                    unsigned long long &binned, unsigned long long &nonfinite) {
-                   shell_located(S, G, IR, s, own2, planes2, binned, nonfinite);
+                   shell_located<void>(S, G, IR, s, own2, planes2, binned, nonfinite);
                });
 }
 
 // ShellMap(moments=True): k_shell's pass over seven columns; a sample filed under its record with
 // w != 0 also adds its twelve velocity sums, resolved in the local spherical basis, to the same
-// record of the six planes of mom2, [6][cells][nalt + 2] 16-byte records (shell_front,
+// record of the six planes of mom2, [6][cells][nalt + 2] 16-byte records (shell_located<ShellHit>,
 // shell_moments_add): at most nine atomic requests per binned sample.  Block size, LDS blob and the
 // copies of the pair array are k_shell's.
 template <typename T>
@@ -3256,14 +3252,14 @@ k_shell_moments(ShellK S, const unsigned char *__restrict__ blob, int64_t stage_
                (int64_t)gridDim.x * blockDim.x,
                [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
                    unsigned long long &binned, unsigned long long &nonfinite) {
-                   const ShellHit h = shell_front(S, G, IR, s, own2, planes2, binned, nonfinite);
+                   const auto h = shell_located<ShellHit>(S, G, IR, s, own2, planes2, binned, nonfinite);
                    shell_moments_add(S, h, s, vx, vz, mom2);
                });
 }
 
 // ShellMap(ages=...): k_shell's pass over six columns, time first; a sample filed under its record
 // with w != 0 also adds {w, w w} and {c, c c} to that record's plane of its age in the two planes
-// of ages2, [2][cells (nalt + 2)][na + 2] 16-byte records (shell_ages_front, shell_ages_add): at
+// of ages2, [2][cells (nalt + 2)][na + 2] 16-byte records (shell_located<ShellAgesHit>, shell_ages_add): at
 // most five atomic requests per binned sample.  The time column is read by the lanes that file a
 // weight.  The age scalars travel as a kernel argument of their own; block size, LDS blob and the
 // copies of the pair array are k_shell's.
@@ -3280,7 +3276,7 @@ k_shell_ages(ShellK S, AgeK Q, const unsigned char *__restrict__ blob, int64_t s
                (int64_t)gridDim.x * blockDim.x,
                [&](const ImageK &G, const ImageRegs &IR, const PixelSample &s,
                    unsigned long long &binned, unsigned long long &nonfinite) {
-                   const ShellAgesHit h = shell_ages_front(S, G, IR, s, own2, planes2, binned, nonfinite);
+                   const auto h = shell_located<ShellAgesHit>(S, G, IR, s, own2, planes2, binned, nonfinite);
                    shell_ages_add(S, Q, h, s.i, time, ages2);
                });
 }

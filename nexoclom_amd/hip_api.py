@@ -975,9 +975,16 @@ class Context:
         setattr(self, f'_{prefix}_ages_na', na)
         self.ages_owner.pop(prefix, None)
 
+    def _block_shape(self, prefix):
+        """(sets, records) of a block of sums: ((), the grid's shape), or for the shell map its two
+        planes and ``_shell_records()``"""
+        if prefix == 'shell':
+            return (2,), self._shell_records()
+        return (), tuple(getattr(self, prefix + '_shape', None) or (0, 0))
+
     def _ages_upload(self, prefix, sums):
-        shape = tuple(getattr(self, prefix + '_shape', None) or (0, 0)) + \
-            (getattr(self, f'_{prefix}_ages_na', 0) + 2, 2)
+        sets, records = self._block_shape(prefix)
+        shape = sets + records + (getattr(self, f'_{prefix}_ages_na', 0) + 2, 2)
         sums = _f64(sums)
         if sums.shape != shape:
             raise ValueError(f'ages_upload: sums of shape {sums.shape}, the block has {shape}')
@@ -989,14 +996,27 @@ class Context:
         if K.ndim != 2 or K.shape[0] != getattr(self, f'_{prefix}_ages_na', 0) + 2:
             raise ValueError('ages_apply: K must have one row per plane, (na + 2, ne)')
         ne = K.shape[1]
-        out = np.zeros((ne,) + tuple(getattr(self, prefix + '_shape', None) or (0, 0)) + (2,))
+        sets, records = self._block_shape(prefix)
+        out = np.zeros(sets + (ne,) + records + (2,))
         self._check(getattr(self.lib, f'nxc_{prefix}_ages_apply')(self._h, ne, _p(K), _p(out)))
         return out
+
+    def ages_transient(self, prefix, token, setup, sums, K):
+        """The device's part of a product's ``transient()``.  Unless the resident ``prefix`` block
+        is the total of the object that holds ``token``, it is seated again: ``setup(self)`` sets
+        up and enables, ``sums()`` is uploaded and the owner recorded.  Returns the block
+        contracted with ``K`` (``<prefix>_ages_apply``)."""
+        if self.ages_owner.get(prefix) is not token:
+            setup(self)
+            getattr(self, prefix + '_ages_upload')(sums())
+            self.ages_owner[prefix] = token
+        return getattr(self, prefix + '_ages_apply')(K)
 
     def _pixel_sums_download(self, prefix, what):
         bins = {'cube': f'_{prefix}_cube_nv', 'ages': f'_{prefix}_ages_na'}
         per_pixel = (4,) if what == 'moments' else (getattr(self, bins[what], 0) + 2, 2)
-        sums = np.zeros(tuple(getattr(self, prefix + '_shape', None) or (0, 0)) + per_pixel)
+        sets, records = self._block_shape(prefix)
+        sums = np.zeros(sets + records + per_pixel)
         self._check(getattr(self.lib, f'nxc_{prefix}_{what}_download')(self._h, _p(sums)))
         return sums
 
@@ -1486,30 +1506,17 @@ class Context:
         """(2, nlon, nlat, nalt + 2, na + 2, 2) float64: {sum w, sum w w} and {sum c, sum c c},
         c = w / r^2, per cell, altitude record and age plane (0 below, 1..na the bins, na + 1
         above; include/nexoclom_hip.h, "ShellMap ages")."""
-        sums = np.zeros((2,) + self._shell_records() + (getattr(self, '_shell_ages_na', 0) + 2, 2))
-        self._check(self.lib.nxc_shell_ages_download(self._h, _p(sums)))
-        return sums
+        return self._pixel_sums_download('shell', 'ages')
 
     def shell_ages_upload(self, sums):
         """Replace the age block by ``sums`` (2, nlon, nlat, nalt + 2, na + 2, 2)."""
-        shape = (2,) + self._shell_records() + (getattr(self, '_shell_ages_na', 0) + 2, 2)
-        sums = _f64(sums)
-        if sums.shape != shape:
-            raise ValueError(f'ages_upload: sums of shape {sums.shape}, the block has {shape}')
-        self.ages_owner.pop('shell', None)
-        self._check(self.lib.nxc_shell_ages_upload(self._h, _p(sums)))
+        self._ages_upload('shell', sums)
 
     def shell_ages_apply(self, K):
         """(2, ne, nlon, nlat, nalt + 2, 2) = both planes of the resident age block contracted
         with ``K`` (na + 2, ne), as ``image_ages_apply`` does it for pixels: {sum_k S K,
         sum_k WW K K} per epoch and record, summed over the age planes in their order."""
-        K = _f64(K)
-        if K.ndim != 2 or K.shape[0] != getattr(self, '_shell_ages_na', 0) + 2:
-            raise ValueError('ages_apply: K must have one row per plane, (na + 2, ne)')
-        ne = K.shape[1]
-        out = np.zeros((2, ne) + self._shell_records() + (2,))
-        self._check(self.lib.nxc_shell_ages_apply(self._h, ne, _p(K), _p(out)))
-        return out
+        return self._ages_apply('shell', K)
 
     # -- LOSResultFitted ----------------------------------------------------------------------
     def pairs_create(self, capacity):

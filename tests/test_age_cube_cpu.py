@@ -403,6 +403,76 @@ def test_argument_check_and_plan_as_a_host_program(tmp_path):
     assert hip_api.ages_apply_plan(66, 64) == (67, 15, 30)
 
 
+# The complete text of every refusal of the one check (nxc_ages_check.hpp) per subject, as each
+# subject's driver under tests/tools prints it: {driver: {the driver's case: the refusal}}.  Written
+# down from what the drivers printed while each subject still had a check header of its own.
+REFUSALS = {
+    'ages_check': {
+        'no pixels': 'age cube: the image has no pixels',
+        'na = 0': 'age cube: na must be at least 1',
+        't0 NaN': 'age cube: t0 must be finite',
+        'a_lo NaN': 'age cube: a_lo and a_hi must be finite',
+        'empty range': 'age cube: a_lo must be below a_hi',
+        'width overflows': 'age cube: a_hi - a_lo must be finite',
+        '1 pixel, 2^31 records': 'age cube: n_pix * (na + 2) must be below 2^31 records',
+        'na = INT64_MAX': 'age cube: n_pix * (na + 2) must be below 2^31 records',
+        'ne = 0': 'age cube: ne must be at least 1',
+        'ne = 2^31': 'age cube: ne must be below 2^31',
+        'K null': 'age cube: K is null',
+        'K with a NaN at its end': 'age cube: K holds a value that is not finite',
+    },
+    'density_ages_check': {
+        'no points': 'density ages: the index has no points',
+        'na = 0': 'density ages: na must be at least 1',
+        't0 NaN': 'density ages: t0 must be finite',
+        'a_lo NaN': 'density ages: a_lo and a_hi must be finite',
+        'empty range': 'density ages: a_lo must be below a_hi',
+        'width overflows': 'density ages: a_hi - a_lo must be finite',
+        '1 point, 2^31 records': 'density ages: n_points * (na + 2) must be below 2^31 records',
+        'n_points = INT64_MAX': 'density ages: n_points * (na + 2) must be below 2^31 records',
+    },
+    'los_ages_check': {
+        'no spectra': 'line-of-sight ages: S must be at least 1',
+        'na = 0': 'line-of-sight ages: na must be at least 1',
+        't0 NaN': 'line-of-sight ages: t0 must be finite',
+        'a_lo NaN': 'line-of-sight ages: a_lo and a_hi must be finite',
+        'empty range': 'line-of-sight ages: a_lo must be below a_hi',
+        'width overflows': 'line-of-sight ages: a_hi - a_lo must be finite',
+        '1 spectrum, 2^31 records': 'line-of-sight ages: S * (na + 2) must be below 2^31 records',
+        'S = INT64_MAX': 'line-of-sight ages: S * (na + 2) must be below 2^31 records',
+    },
+    'shell_ages_check': {
+        'no records': 'shell ages: the map has no records',
+        'na = 0': 'shell ages: na must be at least 1',
+        't0 NaN': 'shell ages: t0 must be finite',
+        'a_lo NaN': 'shell ages: a_lo and a_hi must be finite',
+        'empty range': 'shell ages: a_lo must be below a_hi',
+        'width overflows': 'shell ages: a_hi - a_lo must be finite',
+        '1 record, 2^31 age records':
+            'shell ages: nlon * nlat * (nalt + 2) * (na + 2) must be below 2^31 records',
+        'records = INT64_MAX':
+            'shell ages: nlon * nlat * (nalt + 2) * (na + 2) must be below 2^31 records',
+    },
+}
+
+
+@pytest.mark.parametrize('driver', sorted(REFUSALS))
+def test_every_refusal_text_per_subject(tmp_path, driver):
+    """One check composes the refusals of the four subjects from their words (AgesSubject); every
+    text is, byte for byte, what the subject's own check said, and no case of a driver is refused
+    with a text outside the table."""
+    exe = tmp_path / driver
+    subprocess.check_call(['g++', '-std=c++17', '-O1', '-Wall', '-Werror',
+                           os.path.join(HERE, 'tools', driver + '.cpp'), '-o', str(exe)])
+    done = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert done.returncode == 0, done.stdout + done.stderr
+    got = dict(line.split(' refused: ', 1) for line in done.stdout.splitlines()
+               if ' refused: ' in line)
+    for case, text in REFUSALS[driver].items():
+        assert got[case] == text, case
+    assert set(got.values()) == set(REFUSALS[driver].values())
+
+
 def test_the_library_exports_the_entry_points():
     from nexoclom_amd import hip_api
     names = [f'nxc_{which}_ages_{what}' for which in ('image', 'camera')

@@ -323,7 +323,7 @@ def test_the_library_exports_the_new_entry_points():
                                              '-fno-sanitize-recover=all']],
                          ids=['plain', 'sanitizers'])
 def test_argument_check_as_a_host_program(tmp_path, flags):
-    """nxc_density_ages_enable's refusals are host-only code (nxc_density_ages_check.hpp);
+    """nxc_density_ages_enable's refusals are host-only code (nxc_ages_check.hpp);
     tests/tools/density_ages_check.cpp feeds it good arguments, one bad set per refusal and na one
     below and at the 2^31 record limit.  Built plainly and with the host sanitizers; both runs
     must pass."""

@@ -16,7 +16,7 @@ Every case's inputs come from CASES, so that the guards of all of them can be ch
 ``python -m tests.test_gpu_shell_moments`` restates every case and prints its guards.  The
 thresholds themselves, which the guards keep away from, are covered by
 tests/test_gpu_shell_thresholds.py, which runs the inputs of tests/threshold_cases.py through
-shell_front as well."""
+shell_located<ShellHit> as well."""
 import contextlib
 import io
 

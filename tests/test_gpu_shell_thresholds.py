@@ -1,4 +1,4 @@
-"""k_shell (shell_located) and k_shell_moments (shell_front, its hand-made copy) on the GPU, ON the
+"""k_shell (shell_located) and k_shell_moments (shell_located<ShellHit>, the same front) on the GPU, ON the
 thresholds the guarded tests (tests/test_gpu_shell_map.py, tests/test_gpu_shell_moments.py) keep
 1e-9 away from -- 1e-7 from the seam and 1e-3 from the poles in their case 'seam_and_poles'.
 

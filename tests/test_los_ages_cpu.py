@@ -313,7 +313,7 @@ def test_transient_design():
                                              '-fno-sanitize-recover=all']],
                          ids=['plain', 'sanitizers'])
 def test_argument_check_as_a_host_program(tmp_path, flags):
-    """nxc_los_ages_enable's refusals are host-only code (nxc_los_ages_check.hpp);
+    """nxc_los_ages_enable's refusals are host-only code (nxc_ages_check.hpp);
     tests/tools/los_ages_check.cpp feeds it good arguments, one bad set per refusal of the header's
     list, and na one below and at the 2^31 record limit for several numbers of spectra.  Built
     plainly and with the host sanitizers; run as its own process."""

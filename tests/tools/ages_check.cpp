@@ -1,5 +1,5 @@
-// Stand-alone driver of the host-only side of the age cube (nexoclom_amd/csrc/nxc_ages_check.hpp):
-// the enable's arguments -- good ones, one bad set per refusal, na one below and at the 2^31 record
+// Stand-alone driver of the host-only side of the age cube (nexoclom_amd/csrc/nxc_ages_check.hpp,
+// the subject AGES_OF_PIXELS): the enable's arguments -- good ones, one bad set per refusal, na one below and at the 2^31 record
 // limit of add_record_pairs -- the apply's arguments, and the plan that cuts k_ages_apply to a
 // workgroup's LDS: at 64 KiB and 160 KiB, for (planes, epochs) of (3, 1), (66, 1), (66, 1000) and
 // the most planes that still fit one pixel; every planned chunk must fit, and the chunks must
@@ -34,7 +34,7 @@ void verdict(const char *name, const std::string &why, const char *text)
 void expect(const char *name, int64_t n_pix, int64_t na, double t0, double a_lo, double a_hi,
             const char *text)
 {
-    verdict(name, check_ages_args(n_pix, na, t0, a_lo, a_hi), text);
+    verdict(name, check_ages_args(AGES_OF_PIXELS, n_pix, na, t0, a_lo, a_hi), text);
 }
 
 // the largest number of planes whose one pixel and one epoch fit lds bytes, by the plan's own sizes

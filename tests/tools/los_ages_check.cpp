@@ -1,5 +1,5 @@
 // Stand-alone driver of the host-only check of the line-of-sight ages' arguments
-// (nexoclom_amd/csrc/nxc_los_ages_check.hpp): good arguments, then one bad set per refusal, and na
+// (nexoclom_amd/csrc/nxc_ages_check.hpp, the subject AGES_OF_SPECTRA): good arguments, then one bad set per refusal, and na
 // one below and at the 2^31 record limit for several numbers of spectra -- nothing is allocated, so
 // the limit is cheap to reach.  Build and run on the CPU, for instance
 //     g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all
@@ -9,7 +9,7 @@
 #include <cstdio>
 #include <limits>
 
-#include "../../nexoclom_amd/csrc/nxc_los_ages_check.hpp"
+#include "../../nexoclom_amd/csrc/nxc_ages_check.hpp"
 
 namespace {
 
@@ -18,7 +18,7 @@ int unexpected = 0;
 
 void expect(const char *name, int64_t S, int64_t na, double t0, double a_lo, double a_hi, const char *text)
 {
-    const std::string why = check_los_ages_args(S, na, t0, a_lo, a_hi);
+    const std::string why = check_ages_args(AGES_OF_SPECTRA, S, na, t0, a_lo, a_hi);
     if (!text) {
         std::printf("%s accepted%s\n", name, why.empty() ? "" : " -- UNEXPECTED refusal");
         if (!why.empty()) { std::printf("    %s\n", why.c_str()); unexpected++; }

@@ -1,5 +1,5 @@
 // Stand-alone driver of the host-only check of the shell ages' arguments
-// (nexoclom_amd/csrc/nxc_shell_ages_check.hpp): good arguments, then one bad set per refusal, and
+// (nexoclom_amd/csrc/nxc_ages_check.hpp, the subject AGES_OF_SHELLS): good arguments, then one bad set per refusal, and
 // R * (na + 2) one below and at the 2^31 record limit for several record counts R -- nothing is
 // allocated, so the limit is cheap to reach.  Build and run on the CPU, for instance
 //     g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all
@@ -9,7 +9,7 @@
 #include <cstdio>
 #include <limits>
 
-#include "../../nexoclom_amd/csrc/nxc_shell_ages_check.hpp"
+#include "../../nexoclom_amd/csrc/nxc_ages_check.hpp"
 
 namespace {
 
@@ -18,7 +18,7 @@ int unexpected = 0;
 
 void expect(const char *name, int64_t R, int64_t na, double t0, double a_lo, double a_hi, const char *text)
 {
-    const std::string why = check_shell_ages_args(R, na, t0, a_lo, a_hi);
+    const std::string why = check_ages_args(AGES_OF_SHELLS, R, na, t0, a_lo, a_hi);
     if (!text) {
         std::printf("%s accepted%s\n", name, why.empty() ? "" : " -- UNEXPECTED refusal");
         if (!why.empty()) { std::printf("    %s\n", why.c_str()); unexpected++; }
@@ -34,7 +34,7 @@ void expect(const char *name, int64_t R, int64_t na, double t0, double a_lo, dou
 
 void expect_bytes(const char *name, int64_t R, int64_t na, size_t bytes)
 {
-    const size_t got = shell_ages_bytes(R, na);
+    const size_t got = ages_block_bytes(NXC_SHELL_AGE_PLANES, R, na);
     std::printf("%s: %zu bytes%s\n", name, got, got == bytes ? " ok" : " -- UNEXPECTED");
     if (got != bytes) unexpected++;
 }
